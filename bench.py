@@ -15,9 +15,14 @@ row shard of every table, draws its own batch of 65 536 samples over the GLOBAL 
 is ShardedTables.lookup (route -> all_to_all ids -> owner gather -> all_to_all rows -> un-permute) followed
 by the FM kernel.  value = samples all ranks processed / max-over-ranks time.
 
-The default line also carries two secondary legs, timed after the primary steps: `secondary_zipf` (N = 1: the same kernel on
-Zipf(1.05) ids) and `secondary_cfg5_xdeepfm_cin` (every N: BASELINE configs[4], xDeepFM CIN 3 x 128 on a 1e8-row table,
-row-sharded when N > 1; if this leg hangs a watchdog prints the primary line and exits with code 3).
+A plain run sets up, warms up, times the --steps steps and prints the line.  --full adds, after the timed steps: the
+cpu_baseline leg, the measured streaming ceilings, batch sweep, output window and per-launch distribution of the roofline, and
+two secondary legs: `secondary_zipf` (N = 1: the same kernel on Zipf(1.05) ids) and `secondary_cfg5_xdeepfm_cin` (every N:
+BASELINE configs[4], xDeepFM CIN 3 x 128 on a 1e8-row table, row-sharded when N > 1; if this leg hangs a watchdog prints the
+primary line and exits with code 3).
+
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, 64 MB at most in
+all): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -137,7 +142,13 @@ def parse():
     ap.add_argument("--graph", action="store_true",
                     help="capture the step in HIP graphs (torch.cuda.CUDAGraph, one per rotated id batch) after the warmup and time the replays: "
                          "what a launch-bound step costs without the host's launch gaps (training workloads; N = 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the cpu_baseline leg, the roofline's "
+                         "measured ceilings / batch sweep / output window / per-launch distribution, the Zipf and config-5 secondary legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the timed path returned in its last step to DIR/<name>.npy (float32 / float64, at most 64 MB "
+                         "in all: larger arrays as a fixed, seeded sample of rows, the row numbers in DIR/<name>_rows.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--torch-profile", default=None, help="development: write torch.profiler's device time per (op, input shapes) of 4 untimed "
                                                           "steps after the warmup to this file (which torch ops a step still runs beside the HIP kernels)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
@@ -457,6 +468,33 @@ def measured_ceilings(torch, ops_lib, slab, stream_ptr, sizes=(("at_gather_size"
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(torch, path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array of {name: tensor}, float64 for float64 and integer tensors, float32 otherwise.
+    An array larger than its share of the 64 MB is cut to a fixed, seeded sample of its rows (the same rows in every run with the same
+    shapes); the sampled row numbers are written beside it as <name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - (1 << 20)) // len(arrays)
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        item = 8 if dt == torch.float64 else 4
+        if t.numel() * item > share and t.dim() > 0 and t.shape[0] > 1:
+            row_bytes = item * (t.numel() // t.shape[0])
+            k = max(1, min(t.shape[0], share // (row_bytes + 8)))
+            rows = np.sort(np.random.default_rng(20261016).choice(t.shape[0], size=k, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        a = t.to(dt).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def primary_line(args, wl, cfg, roof, units, world, el, dev_ms, traffic, extra):
     """The contract line without the optional legs (used by the watchdog path)."""
     launch_us = dev_ms * 1e3 / args.steps
@@ -711,7 +749,7 @@ def main():
                              "and let it start the ranks itself)\n" % (args.gpus, world, args.gpus, args.gpus))
         return 2
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.workload in CPU_BASELINE_WORKLOADS:
+    if args.full and world == 1 and not args.no_cpu_baseline and args.workload in CPU_BASELINE_WORKLOADS:
         cpu = CpuBaseline()         # started before torch / HIP are touched; idle (blocked on stdin) until the GPU timing is over
     import torch
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -753,6 +791,7 @@ def main():
     wl = args.workload
     roof = None
     step = None
+    outputs = None        # last step index -> {name: tensor}: what the timed path returned in that step (--dump-outputs)
     units = B
     cfg = {"workload": wl, "batch": B}
     multi = {}            # N > 1: parity_check / stage_us of the sharded lookup, measured before the timed region
@@ -774,21 +813,25 @@ def main():
             fm = torch.empty((B, 1), dtype=torch.float32, device=device)
             if wl == "deepfm_gather_fm":
                 step = lambda i: ops.gather_fm(ts, idsl[i % len(idsl)], out=out, fm=fm)  # noqa: E731
+                outputs = lambda last: {"emb": out, "fm": fm}  # noqa: E731
                 alg = B * (F * (8 + 2 * 4 * K) + 4)      # ids + rows read + concat written + logit
                 kname = "gather_onehot_k<fm,out>"
             elif wl == "gather_only":
                 step = lambda i: ops.embedding_bag(ts, idsl[i % len(idsl)], out=out)  # noqa: E731
+                outputs = lambda last: {"emb": out}  # noqa: E731
                 alg = B * F * (8 + 2 * 4 * K)
                 kname = "gather_onehot_k<out>"
             elif wl == "fm_only":
                 ops.embedding_bag(ts, idsl[0], out=out)
                 step = lambda i: ops.fm_logit(out, F, K, out=fm)  # noqa: E731
+                outputs = lambda last: {"fm": fm}  # noqa: E731
                 alg = B * (4 * F * K + 4)
                 kname = "fm_k"
             elif wl == "linear":
                 wts = ops.TableSet([torch.randn((V,), generator=gen, device=device) * 0.01 for _ in range(F)])
                 bias = torch.zeros(1, device=device)
                 step = lambda i: ops.linear_logit(wts, idsl[i % len(idsl)], bias=bias, out=fm)  # noqa: E731
+                outputs = lambda last: {"linear": fm}  # noqa: E731
                 alg = B * (F * (8 + 4) + 4)
                 kname = "linear_onehot_k"
             else:  # deepfm_full[_packed]: the whole DeepFM forward (gather+FM, linear term, 400-400-400 tower on dir_dense_f32)
@@ -834,6 +877,7 @@ def main():
                 cur = inflight.pop(i, None) or st.lookup_async(idsl[i % len(idsl)], want_fm=True, out=outs[i % 2], fm=fms[i % 2])
                 inflight[i + 1] = st.lookup_async(idsl[(i + 1) % len(idsl)], want_fm=True, out=outs[(i + 1) % 2], fm=fms[(i + 1) % 2])
                 cur.result()
+            outputs = lambda last: {"emb": outs[last % 2], "fm": fms[last % 2]}  # noqa: E731  (this rank's batch)
             alg = B * (F * (8 + 2 * 4 * K) + 4)
             # what bounds the lookup-only line at N > 1: with uniform ids (P-1)/P of every batch's rows (4K bytes) and ids (8 bytes) cross
             # xGMI, 1/P of them to each peer over that pair's own link (the node is fully connected: 7 links x ~153.6 GB/s per GPU)
@@ -890,6 +934,7 @@ def main():
         fm = torch.empty((B, 1), dtype=torch.float32, device=device)
         lin = torch.empty((B, 1), dtype=torch.float32, device=device)
         step = lambda i: ops.gather_fm_linear(pt, idsl[i % len(idsl)], bias=bias, out=out, fm=fm, lin=lin)  # noqa: E731
+        outputs = lambda last: {"emb": out, "fm": fm, "linear": lin}  # noqa: E731
         roof = {"bound": "hbm", "alg_bytes": B * (F * (8 + 2 * 4 * K + 4) + 8), "kernel": "gather_packed_rows_k (concat + FM + linear)"}
         cfg.update({"fields": F, "vocab_per_field": V, "dim": K, "row_bytes": pt.ld * 4})
     elif wl == "train_sparse":
@@ -1389,6 +1434,12 @@ def main():
                           "(layer-1 dW, pooled top layer), f32 accumulate") if "f16x2" in modes.values() else "f32 via bf16x3 split, f32 accumulate"}
         cfg.update({"m": m, "D": D, "layers": list(Hs)})
 
+    if args.dump_outputs and outputs is None:
+        sys.stderr.write("bench.py: --dump-outputs is not available for --workload %s%s\n" % (wl, " at N > 1" if world > 1 else ""))
+        if cpu is not None:
+            cpu.close()
+        return 2
+
     # ---- warmup, then EXACTLY --steps timed steps bracketed by barrier + synchronize ------------------
     if args.graph:
         if world > 1:
@@ -1438,12 +1489,16 @@ def main():
         t = torch.tensor([el], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the buffers still hold the last timed step's results: nothing has run on them since
+        dumped = dump_outputs(torch, args.dump_outputs, outputs(args.warmup + args.steps - 1))
 
-    # ---- secondary leg of the default run: BASELINE config 5 (xDeepFM CIN 3 x 128 over a 10^8-row table, row-sharded when N > 1).
-    # Same contract (barrier-bracketed, max over ranks, whole-job samples/s); never allowed to cost the primary line: a watchdog on
-    # every rank gives up after DIR_BENCH_SECONDARY_TIMEOUT seconds and rank 0 then prints the primary result alone.
+    # ---- --full: secondary leg of the default workload: BASELINE config 5 (xDeepFM CIN 3 x 128 over a 10^8-row table, row-sharded when
+    # N > 1).  Same contract (barrier-bracketed, max over ranks, whole-job samples/s); never allowed to cost the primary line: a watchdog
+    # on every rank gives up after DIR_BENCH_SECONDARY_TIMEOUT seconds and rank 0 then prints the primary result alone.
     secondary = None
-    if wl == "deepfm_gather_fm" and args.id_dist == "uniform" and os.environ.get("DIR_BENCH_NO_SECONDARY") != "1":
+    if args.full and wl == "deepfm_gather_fm" and args.id_dist == "uniform" and os.environ.get("DIR_BENCH_NO_SECONDARY") != "1":
         import threading
         done = threading.Event()
         primary = {"el": el, "dev_ms": dev_ms}
@@ -1538,7 +1593,7 @@ def main():
                 dram = B * F * (8 + (2 * row_b if row_b < 128 else row_b) + row_b) + (4 * B if wl == "deepfm_gather_fm" else 0)
                 res["roofline"]["dram_side_bytes"] = dram
                 res["roofline"]["dram_side_GBps"] = dram / (launch_us * 1e-6) / 1e9
-                # (b) this box's streaming ceilings, measured now (rotating windows of the tables: nothing cache-resident)
+            if args.full and world == 1 and wl in ("deepfm_gather_fm", "gather_only"):
                 # (b) this box's streaming ceilings, measured now: at the gather's own size (a ~20 us kernel: ramp and tail included) and
                 # asymptotically (512 MB windows); nothing cache-resident (see measured_ceilings)
                 import ctypes
@@ -1629,7 +1684,7 @@ def main():
         res["roofline"]["clock"] = "host clock over the timed region (the one ms_per_step and value use)"
         res["roofline"]["hip_event_avg_launch_us"] = hip_us
         res["roofline"]["frac_hip_events"] = res["roofline"]["frac"] * launch_us / hip_us if hip_us > 0 else None
-        if world == 1 and roof["bound"] in ("hbm", "mfma"):
+        if args.full and world == 1 and roof["bound"] in ("hbm", "mfma"):
             # per-launch distribution (median + p10 / p90 of >= 100 launches), at any --steps, outside the timed region: one HIP
             # event per step on the launch stream (events inside the timed region would put a timestamp packet between the launches)
             nl = 200 if launch_us < 2000 else 30
@@ -1648,7 +1703,7 @@ def main():
                 res["roofline"]["frac_at_median"] = roof["alg_bytes"] / (per[nl // 2] * 1e-6) / 1e9 / HBM_PEAK_GBS
             else:
                 res["roofline"]["frac_at_median"] = res["roofline"]["pipe_flops_per_step"] / (per[nl // 2] * 1e-6) / 1e12 / MFMA_BF16_PEAK_TF
-        if world == 1 and wl == "deepfm_gather_fm" and args.id_dist == "uniform":
+        if args.full and world == 1 and wl == "deepfm_gather_fm" and args.id_dist == "uniform":
             # secondary, cache-assisted case: Zipf(1.05) ids, rows read with the cacheable policy
             import copy
             zargs = copy.copy(args)
@@ -1688,6 +1743,8 @@ def main():
             cpu.close()
         if secondary is not None:
             res["secondary_cfg5_xdeepfm_cin"] = secondary
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.destroy_process_group()

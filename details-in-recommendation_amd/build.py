@@ -100,7 +100,8 @@ def build(force=False, jobs=None):
     if force:
         for f in os.listdir(BUILD):
             os.remove(os.path.join(BUILD, f))
-    jobs = jobs or min(len(SOURCES), max(1, (os.cpu_count() or 2) // 2))
+    # MAX_JOBS (the usual cap of extension builds) wins over the machine's CPU count, which may be far more than this process may use
+    jobs = jobs or int(os.environ.get("MAX_JOBS") or 0) or min(len(SOURCES), max(1, (os.cpu_count() or 2) // 2))
     with ThreadPoolExecutor(jobs) as ex:
         objs = list(ex.map(_compile, SOURCES))
     _isa_check(objs)

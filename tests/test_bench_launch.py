@@ -74,8 +74,9 @@ def test_gpus_2_launches_two_ranks(built_lib):
 
 @pytest.mark.gpu
 def test_gpus_2_cfg5_leg_checks_itself(built_lib):
-    """The config-5 secondary leg of the same command (xDeepFM CIN on the row-sharded 1e8-row table; here a small batch): its own parity check."""
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4096", "--no-cpu-baseline"],
+    """The config-5 secondary leg of the same command under --full (xDeepFM CIN on the row-sharded 1e8-row table; here a small batch): its
+    own parity check."""
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4096", "--no-cpu-baseline", "--full"],
              {"DIR_BENCH_BACKEND": "gloo", "DIR_BENCH_SAME_DEVICE": "1", "DIR_SHARD_HOST_STAGED": "1", "DIR_BENCH_CFG5_ROWS": "2600000", "DIR_BENCH_CFG5_WARMUP": "2"})
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.lstrip().startswith("{")][-1])
@@ -95,3 +96,55 @@ def test_synthetic_rows_are_a_closed_form():
     assert torch.equal(bench.synth_rows(torch, 5, pick, 16, 0.25), full[pick])
     assert abs(float(full.mean())) < 5e-3 and abs(float(full.std()) - 0.25) < 5e-3
     assert not torch.equal(bench.synth_rows(torch, 6, pick, 16, 0.25), full[pick])
+
+
+def test_dump_outputs_writes_a_bounded_fixed_sample(tmp_path):
+    """bench.dump_outputs: float32 / float64 files only, 64 MB at most in all, an oversized array cut to the same seeded rows every time
+    (row numbers written beside it), small arrays whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(70000 * 300, dtype=torch.float32).reshape(70000, 300)          # 84 MB
+    small = torch.arange(1000, dtype=torch.int64)
+    runs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, str(tmp_path / d), {"emb": big, "ids": small, "fm": big[:, :1].double()})
+        runs.append({f: np.load(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))})
+        assert sum(os.path.getsize(str(tmp_path / d / f)) for f in os.listdir(str(tmp_path / d))) <= bench.DUMP_LIMIT_BYTES
+    a, b = runs
+    assert set(a) == {"emb.npy", "emb_rows.npy", "ids.npy", "fm.npy"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    rows = a["emb_rows.npy"].astype(np.int64)
+    assert a["emb.npy"].dtype == np.float32 and 1000 < rows.size < 70000 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(a["emb.npy"], big.numpy()[rows])
+    np.testing.assert_array_equal(a["ids.npy"], np.arange(1000, dtype=np.float64))
+    np.testing.assert_array_equal(a["fm.npy"], big.numpy()[:, :1].astype(np.float64))
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_one(built_lib, oracle, tmp_path):
+    """A plain `bench.py --gpus 1` line: exactly --steps timed steps and ms_per_step, none of the --full legs; --dump-outputs writes the
+    last step's concat and FM logit, the same in two runs, and the logit is the oracle's FM of the dumped concat bit for bit."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "4096", "--vocab", "20000", "--dump-outputs", str(tmp_path / d)],
+                 timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.lstrip().startswith("{")]
+        assert len(lines) == 1
+        res = json.loads(lines[0])
+        assert res["steps"] == 3 and res["warmup"] == 2 and res["ms_per_step"] > 0 and res["value"] > 0
+        assert res["unit"] == "samples/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+        assert not {"cpu_baseline", "secondary_zipf", "secondary_cfg5_xdeepfm_cin"} & set(res)
+        assert not {"measured_ceilings", "batch_sweep", "launch_us_median"} & set(res["roofline"])
+        assert res["dumped_outputs"] == {"emb": [4096, 416], "fm": [4096, 1]}
+        outs.append((np.load(str(tmp_path / d / "emb.npy")), np.load(str(tmp_path / d / "fm.npy"))))
+    (emb, fm), (emb2, fm2) = outs
+    assert emb.dtype == np.float32 and fm.dtype == np.float32 and np.any(emb != 0)
+    np.testing.assert_array_equal(emb, emb2)
+    np.testing.assert_array_equal(fm, fm2)
+    np.testing.assert_array_equal(fm[:, 0], oracle.fm_second_order(emb, 26, 16))
