@@ -100,6 +100,7 @@ def check_onehot_matrix(cats, ids_bf, device):
         if len(_BOUNDS) > 64:
             _BOUNDS.clear()
         bounds = _BOUNDS[key] = torch.tensor(b, dtype=torch.int64, device=device)
+    ops.held(bounds)                               # a graph captured now reads it: kept alive past the cache's .clear()
     bad = torch.empty(1, dtype=torch.int32, device=device)
     B, F = ids_bf.shape
     _lib.check(_lib.load().dir_check_ids(ops._ptr(bounds), F, ops._ptr(ids_bf), None, ids_bf.stride(0), ids_bf.stride(1), B, ops._ptr(bad),

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256, KC == 16 ? 4 : 2) void dense_k(const float* __
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     float v = acc[mt][nt][g] + bcol;
-                    if (RELU) v = fmaxf(v, 0.f);
+                    if (RELU) v = (v != v) ? v : fmaxf(v, 0.f);      // a NaN stays NaN, as torch.relu keeps it
                     if (pscale) v = v * sc + sf;     // the inference batch-norm that follows the activation, per column
                     ep[(4 * kk + g) * EPS + 16 * nt + r16] = v;
                 }
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256, KC == 16 ? 4 : 2) void dense_k(const float* __
             for (int g = 0; g < 4; ++g) {
                 const int64_t row = m0 + 32 * w + 16 * mt + 4 * kk + g;
                 float v = acc[mt][nt][g] + bcol;
-                if (RELU) v = fmaxf(v, 0.f);
+                if (RELU) v = (v != v) ? v : fmaxf(v, 0.f);      // a NaN stays NaN, as torch.relu keeps it
                 if (pscale) v = v * sc + sf;
                 if (row < M && col < N) {
                     if (gate && !(gate[row * gate_ld + col] > 0.f)) v = 0.f;
@@ -344,7 +344,7 @@ __global__ __launch_bounds__(256) void dense_small_k(const float* __restrict__ X
         for (int g = 0; g < 4; ++g) {
             const int64_t row = row0 + 16 * t + 4 * kk + g;
             float v = sv[g] + b;
-            if (RELU) v = v > 0.f ? v : 0.f;
+            if (RELU) v = (v > 0.f || v != v) ? v : 0.f;      // a NaN stays NaN, as torch.relu keeps it
             if (pscale) v = v * sc + sf;
             if (row < M) Y[row * y_ld + col] = v;
         }
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(256) void dense_mid_k(const float* __restrict__ X, 
             for (int g = 0; g < 4; ++g) {
                 const int64_t row = row0 + 16 * RT * wm + 16 * t + 4 * kk + g;
                 float v = acc[t][u][g] + bv;
-                if (RELU) v = v > 0.f ? v : 0.f;
+                if (RELU) v = (v > 0.f || v != v) ? v : 0.f;      // a NaN stays NaN, as torch.relu keeps it
                 if (pscale) v = v * sc + sf;
                 if (row < M) Y[row * y_ld + col] = v;
             }

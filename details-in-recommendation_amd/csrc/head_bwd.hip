@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256) void esmm_head_k(const float* __restrict__ ctr
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < B; i += (int64_t)gridDim.x * 256) {
         const float a = 1.0f / (1.0f + expf(-ctr[i])), b = 1.0f / (1.0f + expf(-cvr[i]));
         float p = a * b;
-        p = fminf(fmaxf(p, eps), 1.0f - eps);
+        p = (p != p) ? p : fminf(fmaxf(p, eps), 1.0f - eps);      // a NaN stays NaN, as torch.clamp keeps it (fmaxf would return eps)
         ctcvr_logit[i] = logf(p / (1.0f - p));
     }
 }

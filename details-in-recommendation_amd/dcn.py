@@ -134,13 +134,30 @@ class DeepCrossNetwork(nn.Module):
         return deep_logit + _Units1Fn.apply(cross, wl[:, :d], None)
 
     def _padded_cross_params(self):
-        """cross_w / cross_b zero-padded to a multiple of 4 columns, cached until the parameters change."""
-        key = (self.cross_w._version, self.cross_b._version, self.cross_w.data_ptr())
+        """cross_w / cross_b zero-padded to a multiple of 4 columns, cached until the parameters change.  Under a default graph capture
+        (ops.capture_bypasses_caches) the pad is computed inline and nothing is remembered: the graph pads the parameters as they are at
+        replay time."""
+        pad = ops.pad4(self.column_num) - self.column_num
+        if ops.capture_bypasses_caches(self.cross_w):
+            return torch.nn.functional.pad(self.cross_w.data, (0, pad)), torch.nn.functional.pad(self.cross_b.data, (0, pad))
+        key = (self.cross_w._version, self.cross_b._version, self.cross_w.data_ptr(), ops._CACHE_GEN[0])
         if getattr(self, "_cross_pad_key", None) != key:
-            pad = ops.pad4(self.column_num) - self.column_num
             self._cross_pad = (torch.nn.functional.pad(self.cross_w.data, (0, pad)), torch.nn.functional.pad(self.cross_b.data, (0, pad)))
             self._cross_pad_key = key
-        return self._cross_pad
+        return ops.held(self._cross_pad)
+
+    def _logit_split_params(self):
+        """The two halves of the final dense(1)'s weight (cross | deep), aligned copies, once per version (inline under a default capture,
+        as _padded_cross_params)."""
+        d, dp = self.column_num, ops.pad4(self.column_num)
+        wl = self.logits_layer.weight                                            # [1, d + h]
+        if ops.capture_bypasses_caches(wl):
+            return torch.nn.functional.pad(wl.data[:, :d], (0, dp - d)), wl.data[:, d:].clone()
+        key = (wl._version, wl.data_ptr(), ops._CACHE_GEN[0])
+        if getattr(self, "_logit_split_key", None) != key:
+            self._logit_split = (torch.nn.functional.pad(wl.data[:, :d], (0, dp - d)), wl.data[:, d:].clone())
+            self._logit_split_key = key
+        return ops.held(self._logit_split)
 
     def _forward_padded(self, features):
         """Inference with an input width that is not a multiple of 4 (429 = 26 x 16 + 13): the input layer writes x0 with row
@@ -148,15 +165,9 @@ class DeepCrossNetwork(nn.Module):
         the pad columns exactly 0), the first deep layer reads the same buffer with Kd = pad4(d) against a zero-padded weight,
         and the final dense(1) over concat([cross, deep]) (:136-137) is evaluated as cross . w_c + deep . w_d + bias -- the
         concat is never materialised, and cross . w_c comes out of the cross kernel itself (the cross output has no other reader).  Values: the same sums over the same real columns."""
-        d, dp = self.column_num, ops.pad4(self.column_num)
         x0p = self.input_layer(features, pad_to=4)
         wp, bp = self._padded_cross_params()
-        wl = self.logits_layer.weight                                            # [1, d + h]
-        key = (wl._version, wl.data_ptr())
-        if getattr(self, "_logit_split_key", None) != key:                       # the two halves of the final dense(1)'s weight, aligned copies, once per version
-            self._logit_split = (torch.nn.functional.pad(wl.data[:, :d], (0, dp - d)), wl.data[:, d:].clone())
-            self._logit_split_key = key
-        wc, wd = self._logit_split
+        wc, wd = self._logit_split_params()
         cross_logit = ops.cross_network_head(x0p, wp, bp, wc)                    # [B, 1] = x_L . w_c in the cross kernel's epilogue: x_L is not written
         out = cross_logit.add_(self.logits_layer.bias)
         deep_logit = self._deep_logit(x0p, wd)                                   # the last deep layer with deep . w_d in its epilogue, when covered

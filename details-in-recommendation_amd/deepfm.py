@@ -150,7 +150,7 @@ class DeepFM(nn.Module):
             if self._lin_ts is not None:
                 self._lin_ts.owners = list(self.linear_weights)
             self._ts_key = key
-        return self._emb_ts, self._lin_ts
+        return ops.held((self._emb_ts, self._lin_ts))
 
     # ---- logit builders ---------------------------------------------------------------------------
     def _logits_of(self, net):
@@ -372,14 +372,20 @@ class DeepFM(nn.Module):
             return None
         sig = self._pack_signature()
         if getattr(self, "_packed", None) is not None and getattr(self, "_packed_sig", None) == sig and self._packed_extra is None:
-            return self._packed
+            return self._held_pack()
         ld = 32
         while ld < self.K + 1:
             ld *= 2
         if sum(int(p.shape[0]) for p in self.embedding_weights) * ld * 4 > self.AUTO_PACK_MAX_BYTES:
             return None
         self.pack_for_serving()
-        return self._packed
+        return self._held_pack()
+
+    def _held_pack(self):
+        """self._packed, kept alive by the graph being captured (if any) and guarded by the tensors it copies: the packed rows are a copy of
+        the whole tables, so even a default capture reads them as they are at capture time -- serving.GraphedForward captures again
+        when one of the guards was modified in place (ops.capture_hold)."""
+        return ops.held(self._packed, guards=list(self.embedding_weights) + list(self.linear_weights))
 
     def pack_for_serving(self):
         """Inference-only: copy the embedding tables and the first-order weights of the same categorical columns into
@@ -414,9 +420,9 @@ class DeepFM(nn.Module):
             self._serving_pack()                                                 # the default inference layout (built / refreshed here)
         if (getattr(self, "_packed", None) is not None and linear_ids is not None and not torch.is_grad_enabled()
                 and getattr(self, "_packed_sig", None) == self._pack_signature()):
-            logits = self._packed_logits(dnn_ids, self._packed)
+            logits = self._packed_logits(dnn_ids, self._held_pack())
             if self._packed_extra is not None:
-                logits = logits + ops.linear_logit(self._packed_extra, linear_ids[:, self.F:])
+                logits = logits + ops.linear_logit(ops.held(self._packed_extra), linear_ids[:, self.F:])
             return logits
         emb_ts, lin_ts = self._tablesets()
         train = torch.is_grad_enabled()

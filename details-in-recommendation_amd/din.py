@@ -41,14 +41,19 @@ class Dice(nn.Module):
 
     def scale_shift(self):
         """(scale, shift) with p = sigmoid(scale * s + shift): the inference form the HIP unit takes.  Folded once per version
-        of the moving statistics (four library kernels per call otherwise: 8 % of the cfg-4 model's forward)."""
+        of the moving statistics (four library kernels per call otherwise: 8 % of the cfg-4 model's forward); under a default graph capture
+        (ops.capture_bypasses_caches) folded inline, so that a replay reads the statistics as they are then."""
+        if ops.capture_bypasses_caches(self.moving_mean):
+            with torch.no_grad():
+                scale = torch.rsqrt(self.moving_variance + self.eps)
+                return scale, -self.moving_mean * scale
         key = (self.moving_mean._version, self.moving_variance._version, self.moving_mean.data_ptr(),
-               self.moving_variance.data_ptr(), self.eps)
+               self.moving_variance.data_ptr(), self.eps, ops._CACHE_GEN[0])
         if self._folded is None or self._folded[0] != key:
             with torch.no_grad():
                 scale = torch.rsqrt(self.moving_variance + self.eps)
                 self._folded = (key, scale, -self.moving_mean * scale)
-        return self._folded[1], self._folded[2]
+        return ops.held(self._folded[1]), ops.held(self._folded[2])
 
     def forward(self, s, valid=None):
         """valid (optional, broadcastable to s without its last dimension): rows that take part in the batch statistics."""
@@ -116,19 +121,22 @@ class DINAttentionPool(nn.Module):
         """[3 H1 + 3 H2] for the HIP unit (alpha, scale, shift per layer), from the activation modules' inference form."""
         if self.activation == "sigmoid":
             return None
+        if ops.capture_bypasses_caches(self.act1.alpha):
+            return self._build_act_params()                                 # a default capture: built inside the graph, from the values at replay
         src = [self.act1.alpha, self.act2.alpha]
         if self.activation == "dice":
             src += [self.act1.moving_mean, self.act1.moving_variance, self.act2.moving_mean, self.act2.moving_variance]
-        key = tuple((t._version, t.data_ptr()) for t in src)
+        key = tuple((t._version, t.data_ptr()) for t in src) + (ops._CACHE_GEN[0],)
         if self._act_cache is None or self._act_cache[0] != key:           # rebuilt when a parameter / statistic is written
-            if self.activation == "prelu":
-                vec = ops.din_act_params(self.b1.numel(), self.b2.numel(), self.act1.alpha, self.act2.alpha)
-            else:
-                s1, t1 = self.act1.scale_shift()
-                s2, t2 = self.act2.scale_shift()
-                vec = ops.din_act_params(self.b1.numel(), self.b2.numel(), self.act1.alpha, self.act2.alpha, s1, t1, s2, t2)
-            self._act_cache = (key, vec)
-        return self._act_cache[1]
+            self._act_cache = (key, self._build_act_params())
+        return ops.held(self._act_cache[1])
+
+    def _build_act_params(self):
+        if self.activation == "prelu":
+            return ops.din_act_params(self.b1.numel(), self.b2.numel(), self.act1.alpha, self.act2.alpha)
+        s1, t1 = self.act1.scale_shift()
+        s2, t2 = self.act2.scale_shift()
+        return ops.din_act_params(self.b1.numel(), self.b2.numel(), self.act1.alpha, self.act2.alpha, s1, t1, s2, t2)
 
     def _composite(self, hist, hist_len, cand):
         """The unit as differentiable torch ops (PReLU / Dice in TRAIN mode): same definition as include/dir_hip.h A13."""

@@ -80,7 +80,7 @@ class InputLayer(nn.Module):
                     run.append(i)
                 close(run, mn)
             self._ts_key = key
-        return self._groups
+        return ops.held(self._groups)
 
     def fused_sparse_adagrad(self, lr, initial_accumulator_value=0.1):
         """Attach the fused sparse Adagrad (include/dir_hip.h: dir_sparse_adagrad_sorted_f32; the reference's Adagrad on

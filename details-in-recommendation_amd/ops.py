@@ -15,6 +15,7 @@ Reference closures (relative to /root/reference):
   cin_layer                  (no reference code; README.md:28)
 """
 import ctypes
+import operator
 import os
 
 import torch
@@ -150,6 +151,7 @@ class TableSet:
         sync per `every` steps.  Any other version change (load_state_dict, a copy_, a torch optimiser) re-measures at once, and so does
         invalidate_caches() (a checkpoint loaded after one eval forward used to keep the pre-load figure for 32 x F bumps)."""
         watched = list(self.tables) + list(self.owners)
+        capture_guard(watched)
         sig = tuple(t._version for t in watched)
         hit = getattr(self, "_absmax", None)
         stale = hit is None or hit[3] != _CACHE_GEN[0] or len(hit[0]) != len(sig)
@@ -231,23 +233,82 @@ def mark_written(*tensors):
                 _HIP_BUMPS[o] = _HIP_BUMPS.get(o, 0) + 1
 
 _FROZEN_WEIGHTS = [False]
+_HOLDS = []                      # the keep-alive lists of the captures in progress (capture_hold / frozen_weights), innermost last
+_VERSION = operator.attrgetter("_version")
 
 
-class frozen_weights:
-    """with ops.frozen_weights(): ... capture ...  -- a capture taken inside takes the VALID per-version cache entries (weight images, packed
-    weights, folded batch norms: built by an earlier eager call on the same versions) instead of re-packing inside the graph.  For SERVING
-    graphs whose weights do not change between replays: a one-launch DeepFM forward at 1 024-4 096 rows carries three pack launches
-    otherwise (15-20 us of ~70).  The price is the rule CapturedStep keeps: a replay after an in-place weight update still runs the images
-    of capture time -- capture again after loading new weights.  serving.GraphedForward(..., frozen_weights=True) uses it."""
+class capture_hold:
+    """with ops.capture_hold() as hold: ... capture ...  -- what a graph captured inside reads through a cache.  A graph keeps raw pointers
+    only: a cache entry it read may be dropped afterwards (an eager call at a new weight version replaces it, invalidate_caches() and the
+    caches' size limits clear it) and the allocator may hand its block out again.  So every cache hit served while a stream is capturing
+    appends what it returned to `keep` (tensors; a TableSet / PackedTables object) -- the owner of the graph stores the hold for the
+    graph's lifetime -- and a cache that is NOT bypassed under a default capture (DeepFM's packed serving rows: a copy of the tables)
+    records the tensors its entry was built from in `guards`: moved() is True once one of them was modified in place or invalidate_caches()
+    ran, and the owner captures again (GraphedForward).  serving.GraphedForward and CapturedStep open one around their capture."""
+
+    def __init__(self):
+        self.keep, self._guard_ts, self._guard_ids = [], [], set()
+        self._guard_vs, self._gen = [], _CACHE_GEN[0]
+
+    def __enter__(self):
+        _HOLDS.append(self)
+        return self
+
+    def __exit__(self, *exc):
+        _HOLDS.remove(self)
+        return False
+
+    def guard(self, tensors):
+        for t in tensors:
+            if id(t) not in self._guard_ids:
+                self._guard_ids.add(id(t))
+                self._guard_ts.append(t)
+                self._guard_vs.append(t._version)
+
+    @property
+    def guarded(self):
+        return bool(self._guard_ts)
+
+    def moved(self):
+        """Whether a guarded tensor was modified in place (tensor._version) or invalidate_caches() ran since the capture."""
+        return self._gen != _CACHE_GEN[0] or list(map(_VERSION, self._guard_ts)) != self._guard_vs
+
+
+def held(obj, guards=()):
+    """A cache hands `obj` to its caller: while a stream is capturing inside a capture_hold / frozen_weights, the hold keeps it alive (and
+    records `guards`, see capture_hold).  Returns obj.  Outside a capture: nothing (one list test)."""
+    if _HOLDS and torch.cuda.is_current_stream_capturing():
+        h = _HOLDS[-1]
+        h.keep.append(obj)
+        if guards:
+            h.guard(guards)
+    return obj
+
+
+def capture_guard(tensors):
+    """A decision taken from the values of `tensors` now (a measured magnitude that picks a kernel's split) is baked into the graph being
+    captured: the open hold records them as guards (capture_hold.moved)."""
+    if _HOLDS and torch.cuda.is_current_stream_capturing():
+        _HOLDS[-1].guard(tensors)
+
+
+class frozen_weights(capture_hold):
+    """with ops.frozen_weights() as hold: ... capture ...  -- a capture taken inside takes the VALID per-version cache entries (weight images,
+    packed weights, folded batch norms: built by an earlier eager call on the same versions) instead of re-packing inside the graph.  For
+    SERVING graphs whose weights do not change between replays: a one-launch DeepFM forward at 1 024-4 096 rows carries three pack launches
+    otherwise (15-20 us of ~70).  The price: a replay after an in-place weight update still runs the images of capture time -- capture again
+    after loading new weights.  What the graph reads stays valid: every entry it took is in `hold.keep` (capture_hold), which the owner of the
+    graph stores, so an eager call at new weights, invalidate_caches() or a cache's size limit cannot free it under the graph.
+    serving.GraphedForward(..., frozen_weights=True) uses it."""
 
     def __enter__(self):
         self._old = _FROZEN_WEIGHTS[0]
         _FROZEN_WEIGHTS[0] = True
-        return self
+        return super().__enter__()
 
     def __exit__(self, *exc):
         _FROZEN_WEIGHTS[0] = self._old
-        return False
+        return super().__exit__(*exc)
 
 
 def capture_bypasses_caches(t=None):
@@ -265,8 +326,10 @@ class CapturedStep:
     nothing on the host moves their version counters, so everything cached per version (serving rows, weight images, folded batch norms)
     would stay stale for an eager eval after the replays.  replay() bumps the counters of `written` after every replay, exactly as the
     eager updaters do (mark_written).  Inside the capture every per-version cache is bypassed (dense_bf3_image, tower_image, the modules'
-    packed weights): the pack kernels are part of the graph and read the weights as they are at replay time.  What a captured step must
-    not do: anything that syncs (a first-time range measurement: run one eager step before capturing -- the constructor does)."""
+    packed weights, DCN's padded cross parameters, DIN's folded activations): the pack kernels are part of the graph and read the weights as
+    they are at replay time.  What a cache still serves under the capture (TableSets, workspaces) is kept alive in self.hold (capture_hold)
+    for the graph's lifetime.  What a captured step must not do: anything that syncs (a first-time range measurement: run one eager step
+    before capturing -- the constructor does)."""
 
     def __init__(self, fn, written=(), warmup=3, pool=None):
         self.fn, self.written = fn, [t for t in written if isinstance(t, torch.Tensor)]
@@ -279,7 +342,7 @@ class CapturedStep:
         torch.cuda.synchronize()
         mark_written(*self.written)
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, pool=pool):
+        with capture_hold() as self.hold, torch.cuda.graph(self.graph, pool=pool):
             self.out = fn()
         mark_written(*self.written)                        # (the capture itself does not run the kernels; counters move like a step's anyway)
 
@@ -683,7 +746,7 @@ def din_pack_image(owners, args, activation, ap):
     sig = tuple((id(t), t._version if not t.is_inference() else -1) for t in watched) + (_CACHE_GEN[0],)
     hit = _DIN_PACK_IMAGES.get(key)
     if hit is not None and not capture_bypasses_caches() and hit[0] == sig and all(r() is t for r, t in zip(hit[1], watched)):
-        return hit[2]
+        return held(hit[2])
     img = torch.empty(int(lib.dir_din_pack_image_bytes()), dtype=torch.uint8, device=W1.device)
     _lib.check(lib.dir_din_pack_weights_f32(_ptr(W1), _ptr(b1), H1, _ptr(W2), _ptr(b2), H2, _ptr(W3), DIN_ACTIVATIONS[activation], _ptr(ap),
                                             _ptr(img), _stream()))
@@ -700,7 +763,7 @@ def _din_pack_ws(device, nbytes):
     ws = _DIN_PACK_WS.get(key)
     if ws is None or ws.numel() < nbytes:
         ws = _DIN_PACK_WS[key] = torch.empty(max(nbytes, 4096), dtype=torch.uint8, device=device)
-    return ws
+    return held(ws)
 
 
 def din_attention_pool(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, normalize=False, want_scores=False, activation="sigmoid",
@@ -1081,7 +1144,7 @@ def dense_bf3_image(weight, split="bf16x3"):
     capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
     hit = _DENSE_IMAGES.get(key)
     if hit is not None and hit[0]() is weight and hit[1] == sig and not capture_bypasses_caches(weight):
-        return hit[2]
+        return held(hit[2])
     N, Kd = weight.shape
     lib = _lib.load()
     nbytes = int(lib.dir_dense_bf16x3_image_bytes(Kd, N))
@@ -1306,7 +1369,7 @@ def tower_image(weight, split=None):
     capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
     hit = _TOWER_IMAGES.get(key)
     if hit is not None and hit[0]() is weight and hit[1] == sig and not capture_bypasses_caches(weight):
-        return hit[2]
+        return held(hit[2])
     N, K = weight.shape
     lib = _lib.load()
     nbytes = int(lib.dir_tower_cs_image_bytes(K, N) if split == "f16x2cs" else lib.dir_tower_bf16x3_image_bytes(K, N))
@@ -1330,6 +1393,7 @@ def weight_absmax(weight, every=1):
     packed for it -- ADVICE r4: the tower's guard used to build the fp16 x 2 image just to read this number).  every > 1: a measurement may
     be up to `every` in-place updates old (training loops: one pass and one sync per `every` steps, see TableSet.absmax)."""
     import weakref
+    capture_guard((weight,))
     key = weight.data_ptr()
     sig = (weight._version, tuple(weight.shape))
     hit = _WEIGHT_ABSMAX.get(key)
@@ -1893,7 +1957,7 @@ def cin_pooled_fused_covers(m, Hp, H, D):
 
 def cin_pooled_image(W, m, Hp, D, owner=None):
     """The fused pooled layer's weight image (dir_cin_pooled_pack_f32), once per version of W (while a stream is capturing: packed inside the
-    graph, nothing remembered -- the rule of every per-version cache here).  owner: the LONG-LIVED tensor whose identity and version stand for
+    graph, nothing remembered, unless under frozen_weights -- the rule of every per-version cache here).  owner: the LONG-LIVED tensor whose identity and version stand for
     W's (a module passes its nn.Parameter and `.data` as W: a `.data` view is a new object with a fresh version counter on every call)."""
     import weakref
     lib = _lib.load()
@@ -1903,8 +1967,8 @@ def cin_pooled_image(W, m, Hp, D, owner=None):
     key = (W.data_ptr(), tuple(W.shape), tuple(W.stride()), m, Hp)
     sig = (own._version if not own.is_inference() else -1, _CACHE_GEN[0])
     hit = _CIN_POOLED_IMAGES.get(key)
-    if hit is not None and not capturing and hit[0]() is own and hit[1] == sig:
-        return hit[2]
+    if hit is not None and not capture_bypasses_caches(W) and hit[0]() is own and hit[1] == sig:
+        return held(hit[2])
     Wc = W if W.is_contiguous() else W.contiguous()
     nbytes = int(lib.dir_cin_pooled_image_bytes(m, Hp, H, D))
     img = torch.empty(nbytes, dtype=torch.uint8, device=W.device)

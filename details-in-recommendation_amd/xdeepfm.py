@@ -65,7 +65,7 @@ class XDeepFM(nn.Module):
             if self._lin_ts is not None:
                 self._lin_ts.owners = list(self.linear_weights)
             self._ts_key = key
-        return self._emb_ts, self._lin_ts
+        return ops.held((self._emb_ts, self._lin_ts))
 
     def fused_sparse_adagrad(self, lr, initial_accumulator_value=0.1):
         """Attach the fused HIP sparse Adagrad to the embedding tables (as DeepFM.fused_sparse_adagrad; the xDeepFM paper trains with

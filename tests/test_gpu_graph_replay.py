@@ -1,0 +1,432 @@
+"""Graph replays (serving.GraphedForward) of every model against the eager forward, after weight updates and cache evictions.
+
+A captured graph keeps raw pointers only.  Default capture: every per-version cache is bypassed inside the capture, so a replay must
+follow an in-place update of any parameter group bit for bit (E1); frozen_weights=True: a replay keeps computing from the weight images of
+capture time (E1), and those must stay alive whatever evicts them from the caches -- an eager call at new weights, ops.invalidate_caches()
+or a cache's size limit (E2: evict, then take the freed blocks back with NaN-filled tensors of the same sizes from the caching allocator).
+E3: a hidden weight scaled by 2^20 / 2^-20 after a default capture (a magnitude that routes a kernel's split).  The eager results are
+anchored to float64 restatements (oracle/np_ref.py) at the existing model tests' tolerances, so "replay == eager" cannot hold with both
+wrong.  The allocator's pool stays mapped throughout (no empty_cache): a stale pointer reads poisoned live memory."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import np_ref as R
+
+pytestmark = pytest.mark.gpu
+
+MODES = ["default", "frozen"]
+_DT = [np.float64]           # the restatements' precision: float64, or float32 to measure what fp32 arithmetic itself loses (E3)
+
+
+def _np(t):
+    return t.detach().cpu().numpy().astype(_DT[0])
+
+
+def _close(got, ref, tol):
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    err = np.abs(got - ref) / (1 + np.abs(ref))
+    assert float(err.max()) <= tol, "max scaled err %.3e" % float(err.max())
+
+
+class _Case:
+    """model, fn(*inputs) -> logits tensor, inputs, ref64() -> float64 logits of the current weights, tol, parameter groups."""
+
+    def __init__(self, model, fn, inputs, ref64, tol, groups, hidden):
+        self.model, self.fn, self.inputs, self.ref64, self.tol, self.groups, self.hidden = model, fn, inputs, ref64, tol, groups, hidden
+
+    def eager(self):
+        with torch.no_grad():
+            out = self.fn(*self.inputs).clone()
+        torch.cuda.synchronize()
+        return out
+
+    def anchor(self, got):
+        _close(_np(got), self.ref64(), self.tol)
+
+
+def _mlp_groups(hidden, head):
+    g = {}
+    for i, lin in enumerate(hidden):
+        g["hidden%d.weight" % i] = [lin.weight]
+        g["hidden%d.bias" % i] = [lin.bias]
+    g["logits.weight"] = [head.weight]
+    g["logits.bias"] = [head.bias]
+    return g
+
+
+def _deepfm(B):
+    from dir_amd.deepfm import DeepFM
+    from dir_amd import feature_column as fc
+    F, K, V = 26, 16, 1000
+    gen = torch.Generator().manual_seed(B)
+    cats = [fc.categorical_column_with_identity("C%d" % i, V) for i in range(F)]
+    model = DeepFM(linear_feature_columns=cats, dnn_feature_columns=[fc.embedding_column(c, K) for c in cats],
+                   dnn_hidden_units=[256, 128], fm_embedding_size=K).cuda().eval()
+    with torch.no_grad():
+        for w in model.linear_weights:
+            w.copy_(torch.randn(w.shape, generator=gen) * 0.05)
+        model.linear_bias.fill_(0.2)
+        for lin in model.hidden:
+            lin.bias.copy_(torch.randn(lin.bias.shape, generator=gen) * 0.05)
+    ids = torch.randint(0, V, (B, F), generator=gen).cuda()
+
+    def ref64():
+        idn = ids.cpu().numpy()
+        emb = np.concatenate([_np(t)[idn[:, i]] for i, t in enumerate(model.embedding_weights)], 1)
+        fm = np.asarray(R.fm_logit(emb, F, K, _DT[0])).reshape(B, 1)
+        layers = [(_np(l.weight).T, _np(l.bias)) for l in model.hidden]
+        dnn = np.asarray(R.dnn_logit(emb, layers, (_np(model.logits_layer.weight).T, _np(model.logits_layer.bias)))).reshape(B, 1)
+        lin = sum(_np(w).reshape(-1)[idn[:, f]] for f, w in enumerate(model.linear_weights)) + _np(model.linear_bias).reshape(-1)
+        return fm + dnn + lin.reshape(B, 1)
+
+    groups = _mlp_groups(model.hidden, model.logits_layer)
+    groups["embedding"] = [model.embedding_weights[3]]
+    groups["linear"] = [model.linear_weights[5]]
+    return _Case(model, lambda x: model.forward_ids(x, x), [ids], ref64, 1e-5, groups, model.hidden[0].weight)
+
+
+def _dcn(d):
+    from dir_amd.dcn import DeepCrossNetwork
+    from dir_amd import feature_column as fc
+    F, K, V, B = 26, 16, 500, 256
+    nnum = d - F * K
+    gen = torch.Generator().manual_seed(d)
+    cols = [fc.embedding_column(fc.categorical_column_with_identity("C%02d" % i, V), K) for i in range(F)]
+    cols += [fc.numeric_column("I%02d" % i) for i in range(nnum)]
+    model = DeepCrossNetwork(columns=cols, cross_layer_num=3, dnn_hidden_units=[128, 64], batch_norm=(d % 4 != 0)).cuda().eval()
+    assert model.column_num == d
+    with torch.no_grad():
+        model.cross_w.copy_(torch.randn(model.cross_w.shape, generator=gen) * 0.05)
+        model.cross_b.copy_(torch.randn(model.cross_b.shape, generator=gen) * 0.05)
+        for bn in model.bns:
+            bn.moving_mean.copy_(torch.randn(bn.moving_mean.shape, generator=gen) * 0.1)
+            bn.moving_variance.copy_(torch.rand(bn.moving_variance.shape, generator=gen) + 0.5)
+            bn.beta.copy_(torch.randn(bn.beta.shape, generator=gen) * 0.1)
+    ids = torch.randint(0, V, (B, F), generator=gen).cuda()
+    dense = torch.rand((B, max(nnum, 1)), generator=gen).cuda()
+
+    def fn(ids, dense):
+        feats = {"C%02d" % i: ids[:, i] for i in range(F)}
+        feats.update({"I%02d" % i: dense[:, i] for i in range(nnum)})
+        return model(feats)
+
+    def ref64():
+        idn = ids.cpu().numpy()
+        blocks = {c.name: _np(w)[idn[:, int(c.name[1:3])]] for c, w in zip(model.input_layer.emb_cols, model.input_layer.embedding_weights)}
+        blocks.update({"I%02d" % i: _np(dense[:, i:i + 1]) for i in range(nnum)})
+        x0 = np.concatenate([blocks[c.name] for c in model.input_layer.columns], 1)
+        cross = R.cross_network(x0, _np(model.cross_w), _np(model.cross_b))
+        layers = [(_np(l.weight).T, _np(l.bias)) for l in model.hidden]
+        bn = [(_np(b.moving_mean), _np(b.moving_variance), _np(b.beta)) for b in model.bns] if len(model.bns) else None
+        deep = R.deep_architecture(x0, layers, bn)
+        return np.concatenate([cross, deep], -1) @ _np(model.logits_layer.weight).T + _np(model.logits_layer.bias)
+
+    groups = _mlp_groups(model.hidden, model.logits_layer)
+    groups["embedding"] = [model.input_layer.embedding_weights[2]]
+    groups["cross"] = [model.cross_w, model.cross_b]
+    if len(model.bns):
+        groups["bn_moving"] = [model.bns[0].moving_mean, model.bns[0].moving_variance]
+    return _Case(model, fn, [ids, dense], ref64, 1e-5, groups, model.hidden[0].weight)
+
+
+def _din(act):
+    from dir_amd.din import DIN
+    from tests.test_gpu_din_model import _randomize, _mlp_np, _act_params_np
+    rng = np.random.default_rng({"sigmoid": 1, "prelu": 2, "dice": 3}[act])
+    V, K, B, T = 800, 64, 129, 24
+    dnn_act = {"sigmoid": "relu", "prelu": "prelu", "dice": "dice"}[act]
+    model = DIN(item_vocab_size=V, embedding_dim=K, attention_activation=act, dnn_hidden_units=(64, 32), dnn_activation_fn=dnn_act).cuda().eval()
+    _randomize(model, rng)
+    hist = torch.from_numpy(rng.integers(-1, V, size=(B, T)).astype(np.int64)).cuda()
+    hl = torch.from_numpy(rng.integers(0, T + 1, size=B).astype(np.int32)).cuda()
+    cand = torch.from_numpy(rng.integers(0, V, size=B).astype(np.int64)).cuda()
+
+    def fn(hist, hl, cand):
+        return model({"hist": hist, "hist_len": hl, "cand": cand})
+
+    def ref64():
+        a = model.attention
+        return R.din_model_logits(None, _np(a.table), hist.cpu().numpy(), hl.cpu().numpy(), cand.cpu().numpy(),
+                                  (_np(a.W1), _np(a.b1), _np(a.W2), _np(a.b2), _np(a.W3), _np(a.b3)), _mlp_np(model),
+                                  (_np(model.logits_layer.weight), _np(model.logits_layer.bias)), activation=act, act_params=_act_params_np(a),
+                                  dtype=_DT[0])
+
+    a = model.attention
+    groups = _mlp_groups(model.hidden, model.logits_layer)
+    groups["embedding"] = [a.table]
+    groups.update({"unit.W1": [a.W1], "unit.b1": [a.b1], "unit.W2": [a.W2], "unit.b2": [a.b2], "unit.W3": [a.W3], "unit.b3": [a.b3]})
+    if act in ("prelu", "dice"):
+        groups["unit.alpha"] = [a.act1.alpha, a.act2.alpha]
+        groups["mlp.alpha"] = [model.acts[0].alpha]
+    if act == "dice":
+        groups["unit.dice_moving"] = [a.act1.moving_mean, a.act1.moving_variance]
+        groups["mlp.dice_moving"] = [model.acts[0].moving_mean, model.acts[0].moving_variance]
+    return _Case(model, fn, [hist, hl, cand], ref64, 2e-5, groups, model.hidden[0].weight)
+
+
+def _xdeepfm():
+    from dir_amd.xdeepfm import XDeepFM
+    from dir_amd import feature_column as fc
+    from dir_amd import ops
+    B, m, D, V = 130, 26, 16, 500
+    gen = torch.Generator().manual_seed(9)
+    cats = [fc.categorical_column_with_identity("C%d" % i, V) for i in range(m)]
+    model = XDeepFM(linear_feature_columns=cats, dnn_feature_columns=[fc.embedding_column(c, D) for c in cats],
+                    cin_layer_sizes=(64, 32), dnn_hidden_units=(64, 32)).cuda().eval()
+    assert ops.cin_pooled_fused_covers(m, 64, 32, D)                          # the last layer runs the fused pooled kernel (cin_pooled_image)
+    with torch.no_grad():
+        for w in model.linear_weights:
+            w.copy_(torch.randn(w.shape, generator=gen) * 0.05)
+    ids = torch.randint(0, V, (B, m), generator=gen).cuda()
+
+    def fn(ids):
+        return model({"C%d" % i: ids[:, i] for i in range(m)})
+
+    def ref64():
+        idn = ids.cpu().numpy()
+        emb = np.concatenate([_np(t)[idn[:, i]] for i, t in enumerate(model.embedding_weights)], 1)
+        x0 = emb.reshape(B, m, D)
+        xk, pooled = x0, []
+        for W in model.cin_W:
+            xk, p = R.cin_layer(x0, xk, _np(W))
+            pooled.append(p)
+        logit = np.concatenate(pooled, 1) @ _np(model.cin_out.weight).T + _np(model.cin_out.bias)
+        net = emb
+        for l in model.hidden:
+            net = R.relu(net @ _np(l.weight).T + _np(l.bias))
+        logit = logit + net @ _np(model.dnn_out.weight).T + _np(model.dnn_out.bias)
+        return logit + (sum(_np(w).reshape(-1)[idn[:, f]] for f, w in enumerate(model.linear_weights)) + _np(model.linear_bias))[:, None]
+
+    groups = _mlp_groups(model.hidden, model.dnn_out)
+    groups["embedding"] = [model.embedding_weights[4]]
+    groups["linear"] = [model.linear_weights[7]]
+    groups["cin.W0"] = [model.cin_W[0]]
+    groups["cin.W1"] = [model.cin_W[1]]
+    groups["cin_out"] = [model.cin_out.weight]
+    return _Case(model, fn, [ids], ref64, 1e-5, groups, model.hidden[0].weight)
+
+
+def _esmm():
+    from dir_amd.esmm import ESMM
+    from dir_amd import feature_column as fc
+    B = 300
+    gen = torch.Generator().manual_seed(21)
+    cols = [fc.numeric_column("age"), fc.embedding_column(fc.categorical_column_with_identity("item", 500), dimension=8),
+            fc.embedding_column(fc.categorical_column_with_identity("user", 300), dimension=8)]
+    model = ESMM(columns=cols, dnn_hidden_units=[32, 16]).cuda().eval()
+    age = torch.rand(B, generator=gen).cuda()
+    item = torch.randint(0, 500, (B,), generator=gen).cuda()
+    user = torch.randint(0, 300, (B,), generator=gen).cuda()
+
+    def fn(age, item, user):
+        out = model({"age": age, "item": item, "user": user})
+        return torch.cat([out["ctr_logits"], out["ctcvr_logits"]], 1)
+
+    def ref64():
+        def tower(t):
+            il = t.input_layer
+            names = [c.name for c in il.emb_cols]
+            parts = {"age": _np(age)[:, None], "item_embedding": _np(il.embedding_weights[names.index("item_embedding")])[item.cpu().numpy()],
+                     "user_embedding": _np(il.embedding_weights[names.index("user_embedding")])[user.cpu().numpy()]}
+            assert [c.name for c in il.columns] == sorted(parts)
+            net = np.concatenate([parts[k] for k in sorted(parts)], 1)
+            for l in t.hidden:
+                net = R.relu(net @ _np(l.weight).T + _np(l.bias))
+            return net @ _np(t.logits.weight).T + _np(t.logits.bias)
+        ctr, cvr = tower(model.ctr_model), tower(model.cvr_model)
+        p = np.clip(R.sigmoid(ctr) * R.sigmoid(cvr), 1e-7, 1 - 1e-7)
+        return np.concatenate([ctr, np.log(p / (1 - p))], 1)
+
+    groups = _mlp_groups(model.ctr_model.hidden, model.cvr_model.logits)
+    groups["embedding"] = [model.ctr_model.input_layer.embedding_weights[0]]
+    return _Case(model, fn, [age, item, user], ref64, 2e-5, groups, model.ctr_model.hidden[0].weight)
+
+
+BUILDERS = {"deepfm_b256": lambda: _deepfm(256), "deepfm_b2048": lambda: _deepfm(2048), "dcn_d429_bn": lambda: _dcn(429),
+            "dcn_d416_nobn": lambda: _dcn(416), "din_sigmoid": lambda: _din("sigmoid"), "din_prelu": lambda: _din("prelu"),
+            "din_dice": lambda: _din("dice"), "xdeepfm": _xdeepfm, "esmm": _esmm}
+
+_MLP = ["hidden0.weight", "hidden0.bias", "hidden1.weight", "hidden1.bias", "logits.weight", "logits.bias", "embedding"]
+GROUPS = {"deepfm_b256": _MLP + ["linear"], "deepfm_b2048": _MLP + ["linear"], "dcn_d429_bn": _MLP + ["cross", "bn_moving"],
+          "dcn_d416_nobn": _MLP + ["cross"],
+          "din_sigmoid": _MLP + ["unit.W1", "unit.b1", "unit.W2", "unit.b2", "unit.W3", "unit.b3"],
+          "din_prelu": _MLP + ["unit.W1", "unit.b2", "unit.W3", "unit.alpha", "mlp.alpha"],
+          "din_dice": _MLP + ["unit.W1", "unit.b1", "unit.W2", "unit.W3", "unit.alpha", "unit.dice_moving", "mlp.alpha", "mlp.dice_moving"],
+          "xdeepfm": _MLP + ["linear", "cin.W0", "cin.W1", "cin_out"], "esmm": _MLP}
+E1_CASES = [(m, g) for m in BUILDERS for g in GROUPS[m]]
+# groups a frozen capture must read from capture-time cache entries whatever the kernel routing: DeepFM's packed serving rows copy the tables
+FROZEN_CACHED = {"deepfm_b256": {"embedding", "linear"}, "deepfm_b2048": {"embedding", "linear"}}
+
+
+def _update(params):
+    """An in-place update that moves every element (zero-initialised biases and PReLU / Dice alphas included); a variance stays positive."""
+    with torch.no_grad():
+        for p in params:
+            p.mul_(0.75).add_(0.03125)
+
+
+@pytest.fixture
+def graphs():
+    """The graphs a test captures, torn down when it ends -- after a sync, passed or failed: a failed test's frames would otherwise keep its
+    graphs alive until a garbage collection destroys them at an arbitrary point of a later test."""
+    made = []
+    yield made
+    torch.cuda.synchronize()
+    for g in made:
+        g.graph.reset()
+    made.clear()
+
+
+def _graphed(case, mode, graphs):
+    from dir_amd.serving import GraphedForward
+    g = GraphedForward(case.fn, *case.inputs, frozen_weights=(mode == "frozen"))
+    graphs.append(g)
+    return g
+
+
+def _replay(g, case):
+    out = g(*case.inputs).clone()
+    torch.cuda.synchronize()
+    return out
+
+
+def _storage_bytes(obj, out):
+    if isinstance(obj, torch.Tensor):
+        if obj.is_cuda and (obj.dtype.is_floating_point or obj.dtype == torch.uint8):
+            out.append(obj.untyped_storage().nbytes())
+    elif isinstance(obj, (tuple, list)):
+        for o in obj:
+            _storage_bytes(o, out)
+
+
+def _cached_image_sizes(model):
+    """Byte sizes of every cached weight image / packed weight the caches hold now (float and byte images only: never a pointer or an
+    index array -- a poisoned pointer would be dereferenced, not read)."""
+    from dir_amd import ops, dense
+    sizes = []
+    for cache in (ops._DENSE_IMAGES, ops._TOWER_IMAGES, ops._DIN_PACK_IMAGES, ops._CIN_POOLED_IMAGES, dense._PACK_CACHE, dense._BN_CACHE):
+        for entry in list(cache.values()):
+            _storage_bytes([e for e in entry if isinstance(e, torch.Tensor)], sizes)
+    for mod in model.modules():
+        for attr in ("_cross_pad", "_logit_split", "_folded", "_act_cache"):
+            _storage_bytes(getattr(mod, attr, None), sizes)
+        pk = getattr(mod, "_packed", None)
+        if pk is not None:
+            sizes.append(pk.arena.untyped_storage().nbytes())
+    return sizes
+
+
+def _poison(sizes, copies=3):
+    """NaN-filled (0xFF bytes) tensors of the given byte sizes, on the current stream: the caching allocator hands the blocks the evicted
+    images left back to them.  Kept small: a few copies of each size."""
+    keep = []
+    for n in sizes:
+        for _ in range(copies):
+            keep.append(torch.full((n,), 255, dtype=torch.uint8, device="cuda"))
+    torch.cuda.synchronize()
+    return keep
+
+
+def _overflow_image_caches():
+    """Push enough distinct dummy weights through dense_bf3_image / tower_image to pass their .clear() limit (256 entries)."""
+    from dir_amd import ops
+    dummies = [torch.full((16, 16), 0.5, device="cuda") for _ in range(300)]
+    for w in dummies:
+        ops.dense_bf3_image(w)
+        ops.tower_image(w)
+    torch.cuda.synchronize()
+    assert len(ops._DENSE_IMAGES) < 300 and len(ops._TOWER_IMAGES) < 300
+    return dummies
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name", list(BUILDERS))
+def test_e0_replay_equals_eager(built_lib, graphs, name, mode):
+    case = BUILDERS[name]()
+    ref = case.eager()
+    case.anchor(ref)
+    g = _graphed(case, mode, graphs)
+    assert torch.equal(_replay(g, case), ref)
+    assert torch.equal(_replay(g, case), ref)                                 # a second replay: the same bits
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name,group", E1_CASES)
+def test_e1_in_place_update(built_lib, graphs, name, group, mode):
+    """Default capture: the replay follows the update bit for bit.  Frozen: the replay computes from ONE consistent set of weights, bit for
+    bit -- capture time's where the graph took a cache entry (always for FROZEN_CACHED), the updated one where a kernel reads the parameter
+    itself; never a mixture, never freed memory."""
+    case = BUILDERS[name]()
+    ref0 = case.eager()
+    case.anchor(ref0)
+    g = _graphed(case, mode, graphs)
+    assert torch.equal(_replay(g, case), ref0)
+    _update(case.groups[group])
+    got = _replay(g, case)                                                    # before any eager call at the new weights
+    new = case.eager()
+    assert not torch.equal(new, ref0), "the update does not reach the logits"
+    case.anchor(new)
+    if mode == "default":
+        assert torch.equal(got, new), "default capture does not follow the update of %s" % group
+    else:
+        assert torch.equal(got, ref0) or (group not in FROZEN_CACHED.get(name, ()) and torch.equal(got, new)), \
+            "frozen capture: neither the capture-time nor the updated forward (%s)" % group
+    assert torch.equal(_replay(g, case), got)                                 # after the eager call replaced the cache entries
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("evict", ["eager_after_update", "invalidate_caches", "cache_limit"])
+@pytest.mark.parametrize("name", list(BUILDERS))
+def test_e2_eviction_then_poison(built_lib, graphs, name, evict, mode):
+    """The cache entries a graph reads are evicted and their blocks handed to NaN-filled tensors: the replay must not see them."""
+    from dir_amd import ops
+    case = BUILDERS[name]()
+    ref0 = case.eager()
+    g = _graphed(case, mode, graphs)
+    assert torch.equal(_replay(g, case), ref0)
+    sizes = _cached_image_sizes(case.model)
+    assert sizes
+    dummies, cur = None, ref0
+    if evict == "eager_after_update":
+        _update(case.groups["hidden0.weight"])
+        cur = case.eager()
+    elif evict == "invalidate_caches":
+        ops.invalidate_caches()
+    else:
+        dummies = _overflow_image_caches()
+    poison = _poison(sizes)
+    got = _replay(g, case)
+    del poison, dummies
+    assert bool(torch.isfinite(got).all()), "the replay read a freed (poisoned) block"
+    if mode == "default":
+        cur = case.eager()
+        assert torch.equal(got, cur)
+        case.anchor(cur)
+    else:                                     # (a layer whose weight a kernel reads itself follows the update: see test_e1_in_place_update)
+        assert torch.equal(got, ref0) or torch.equal(got, cur)
+
+
+@pytest.mark.parametrize("scale", [2.0 ** 20, 2.0 ** -20], ids=["x2^20", "x2^-20"])
+@pytest.mark.parametrize("name", list(BUILDERS))
+def test_e3_hidden_weight_magnitude(built_lib, graphs, name, scale):
+    """A default capture, then one hidden weight scaled in place far outside the fp16 window: the replay stays finite and within the model's
+    tolerance of float64 at the new weights (a split picked from the capture-time magnitude would overflow or lose the small values).  At
+    2^20 the unscaled biases make the model ill-conditioned for fp32 arithmetic itself: the bar is then the model's tolerance or four
+    times the float32 restatement's own distance from float64, whichever is larger."""
+    case = BUILDERS[name]()
+    g = _graphed(case, "default", graphs)
+    with torch.no_grad():
+        case.hidden.mul_(scale)
+    got = _replay(g, case)
+    assert bool(torch.isfinite(got).all())
+    ref = case.ref64()
+    _DT[0] = np.float32
+    try:
+        ref32 = np.asarray(case.ref64(), np.float64)
+    finally:
+        _DT[0] = np.float64
+    err32 = float((np.abs(ref32 - ref) / (1 + np.abs(ref))).max())
+    _close(_np(got), ref, max(case.tol, 4 * err32))
+    assert torch.equal(got, case.eager())

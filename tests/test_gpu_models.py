@@ -1059,6 +1059,45 @@ def test_esmm_head_entry_matches_the_reference_op_sequence(built_lib):
     err_lib = float(((lib_form.double() - ref).abs() / (1 + ref.abs())).max())
     assert err <= max(2e-6, 2 * err_lib), (err, err_lib)
     assert built_lib.dir_esmm_head_f32(None, None, 8, 1e-7, None, None) != 0 and b"null pointer" in built_lib.dir_last_error()
+    # non-finite logits in either input: where float64 (torch.clamp keeps a NaN) is NaN the kernel returns NaN -- a diverged model must not
+    # look healthy at serving time --, where it is finite the kernel matches it as above
+    sp = torch.tensor([float("nan"), float("inf"), float("-inf"), 0.0, 3.0, -40.0, 40.0])
+    s_ctr, s_cvr = sp.repeat_interleave(len(sp)).reshape(-1, 1), sp.repeat(len(sp)).reshape(-1, 1)
+    got = ops.esmm_head(s_ctr.cuda(), s_cvr.cuda(), 1e-7).cpu()
+    p = (torch.sigmoid(s_ctr.double()) * torch.sigmoid(s_cvr.double())).clamp(1e-7, 1 - 1e-7)
+    ref = torch.log(p / (1 - p))
+    p32 = (torch.sigmoid(s_ctr) * torch.sigmoid(s_cvr)).clamp(1e-7, 1 - 1e-7)
+    lib_form = torch.log(p32 / (1 - p32))
+    nan = torch.isnan(ref)
+    assert int(nan.sum()) == 2 * len(sp) - 1
+    assert torch.equal(torch.isnan(got), nan), torch.cat([s_ctr, s_cvr, got], 1)[torch.isnan(got) != nan]
+    fin = ~nan
+    assert bool(torch.isfinite(got[fin]).all())
+    err = float(((got[fin].double() - ref[fin]).abs() / (1 + ref[fin].abs())).max())
+    err_lib = float(((lib_form[fin].double() - ref[fin]).abs() / (1 + ref[fin].abs())).max())
+    assert err <= max(2e-6, 2 * err_lib), (err, err_lib)
+
+
+def test_esmm_inference_and_training_forms_agree_on_non_finite_rows(built_lib):
+    """A NaN planted in one embedding row that a few samples look up: the inference forward (dir_esmm_head_f32) and the grad-enabled
+    forward (the library's clamp) mark the same rows non-finite, in every output."""
+    from dir_amd.esmm import ESMM
+    from dir_amd import feature_column as fc
+    B = 300
+    gen = torch.Generator().manual_seed(5)
+    cols = [fc.numeric_column("age"), fc.embedding_column(fc.categorical_column_with_identity("item", 500), dimension=8)]
+    model = ESMM(columns=cols, dnn_hidden_units=[32, 16]).cuda().eval()
+    item = torch.randint(0, 500, (B,), generator=gen)
+    item[[3, 77, 150, 299]] = 123
+    feats = {"age": torch.rand(B, generator=gen).cuda(), "item": item.cuda()}
+    with torch.no_grad():
+        model.ctr_model.input_layer.embedding_weights[0][123, 2] = float("nan")
+        inf = model(feats)
+    train = model(feats)
+    bad = (item == 123).reshape(-1, 1)
+    for k in ("ctr_logits", "ctcvr_logits"):
+        assert torch.equal(~torch.isfinite(inf[k]).cpu(), bad), k
+        assert torch.equal(~torch.isfinite(train[k].detach()).cpu(), bad), k
 
 
 def test_graphed_forward_with_frozen_weights_takes_the_cached_images(built_lib):

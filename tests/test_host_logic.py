@@ -583,3 +583,81 @@ def test_round5_routing_rules():
     ops.invalidate_caches()
     assert ts.absmax(every=32) == 8.0
     assert ops.din_arith(w, (), arith="bf16x3") == ops.DIN_ARITHS["bf16x3"]
+
+
+def test_graphed_forward_recaptures_when_a_guard_moved(monkeypatch):
+    """serving.GraphedForward's host logic with the capture mocked: what a cache serves during the capture is kept alive for the graph
+    (ops.held), a default capture is taken again once a guarded tensor was modified in place or ops.invalidate_caches() ran -- and only
+    then --, a frozen_weights capture never is, and no hold stays open after a capture."""
+    import contextlib
+    from dir_amd import ops
+    from dir_amd.serving import GraphedForward
+    state = {"capturing": False}
+
+    class FakeGraph:
+        def __init__(self):
+            self.replays = 0
+
+        def replay(self):
+            self.replays += 1
+
+    class FakeStream:
+        def wait_stream(self, s):
+            pass
+
+        def synchronize(self):
+            pass
+
+    @contextlib.contextmanager
+    def fake_graph(graph, pool=None, stream=None):
+        state["capturing"] = True
+        try:
+            yield
+        finally:
+            state["capturing"] = False
+
+    monkeypatch.setattr(torch.cuda, "Stream", lambda *a, **k: FakeStream())
+    monkeypatch.setattr(torch.cuda, "stream", lambda s: contextlib.nullcontext())
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a: FakeStream())
+    monkeypatch.setattr(torch.cuda, "CUDAGraph", FakeGraph)
+    monkeypatch.setattr(torch.cuda, "graph", fake_graph)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: state["capturing"])
+    w, other = torch.nn.Parameter(torch.ones(4)), torch.nn.Parameter(torch.ones(4))
+    served = []
+
+    def fn(x):
+        img = w.detach() * 2                                   # a "cache entry" built from w
+        served.append(img)
+        return x + ops.held(img, guards=[w]) + other.detach()
+
+    x = torch.zeros(4)
+    g = GraphedForward(fn, x, warmup=2)
+    assert g.captures == 1 and g.hold.guarded and any(k is served[-1] for k in g.hold.keep)
+    assert ops._HOLDS == [] and not ops._FROZEN_WEIGHTS[0]
+    assert len(g.hold.keep) == 1                               # the warm-up calls ran outside the capture: nothing held for them
+    g(x)
+    g(x)
+    assert g.captures == 1 and g.graph.replays == 2
+    with torch.no_grad():
+        other.add_(1.0)                                        # not a guard: a default capture reads it live
+    g(x)
+    assert g.captures == 1
+    with torch.no_grad():
+        w.mul_(3.0)
+    g(x)
+    assert g.captures == 2 and g.graph.replays == 1            # captured again, then replayed
+    g(x)
+    assert g.captures == 2
+    ops.invalidate_caches()
+    g(x)
+    assert g.captures == 3
+    assert ops.held("outside", guards=[w]) == "outside" and g.hold.keep == [served[-1]]      # outside a capture nothing is recorded
+
+    gf = GraphedForward(fn, x, frozen_weights=True)
+    assert gf.captures == 1 and isinstance(gf.hold, ops.frozen_weights) and any(k is served[-1] for k in gf.hold.keep)
+    assert not ops._FROZEN_WEIGHTS[0] and ops._HOLDS == []
+    with torch.no_grad():
+        w.mul_(3.0)
+    ops.invalidate_caches()
+    gf(x)
+    assert gf.captures == 1 and gf.graph.replays == 1         # frozen: replays keep the capture-time entries, never re-captured
