@@ -209,6 +209,11 @@ SIGNATURES = {
     "dir_shard_slab_stat": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp]),
     "dir_gather_slabs_f32": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_i32, c_vp, c_vp]),
     "dir_gather_packed_f32": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp, c_vp]),
+    "dir_shard_bags_workspace_bytes": (c_i64, [c_i32]),
+    "dir_shard_bags_bucket": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i64,
+                                      c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "dir_shard_bags_pool_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, ctypes.c_float, c_i32, c_vp, c_vp, c_vp]),
+    "dir_shard_bags_combine_f32": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp]),
 }
 
 DIR_OK, DIR_E_BADARG, DIR_E_RANGE, DIR_E_HIP, DIR_E_UNSUPPORTED = 0, -1, -2, -3, -4

@@ -9,6 +9,7 @@
 // Fingerprint64 is farmhashna::Hash64 of FarmHash 1.1, restated from the public algorithm; checked
 // against published known answers in tests/ (lengths <= 16; longer branches have no published vector).
 #include "common.hpp"
+#include "shard_route.hpp"
 #include <type_traits>
 
 namespace dir {
@@ -251,18 +252,6 @@ __global__ void bucketize_k(const float* __restrict__ x, int64_t n, const float*
     }
 }
 
-__host__ __device__ inline void div_owner(int64_t id, int64_t q, int64_t r, int64_t thr, int* owner, int64_t* local) {
-    if (id < thr) {
-        const int64_t o = id / (q + 1);
-        *owner = (int)o;
-        *local = id - o * (q + 1);
-    } else {
-        const int64_t o = r + (q > 0 ? (id - thr) / q : 0);
-        *owner = (int)o;
-        *local = id - (thr + (o - r) * q);
-    }
-}
-
 __global__ void shard_route_k(const int64_t* __restrict__ ids, int64_t n, const int64_t* __restrict__ vocab, int F,
                               int P, int32_t* __restrict__ owner, int64_t* __restrict__ local) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -321,40 +310,6 @@ __global__ __launch_bounds__(256) void gather_rows_k(const float* const* __restr
 // ------------------------------------------------------------------------------------------------
 constexpr int BK_EPB = 4096;   // elements per workgroup
 constexpr int BK_MAXF = 256;   // fields whose 'div' constants are cached in LDS (more: read from global)
-
-// per-field 'div' constants q = V / Pf, thr = (V % Pf) * (q + 1), r = V % Pf, staged once per workgroup.  Pf = the number of
-// row slices of the table (parts[f]; P when parts == NULL) and first = the rank holding slice 0 (slice j lives on rank
-// (first + j) % P): the reference's min_max_variable_partitioner cuts a table into <= P slices of >= min_slice_size bytes
-// (models/DeepFM/deepFM.py:163-167) and [TF-upstream] replica_device_setter deals the slices round-robin over the ps tasks.
-struct FieldDiv { int64_t q, thr, V; int r; int small; int first; };
-
-__device__ __forceinline__ FieldDiv make_fielddiv(int64_t V, int Pf, int first = 0) {
-    FieldDiv d;
-    d.q = V / Pf;
-    d.r = (int)(V % Pf);
-    d.thr = (int64_t)d.r * (d.q + 1);
-    d.V = V;
-    d.small = V < (int64_t)0x7fffffff ? 1 : 0;   // every quotient fits 32-bit unsigned arithmetic
-    d.first = first;
-    return d;
-}
-
-__device__ __forceinline__ void route_fd(int64_t id, const FieldDiv& d, int* owner, int64_t* local) {
-    if (d.small) {   // 32-bit divisions (ids < vocab < 2^31): ~4x cheaper than the 64-bit software division
-        const uint32_t u = (uint32_t)id, q = (uint32_t)d.q, thr = (uint32_t)d.thr;
-        if (u < thr) {
-            const uint32_t o = u / (q + 1);
-            *owner = (int)o;
-            *local = (int64_t)(u - o * (q + 1));
-        } else {
-            const uint32_t o = (uint32_t)d.r + (q > 0 ? (u - thr) / q : 0u);
-            *owner = (int)o;
-            *local = (int64_t)(u - (thr + (o - (uint32_t)d.r) * q));
-        }
-    } else {
-        div_owner(id, d.q, d.r, d.thr, owner, local);
-    }
-}
 
 // element e of workgroup `wg`: its id, slot f = i % F and owner / local row; pruned ids spread as i % P
 #define BK_ROUTE_ELEMENT()                                                        \

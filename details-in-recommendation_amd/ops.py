@@ -2413,6 +2413,42 @@ def gather_packed(tables, payload, out=None):
     return out
 
 
+def shard_bags_bucket(values, offsets, weights, B, sb, sf, vocab_dev, P, slot_comb, comb, flags, cap_e, cap_b, slabs, pos, mask, denom,
+                      workspace, parts=None, first=None, stat=None):
+    """Requester side of the row-sharded multi-hot bags (include/dir_hip.h: dir_shard_bags_bucket) into caller-owned buffers: slabs
+    [P*(cap_e+1)*2] int64, pos [B*F*P] int32, mask [B*F] int64, denom [B*F] fp32, workspace (zeroed once) -- no host read."""
+    _dev(values, torch.int64, "values")
+    _dev(offsets, torch.int64, "offsets")
+    if weights is not None:
+        _dev(weights, torch.float32, "weights")
+    if not (values.is_contiguous() and offsets.is_contiguous() and (weights is None or weights.is_contiguous())):
+        raise ValueError("shard_bags_bucket: values / offsets / weights must be contiguous")
+    _lib.check(_lib.load().dir_shard_bags_bucket(_ptr(values), _ptr(offsets), _ptr(weights), values.numel(), sb, sf, B, _ptr(vocab_dev),
+                                                 _ptr(parts), _ptr(first), vocab_dev.numel(), P, _ptr(slot_comb), comb, flags, cap_e, cap_b,
+                                                 _ptr(slabs), _ptr(pos), _ptr(mask), _ptr(denom), _ptr(stat), _ptr(workspace), _stream()))
+
+
+def shard_bags_pool(tables, recv, P, cap_e, cap_b, slot_mn, mn, out, stat=None):
+    """Owner side of the row-sharded bags (dir_shard_bags_pool_f32): recv = the P received slabs -> out [P*cap_b, K] partial rows;
+    stat int64 [3] (optional) = {overflow, largest entry demand, largest pair demand} read off the received headers."""
+    ts = _as_tableset(tables)
+    _dev(recv, torch.int64, "recv")
+    _dev(out, torch.float32, "out")
+    _lib.check(_lib.load().dir_shard_bags_pool_f32(_ptr(ts.ptrs), _ptr(ts.vocab_dev), ts.F, ts.K, _ptr(recv), P, cap_e, cap_b, _ptr(slot_mn),
+                                                   mn, ts.gather_flags(), _ptr(out), _ptr(stat), _stream()))
+    return out
+
+
+def shard_bags_combine(back, P, pos, mask, denom, B, F, slot_comb, comb, out, fm=None):
+    """Requester side after the row exchange (dir_shard_bags_combine_f32): back [P*cap_b, K] partial rows -> out [B, F*K] (+ the FM
+    logit into fm [B, 1])."""
+    _dev(back, torch.float32, "back")
+    _dev(out, torch.float32, "out")
+    _lib.check(_lib.load().dir_shard_bags_combine_f32(_ptr(back), back.shape[1], P, _ptr(pos), _ptr(mask), _ptr(denom), B, F, _ptr(slot_comb),
+                                                      comb, _ptr(out), out.stride(0), _ptr(fm), _stream()))
+    return out
+
+
 # ---- backward of the interaction ops (SURVEY 8f rank 2) --------------------------------------------------
 def fm_logit_backward(emb, g, F, K, add_in=None, out=None):
     """d fm_logit / d emb: demb[b,f,:] = g[b] * (sum_f' e[b,f',:] - e[b,f,:]) (+ add_in).  g: [B] or [B,1]."""

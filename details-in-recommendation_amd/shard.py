@@ -153,6 +153,23 @@ class HipBackend:
         else:
             ops.embedding_bag(ts, inv2d, out=out)
 
+    # ---- multi-hot bags, pooled on the owner (lookup_bags) ------------------------------------------------
+    def new_bags_workspace(self, device):
+        return torch.zeros(256, dtype=torch.int32, device=device)      # dir_shard_bags_workspace_bytes: 1024 bytes
+
+    def bags_bucket(self, values, offsets, weights, B, sb, sf, combiner, flags, cap_e, cap_b, slabs, pos, mask, denom, workspace):
+        slot_comb, comb = ops.slot_combiners(self.ts, combiner)
+        ops.shard_bags_bucket(values, offsets, weights, B, sb, sf, self.vocab_dev, self.P, slot_comb, comb, flags, cap_e, cap_b, slabs, pos,
+                              mask, denom, workspace, parts=self.parts_dev, first=self.first_dev)
+
+    def bags_pool(self, recv, cap_e, cap_b, max_norm, rows, stat=None):
+        slot_mn, mn = ops.slot_max_norms(self.ts, max_norm)
+        ops.shard_bags_pool(self.ts, recv, self.P, cap_e, cap_b, slot_mn, mn, rows, stat=stat)
+
+    def bags_combine(self, back, cap_b, pos, mask, denom, B, combiner, out, fm=None):
+        slot_comb, comb = ops.slot_combiners(self.ts, combiner)
+        ops.shard_bags_combine(back, self.P, pos, mask, denom, B, self.ts.F, slot_comb, comb, out, fm=fm)
+
 
 _ROWS_TS = {}
 
@@ -203,6 +220,27 @@ class _Plan:
         self.stat = torch.zeros(2, **i64)                 # ... over all chunks and ranks, read off the received slab headers
         self.host = torch.empty(2, dtype=torch.int64, pin_memory=dev.type == "cuda")
         self.fin = None                                   # events behind the last enqueued lookup's final kernels (one per side stream)
+
+
+class _BagPlan:
+    """Persistent buffers of lookup_bags for one (local batch size, entry capacity, pair capacity): stable addresses, so that a lookup can
+    be captured in a HIP graph after one eager call.  Only the two capacities have to agree across the ranks."""
+
+    def __init__(self, st, B, cap_e, cap_b):
+        dev, P, F, K = st.device, st.P, st.F, st.K
+        self.cap_e, self.cap_b = cap_e, cap_b
+        i64 = dict(dtype=torch.int64, device=dev)
+        alias = not st._collective()                     # one rank, no collectives: receive buffers ARE the send buffers
+        self.send = torch.empty(P * (cap_e + 1) * 2, **i64)         # P slabs of (cap_e + 1) 16-byte records
+        self.recv = self.send if alias else torch.empty_like(self.send)
+        nb = B * F
+        self.pos = torch.empty(max(1, nb * P), dtype=torch.int32, device=dev)
+        self.mask = torch.empty(max(1, nb), **i64)
+        self.denom = torch.empty(max(1, nb), dtype=torch.float32, device=dev)
+        self.rows = torch.empty((P * cap_b, K), dtype=torch.float32, device=dev)
+        self.back = self.rows if alias else torch.empty_like(self.rows)
+        self.ws = st.backend.new_bags_workspace(dev)
+        self.stat = torch.zeros(3, **i64)                 # [overflow, largest entry demand, largest pair demand], off the received headers
 
 
 class _Lookup:
@@ -324,6 +362,10 @@ class ShardedTables:
         self.stats = {"lookups": 0, "fallbacks": 0, "cap": None}
         self._updates = 0             # owner-side optimiser steps applied so far (the same on every rank: absmax()'s collective decision)
         self._absmax_all = None
+        self._bag_cap = None          # lookup_bags: the agreed (entry, partial-row) slab capacities -- separate from the one-hot ones
+        self._bag_plans = {}
+        self._bag_unchecked = []      # lookup_bags verdicts not read yet (check = lazy / never): (event | None, host words)
+        self._bag_hosts, self._bag_host_i = None, 0
 
     @classmethod
     def from_full(cls, full_tables, group=None, **kw):
@@ -678,8 +720,9 @@ class ShardedTables:
         self._unchecked = keep
 
     def check_overflow(self):
-        """check="lazy"/"never": read the verdicts of the fixed-capacity lookups not checked yet; raises if a slab overflowed (that
-        result was incomplete: repeat it with mode="exact" or a larger slack)."""
+        """check="lazy"/"never": read the verdicts of the fixed-capacity lookups (and lookup_bags calls) not checked yet; raises if a slab
+        overflowed (that result was incomplete: repeat it with mode="exact" or a larger slack; the bag capacities have grown already)."""
+        self._drain_bag_unchecked()
         self._drain_unchecked(block=True)
         return False
 
@@ -830,6 +873,127 @@ class ShardedTables:
 
     def lookup_rows(self, ids):
         return self.lookup_rows_async(ids).result()
+
+    # ---- multi-hot bags, pooled on the owning rank -----------------------------------------------------------
+    def _bag_caps(self, B, nnz):
+        """(entry capacity, partial-row capacity) of the bag slabs.  One rank: slabs that hold the whole batch (nothing can overflow, no
+        verdict to read).  Several: agreed once, at the first lookup_bags (one host MAX over the ranks' defaults); afterwards changed only
+        by verdicts every rank reads identically off the slab headers."""
+        if not self._collective():
+            # entry capacity rounded up to an eighth of its power of two (<= 12.5 % padding): batches of similar nnz share one plan
+            n = max(int(nnz), 16)
+            return _round_up(n, max(16, 1 << max(0, n.bit_length() - 4))), _round_up(max(B * self.F, 16), 16)
+        if self._bag_cap is None:
+            ce = self._default_cap(max(1, nnz))
+            cb = min(ce, _round_up(max(B * self.F, 16), 16))           # every partial row has at least one entry
+            t = torch.tensor([ce, cb], dtype=torch.int64)
+            if dist.get_backend(self.group) == "gloo":
+                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+            else:
+                td = t.to(self.device)
+                dist.all_reduce(td, op=dist.ReduceOp.MAX, group=self.group)
+                t = td.cpu()
+            self._bag_cap = (int(t[0]), int(t[1]))
+        return self._bag_cap
+
+    def _bag_plan(self, B, cap_e, cap_b):
+        key = (B, cap_e, cap_b)
+        plan = self._bag_plans.get(key)
+        if plan is None:
+            if len(self._bag_plans) >= 4:
+                self._bag_plans.clear()
+            plan = self._bag_plans[key] = _BagPlan(self, B, cap_e, cap_b)
+        # a graph captured now writes these buffers through raw pointers: the capture's hold keeps the plan alive past the clear() above
+        return ops.held(plan)
+
+    def _bag_host(self):
+        """A pinned 3-word buffer for one lookup_bags verdict: a ring of three, so that the verdicts still unread (at most two) keep theirs."""
+        if self._bag_hosts is None:
+            self._bag_hosts = [torch.empty(3, dtype=torch.int64, pin_memory=True) for _ in range(3)]
+        self._bag_host_i = (self._bag_host_i + 1) % 3
+        return self._bag_hosts[self._bag_host_i]
+
+    def _bag_verdict(self, pend):
+        """Read one lookup_bags verdict (the same words on every rank) and grow the capacities after an overflow.  -> overflowed?"""
+        done, host = pend
+        if done is not None:
+            done.synchronize()
+        over, de, db = (int(v) for v in host.tolist())
+        if over:
+            self.stats["bag_fallbacks"] = self.stats.get("bag_fallbacks", 0) + 1
+            ce, cb = self._bag_cap
+            self._bag_cap = (max(ce, _round_up(de * 1.25 + 64, 16)), max(cb, _round_up(db * 1.25 + 64, 16)))
+        return over
+
+    def _drain_bag_unchecked(self):
+        pend, self._bag_unchecked = self._bag_unchecked, []
+        over = [self._bag_verdict(p) for p in pend]
+        if any(over):
+            raise RuntimeError("ShardedTables: a slab of an earlier lookup_bags overflowed: that result was incomplete (the capacities have "
+                               "grown to %s)" % (self._bag_cap,))
+
+    def lookup_bags(self, values, offsets, weights=None, combiner="mean", max_norm=None, field_major=False, flags=0, want_fm=False):
+        """Multi-hot bags over the row-sharded tables, pooled on the owning rank: the sharded form of ops.embedding_bag(values, offsets,
+        weights, combiner, field_major, flags, max_norm=) (values [nnz] global row ids, offsets [B_local*F+1], bag (b, f) = b*F+f, or f*B+b
+        when field_major; weights [nnz] or None; combiner / max_norm: one value or one per slot).  -> (emb [B_local, F*K], fm [B_local, 1]
+        or None).
+
+        Every owner pools the entries of a bag it holds (max_norm clip, w * row summed in entry order) and returns ONE partial row per
+        (bag, owner); the requester adds a bag's partials in ascending owner order and applies the combiner.  A bag of L entries brings
+        back at most min(L, P) rows instead of L.  With one owner per bag -- world size 1, or all of a bag's live entries on one rank --
+        the result is ops.embedding_bag's bit for bit; otherwise the partial sums are added in a different order (fp32 rounding only).
+        Both exchanges are equal-split all-to-alls; at world size 1 there are none, nothing can overflow and the lookup can be captured
+        in a HIP graph after one eager call.  With several ranks the overflow verdict is read off the received headers (the same words on
+        every rank) and the capacities grow to the demands the headers carry; the constructor's `check` decides when: "eager" reads it
+        after the whole lookup has been enqueued and repeats an overflowing lookup; "lazy" reads it after the NEXT lookup_bags has been
+        enqueued (no host wait on a lookup's own work; an overflow raises there, the result it reports on was incomplete); "never" leaves
+        it to check_overflow().  Every rank must call it the same number of times (SPMD)."""
+        F, K, be = self.F, self.K, self.backend
+        if values.dim() != 1 or offsets.dim() != 1 or (offsets.numel() - 1) % F:
+            raise ValueError("lookup_bags: values [nnz], offsets [B*F+1] with F=%d" % F)
+        B = (offsets.numel() - 1) // F
+        if weights is not None and weights.numel() != values.numel():
+            raise ValueError("lookup_bags: weights must be [nnz]")
+        sb, sf = (1, B) if field_major else (F, 1)
+        nnz = values.numel()
+        self.stats["bag_lookups"] = self.stats.get("bag_lookups", 0) + 1
+        dev = values.device
+        while True:
+            cap_e, cap_b = self._bag_caps(B, nnz)
+            plan = self._bag_plan(B, cap_e, cap_b)
+            self.stats["bag_cap"] = (cap_e, cap_b)
+            be.bags_bucket(values, offsets, weights, B, sb, sf, combiner, flags, cap_e, cap_b, plan.send, plan.pos, plan.mask, plan.denom,
+                           plan.ws)
+            w = self._a2a_equal(plan.recv, plan.send)
+            if w is not None:
+                w.wait()
+            check = self._collective()
+            be.bags_pool(plan.recv, cap_e, cap_b, max_norm, plan.rows, stat=plan.stat if check else None)
+            pend = None
+            if check and dev.type == "cuda":
+                host = self._bag_host()
+                host.copy_(plan.stat, non_blocking=True)
+                pend = (torch.cuda.current_stream(dev).record_event(), host)
+            elif check:
+                pend = (None, plan.stat.clone())
+            w = self._a2a_equal(plan.back, plan.rows)
+            if w is not None:
+                w.wait()
+            out = torch.empty((B, F * K), dtype=torch.float32, device=dev)
+            fm = torch.empty((B, 1), dtype=torch.float32, device=dev) if want_fm else None
+            be.bags_combine(plan.back, cap_b, plan.pos, plan.mask, plan.denom, B, combiner, out, fm)
+            if not check:
+                return out, fm
+            if self.check != "eager":
+                prev, self._bag_unchecked = self._bag_unchecked, (self._bag_unchecked + [pend])[-2:]
+                if self.check == "lazy":          # the earlier lookups' verdicts: their header scans finished long ago
+                    self._bag_unchecked = [pend]
+                    if any([self._bag_verdict(p) for p in prev]):
+                        raise RuntimeError("ShardedTables: a slab of the previous lookup_bags overflowed: that result was incomplete "
+                                           "(the capacities have grown to %s)" % (self._bag_cap,))
+                return out, fm
+            if not self._bag_verdict(pend):       # the verdict, read after the whole lookup has been enqueued
+                return out, fm
 
     def lookup(self, ids, want_fm=False, out=None, fm=None):
         """ids [B_local, F] int64 (global row ids; < 0 or >= vocab_f -> zeros) -> emb [B_local, F*K] fp32
@@ -1006,5 +1170,21 @@ class ShardedDeepFMTrainer:
                 return out
             emb, fm = self.tables.lookup(ids, want_fm=True)
             return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(amax))      # the SHARDED tables' magnitude, not the model's own
+        finally:
+            m.train(was_training)
+
+    @torch.no_grad()
+    def predict_bags(self, values, offsets, weights=None, field_major=False):
+        """Inference logits [B_local, 1] of the same FM + DNN model over multi-hot bags of the row-sharded tables (a history column of the
+        reference's DeepFM, deepFM.py:53,77,84): lookup_bags(want_fm=True) with every column's combiner and max_norm, then the tower with
+        the FM term added -- what predict() does for one-hot ids."""
+        m = self.model
+        was_training = m.training
+        m.eval()
+        try:
+            comb = [c.combiner for c in m.dnn_feature_columns]
+            emb, fm = self.tables.lookup_bags(values, offsets, weights, combiner=comb, max_norm=m._max_norm(), field_major=field_major,
+                                              want_fm=True)
+            return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(self.tables.absmax()))
         finally:
             m.train(was_training)

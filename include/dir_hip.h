@@ -478,6 +478,41 @@ int dir_gather_slabs_f32(const float* const* tables, int F, int K, int64_t* recv
 int dir_gather_packed_f32(const float* const* tables, int F, int K, const int64_t* payload, int64_t n,
                           int flags /* DIR_GATHER_STREAM_ROWS */, float* out, dir_stream_t stream);
 
+/* Multi-hot bags over the row-sharded tables, pooled on the owning rank (ShardedTables.lookup_bags): the sharded form of
+ * dir_embedding_bag_ex2_f32's CSR path.  Three steps around two equal-split all-to-alls:
+ *
+ * dir_shard_bags_bucket (requester): ids [nnz], offsets [B*F+1], weights [nnz] or NULL, bag (b, f) at offsets[b*stride_b + f*stride_f]
+ *   (sample-major: (F, 1); field-major: (1, B)).  Entries are dropped as the bag kernel drops them (id < 0, id >= vocab[f], weight <= 0
+ *   under DIR_BAG_PRUNE_NONPOSITIVE_WEIGHTS) and routed with the 'div' rule of their slot (parts / first as dir_shard_bucket_cap).
+ *   slabs [P * (cap_e + 1) * 2] int64 = P slabs of (cap_e + 1) 16-byte records:
+ *     record 0  header: u32 entries (<= cap_e), u32 partial rows (<= cap_b), u32 u32 = the SENDER's largest per-owner demand of
+ *               entries and of partial rows (may exceed the capacities)
+ *     record j  entry : int64 local_row * F + slot, fp32 weight (1 without weights), int32 return position in [0, cap_b) (-1: none)
+ *   Every (bag, owner) pair gets ONE return position and a contiguous run of entries, in entry order.  Per logical bag g = b*F + f:
+ *   mask[g] int64 = the owners holding a partial (bit o), pos[g*P + o] int32 = row o*cap_b + q of that partial in the returned
+ *   [P*cap_b, K] buffer (-1: did not fit), denom[g] fp32 = the combiner's divisor (sum w for mean, sqrt(sum w^2) for sqrtn, the count
+ *   without weights; summed in entry order as the bag kernel does).  stat (optional) int64 [3] = {some demand > its capacity, largest
+ *   entry demand, largest pair demand} of THIS sender.  workspace: dir_shard_bags_workspace_bytes(P) bytes, ZERO before the first call
+ *   (left zero).  Needs P <= 64, nnz, cap_e and P * cap_b < 2^31.
+ * dir_shard_bags_pool_f32 (owner): recv = the P slabs as received; for every run: rows of the local tables (local_vocab [F] = their row
+ *   counts; records outside them contribute nothing), clipped to the slot's max_norm (slot_max_norm [F] or NULL + max_norm, as the bag
+ *   kernel), acc += w * row in entry order -> out[(s*cap_b + q), :].  Rows nobody asked for are left untouched.  stat (optional) int64
+ *   [3] = the verdict read off the RECEIVED headers: the same numbers on every rank.  flags: DIR_GATHER_STREAM_ROWS.
+ * dir_shard_bags_combine_f32 (requester): back = the [P*cap_b, K] partial rows as received -> out[b, f*K..] = the bag's partials in
+ *   ascending owner order, then / denom for mean and sqrtn (slot_combiner / combiner as dir_embedding_bag_ex2_f32).  fm [B] or NULL:
+ *   the FM second-order logit of out, bit for bit dir_fm_second_order_f32's.
+ * With one owner per bag (world size 1) out is dir_embedding_bag_ex2_f32's bit for bit. */
+int64_t dir_shard_bags_workspace_bytes(int P);
+int dir_shard_bags_bucket(const int64_t* ids, const int64_t* offsets, const float* weights, int64_t nnz, int64_t stride_b, int64_t stride_f,
+                          int64_t B, const int64_t* vocab, const int32_t* parts, const int32_t* first, int F, int P,
+                          const int32_t* slot_combiner, int combiner, int flags, int64_t cap_e, int64_t cap_b, int64_t* slabs, int32_t* pos,
+                          int64_t* mask, float* denom, int64_t* stat, void* workspace, dir_stream_t stream);
+int dir_shard_bags_pool_f32(const float* const* tables, const int64_t* local_vocab, int F, int K, const int64_t* recv, int P, int64_t cap_e,
+                            int64_t cap_b, const float* slot_max_norm, float max_norm, int flags, float* out, int64_t* stat,
+                            dir_stream_t stream);
+int dir_shard_bags_combine_f32(const float* back, int K, int P, const int32_t* pos, const int64_t* mask, const float* denom, int64_t B, int F,
+                               const int32_t* slot_combiner, int combiner, float* out, int64_t out_ld, float* fm, dir_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * A5 / A9  hidden layers of the DNN towers: Y[M, N] = act(X[M, Kd] . Wt[N, Kd]^T + bias[N])   (row strides x_ld, w_ld, y_ld).
  *   reference: dnn_logit_fn, models/DeepFM/deepFM.py:295-300; _deep_architecture,
