@@ -419,6 +419,43 @@ __global__ __launch_bounds__(256) void adagrad_keys_payload_k(const int64_t* __r
     }
 }
 
+// bag entries of the sharded multi-hot backward (ShardedTables.lookup_bags_train, owner side): entry e = record e % cap_e of received
+// slab e / cap_e (shard_bags.hip's 16-byte records).  Records past the slab header's count, and records that fail bags_pool_k's checks
+// (row < the local table's rows, return position in [0, cap_b)), sort behind every row.  The record is read unconditionally: j < cap_e
+// always lies inside the slab.
+__global__ __launch_bounds__(256) void adagrad_keys_bags_k(const int4* __restrict__ recv, int64_t n, int64_t cap_e, int64_t cap_b, int F,
+                                                           const int64_t* __restrict__ row_base, uint32_t total_rows,
+                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int64_t src = (uint32_t)e / (uint32_t)cap_e;                 // n < 2^30
+        const int64_t j = e - src * cap_e;
+        const int4* slab = recv + src * (cap_e + 1);
+        const int64_t ne = min((int64_t)(unsigned int)slab[0].x, cap_e);
+        const int4 r = slab[1 + j];
+        const int64_t p = (int64_t)(((uint64_t)(uint32_t)r.y << 32) | (uint32_t)r.x);
+        uint32_t key = total_rows;
+        if (j < ne && p >= 0 && r.w >= 0 && (int64_t)r.w < cap_b) {
+            const int64_t rr = p / F;
+            const int sl = (int)(p - rr * F);
+            const int64_t vf = (sl + 1 < F ? row_base[sl + 1] : (int64_t)total_rows) - row_base[sl];
+            if (rr < vf) key = (uint32_t)(row_base[sl] + rr);
+        }
+        keys[e] = key;
+        vals[e] = (uint32_t)e;
+    }
+}
+
+// bag mode of adagrad_tile_k / adagrad_fix_k: entry e's gradient is w * grecv[src*cap_b + ret] of its record (src, j) -- formed where it
+// is summed, never written out as a [n, K] buffer; the run's sum goes through the slot's max_norm clip derivative at the row's
+// pre-update value (autograd._clip_backward) before the Adagrad step
+struct BagSrc {
+    const int4* recv = nullptr;       // the P received slabs of (cap_e + 1) records
+    const float* grecv = nullptr;     // [P*cap_b, K]: the gradient of every partial row, where the pool kernel stored that row
+    int64_t cap_e = 1, cap_b = 1;
+    const float* slot_mn = nullptr;   // [F] per-slot max_norm, or NULL: mn for every slot (0: no clip)
+    float mn = 0.f;
+};
+
 // per-row update rules of the sorted path: g = the summed gradient chunk of one row
 struct AdagradUpd {   // accum += g^2; w -= lr * g / sqrt(accum)   ([TF-upstream] tf.train.AdagradOptimizer, deepFM.py:61)
     float* const* tables;
@@ -542,6 +579,47 @@ struct AdamUpd {
 template <class U, class = void> struct IsNorm { static constexpr bool value = false; };
 template <class U> struct IsNorm<U, std::void_t<decltype(U::kNorm)>> { static constexpr bool value = U::kNorm; };
 
+// bag mode: the update of one run (slot f, local row id) from its summed gradient chunk.  All LPS lanes of the group call it (lanes
+// c >= kv of a padded group bring zeros): the clip derivative needs ||row||^2 and row . sum over the whole row.  [TF-upstream] clip_by_norm
+// y = r m / max(||r||, m): for ||r|| > m, dL/dr = m (g / ||r|| - r (r . g) / ||r||^3), else g -- applied once to the run's sum (it is
+// linear in g), at the row already loaded for the update.
+template <int LPS, int VEC>
+__device__ __forceinline__ void bag_apply(const AdagradUpd& upd, const BagSrc& bag, int f, int64_t id, int c, int kv, typename BV<VEC>::T sum) {
+    using V = BV<VEC>;
+    using T = typename V::T;
+    const bool act = c < kv;
+    const int64_t off = id * upd.ld + (int64_t)(act ? c : 0) * VEC;
+    float* wp = upd.tables[f] + off;
+    float* ap = upd.accums[f] + off;
+    T wv = V::ld(wp), acc = V::ld(ap);
+    if (!act) {
+        wv = V::zero();
+        sum = V::zero();
+    }
+    const float mn = bag.slot_mn ? bag.slot_mn[f] : bag.mn;      // (group-uniform)
+    if (mn > 0.f) {
+        float n2 = V::dot(wv, wv, 0.f), rg = V::dot(wv, sum, 0.f);
+#pragma unroll
+        for (int o = LPS / 2; o > 0; o >>= 1) {                    // butterfly inside the group: every lane ends with the same sums
+            n2 += __shfl_xor(n2, o, 64);
+            rg += __shfl_xor(rg, o, 64);
+        }
+        const float nrm = sqrtf(n2);
+        if (nrm > mn) sum = V::scale(V::sub(V::scale(sum, 1.f / nrm), V::scale(wv, rg / (nrm * nrm * nrm))), mn);
+    }
+    if (!act) return;
+    if constexpr (VEC == 4) {
+        acc = make_float4(acc.x + sum.x * sum.x, acc.y + sum.y * sum.y, acc.z + sum.z * sum.z, acc.w + sum.w * sum.w);
+        wv = make_float4(wv.x - upd.lr * sum.x / sqrtf(acc.x), wv.y - upd.lr * sum.y / sqrtf(acc.y), wv.z - upd.lr * sum.z / sqrtf(acc.z),
+                         wv.w - upd.lr * sum.w / sqrtf(acc.w));
+    } else {
+        acc = acc + sum * sum;
+        wv = wv - upd.lr * sum / sqrtf(acc);
+    }
+    V::st(ap, acc);
+    V::st(wp, wv);
+}
+
 // every row of table f NOT stepped by AdamUpd this step (mark == 0): zero gradient -> m *= b1, v *= b2, var -= lr_t * m / (sqrt(v) + eps);
 // marked rows are skipped and their mark cleared.  LPS = K / 4 adjacent lanes own a row (all of them read the mark before lane 0 of
 // the group clears it: one wave instruction apart).
@@ -584,7 +662,7 @@ __global__ __launch_bounds__(256) void adam_decay_k(float* const* __restrict__ t
     }
 }
 
-template <int LPS, int VEC, class U, bool FM = false>
+template <int LPS, int VEC, class U, bool FM = false, bool BAG = false>
 __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
                                                       int64_t n, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                       const float* __restrict__ grad, int64_t g_ld, int64_t g_fs /* grad stride per slot */,
@@ -593,7 +671,8 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
                                                       float* __restrict__ carry /* [tiles][2][K] */,
                                                       const float* __restrict__ fm_g = nullptr /* FM: d loss / d fm_logit [B] */,
                                                       const float* __restrict__ fm_sum = nullptr /* FM: S[b] = sum_f e[b,f], [B, K] */,
-                                                      int stage_min_dups = 8 /* stage the tile's gradients in LDS when it holds at least this many duplicates */) {
+                                                      int stage_min_dups = 8 /* stage the tile's gradients in LDS when it holds at least this many duplicates */,
+                                                      BagSrc bag = BagSrc{} /* BAG: where the entry gradients come from */) {
     using V = BV<VEC>;
     using T = typename V::T;
     constexpr int NG = 256 / LPS;
@@ -632,6 +711,13 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
     __shared__ __attribute__((aligned(16))) float sd[STAGE ? ADA_TILE * LPS * VEC : 4];
     auto entry_grad = [&](int i, T wv, bool have_w) {
         const uint32_t ent = sval[i];
+        if constexpr (BAG) {
+            // the record's weight times the gradient of its partial row (the key pass checked the return position; clamped anyway)
+            const uint32_t src = ent / (uint32_t)bag.cap_e;
+            const int4 r = bag.recv[(int64_t)src * (bag.cap_e + 1) + 1 + (ent - (int64_t)src * bag.cap_e)];
+            const int64_t ret = r.w < 0 ? 0 : ((int64_t)r.w < bag.cap_b ? r.w : bag.cap_b - 1);
+            return V::scale(V::ld(bag.grecv + ((int64_t)src * bag.cap_b + ret) * K + (c < kv ? c : 0) * VEC), __int_as_float(r.z));
+        }
         const uint32_t b = ent / (uint32_t)F;
         const int f = (int)(ent - b * (uint32_t)F);
         if constexpr (FM) {
@@ -726,7 +812,7 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
     for (int r = g; r < nruns; r += NG) {
         const int s = rstart[r], e = rstart[r + 1];
         const uint32_t rk = skey[s];
-        if (rk >= total_rows || c >= kv) continue;          // pruned ids / idle lanes of a padded group
+        if (rk >= total_rows || (!BAG && c >= kv)) continue;  // pruned ids / idle lanes of a padded group (BAG: they join bag_apply)
         T sum = V::zero();
         int f = (int)(sval[s] % (uint32_t)F);
         if (staged) {
@@ -749,13 +835,15 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
         const bool open_l = r == 0 && cont_l, open_r = r == nruns - 1 && cont_r;
         if (!open_l && !open_r) {
             const int64_t id = (int64_t)rk - row_base[f];
-            if constexpr (IsNorm<U>::value) {
+            if constexpr (BAG) {
+                bag_apply<LPS, VEC>(upd, bag, f, id, c, kv, sum);
+            } else if constexpr (IsNorm<U>::value) {
                 const double d = (double)V::dot(sum, sum, 0.f) * ADAM_FX;
                 atomicAdd(&nsq[f & 63], (unsigned long long)(d < 4.0e18 ? d : 4.0e18));
             } else {
                 upd.template apply<VEC>(f, id, c * VEC, sum);
             }
-        } else {
+        } else if (c < kv) {
             V::st(carry + (t * 2 + (open_l ? 0 : 1)) * K + c * VEC, sum);   // a run open on both sides goes to slot 0
         }
     }
@@ -767,17 +855,18 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
 
 // one thread group per tile: if a run STARTS in this tile and continues to the right, add the partials of the tiles it
 // runs through (in tile order) and apply
-template <int LPS, int VEC, class U>
+template <int LPS, int VEC, class U, bool BAG = false>
 __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
                                                      int64_t n, int64_t ntiles, const uint32_t* __restrict__ keys,
                                                      const uint32_t* __restrict__ vals, const int64_t* __restrict__ row_base,
-                                                     uint32_t total_rows, int nt, const float* __restrict__ carry) {
+                                                     uint32_t total_rows, int nt, const float* __restrict__ carry, BagSrc bag = BagSrc{}) {
     using V = BV<VEC>;
     using T = typename V::T;
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t t = q / LPS;
-    const int c = (int)(q - t * LPS), kv = K / VEC;
-    if (t >= ntiles || c >= kv) return;
+    const int c0 = (int)(q - t * LPS), kv = K / VEC;
+    if (t >= ntiles || (!BAG && c0 >= kv)) return;                    // (BAG: a padded group's idle lanes join bag_apply)
+    const int c = c0 < kv ? c0 : 0;
     const int64_t e0 = t * ADA_TILE;
     const int64_t e1 = (e0 + ADA_TILE < n) ? e0 + ADA_TILE : n;      // first entry of the next tile
     if (e1 >= n) return;
@@ -797,7 +886,9 @@ __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
         for (int q = 1; q < nt; ++q) f += (int64_t)kl >= row_base[q] ? 1 : 0;
     }
     const int64_t id = (int64_t)kl - row_base[f];
-    if constexpr (IsNorm<U>::value) {
+    if constexpr (BAG) {
+        bag_apply<LPS, VEC>(upd, bag, f, id, c0, kv, sum);
+    } else if constexpr (IsNorm<U>::value) {
         const double d = (double)V::dot(sum, sum, 0.f) * ADAM_FX;
         atomicAdd(upd.norm2 + (f & 63), (unsigned long long)(d < 4.0e18 ? d : 4.0e18));
     } else {
@@ -1369,6 +1460,90 @@ extern "C" int dir_adagrad_dense_f32(float* w, float* accum, const float* grad, 
     if (count == 0) return DIR_OK;
     DIR_CHECK_ARG(w && accum && grad, "%s: null pointer", name);
     hipLaunchKernelGGL(adagrad_dense_k, dim3(grid_for((count + 255) / 256)), dim3(256), 0, as_stream(stream), w, accum, grad, count, lr, eps);
+    DIR_CHECK_LAUNCH(name);
+    return DIR_OK;
+}
+
+// The owner side of ShardedTables.lookup_bags_train's backward: the sorted Adagrad over the received bag records (see adagrad_keys_bags_k,
+// BagSrc, bag_apply).  The sort runs on all P * cap_e entry slots (the dead ones sort behind every row); the workspace is the payload
+// form's for n = P * cap_e entries.
+extern "C" int dir_sparse_adagrad_sorted_bags_f32(float* const* tables, float* const* accums, int F, int K, const int64_t* recv, int P,
+                                                  int64_t cap_e, int64_t cap_b, const float* grecv, const float* slot_max_norm,
+                                                  float max_norm, float lr, const int64_t* row_base, int64_t total_rows, void* workspace,
+                                                  int64_t workspace_bytes, dir_stream_t stream) {
+    const char* name = "dir_sparse_adagrad_sorted_bags_f32";
+    DIR_CHECK_ARG(F > 0 && K > 0 && P > 0 && P <= 64, "%s: F=%d K=%d P=%d (P <= 64)", name, F, K, P);
+    DIR_CHECK_ARG(cap_e > 0 && cap_b > 0 && cap_e < ((int64_t)1 << 31) && (int64_t)P * cap_b < ((int64_t)1 << 31),
+                  "%s: cap_e=%lld cap_b=%lld (each < 2^31, P*cap_b too)", name, (long long)cap_e, (long long)cap_b);
+    DIR_CHECK_ARG(!(max_norm < 0.f), "%s: max_norm=%g", name, max_norm);
+    DIR_CHECK_ARG(tables && accums && recv && grecv && row_base && workspace, "%s: null pointer", name);
+    const bool vec = (K % 4 == 0) && aligned16(grecv);
+    int lps = 1;
+    while (lps < (vec ? K / 4 : K)) lps <<= 1;
+    if (lps > 64) return fail(DIR_E_UNSUPPORTED, "%s: K=%d is wider than one wave covers (max %d)", name, K, vec ? 256 : 64);
+    const int64_t n = (int64_t)P * cap_e;
+    if (n >= ((int64_t)1 << 30)) return fail(DIR_E_UNSUPPORTED, "%s: P*cap_e=%lld entry slots (the sort takes < 2^30)", name, (long long)n);
+    if (total_rows < 0 || total_rows >= 0xffffffffll) return fail(DIR_E_UNSUPPORTED, "%s: total_rows must be in [0, 2^32-1)", name);
+    if (total_rows == 0) return DIR_OK;          // this rank holds no rows: no record can name one
+    AdaSortedPlan p;
+    if (!adagrad_sorted_plan(n, K, total_rows, p)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
+    if ((int64_t)p.total > workspace_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(DIR_E_BADARG, "%s: workspace needs %lld bytes, 256-byte aligned", name, (long long)p.total);
+    hipStream_t st = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + p.off_keys[0]);
+    uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + p.off_keys[1]);
+    uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + p.off_vals[0]);
+    uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + p.off_vals[1]);
+    float* carry = reinterpret_cast<float*>(ws + p.off_carry);
+    const bool second = radix_sort_input_buffer((size_t)n, p.bits) == 1;
+    const int4* r = reinterpret_cast<const int4*>(recv);
+    hipLaunchKernelGGL(adagrad_keys_bags_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, r, n, cap_e, cap_b, F, row_base,
+                       (uint32_t)total_rows, second ? k1 : k0, second ? v1 : v0);
+    DIR_CHECK_LAUNCH(name);
+    if (radix_sort_pairs_u32(ws + p.off_tmp, k0, k1, v0, v1, (size_t)n, p.bits, st) != hipSuccess) return fail(DIR_E_HIP, "%s: radix sort failed", name);
+    const AdagradUpd upd{tables, accums, lr, (int64_t)K};
+    BagSrc bag;
+    bag.recv = r;
+    bag.grecv = grecv;
+    bag.cap_e = cap_e;
+    bag.cap_b = cap_b;
+    bag.slot_mn = slot_max_norm;
+    bag.mn = max_norm;
+    const int64_t ntiles = (int64_t)p.ntiles;
+    static const int stage_min = dev_env_int("DIR_ADA_STAGE_MIN", 8);       // development A/B switch
+    dim3 gfix((unsigned)((ntiles * lps + 255) / 256));
+    // one "slot" per entry for the sort (F = 1); the table is found from the key among the F tables (nt = F), as in the payload form
+#define DIR_CASE(L, V)                                                                                                                  \
+    do {                                                                                                                                \
+        hipLaunchKernelGGL((adagrad_tile_k<L, V, AdagradUpd, false, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, 1, K, n, k1, \
+                           v1, nullptr, (int64_t)0, (int64_t)0, row_base, (uint32_t)total_rows, F, carry, nullptr, nullptr, stage_min,   \
+                           bag);                                                                                                        \
+        hipLaunchKernelGGL((adagrad_fix_k<L, V, AdagradUpd, true>), gfix, dim3(256), 0, st, upd, 1, K, n, ntiles, k1, v1, row_base,     \
+                           (uint32_t)total_rows, F, carry, bag);                                                                        \
+    } while (0)
+    if (vec) {
+        switch (lps) {
+            case 1: DIR_CASE(1, 4); break;
+            case 2: DIR_CASE(2, 4); break;
+            case 4: DIR_CASE(4, 4); break;
+            case 8: DIR_CASE(8, 4); break;
+            case 16: DIR_CASE(16, 4); break;
+            case 32: DIR_CASE(32, 4); break;
+            default: DIR_CASE(64, 4); break;
+        }
+    } else {
+        switch (lps) {
+            case 1: DIR_CASE(1, 1); break;
+            case 2: DIR_CASE(2, 1); break;
+            case 4: DIR_CASE(4, 1); break;
+            case 8: DIR_CASE(8, 1); break;
+            case 16: DIR_CASE(16, 1); break;
+            case 32: DIR_CASE(32, 1); break;
+            default: DIR_CASE(64, 1); break;
+        }
+    }
+#undef DIR_CASE
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
 }

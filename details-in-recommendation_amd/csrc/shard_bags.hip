@@ -400,6 +400,43 @@ __global__ __launch_bounds__(256) void bags_combine_k(const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// requester, backward: scatter the bag gradients to the partial rows they came from
+// ------------------------------------------------------------------------------------------------
+// The transpose of bags_combine_k with its lane mapping: every owner o in mask[g] gets c_bag * g[b, f*K..] (c_bag = 1 / denom for mean
+// and sqrtn, 1 for sum) at row pos[g*P + o] of `send` -- the row where the forward received that partial.  Rows no partial came back
+// from are not written (the owners never read them).  The buffer then travels the partial-row exchange in reverse.
+template <int LPS, int VEC>
+__global__ __launch_bounds__(256) void bags_grad_k(const float* __restrict__ g, int64_t g_ld, int K, int P, const int32_t* __restrict__ pos,
+                                                   const uint64_t* __restrict__ mask, const float* __restrict__ denom,
+                                                   const int32_t* __restrict__ slot_combiner, int combiner, int64_t B, int F,
+                                                   float* __restrict__ send, int64_t n_rows) {
+    using V = typename VecT<VEC>::T;
+    constexpr int SPW = 64 / LPS;
+    const int lane = threadIdx.x & 63;
+    const int c = lane & (LPS - 1);
+    const int s = lane / LPS;
+    const int kv = (K + VEC - 1) / VEC;
+    const bool cact = c < kv;
+    const int64_t nwave = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t gw = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); gw * SPW < B; gw += nwave) {
+        const int64_t b = gw * SPW + s;
+        if (b >= B) continue;
+        for (int f = 0; f < F; ++f) {
+            const int64_t gi = b * F + f;
+            const uint64_t m = mask[gi];
+            if (!m) continue;
+            const int comb = slot_combiner ? slot_combiner[f] : combiner;
+            V gv = ldv(g + b * g_ld + (int64_t)f * K + (cact ? c * VEC : 0), (V*)nullptr);
+            if (comb != DIR_COMBINER_SUM) gv = vdiv(gv, denom[gi]);
+            for (uint64_t mm = m; mm; mm &= mm - 1ull) {
+                const int32_t p = pos[gi * P + (__ffsll((long long)mm) - 1)];
+                if (p >= 0 && (int64_t)p < n_rows && cact) stv(send + (int64_t)p * K + c * VEC, gv);
+            }
+        }
+    }
+}
+
 static int next_pow2_sb(int v) {
     int p = 1;
     while (p < v) p <<= 1;
@@ -541,5 +578,53 @@ extern "C" int dir_shard_bags_combine_f32(const float* back, int K, int P, const
     }
 #undef DIR_CASE
     DIR_CHECK_LAUNCH("shard_bags_combine");
+    return DIR_OK;
+}
+
+extern "C" int dir_shard_bags_grad_f32(const float* g, int64_t g_ld, int K, int P, const int32_t* pos, const int64_t* mask, const float* denom,
+                                       int64_t B, int F, const int32_t* slot_combiner, int combiner, int64_t cap_b, float* send,
+                                       dir_stream_t stream) {
+    const char* name = "dir_shard_bags_grad_f32";
+    DIR_CHECK_ARG(F > 0 && K > 0 && P > 0 && P <= 64 && B >= 0, "%s: F=%d K=%d P=%d B=%lld (P <= 64)", name, F, K, P, (long long)B);
+    DIR_CHECK_ARG(cap_b > 0 && (int64_t)P * cap_b < ((int64_t)1 << 31), "%s: cap_b=%lld (P*cap_b < 2^31)", name, (long long)cap_b);
+    DIR_CHECK_ARG(combiner >= DIR_COMBINER_SUM && combiner <= DIR_COMBINER_SQRTN, "%s: combiner=%d", name, combiner);
+    DIR_CHECK_ARG(g_ld >= (int64_t)F * K, "%s: g_ld=%lld < F*K=%lld", name, (long long)g_ld, (long long)F * K);
+    DIR_CHECK_ARG(send, "%s: null pointer", name);
+    DIR_CHECK_ARG(B == 0 || (g && pos && mask && denom), "%s: null pointer", name);
+    const bool vec = (K % 4 == 0) && (g_ld % 4 == 0) && aligned16(g) && aligned16(send);
+    const int lps = next_pow2_sb(vec ? K / 4 : K);
+    if (lps > 64) return fail(DIR_E_UNSUPPORTED, "%s: K=%d is wider than one wave covers (max %d)", name, K, vec ? 256 : 64);
+    if (B == 0) return DIR_OK;
+    const int spw = 64 / lps;
+    const int64_t waves = (B + spw - 1) / spw;
+    dim3 grid(grid_for((waves + 3) / 4));
+    hipStream_t st = as_stream(stream);
+    const uint64_t* m = reinterpret_cast<const uint64_t*>(mask);
+    const int64_t n_rows = (int64_t)P * cap_b;
+#define DIR_CASE(L, V)                                                                                                                  \
+    hipLaunchKernelGGL((bags_grad_k<L, V>), grid, dim3(256), 0, st, g, g_ld, K, P, pos, m, denom, slot_combiner, combiner, B, F, send, n_rows)
+    if (vec) {
+        switch (lps) {
+            case 1: DIR_CASE(1, 4); break;
+            case 2: DIR_CASE(2, 4); break;
+            case 4: DIR_CASE(4, 4); break;
+            case 8: DIR_CASE(8, 4); break;
+            case 16: DIR_CASE(16, 4); break;
+            case 32: DIR_CASE(32, 4); break;
+            default: DIR_CASE(64, 4); break;
+        }
+    } else {
+        switch (lps) {
+            case 1: DIR_CASE(1, 1); break;
+            case 2: DIR_CASE(2, 1); break;
+            case 4: DIR_CASE(4, 1); break;
+            case 8: DIR_CASE(8, 1); break;
+            case 16: DIR_CASE(16, 1); break;
+            case 32: DIR_CASE(32, 1); break;
+            default: DIR_CASE(64, 1); break;
+        }
+    }
+#undef DIR_CASE
+    DIR_CHECK_LAUNCH("shard_bags_grad");
     return DIR_OK;
 }

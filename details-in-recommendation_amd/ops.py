@@ -2449,6 +2449,19 @@ def shard_bags_combine(back, P, pos, mask, denom, B, F, slot_comb, comb, out, fm
     return out
 
 
+def shard_bags_grad(g, P, pos, mask, denom, B, F, slot_comb, comb, cap_b, send):
+    """Requester side of the bags' backward (dir_shard_bags_grad_f32): g [B, F*K] = d loss / d the combined bags -> send [P*cap_b, K], the
+    row of every partial the forward received (pos) set to c_bag * g[b, f] (c_bag = 1 / denom for mean and sqrtn, 1 for sum); rows no
+    partial came back from are left as they are."""
+    _dev(g, torch.float32, "g")
+    _dev(send, torch.float32, "send")
+    if g.shape[0] != B or g.shape[1] != F * send.shape[1] or (B and g.stride(1) != 1) or not send.is_contiguous():
+        raise ValueError("shard_bags_grad: g [B, F*K] with unit inner stride, send a contiguous [P*cap_b, K] buffer")
+    _lib.check(_lib.load().dir_shard_bags_grad_f32(_ptr(g), g.stride(0) if B else g.shape[1], send.shape[1], P, _ptr(pos), _ptr(mask), _ptr(denom), B, F,
+                                                   _ptr(slot_comb), comb, cap_b, _ptr(send), _stream()))
+    return send
+
+
 # ---- backward of the interaction ops (SURVEY 8f rank 2) --------------------------------------------------
 def fm_logit_backward(emb, g, F, K, add_in=None, out=None):
     """d fm_logit / d emb: demb[b,f,:] = g[b] * (sum_f' e[b,f',:] - e[b,f,:]) (+ add_in).  g: [B] or [B,1]."""
@@ -2946,6 +2959,29 @@ class SparseAdagrad:
         _lib.check(lib.dir_sparse_adagrad_sorted_payload_f32(_ptr(ts.ptrs), _ptr(self.acc_ptrs), ts.F, ts.K, _ptr(payload), n,
                                                              _ptr(grad), self.lr, _ptr(self.head_base), self.total_rows, ws, need,
                                                              _stream()))
+        self._written()
+
+
+    def step_bags(self, recv, P, cap_e, cap_b, grad_rows, slot_mn=None, mn=0.0):
+        """Owner side of a sharded multi-hot backward (shard.ShardedTables.lookup_bags_train; include/dir_hip.h:
+        dir_sparse_adagrad_sorted_bags_f32): recv = the P bag slabs of (cap_e + 1) 16-byte records the forward received, grad_rows
+        [P*cap_b, K] = the gradients of the partial rows as received.  Entry (s, j) adds w * grad_rows[s*cap_b + ret] to its row; every
+        touched row takes one Adagrad step with its summed gradient, through the slot's max_norm clip derivative (slot_mn [F] device
+        fp32 or None + mn, as ops.slot_max_norms gives them) at its pre-update value."""
+        ts = self.ts
+        _dev(recv, torch.int64, "recv")
+        _dev(grad_rows, torch.float32, "grad_rows")
+        if ts.ld != ts.K:
+            raise ValueError("step_bags: plain [vocab, K] tables")
+        if recv.numel() < P * (cap_e + 1) * 2 or grad_rows.shape != (P * cap_b, ts.K) or not grad_rows.is_contiguous():
+            raise ValueError("step_bags: recv [P*(cap_e+1)*2] int64, grad_rows a contiguous [P*cap_b, K] tensor")
+        if self.total_rows == 0:
+            return
+        lib = _lib.load()
+        ws, need = _sorted_ws(self, lib, P * cap_e, 1, ts.K, self.total_rows, ts.device)
+        _lib.check(lib.dir_sparse_adagrad_sorted_bags_f32(_ptr(ts.ptrs), _ptr(self.acc_ptrs), ts.F, ts.K, _ptr(recv), P, cap_e, cap_b,
+                                                          _ptr(grad_rows), _ptr(slot_mn), float(mn), self.lr, _ptr(self.head_base),
+                                                          self.total_rows, ws, need, _stream()))
         self._written()
 
 

@@ -170,6 +170,17 @@ class HipBackend:
         slot_comb, comb = ops.slot_combiners(self.ts, combiner)
         ops.shard_bags_combine(back, self.P, pos, mask, denom, B, self.ts.F, slot_comb, comb, out, fm=fm)
 
+    # ---- their backward (lookup_bags_train) ----
+    def bags_grad(self, g, cap_b, pos, mask, denom, B, combiner, send):
+        """Requester: g [B, F*K] -> c_bag * g[b, f] at every partial row the forward received (send [P*cap_b, K])."""
+        slot_comb, comb = ops.slot_combiners(self.ts, combiner)
+        ops.shard_bags_grad(g, self.P, pos, mask, denom, B, self.ts.F, slot_comb, comb, cap_b, send)
+
+    def bags_adagrad(self, opt, recv, cap_e, cap_b, grad_rows, max_norm):
+        """Owner: the sorted Adagrad over the received bag records, entry gradient w * grad_rows[src*cap_b + ret]."""
+        slot_mn, mn = ops.slot_max_norms(self.ts, max_norm)
+        opt.step_bags(recv, self.P, cap_e, cap_b, grad_rows, slot_mn, mn)
+
 
 _ROWS_TS = {}
 
@@ -366,6 +377,8 @@ class ShardedTables:
         self._bag_plans = {}
         self._bag_unchecked = []      # lookup_bags verdicts not read yet (check = lazy / never): (event | None, host words)
         self._bag_hosts, self._bag_host_i = None, 0
+        self._bag_train_plans = {}    # lookup_bags_train's own plans: an inference lookup_bags between a forward and its backward never
+                                      # touches the slabs, pos, mask and denom that backward reads
 
     @classmethod
     def from_full(cls, full_tables, group=None, **kw):
@@ -995,6 +1008,96 @@ class ShardedTables:
             if not self._bag_verdict(pend):       # the verdict, read after the whole lookup has been enqueued
                 return out, fm
 
+    def _bag_args(self, values, offsets, weights, what):
+        F = self.F
+        if values.dim() != 1 or offsets.dim() != 1 or (offsets.numel() - 1) % F:
+            raise ValueError("%s: values [nnz], offsets [B*F+1] with F=%d" % (what, F))
+        if weights is not None and weights.numel() != values.numel():
+            raise ValueError("%s: weights must be [nnz]" % what)
+        return (offsets.numel() - 1) // F
+
+    def lookup_bags_train(self, values, offsets, weights=None, combiner="mean", max_norm=None, field_major=False, flags=0):
+        """Differentiable lookup_bags (the same arguments but want_fm): emb [B_local, F*K] with a grad_fn, equal to lookup_bags(...)[0] bit
+        for bit; the tables get no .grad.  emb.backward(g) performs ONE synchronous sparse Adagrad step over the global batch on every
+        rank's shard (the optimiser of enable_training, shared with lookup_train): entry e of bag (b, f) contributes w_e * c_bag *
+        g[b, f*K:(f+1)*K] to its row (c_bag = 1 / denom for mean and sqrtn, 1 for sum; through the slot's max_norm clip derivative at the
+        row's pre-update value), and all contributions to a row -- inside a bag, across bags, across ranks -- are summed before its
+        accumulator moves.  Entries the forward drops contribute nothing.
+        The backward is the forward's exchange in reverse: the requester puts c_bag * g[b, f] where each partial row came back from, the
+        same equal-split all-to-all carries at most min(L, P) gradient rows per bag back to the owners, and each owner runs the sorted
+        Adagrad over the bag records it kept (include/dir_hip.h: dir_shard_bags_grad_f32, dir_sparse_adagrad_sorted_bags_f32).
+        Training uses its own plans: inference lookups in between leave the backward's buffers alone.  The forward reads its own overflow
+        verdict (every rank the same words) and repeats with grown capacities; verdicts pending from check="lazy" / "never" lookup_bags
+        calls stay pending.  As with lookup_train, where duplicate contributions sit in the slabs depends on atomic order: once a row has
+        duplicates, results agree to fp32 rounding, not bit for bit, from run to run.  Every rank must call it (SPMD)."""
+        if getattr(self, "optimizer", None) is None:
+            raise RuntimeError("call enable_training(lr) first")
+        self._bag_args(values, offsets, weights, "lookup_bags_train")
+        anchor = torch.zeros((), dtype=torch.float32, device=values.device, requires_grad=True)
+        return _ShardedBagLookup.apply(self, values, offsets, weights, combiner, max_norm, field_major, flags, torch.is_grad_enabled(), anchor)
+
+    def _bag_train_plan(self, B, cap_e, cap_b):
+        key = (B, cap_e, cap_b)
+        plan = self._bag_train_plans.get(key)
+        if plan is not None and not plan.busy:
+            return plan
+        fresh = _BagPlan(self, B, cap_e, cap_b)
+        fresh.busy = False
+        fresh.host = torch.empty(3, dtype=torch.int64, pin_memory=True) if self.device.type == "cuda" else None
+        if plan is None:                    # (a plan still held by a forward whose backward has not run is left to it)
+            if len(self._bag_train_plans) >= 4:
+                self._bag_train_plans = {k: v for k, v in self._bag_train_plans.items() if v.busy}
+            self._bag_train_plans[key] = fresh
+        return fresh
+
+    def _bags_forward_train(self, values, offsets, weights, combiner, max_norm, field_major, flags, hold):
+        F, K, be = self.F, self.K, self.backend
+        B = self._bag_args(values, offsets, weights, "lookup_bags_train")
+        sb, sf = (1, B) if field_major else (F, 1)
+        nnz = values.numel()
+        self.stats["bag_train_lookups"] = self.stats.get("bag_train_lookups", 0) + 1
+        dev = values.device
+        check = self._collective()
+        while True:
+            cap_e, cap_b = self._bag_caps(B, nnz)
+            plan = self._bag_train_plan(B, cap_e, cap_b)
+            be.bags_bucket(values, offsets, weights, B, sb, sf, combiner, flags, cap_e, cap_b, plan.send, plan.pos, plan.mask, plan.denom,
+                           plan.ws)
+            w = self._a2a_equal(plan.recv, plan.send)
+            if w is not None:
+                w.wait()
+            be.bags_pool(plan.recv, cap_e, cap_b, max_norm, plan.rows, stat=plan.stat if check else None)
+            pend = None
+            if check and dev.type == "cuda":
+                plan.host.copy_(plan.stat, non_blocking=True)
+                pend = (torch.cuda.current_stream(dev).record_event(), plan.host)
+            elif check:
+                pend = (None, plan.stat.clone())
+            w = self._a2a_equal(plan.back, plan.rows)
+            if w is not None:
+                w.wait()
+            out = torch.empty((B, F * K), dtype=torch.float32, device=dev)
+            be.bags_combine(plan.back, cap_b, plan.pos, plan.mask, plan.denom, B, combiner, out, None)
+            # this lookup's own verdict only (the same words on every rank: all ranks repeat together); pending lazy verdicts stay pending
+            if pend is None or not self._bag_verdict(pend):
+                plan.busy = bool(hold)
+                return out, plan
+
+    def _bags_backward_apply(self, saved, g):
+        plan, B, combiner, max_norm = saved
+        be = self.backend
+        self._updates += 1
+        try:
+            g2 = g if g.dim() == 2 and (B == 0 or g.stride(1) == 1) else g.contiguous()
+            # the partial rows' buffers are the gradient's: rows = what this rank sends, back = what it receives (the same at world 1)
+            be.bags_grad(g2, plan.cap_b, plan.pos, plan.mask, plan.denom, B, combiner, plan.rows)
+            w = self._a2a_equal(plan.back, plan.rows)
+            if w is not None:
+                w.wait()
+            be.bags_adagrad(self.optimizer, plan.recv, plan.cap_e, plan.cap_b, plan.back, max_norm)
+        finally:
+            plan.busy = False
+
     def lookup(self, ids, want_fm=False, out=None, fm=None):
         """ids [B_local, F] int64 (global row ids; < 0 or >= vocab_f -> zeros) -> emb [B_local, F*K] fp32
         (and the FM second-order logit [B_local, 1] when want_fm).  out / fm: preallocated results (stable addresses)."""
@@ -1046,6 +1149,22 @@ class _ShardedLookup(torch.autograd.Function):
     def backward(ctx, g):
         ctx.st._backward_apply(ctx.saved, g)
         return None, None, None
+
+
+class _ShardedBagLookup(torch.autograd.Function):
+    """emb = ShardedTables.lookup_bags(...)[0] with a backward that sends every bag's gradient back along its partial rows and lets each
+    owner apply the sparse Adagrad update to its shard from the bag records it kept (no gradient tensor is returned for the tables)."""
+
+    @staticmethod
+    def forward(ctx, st, values, offsets, weights, combiner, max_norm, field_major, flags, hold, anchor):
+        emb, plan = st._bags_forward_train(values, offsets, weights, combiner, max_norm, field_major, flags, hold)
+        ctx.st, ctx.saved = st, (plan, emb.shape[0], combiner, max_norm)
+        return emb
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.st._bags_backward_apply(ctx.saved, g)
+        return (None,) * 10
 
 
 # ---- the dense (replicated) side of multi-GPU training -----------------------------------------------------------------
@@ -1135,6 +1254,23 @@ class ShardedDeepFMTrainer:
         self.dense_optimizer.zero_grad(set_to_none=True)
         emb = self.tables.lookup_train(ids)                                   # tables update inside backward()
         logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb)             # fm_logit_fn + dnn_logit_fn, deepFM.py:337-338
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, labels, reduction="sum")
+        loss.backward()
+        allreduce_grads(self.dense_params, self.group)
+        self.dense_optimizer.step()
+        return loss.detach()
+
+    def step_bags(self, values, offsets, labels, weights=None, field_major=False):
+        """step() over multi-hot bags (a history column of the reference's DeepFM, deepFM.py:53,77,84): lookup_bags_train with every
+        column's combiner and max_norm, the FM + DNN logits, the SUM loss, backward (every owner's shard takes its Adagrad step), the
+        dense gradients summed over the ranks and the dense step.  values / offsets / weights as lookup_bags; labels [B_local, 1] ->
+        this rank's summed loss (detached)."""
+        from . import autograd as ag
+        m = self.model
+        self.dense_optimizer.zero_grad(set_to_none=True)
+        comb = [c.combiner for c in m.dnn_feature_columns]
+        emb = self.tables.lookup_bags_train(values, offsets, weights, combiner=comb, max_norm=m._max_norm(), field_major=field_major)
+        logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb)
         loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, labels, reduction="sum")
         loss.backward()
         allreduce_grads(self.dense_params, self.group)

@@ -513,6 +513,28 @@ int dir_shard_bags_pool_f32(const float* const* tables, const int64_t* local_voc
 int dir_shard_bags_combine_f32(const float* back, int K, int P, const int32_t* pos, const int64_t* mask, const float* denom, int64_t B, int F,
                                const int32_t* slot_combiner, int combiner, float* out, int64_t out_ld, float* fm, dir_stream_t stream);
 
+/* The backward of the bags above (ShardedTables.lookup_bags_train): the partial-row exchange in reverse, then the owner's sorted Adagrad.
+ * dir_shard_bags_grad_f32 (requester): g [B, F*K] (row stride g_ld) = d loss / d out of dir_shard_bags_combine_f32, with that call's
+ *   pos / mask / denom / slot_combiner / combiner -> send [P*cap_b, K]: for every bag g and owner o in mask[g] with pos[g*P + o] >= 0,
+ *   row pos[g*P + o] = c_bag * g[b, f*K..] (c_bag = 1 / denom for mean and sqrtn, 1 for sum) -- the row where the forward received
+ *   that partial.  Other rows are left untouched (no owner reads them).  The buffer then travels the same equal-split all-to-all.
+ *   K <= 64, or a multiple of 4 up to 256 (else DIR_E_UNSUPPORTED); P <= 64, P * cap_b < 2^31.
+ * dir_sparse_adagrad_sorted_bags_f32 (owner): recv = the P slabs the forward received (dir_shard_bags_bucket's records), grecv
+ *   [P*cap_b, K] = the gradients as received (the row of slab s's partial q at s*cap_b + q).  Entry (s, j)'s gradient w *
+ *   grecv[s*cap_b + ret] goes to local row / slot of its record -- records past the header's count or failing the pool kernel's checks
+ *   contribute nothing -- and every touched row takes ONE Adagrad step with the sum of all its entries (accum += G^2; w -= lr * G /
+ *   sqrt(accum), TF's _apply_sparse_duplicate_indices).  slot_max_norm [F] or NULL + max_norm: G goes through the clip derivative at
+ *   the row's pre-update value first (for ||r|| > m: m (G / ||r|| - r (r . G) / ||r||^3)).  tables / accums / row_base / total_rows:
+ *   this rank's shards, as dir_sparse_adagrad_sorted_payload_f32 (total_rows = 0: nothing to do).  No [entries, K] gradient buffer is
+ *   formed.  Workspace: dir_sparse_adagrad_sorted_workspace_bytes(P * cap_e, 1, K, total_rows) device bytes, 256-byte aligned.
+ *   K as above; P <= 64, cap_e and P * cap_b < 2^31, P * cap_e < 2^30. */
+int dir_shard_bags_grad_f32(const float* g, int64_t g_ld, int K, int P, const int32_t* pos, const int64_t* mask, const float* denom, int64_t B,
+                            int F, const int32_t* slot_combiner, int combiner, int64_t cap_b, float* send, dir_stream_t stream);
+int dir_sparse_adagrad_sorted_bags_f32(float* const* tables, float* const* accums, int F, int K, const int64_t* recv, int P, int64_t cap_e,
+                                       int64_t cap_b, const float* grecv, const float* slot_max_norm, float max_norm, float lr,
+                                       const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
+                                       dir_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * A5 / A9  hidden layers of the DNN towers: Y[M, N] = act(X[M, Kd] . Wt[N, Kd]^T + bias[N])   (row strides x_ld, w_ld, y_ld).
  *   reference: dnn_logit_fn, models/DeepFM/deepFM.py:295-300; _deep_architecture,
