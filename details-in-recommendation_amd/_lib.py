@@ -217,6 +217,11 @@ SIGNATURES = {
     "dir_shard_bags_grad_f32": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp]),
     "dir_sparse_adagrad_sorted_bags_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, ctypes.c_float,
                                                    ctypes.c_float, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "dir_shard_linear_gather_f32": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp]),
+    "dir_shard_linear_finish_f32": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "dir_shard_linear_grad_f32": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp]),
+    "dir_sparse_ftrl_rows_sorted_payload_f32": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp,
+                                                        c_i64, c_vp, c_i64, c_vp, c_vp]),
 }
 
 DIR_OK, DIR_E_BADARG, DIR_E_RANGE, DIR_E_HIP, DIR_E_UNSUPPORTED = 0, -1, -2, -3, -4

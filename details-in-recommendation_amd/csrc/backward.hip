@@ -1388,6 +1388,24 @@ extern "C" int dir_sparse_adagrad_sorted_payload_f32(float* const* tables, float
                                 (int64_t)K, 0, n, row_base, total_rows, workspace, workspace_bytes, stream, payload);
 }
 
+// Owner side of the sharded linear term's backward (shard.ShardedTables.lookup_train(with_linear=True)): dir_sparse_ftrl_rows_sorted_f32's
+// update (FtrlUpd, packed [w | n | z | -] rows, units = 1) driven by the payload the owner received, as dir_sparse_adagrad_sorted_payload_f32
+// is for Adagrad.  sorted_from (optional): the workspace of a sorted update of the SAME payload (same n, row_base, total_rows) that has just
+// run on this stream -- the Adagrad step of the embedding rows the weights are co-located with: its sorted (row, entry) pairs are read
+// and the key pass and the sort are skipped (the pair arrays sit at offsets that depend on n only, not on K).
+extern "C" int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F, const int64_t* payload, int64_t n, const float* grad, float lr,
+                                                       float l1, float l2, const int64_t* row_base, int64_t total_rows, void* workspace,
+                                                       int64_t workspace_bytes, const void* sorted_from, dir_stream_t stream) {
+    const char* name = "dir_sparse_ftrl_rows_sorted_payload_f32";
+    DIR_CHECK_ARG(F > 0 && n >= 0, "%s: F=%d n=%lld", name, F, (long long)n);
+    DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
+    DIR_CHECK_ARG(rows && (payload || n == 0), "%s: null pointer", name);
+    FtrlUpd upd{rows, rows, rows, lr, l1, l2, (int64_t)4};
+    upd.rows = true;
+    return sparse_sorted_update(name, upd, F, 1, nullptr, 0, 0, grad, (int64_t)1, 0, n, row_base, total_rows, workspace, workspace_bytes, stream,
+                                payload, nullptr, nullptr, sorted_from);
+}
+
 // ---- tf.train.AdamOptimizer on the embedding tables ------------------------------------------------------------------------------
 extern "C" int64_t dir_sparse_adam_workspace_bytes(int64_t B, int F, int K, int64_t total_rows) {
     if (B < 0 || F <= 0 || F > 64 || K <= 0 || (K & 3) || 64 % (K / 4) || total_rows <= 0 || total_rows >= 0xffffffffll || B * F >= 0x7fffffffll) return 0;

@@ -2462,6 +2462,55 @@ def shard_bags_grad(g, P, pos, mask, denom, B, F, slot_comb, comb, cap_b, send):
     return send
 
 
+def shard_linear_gather(lin_ts, recv, P, cap, out):
+    """Owner side of the sharded linear term (include/dir_hip.h: dir_shard_linear_gather_f32): lin_ts = this rank's packed linear rows
+    (TableSet.ftrl_rows' layout), recv = the received payload -- cap > 0: the P fixed-capacity slabs [P*(cap+1)] int64, cap = None: a flat
+    payload [n] -- -> out [P*cap] / [n] fp32, one weight per payload word (0.0 behind a header and for pruned words: every word is
+    written)."""
+    _dev(recv, torch.int64, "recv")
+    _dev(out, torch.float32, "out")
+    if lin_ts.K != 1 or lin_ts.ld == lin_ts.K:
+        raise ValueError("shard_linear_gather: packed linear training rows (TableSet.ftrl_rows)")
+    n = recv.numel()
+    if not recv.is_contiguous() or not out.is_contiguous() or (cap and n < P * (cap + 1)) or out.numel() < (P * cap if cap else n):
+        raise ValueError("shard_linear_gather: recv [P*(cap+1)] slabs (or a flat payload), out one contiguous float per payload word")
+    _lib.check(_lib.load().dir_shard_linear_gather_f32(_ptr(lin_ts._ptrs), lin_ts.ld, _ptr(lin_ts.vocab_dev), lin_ts.F, _ptr(recv), P,
+                                                       cap or 0, 0 if cap else n, _ptr(out), _stream()))
+    return out
+
+
+def shard_linear_finish(wback, inv2d, bias=None, out=None):
+    """Requester side (dir_shard_linear_finish_f32): wback [n] = the weights as the exchange returned them, inv2d [B, F] int64 (any
+    strides; < 0: pruned) -> out [B, 1] = sum_f wback[inv2d[b, f]] + bias, in ops.linear_logit's order and arithmetic (bit for bit)."""
+    _dev(wback, torch.float32, "wback")
+    _dev(inv2d, torch.int64, "inv")
+    B, F = inv2d.shape
+    if out is None:
+        out = torch.empty((B, 1), dtype=torch.float32, device=wback.device)
+    _dev(out, torch.float32, "out")
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+    if not wback.is_contiguous() or out.shape[0] != B:
+        raise ValueError("shard_linear_finish: wback contiguous, out [B, 1]")
+    _lib.check(_lib.load().dir_shard_linear_finish_f32(_ptr(wback), wback.numel(), _ptr(inv2d), inv2d.stride(0), inv2d.stride(1), F, _ptr(bias),
+                                                       B, _ptr(out), out.stride(0) if B > 1 else 1, _stream()))
+    return out
+
+
+def shard_linear_grad(g, inv2d, send):
+    """Requester side of the linear term's backward (dir_shard_linear_grad_f32): g [B, 1] (or [B]) = d loss / d lin -> send [n] zero-filled,
+    then send[inv2d[b, f]] = g[b] for every entry with inv2d >= 0."""
+    _dev(g, torch.float32, "g")
+    _dev(inv2d, torch.int64, "inv")
+    _dev(send, torch.float32, "send")
+    B, F = inv2d.shape
+    if g.numel() != B or not send.is_contiguous():
+        raise ValueError("shard_linear_grad: g [B, 1], send a contiguous buffer")
+    _lib.check(_lib.load().dir_shard_linear_grad_f32(_ptr(g), g.stride(0) if B > 1 else 1, _ptr(inv2d), inv2d.stride(0), inv2d.stride(1), F, B,
+                                                     _ptr(send), send.numel(), _stream()))
+    return send
+
+
 # ---- backward of the interaction ops (SURVEY 8f rank 2) --------------------------------------------------
 def fm_logit_backward(emb, g, F, K, add_in=None, out=None):
     """d fm_logit / d emb: demb[b,f,:] = g[b] * (sum_f' e[b,f',:] - e[b,f,:]) (+ add_in).  g: [B] or [B,1]."""
@@ -3140,6 +3189,34 @@ class SparseFtrl:
         _lib.check(lib.dir_sparse_ftrl_sorted_f32(*args, _stream()))
         if self._share is not None:
             self._share.leave(self, ids, B, sb, sf, ws)
+
+
+    def step_payload(self, payload, grad, sorted_by=None):
+        """Owner side of the sharded linear term's backward (shard.ShardedTables; include/dir_hip.h:
+        dir_sparse_ftrl_rows_sorted_payload_f32): payload [n] int64 (local_row * F + slot, < 0 pruned) as received from all ranks, grad [n]
+        fp32 in the same order, over packed rows (TableSet.ftrl_rows).  sorted_by: an optimiser whose step_payload has JUST run over the
+        same payload on this stream with the same local vocabularies (the SparseAdagrad of the co-located embedding rows): its sorted
+        (row, entry) pairs are read from its workspace and this call skips the key pass and the sort."""
+        ts = self.ts
+        if not self.packed:
+            raise ValueError("step_payload: packed linear training rows (TableSet.ftrl_rows)")
+        _dev(payload, torch.int64, "payload")
+        _dev(grad, torch.float32, "grad")
+        n = payload.numel()
+        if grad.numel() != n or not grad.is_contiguous() or not payload.is_contiguous():
+            raise ValueError("grad must be a contiguous [n] tensor matching the payload")
+        if n == 0 or self.total_rows == 0:
+            return
+        lib = _lib.load()
+        ws, need = _sorted_ws(self, lib, n, 1, 1, self.total_rows, ts.device)
+        src = None
+        if sorted_by is not None:
+            if sorted_by.total_rows != self.total_rows or list(sorted_by.ts.vocab) != list(ts.vocab) or sorted_by._ws is None:
+                raise ValueError("step_payload: sorted_by must have just sorted the same payload over the same local vocabularies")
+            src = ctypes.c_void_p(sorted_by._ws.data_ptr() + (-sorted_by._ws.data_ptr()) % 256)
+        _lib.check(lib.dir_sparse_ftrl_rows_sorted_payload_f32(_ptr(ts._ptrs), ts.F, _ptr(payload), n, _ptr(grad), self.lr, self.l1, self.l2,
+                                                               _ptr(self.row_base), self.total_rows, ws, need, src, _stream()))
+        ts.written(*self.accums, *self.linears)
 
 
 class PackedTables:

@@ -20,6 +20,11 @@ enqueued, so the stream never drains); the lookup is then repeated on the exact 
 split sizes) and the capacity grows.  `dedup=True` sends each (slot, row) once per owner and chunk ([TF-upstream]
 embedding_lookup_sparse's unique-before-gather): on skewed ids it cuts the link-bound bytes.
 
+DeepFM's first-order weights can live on the shards too (attach_linear: slot f's weights beside slot f's embedding rows, as packed
+[w | n | z | -] rows).  The linear term then rides on the same id exchange -- owner: one weight per received payload word; one float
+per slab slot travels back behind the rows; requester: the sample's F weights summed in slot order -- and lookup_train(with_linear=True)
+sends d logit back the same way for an owner-side FTRL step on the Adagrad step's sort of the payload.
+
 The collectives are torch.distributed.all_to_all_single (backend "nccl" = RCCL on ROCm; "gloo" in the CPU tests).
 world_size == 1 skips the collectives (unless force_collective) but still runs the three HIP steps.  The HIP steps sit
 behind a small backend object so that the CPU (gloo) tests can stand the oracle in for them; the default backend is the
@@ -181,6 +186,39 @@ class HipBackend:
         slot_mn, mn = ops.slot_max_norms(self.ts, max_norm)
         opt.step_bags(recv, self.P, cap_e, cap_b, grad_rows, slot_mn, mn)
 
+    # ---- the first-order (linear) term, co-located with the embedding rows (ShardedTables.attach_linear) -------------
+    def attach_linear(self, rows, arena):
+        """rows[f]: this rank's packed [local rows, 4] = [w | n | z | -] blocks of one arena (TableSet.ftrl_rows' layout)."""
+        ts = ops.TableSet([r[:, 0:1] for r in rows], ld=4)
+        ts.accums = [r[:, 1:2] for r in rows]
+        ts.linears = [r[:, 2:3] for r in rows]
+        ts.arena, ts.rows = arena, rows
+        self.lin_ts, self._ftrl = ts, None
+
+    def linear_gather(self, recv, cap, out):
+        """Owner: one weight per received payload word (cap: the slab capacity, None: recv is a flat payload); every word of out is written."""
+        ops.shard_linear_gather(self.lin_ts, recv, self.P, cap, out)
+
+    def linear_finish(self, wback, inv2d, bias, out):
+        """Requester: out [Bc, 1] = sum_f wback[inv2d[b, f]] + bias, ops.linear_logit's sum bit for bit."""
+        ops.shard_linear_finish(wback, inv2d, bias, out)
+
+    def linear_grad(self, g, inv2d, send):
+        """Requester, backward: send zero-filled, then send[inv2d[b, f]] = g[b]."""
+        ops.shard_linear_grad(g, inv2d, send)
+
+    def apply_ftrl(self, payload, grad, lr, l1, l2, sorted_by=None):
+        """Owner, backward: the sorted FTRL over the payload it kept; sorted_by = the Adagrad optimiser that has just sorted the same
+        payload (apply_adagrad): its sorted pairs are reused and the second key pass and sort are skipped."""
+        o = self._ftrl
+        if o is None or (o.lr, o.l1, o.l2) != (float(lr), float(l1), float(l2)):
+            o = self._ftrl = ops.SparseFtrl(self.lin_ts, lr, l1=l1, l2=l2)
+        o.step_payload(payload, grad, sorted_by=sorted_by)
+
+    def ftrl_dense(self, w, accum, linear, grad, lr, l1, l2):
+        """FTRL step of a replicated dense variable (the linear bias) with its summed gradient."""
+        ops.ftrl_dense_(w, accum, linear, grad, lr, l1, l2)
+
 
 _ROWS_TS = {}
 
@@ -211,6 +249,7 @@ class _Plan:
     def __init__(self, st, B, cap):
         dev, P, F, K = st.device, st.P, st.F, st.K
         self.B, self.cap = B, cap
+        self.P, self.device, self.lrows = P, dev, None
         C = self.C = st._C()
         per = -(-B // C) if B else 0
         self.bounds = [(min(B, c * per), min(B, (c + 1) * per)) for c in range(C)]       # a chunk may be empty (B < C)
@@ -231,6 +270,17 @@ class _Plan:
         self.stat = torch.zeros(2, **i64)                 # ... over all chunks and ranks, read off the received slab headers
         self.host = torch.empty(2, dtype=torch.int64, pin_memory=dev.type == "cuda")
         self.fin = None                                   # events behind the last enqueued lookup's final kernels (one per side stream)
+
+    def lin_buffers(self):
+        """The linear term's buffers, made at the first lookup that wants it: one float per slab slot and micro-batch, sent (lrows) and
+        received (lback); [C, P*cap] each, so that the backward hands all micro-batches to the owner's update as one array in payload order."""
+        if self.lrows is None:
+            n = self.P * self.cap
+            self.lrows_all = torch.zeros((self.C, n), dtype=torch.float32, device=self.device)
+            self.lback_all = self.lrows_all if self.recv_all is self.send_all else torch.zeros_like(self.lrows_all)
+            self.lrows = [self.lrows_all[c] for c in range(self.C)]
+            self.lback = [self.lback_all[c] for c in range(self.C)]
+        return self.lrows, self.lback
 
 
 class _BagPlan:
@@ -259,10 +309,11 @@ class _Lookup:
     applies the overflow policy and returns emb (or (emb, fm)).  Issue the NEXT lookup before calling result() -- or before the
     compute that consumes this one -- and the exchange runs under that compute."""
 
-    def __init__(self, st, plan, ids, want_fm, out, fm, done, exact=None, consumer=None):
+    def __init__(self, st, plan, ids, want_fm, out, fm, done, exact=None, consumer=None, lin=None):
         self.st, self.plan, self.ids, self.want_fm, self.out, self.fm, self.done = st, plan, ids, want_fm, out, fm, done
         self.exact = exact
         self.consumer = consumer
+        self.lin = lin                # None, or (lin [B, 1], bias | None): the first-order term rides along (want_lin)
         self.fin = plan.fin if plan is not None else None      # this lookup's completion events on the side streams
         self.joined = exact is not None
         self.checked = exact is not None or done is False
@@ -289,7 +340,9 @@ class _Lookup:
                 st._learn(self.plan, over, demand)
                 if over:                                      # rare: repeat on the exact path (results overwrite out / fm in stream order)
                     st.stats["fallbacks"] += 1
-                    st._lookup_exact(self.ids, self.want_fm, out=self.out, fm=self.fm, consumer=self.consumer)
+                    st._lookup_exact(self.ids, self.want_fm, out=self.out, fm=self.fm, consumer=self.consumer, lin=self.lin)
+        if self.lin is not None:
+            return (self.out, self.fm, self.lin[0]) if self.want_fm else (self.out, self.lin[0])
         return (self.out, self.fm) if self.want_fm else self.out
 
 
@@ -301,6 +354,7 @@ class _RowsLookup:
 
     def result(self):
         self.lk.result()
+        self.lin = self.lk.lin[0] if self.lk.lin is not None else None        # the first-order term [B, 1] (want_lin), after any repair
         return list(self.chunks)
 
 
@@ -379,6 +433,8 @@ class ShardedTables:
         self._bag_hosts, self._bag_host_i = None, 0
         self._bag_train_plans = {}    # lookup_bags_train's own plans: an inference lookup_bags between a forward and its backward never
                                       # touches the slabs, pos, mask and denom that backward reads
+        self.lin_rows = None          # attach_linear: this rank's packed first-order rows [local rows, 4] = [w | n | z | -], one per slot
+        self._lin_hp = None           # enable_linear_training: (lr, l1, l2) of the owner-side FTRL
 
     @classmethod
     def from_full(cls, full_tables, group=None, **kw):
@@ -398,6 +454,69 @@ class ShardedTables:
             s, e = local_slice(vocab[f], parts[f], first[f], P, rank)
             loc.append(t[s:e].contiguous())
         return cls(loc, vocab, group=group, **kw)
+
+    # ---- the first-order (linear) term: slot f's weights live beside slot f's embedding rows ---------------------------
+    def attach_linear(self, local_weights, initial_accumulator_value=0.1):
+        """Give the shards DeepFM's first-order weights (the reference creates them under the same partitioner as the embedding tables:
+        deepFM.py:206-209 beside :163-175).  local_weights[f]: this rank's slice of slot f's weights -- the rows local_slice(...) gives, i.e.
+        as many as local_tables[f] has; shape [rows] or [rows, 1].  They are stored as packed 16-byte training rows [w | n | z | -]
+        (TableSet.ftrl_rows' layout; n = initial_accumulator_value, z = 0), co-located with the embedding rows: the linear term then
+        rides on the embedding lookup's id exchange (lookup(want_lin=True), lookup_train(with_linear=True))."""
+        local_weights = list(local_weights)
+        if len(local_weights) != self.F:
+            raise ValueError("attach_linear: one weight vector per table (F=%d), got %d" % (self.F, len(local_weights)))
+        n_rows = [int(t.shape[0]) for t in self.local_tables]
+        for f, w in enumerate(local_weights):
+            if w.numel() != n_rows[f] or w.dim() > 2:
+                raise ValueError("attach_linear: slot %d: rank %d holds %d rows, got weights of shape %s (units = 1)"
+                                 % (f, self.rank, n_rows[f], tuple(w.shape)))
+        arena = torch.zeros(sum(n_rows) * 4 + 4, dtype=torch.float32, device=self.device)
+        off = (-(arena.data_ptr() // 4)) % 4               # rows 16-byte aligned
+        rows = []
+        for w, v in zip(local_weights, n_rows):
+            blk = arena[off:off + v * 4].view(v, 4)
+            blk[:, 0] = w.detach().reshape(-1).to(device=self.device, dtype=torch.float32)
+            blk[:, 1] = float(initial_accumulator_value)
+            rows.append(blk)
+            off += v * 4
+        self.lin_rows, self._lin_arena = rows, arena
+        attach = getattr(self.backend, "attach_linear", None)
+        if attach is not None:
+            attach(rows, arena)
+        return self
+
+    def attach_linear_from_full(self, full_weights, initial_accumulator_value=0.1):
+        """attach_linear from replicated full weight vectors ([vocab_f] or [vocab_f, 1]), sliced as from_full slices the tables."""
+        loc = []
+        for f, w in enumerate(full_weights):
+            s, e = local_slice(self.vocab[f], self.parts[f], self.first[f], self.P, self.rank)
+            loc.append(w.reshape(-1)[s:e])
+        return self.attach_linear(loc, initial_accumulator_value)
+
+    def _need_linear(self, what):
+        if self.lin_rows is None:
+            raise RuntimeError("%s: the tables have no first-order weights (call attach_linear first)" % what)
+
+    def linear_weights(self):
+        """This rank's first-order weights, one [local rows] VIEW of the packed rows per slot."""
+        self._need_linear("linear_weights")
+        return [r[:, 0] for r in self.lin_rows]
+
+    def linear_state(self):
+        """(w, n, z): per slot the [local rows] views of the weights and of their FTRL accumulator and linear slots."""
+        self._need_linear("linear_state")
+        return tuple([r[:, c] for r in self.lin_rows] for c in range(3))
+
+    def enable_linear_training(self, lr, l1=0.0, l2=0.0):
+        """Attach the owner-side FTRL-Proximal of the first-order rows (the reference's linear_optimizer='Ftrl', deepFM.py:58, applied by
+        the parameter server that holds the partition): lookup_train(ids, with_linear=True) then also returns the linear term, and its
+        backward takes one synchronous FTRL step over the global batch on every rank's rows.  The accumulators' initial value was fixed when
+        the rows were packed (attach_linear)."""
+        self._need_linear("enable_linear_training")
+        if not lr > 0 or l1 < 0 or l2 < 0:
+            raise ValueError("enable_linear_training: lr > 0, l1 >= 0, l2 >= 0")
+        self._lin_hp = (float(lr), float(l1), float(l2))
+        return self
 
     def _collective(self):
         return self.P > 1 or (self.force_collective and dist.is_initialized())
@@ -441,17 +560,26 @@ class ShardedTables:
         self.optimizer = self.backend.make_optimizer(lr, initial_accumulator_value)
         return self
 
-    def lookup_train(self, ids):
+    def lookup_train(self, ids, with_linear=False):
         """Differentiable lookup: emb [B_local, F*K] with a grad_fn (the tables themselves get no .grad).  Runs the fixed-capacity
         pipeline (no split sizes reach the host; the gradient rows go back through the same equal-split slabs); the exact
         variable-size path only when mode == "exact", after an overflow, or when "auto" has given up on slabs.  One training lookup
-        may be outstanding (forward -> backward) per ShardedTables."""
+        may be outstanding (forward -> backward) per ShardedTables.
+        with_linear: -> (emb, lin) from ONE autograd node; lin [B_local, 1] = the sum of the sample's F first-order weights (no bias: the
+        bias is a replicated dense variable of the caller's).  Its backward receives both gradients: the row gradients and d lin travel
+        the same equal-split exchange, then every owner applies Adagrad to its embedding rows and FTRL to its first-order rows (in that
+        order: the FTRL step reuses the Adagrad step's sort of the payload) -- one optimiser step."""
         if getattr(self, "optimizer", None) is None:
             raise RuntimeError("call enable_training(lr) first")
         anchor = torch.zeros((), dtype=torch.float32, device=ids.device, requires_grad=True)
+        if with_linear:
+            self._need_linear("lookup_train(with_linear=True)")
+            if self._lin_hp is None:
+                raise RuntimeError("call enable_linear_training(lr) first")
+            return _ShardedLookupLinear.apply(self, ids, anchor)
         return _ShardedLookup.apply(self, ids, anchor)
 
-    def _forward_saved(self, ids):
+    def _forward_saved(self, ids, with_lin=False):
         B, F = ids.shape
         K, be = self.K, self.backend
         flat = ids.reshape(-1).contiguous()
@@ -467,16 +595,32 @@ class ShardedTables:
         back = torch.empty((n, K), dtype=torch.float32, device=flat.device)       # private: kept alive by autograd users
         self._a2a(back.view(-1), rows.reshape(-1), [c * K for c in sc], [c * K for c in rc])
         emb, _ = be.finish(back, inv, B, F, False)
+        if with_lin:
+            lin = torch.empty((B, 1), dtype=torch.float32, device=flat.device)
+            self._linear_exact(recv, inv.view(B, F), sc, rc, (lin, None))
+            return emb, ("exact", inv, sc, rc, recv), lin
         return emb, ("exact", inv, sc, rc, recv)
 
-    def _forward_saved_fixed(self, ids):
+    def _linear_exact(self, recv, inv2d, sc, rc, lin):
+        """The linear term on the exact path: one weight per received payload word, sent back with the row exchange's splits (one float
+        per entry), summed per sample."""
+        be = self.backend
+        n = inv2d.numel()
+        lw = torch.empty(recv.numel(), dtype=torch.float32, device=recv.device)
+        be.linear_gather(recv, None, lw)
+        lback = torch.empty(n, dtype=torch.float32, device=recv.device)
+        self._a2a(lback, lw, sc, rc)
+        be.linear_finish(lback, inv2d, lin[1], lin[0])
+
+    def _forward_saved_fixed(self, ids, with_lin=False):
         """Training forward on the fixed-capacity pipeline (never de-duplicated: the backward needs one slab position per entry).
         The overflow verdict is read here (the one host wait of a training lookup; it covers work that is long done when the
         dense part of the model has been enqueued in between)."""
         B, F = ids.shape
         out = torch.empty((B, F * self.K), dtype=torch.float32, device=ids.device)
         plan = self._plan(B, "train")
-        done = self._enqueue(plan, ids, False, out, None, dedup=False)
+        lin = (torch.empty((B, 1), dtype=torch.float32, device=ids.device), None) if with_lin else None
+        done = self._enqueue(plan, ids, False, out, None, dedup=False, lin=lin)
         lk = _Lookup(self, plan, ids, False, out, None, done)
         lk.join()
         if done is not False:
@@ -484,11 +628,15 @@ class ShardedTables:
             self._learn(plan, over, demand)
             if over:
                 self.stats["fallbacks"] += 1
-                return self._forward_saved(ids)
-        return out, ("fixed", plan)
+                return self._forward_saved(ids, with_lin)
+        return (out, ("fixed", plan), lin[0]) if with_lin else (out, ("fixed", plan))
 
-    def _backward_apply(self, saved, g_emb):
+    def _backward_apply(self, saved, g_emb, g_lin=None):
+        """g_lin (lookup_train(with_linear=True)): d loss / d lin [B_local, 1].  Its values go where the weights came back from and travel
+        the same exchange as the gradient rows; the owner's FTRL runs after its Adagrad, over the same payload, on that step's sort."""
         K = self.K
+        be = self.backend
+        hp = self._lin_hp
         self._updates += 1
         if saved[0] == "fixed":
             plan = saved[1]
@@ -510,6 +658,12 @@ class ShardedTables:
                 else:
                     grecv = gsend[:P * cap]
                 grecv_l.append(grecv)
+                if g_lin is not None:
+                    # the forward's linear buffers carry the gradient back: lrows = what this rank sends, lback = what it receives
+                    lrows, lback = plan.lin_buffers()
+                    be.linear_grad(g_lin[s:e], be.inv2d(plan.inv[c], e - s, self.F, False), lrows[c])
+                    if self._collective():
+                        self._a2a(lback[c], lrows[c], None, None)
             # ONE update over all micro-batches (duplicates of a row -- from any chunk, any rank -- are summed before the accumulator
             # moves: a synchronous step over the global batch)
             slabs = plan.recv_all.view(C * P, cap + 1)
@@ -517,6 +671,8 @@ class ShardedTables:
             pos = torch.arange(cap, device=slabs.device)
             pay = torch.where(pos.unsqueeze(0) < hdr.unsqueeze(1), slabs[:, 1:], torch.full_like(slabs[:, 1:], -1)).reshape(-1)
             self.backend.apply_adagrad(self.optimizer, pay, grecv_l[0] if C == 1 else torch.cat(grecv_l, dim=0))
+            if g_lin is not None:
+                be.apply_ftrl(pay, plan.lback_all.view(-1), hp[0], hp[1], hp[2], sorted_by=self.optimizer)
             return
         _, inv, sc, rc, recv = saved
         n = inv.numel()
@@ -526,9 +682,15 @@ class ShardedTables:
         grecv = torch.empty((recv.numel(), K), dtype=torch.float32, device=g.device)
         self._a2a(grecv.view(-1), gsend.view(-1), [c * K for c in rc], [c * K for c in sc])   # the forward exchange, reversed
         self.backend.apply_adagrad(self.optimizer, recv, grecv)
+        if g_lin is not None:
+            lsend = torch.empty(n, dtype=torch.float32, device=g.device)
+            be.linear_grad(g_lin, inv.view(-1, self.F), lsend)
+            lrecv = torch.empty(recv.numel(), dtype=torch.float32, device=g.device)
+            self._a2a(lrecv, lsend, rc, sc)
+            be.apply_ftrl(recv, lrecv, hp[0], hp[1], hp[2], sorted_by=self.optimizer)
 
     # ---- the exact, variable-size lookup (one host read of the split sizes) --------------------------------
-    def _lookup_exact(self, ids, want_fm, out=None, fm=None, consumer=None):
+    def _lookup_exact(self, ids, want_fm, out=None, fm=None, consumer=None, lin=None):
         B, F = ids.shape
         K, be = self.K, self.backend
         flat = ids.reshape(-1).contiguous()
@@ -543,6 +705,8 @@ class ShardedTables:
         rows = be.gather_packed(recv)                                       # HIP (owner side)
         back = be.back_buffer(n, K, flat.device)
         self._a2a(back.view(-1), rows.reshape(-1), [c * K for c in sc], [c * K for c in rc])
+        if lin is not None:
+            self._linear_exact(recv, inv.view(B, F), sc, rc, lin)
         if consumer is not None:                                            # (lookup_consume: the caller's kernel reads the rows where they are)
             consumer(0, B, back, inv.view(B, F))
             return None, None
@@ -607,17 +771,25 @@ class ShardedTables:
             self._chk_stream = torch.cuda.Stream(device=self.device)
         return self._streams
 
-    def _enqueue(self, plan, ids, want_fm, out, fm, dedup, consumer=None):
+    def _enqueue(self, plan, ids, want_fm, out, fm, dedup, consumer=None, lin=None):
         """Enqueue one lookup's pipeline.  -> False (nothing to check: one rank, slabs hold the whole batch), None (statistic in
-        plan.stat, no event: CPU backend) or the event after which plan.host holds [overflow, demand]."""
+        plan.stat, no event: CPU backend) or the event after which plan.host holds [overflow, demand].
+        lin = (lin [B, 1], bias | None): the first-order term rides along -- per micro-batch the owner reads one weight per received
+        slab slot right after the row gather, one float per slot goes back behind the rows, and the requester sums its samples' weights
+        beside the finish pass; without it nothing here changes."""
         B, F = ids.shape
         be, P = self.backend, self.P
         C = plan.C
         cap = plan.cap
+        lrows, lback = plan.lin_buffers() if lin is not None else (None, None)
         if not self._collective():
             # one rank, no exchange: the three kernels back to back on the caller's stream
             be.bucket_cap(ids, cap, plan.send[0], plan.inv[0], plan.counts[0], plan.flags[0], plan.ws[0], stat=plan.cstat[0], dedup=dedup)
             be.gather_slabs(plan.recv[0], cap, plan.rows[0])
+            if lin is not None:
+                be.linear_gather(plan.recv[0], cap, lrows[0])
+                if B:
+                    be.linear_finish(lback[0], be.inv2d(plan.inv[0], B, F, dedup), lin[1], lin[0])
             if B and consumer is not None:
                 consumer(0, B, plan.back[0], be.inv2d(plan.inv[0], B, F, dedup))
             elif B:
@@ -643,12 +815,16 @@ class ShardedTables:
 
         def finish(c):
             s, e = plan.bounds[c]
+            if lin is not None:
+                wait(wl[c])
+                if e > s:
+                    be.linear_finish(lback[c], be.inv2d(plan.inv[c], e - s, F, dedup), lin[1], lin[0][s:e])
             if e > s and consumer is not None:
                 consumer(s, e, plan.back[c], be.inv2d(plan.inv[c], e - s, F, dedup))
             elif e > s:
                 be.finish_chunk(plan.back[c], be.inv2d(plan.inv[c], e - s, F, dedup), want_fm, out[s:e], fm[s:e] if want_fm else None)
 
-        wi, wr = [None] * C, [None] * C
+        wi, wr, wl = [None] * C, [None] * C, [None] * C
         ev_ids = []
         with on(0):
             wi[0] = bucket(0)
@@ -662,6 +838,9 @@ class ShardedTables:
                     ev_ids.append(S[c % 2].record_event())
                 be.gather_slabs(plan.recv[c], cap, plan.rows[c])
                 wr[c] = self._a2a_equal(plan.back[c], plan.rows[c])
+                if lin is not None:
+                    be.linear_gather(plan.recv[c], cap, lrows[c])
+                    wl[c] = self._a2a_equal(lback[c], lrows[c])
             if c >= 1:
                 with on(c - 1):
                     wait(wr[c - 1])
@@ -739,17 +918,28 @@ class ShardedTables:
         self._drain_unchecked(block=True)
         return False
 
-    def lookup_async(self, ids, want_fm=False, out=None, fm=None, consumer=None):
+    def lookup_async(self, ids, want_fm=False, out=None, fm=None, consumer=None, want_lin=False, lin=None, lin_bias=None):
         """Enqueue a lookup and return a handle; handle.result() -> emb [B_local, F*K] (or (emb, fm)).  Two lookups can be in
         flight (double-buffered plans): issue lookup i+1, then consume lookup i -- the exchange of i+1 runs under that compute.
-        consumer: see lookup_consume (no emb / fm are produced then)."""
+        consumer: see lookup_consume (no emb / fm are produced then).
+        want_lin: the result carries the first-order term as its last element -- (emb, lin) or (emb, fm, lin), emb = None under a
+        consumer; lin [B_local, 1] = the sum of the sample's F first-order weights (attach_linear) + lin_bias (a [1] device tensor, or
+        None), ops.linear_logit's over the unsharded packed rows bit for bit.  lin: a preallocated result."""
         B, F = ids.shape
         if F != self.F:
             raise ValueError("ids must be [B, F=%d]" % self.F)
         self.stats["lookups"] += 1
+        lt = None
+        if want_lin:
+            self._need_linear("lookup(want_lin=True)")
+            lt = (lin if lin is not None else torch.empty((B, 1), dtype=torch.float32, device=ids.device), lin_bias)
         if self._use_exact or (B == 0 and not self._collective()):
-            emb, fmo = self._lookup_exact(ids, want_fm, out=out, fm=fm, consumer=consumer)
-            return _Lookup(self, None, ids, want_fm, emb, fmo, None, exact=(emb, fmo) if want_fm else (emb if consumer is None else ()), consumer=consumer)
+            emb, fmo = self._lookup_exact(ids, want_fm, out=out, fm=fm, consumer=consumer, lin=lt)
+            if lt is not None:
+                exact = (emb, fmo, lt[0]) if want_fm else (emb, lt[0])
+            else:
+                exact = (emb, fmo) if want_fm else (emb if consumer is None else ())
+            return _Lookup(self, None, ids, want_fm, emb, fmo, None, exact=exact, consumer=consumer, lin=lt)
         if out is None and consumer is None:
             out = torch.empty((B, F * self.K), dtype=torch.float32, device=ids.device)
         if want_fm and fm is None:
@@ -760,8 +950,8 @@ class ShardedTables:
         if prev is not None:
             prev.join()                                   # its buffers are about to be reused
         plan = self._plan(B, slot)
-        done = self._enqueue(plan, ids, want_fm, out, fm, dedup=self.dedup, consumer=consumer)
-        lk = _Lookup(self, plan, ids, want_fm, out, fm, done, consumer=consumer)
+        done = self._enqueue(plan, ids, want_fm, out, fm, dedup=self.dedup, consumer=consumer, lin=lt)
+        lk = _Lookup(self, plan, ids, want_fm, out, fm, done, consumer=consumer, lin=lt)
         if done is False:
             lk.joined = True                              # ran on the caller's stream
         self._inflight[slot] = lk
@@ -865,7 +1055,7 @@ class ShardedTables:
             raise ValueError("lookup_consume needs check='eager' (the overflow repair calls the consumer again)")
         self.lookup_async(ids, want_fm=False, consumer=consumer).result()
 
-    def lookup_rows_async(self, ids):
+    def lookup_rows_async(self, ids, want_lin=False, lin_bias=None):
         """Enqueue a lookup WITHOUT its finish pass and hand the received rows to the caller (round 6: what lookup_consume gives a callback,
         as a handle -- so that the NEXT lookup can be issued before this one's rows are consumed, like lookup_async).  handle.result() makes
         the caller's stream wait for the exchange, applies the overflow policy and returns a list of (s, e, rows, inv) -- one entry per
@@ -876,13 +1066,13 @@ class ShardedTables:
         Needs check='eager' (an overflow is repaired on the exact path before the rows are handed out: then ONE entry for the whole batch)."""
         if self.check != "eager":
             raise ValueError("lookup_rows needs check='eager' (an overflow is repaired before the rows are handed out)")
-        chunks = []
+        chunks = []      # (want_lin: the handle's .lin holds the first-order term [B, 1] (+ lin_bias) after result())
 
         def collect(s, e, rows, inv):
             if s == 0:
                 chunks.clear()                     # (the repair on the exact path calls again, for the whole batch)
             chunks.append((s, e, rows, inv))
-        return _RowsLookup(self.lookup_async(ids, want_fm=False, consumer=collect), chunks)
+        return _RowsLookup(self.lookup_async(ids, want_fm=False, consumer=collect, want_lin=want_lin, lin_bias=lin_bias), chunks)
 
     def lookup_rows(self, ids):
         return self.lookup_rows_async(ids).result()
@@ -1098,10 +1288,11 @@ class ShardedTables:
         finally:
             plan.busy = False
 
-    def lookup(self, ids, want_fm=False, out=None, fm=None):
+    def lookup(self, ids, want_fm=False, out=None, fm=None, want_lin=False, lin=None, lin_bias=None):
         """ids [B_local, F] int64 (global row ids; < 0 or >= vocab_f -> zeros) -> emb [B_local, F*K] fp32
-        (and the FM second-order logit [B_local, 1] when want_fm).  out / fm: preallocated results (stable addresses)."""
-        return self.lookup_async(ids, want_fm=want_fm, out=out, fm=fm).result()
+        (and the FM second-order logit [B_local, 1] when want_fm).  out / fm: preallocated results (stable addresses).
+        want_lin: the first-order term lin [B_local, 1] (+ lin_bias) comes last -- (emb, lin) or (emb, fm, lin); see lookup_async."""
+        return self.lookup_async(ids, want_fm=want_fm, out=out, fm=fm, want_lin=want_lin, lin=lin, lin_bias=lin_bias).result()
 
 
 _MASKED = []      # (hipStream_t, ExternalStream) pairs kept alive for the life of the process
@@ -1148,6 +1339,25 @@ class _ShardedLookup(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         ctx.st._backward_apply(ctx.saved, g)
+        return None, None, None
+
+
+class _ShardedLookupLinear(torch.autograd.Function):
+    """(emb, lin) = the lookup and the first-order term from ONE node: its backward receives both gradients, sends them along the same
+    exchange and lets each owner apply Adagrad to its embedding rows, then FTRL to its first-order rows -- one optimiser step."""
+
+    @staticmethod
+    def forward(ctx, st, ids, anchor):
+        if st._use_exact or ids.shape[0] == 0 and not st._collective():
+            emb, saved, lin = st._forward_saved(ids, with_lin=True)
+        else:
+            emb, saved, lin = st._forward_saved_fixed(ids, with_lin=True)
+        ctx.st, ctx.saved = st, saved
+        return emb, lin
+
+    @staticmethod
+    def backward(ctx, g, g_lin):
+        ctx.st._backward_apply(ctx.saved, g, g_lin.contiguous())
         return None, None, None
 
 
@@ -1214,19 +1424,32 @@ def xdeepfm_predict(model, tables, ids, linear_logit=None):
     (lookup_rows): per micro-batch the CIN layers and the tower read the received rows through the inverse positions
     (XDeepFM.forward_rows) -- the rank-local passes of the lookup are bucket + owner gather only; otherwise lookup() + forward_embedded().
     Bit for bit the same logits either way wherever a micro-batch and the whole batch take the same dense kernels (those are chosen by row
-    count: ops.dense_small_covers / dense_mid_covers / TOWER_MIN_ROWS).  `model`'s own embedding tables are not used; linear_logit [B_local, 1]: the first-order term,
-    computed by the caller (its 4-byte rows live wherever the caller keeps them)."""
+    count: ops.dense_small_covers / dense_mid_covers / TOWER_MIN_ROWS).  `model`'s own embedding tables are not used; linear_logit [B_local, 1]: the first-order term
+    computed by the caller (extra linear-only columns: their 4-byte rows live wherever the caller keeps them).  linear_logit = None and
+    first-order rows on the shards (ShardedTables.attach_linear): the term comes from the tables, riding on the same lookup, with
+    `model`'s linear_bias if it has one."""
     amax = tables.absmax()
     B = ids.shape[0]
     was_training = model.training
     model.eval()
+    from_tables = linear_logit is None and getattr(tables, "lin_rows", None) is not None
+    bias = getattr(model, "linear_bias", None) if from_tables else None
+    bias = bias.data.reshape(-1)[:1] if bias is not None else None
     try:
         if tables.check == "eager":
             out = torch.empty((B, 1), dtype=torch.float32, device=ids.device)
-            for s, e, rows, inv in tables.lookup_rows(ids):
+            if from_tables:
+                handle = tables.lookup_rows_async(ids, want_lin=True, lin_bias=bias)
+                chunks, linear_logit = handle.result(), handle.lin
+            else:
+                chunks = tables.lookup_rows(ids)
+            for s, e, rows, inv in chunks:
                 if e > s:
                     out[s:e] = model.forward_rows(rows, inv, None if linear_logit is None else linear_logit[s:e], absmax=amax)
             return out
+        if from_tables:
+            emb, linear_logit = tables.lookup(ids, want_lin=True, lin_bias=bias)
+            return model.forward_embedded(emb, linear_logit, range_ok=ops.f16_range_ok(amax))
         return model.forward_embedded(tables.lookup(ids), linear_logit, range_ok=ops.f16_range_ok(amax))
     finally:
         model.train(was_training)
@@ -1238,26 +1461,57 @@ class ShardedDeepFMTrainer:
     tower is replicated and its gradients are summed with bucketed all-reduces.  This is the reference's between-graph
     replicated training on parameter servers (partitioned embedding variables, deepFM.py:163-167; Adagrad on them, :61; the
     canned head's SUM loss reduction, :72 -- so gradients ADD over workers) restated for one process per GPU.
-    `model` supplies the tower (dnn_logit_fn) and F, K; its own embedding_weights are not used."""
+    `model` supplies the tower (dnn_logit_fn) and F, K; its own embedding_weights are not used.
+    linear = dict(lr=, l1=, l2=): the reference's third term, linear_logits (deepFM.py:199-223), trained with linear_optimizer='Ftrl'
+    (:58).  The first-order weights live on the shards (tables.attach_linear: co-located with the embedding rows, owner-side FTRL over the
+    global batch); `model`.linear_bias is replicated and takes a dense FTRL step with its gradient summed over the ranks (FTRL is not
+    linear in the gradient: the all-reduce comes first), so it must not be among dense_optimizer's parameters.  step() and predict() then
+    compute fm + dnn + lin; the multi-hot forms do not carry the term (a first-order term over bags needs linear_sparse_combiner on the
+    owner).  linear = None: the FM + DNN model, as before."""
 
-    def __init__(self, model, tables, lr_sparse, dense_optimizer, group=None, initial_accumulator_value=0.1):
+    def __init__(self, model, tables, lr_sparse, dense_optimizer, group=None, initial_accumulator_value=0.1, linear=None):
         self.model, self.tables, self.group = model, tables, group
         self.dense_params = [p for n, p in model.named_parameters()
                              if not (n.startswith("embedding_weights") or n.startswith("linear_weights"))]
         self.dense_optimizer = dense_optimizer
         tables.enable_training(lr_sparse, initial_accumulator_value)
+        self.linear = None
+        if linear is not None:
+            if getattr(tables, "lin_rows", None) is None:
+                raise ValueError("ShardedDeepFMTrainer(linear=...): the tables have no first-order weights (ShardedTables.attach_linear)")
+            bias = model.linear_bias
+            if any(p is bias for grp in dense_optimizer.param_groups for p in grp["params"]):
+                raise ValueError("ShardedDeepFMTrainer(linear=...): linear_bias takes the FTRL step here; leave it out of dense_optimizer")
+            hp = (float(linear["lr"]), float(linear.get("l1", 0.0)), float(linear.get("l2", 0.0)))
+            tables.enable_linear_training(*hp)
+            self.linear = hp
+            # the bias's FTRL slots ([TF-upstream] FtrlOptimizer: accumulator 0.1, linear 0)
+            self.bias_accum = torch.full_like(bias.data, float(linear.get("initial_accumulator_value", 0.1)))
+            self.bias_linear = torch.zeros_like(bias.data)
+
+    _NO_BAG_LINEAR = ("ShardedDeepFMTrainer(linear=...): the first-order term is not carried over multi-hot bags (it needs "
+                      "linear_sparse_combiner on the owning rank); use step() / predict() or linear=None")
 
     def step(self, ids, labels):
         """ids [B_local, F] global row ids, labels [B_local, 1] -> this rank's summed loss (detached)."""
         from . import autograd as ag
         m = self.model
         self.dense_optimizer.zero_grad(set_to_none=True)
-        emb = self.tables.lookup_train(ids)                                   # tables update inside backward()
-        logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb)             # fm_logit_fn + dnn_logit_fn, deepFM.py:337-338
+        if self.linear is not None:
+            m.linear_bias.grad = None
+            emb, lin = self.tables.lookup_train(ids, with_linear=True)        # both shards' rows update inside backward()
+            logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb) + (lin + m.linear_bias)      # ... + linear_logits, deepFM.py:339
+        else:
+            emb = self.tables.lookup_train(ids)                               # tables update inside backward()
+            logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb)         # fm_logit_fn + dnn_logit_fn, deepFM.py:337-338
         loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, labels, reduction="sum")
         loss.backward()
         allreduce_grads(self.dense_params, self.group)
         self.dense_optimizer.step()
+        if self.linear is not None:                                           # the bias: FTRL with the GLOBAL gradient
+            b = m.linear_bias
+            with torch.no_grad():
+                self.tables.backend.ftrl_dense(b.data, self.bias_accum, self.bias_linear, b.grad.contiguous(), *self.linear)
         return loss.detach()
 
     def step_bags(self, values, offsets, labels, weights=None, field_major=False):
@@ -1266,6 +1520,8 @@ class ShardedDeepFMTrainer:
         dense gradients summed over the ranks and the dense step.  values / offsets / weights as lookup_bags; labels [B_local, 1] ->
         this rank's summed loss (detached)."""
         from . import autograd as ag
+        if self.linear is not None:
+            raise NotImplementedError(self._NO_BAG_LINEAR)
         m = self.model
         self.dense_optimizer.zero_grad(set_to_none=True)
         comb = [c.combiner for c in m.dnn_feature_columns]
@@ -1301,9 +1557,16 @@ class ShardedDeepFMTrainer:
                     emb, fm = ops.gather_fm(rows_as_tables(rows, m.F), inv)
                     lg = m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(amax))
                 out[s:e] = lg
+            bias = m.linear_bias.data.reshape(-1)[:1] if self.linear is not None else None
             if m.units == 1 and self.tables.check == "eager":
+                if self.linear is not None:               # the first-order term rides on the same lookup; added to both routes' logits
+                    _, lin = self.tables.lookup_async(ids, consumer=consumer, want_lin=True, lin_bias=bias).result()
+                    return out + lin
                 self.tables.lookup_consume(ids, consumer)
                 return out
+            if self.linear is not None:
+                emb, fm, lin = self.tables.lookup(ids, want_fm=True, want_lin=True, lin_bias=bias)
+                return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(amax)) + lin
             emb, fm = self.tables.lookup(ids, want_fm=True)
             return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(amax))      # the SHARDED tables' magnitude, not the model's own
         finally:
@@ -1314,6 +1577,8 @@ class ShardedDeepFMTrainer:
         """Inference logits [B_local, 1] of the same FM + DNN model over multi-hot bags of the row-sharded tables (a history column of the
         reference's DeepFM, deepFM.py:53,77,84): lookup_bags(want_fm=True) with every column's combiner and max_norm, then the tower with
         the FM term added -- what predict() does for one-hot ids."""
+        if self.linear is not None:
+            raise NotImplementedError(self._NO_BAG_LINEAR)
         m = self.model
         was_training = m.training
         m.eval()

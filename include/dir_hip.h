@@ -535,6 +535,43 @@ int dir_sparse_adagrad_sorted_bags_f32(float* const* tables, float* const* accum
                                        const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
                                        dir_stream_t stream);
 
+/* The first-order (linear) term of DeepFM over row-sharded weights (ShardedTables.attach_linear / lookup(want_lin=) /
+ * lookup_train(with_linear=); reference: linear_logits under the embedding tables' partitioner, deepFM.py:199-223, 255-275).  Slot f's
+ * weights live beside slot f's embedding rows, on the rank that owns them, as packed 16-byte training rows [w | n | z | -]
+ * (dir_linear_onehot_rows_f32's layout, row stride row_ld floats, the weight in column 0).  The term rides on the embedding lookup's id
+ * exchange: no second bucket pass, no second id all-to-all; one float per entry travels back.
+ * dir_shard_linear_gather_f32 (owner): the received payload -> one weight per payload word.  cap > 0: recv = P slabs of cap + 1 int64
+ *   words as dir_gather_slabs_f32 takes them (header word: low 32 bits = valid slots), out[s*cap + j]; n is ignored; P <= 64,
+ *   P * cap < 2^31.  cap == 0: recv = a flat payload of n words (0 <= n < 2^31), out[i].  A word p = local_row * F + slot reads
+ *   rows[slot][local_row * row_ld]; p < 0, a slot behind its slab's header and a row >= local_rows[slot] (local_rows: int64 [F] device
+ *   array, or NULL = trust the payload) write 0.0f -- unlike dir_gather_slabs_f32 EVERY output word is written, so nothing uninitialised
+ *   enters the exchange.
+ * dir_shard_linear_finish_f32 (requester): out[b * out_ld] = sum_f wback[inv[b*stride_b + f*stride_f]] + bias[0] -- inv < 0 (or >=
+ *   n_back) adds 0.0f, bias may be NULL -- in the order and arithmetic of dir_linear_onehot_rows_f32: acc = 0; acc += w_f for f = 0..F-1;
+ *   acc + bias.  At world size 1, and at any world size (the sum runs per sample in slot order, whoever the owners are), the result is
+ *   dir_linear_onehot_rows_f32's over the unsharded rows bit for bit.  The strides take the sample-major inv (F, 1) and the field-major
+ *   one of dir_shard_bucket_cap_dedup (1, B).
+ * dir_shard_linear_grad_f32 (requester, the transpose of the finish): send [n_send] is zero-filled, then send[inv[b, f]] = g[b * g_ld]
+ *   for every entry with 0 <= inv < n_send.  Training lookups are never de-duplicated: one writer per position, plain stores.
+ *   B * F < 2^31, n_send < 2^31.
+ * dir_sparse_ftrl_rows_sorted_payload_f32 (owner): dir_sparse_ftrl_rows_sorted_f32's update driven by a payload, as
+ *   dir_sparse_adagrad_sorted_payload_f32 is for Adagrad: payload [n] int64 as received from all ranks (p < 0 pruned), grad [n] floats
+ *   in the same order, rows / row_base / total_rows of this rank's packed rows.  All entries of a row -- from one rank or several, from
+ *   any micro-batch -- are summed BEFORE n, z and w move (one synchronous FTRL-Proximal step over the global batch; lr > 0, l1, l2 >= 0).
+ *   Workspace: dir_sparse_adagrad_sorted_workspace_bytes(n, 1, 1, total_rows) device bytes, 256-byte aligned.  sorted_from (or NULL):
+ *   the workspace of a sorted update of the SAME payload (n, row_base, total_rows) that ran just before on this stream -- the Adagrad
+ *   step of the co-located embedding rows (dir_sparse_adagrad_sorted_payload_f32): its sorted (row, entry) pairs are read and the key
+ *   pass and the sort are skipped (the pair arrays' offsets depend on n only). */
+int dir_shard_linear_gather_f32(const float* const* rows, int64_t row_ld, const int64_t* local_rows, int F, const int64_t* recv, int P,
+                                int64_t cap, int64_t n, float* out, dir_stream_t stream);
+int dir_shard_linear_finish_f32(const float* wback, int64_t n_back, const int64_t* inv, int64_t stride_b, int64_t stride_f, int F,
+                                const float* bias, int64_t B, float* out, int64_t out_ld, dir_stream_t stream);
+int dir_shard_linear_grad_f32(const float* g, int64_t g_ld, const int64_t* inv, int64_t stride_b, int64_t stride_f, int F, int64_t B,
+                              float* send, int64_t n_send, dir_stream_t stream);
+int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F, const int64_t* payload, int64_t n, const float* grad, float lr, float l1,
+                                            float l2, const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
+                                            const void* sorted_from, dir_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * A5 / A9  hidden layers of the DNN towers: Y[M, N] = act(X[M, Kd] . Wt[N, Kd]^T + bias[N])   (row strides x_ld, w_ld, y_ld).
  *   reference: dnn_logit_fn, models/DeepFM/deepFM.py:295-300; _deep_architecture,
