@@ -76,8 +76,44 @@ def local_slice(vocab, parts, first, P, rank):
     return div_range(vocab, parts, j) if j < parts else (0, 0)
 
 
+def partition_layout(vocab, K, P, rank, partitions=None):
+    """(parts, first, slices) of tables [vocab_f, K] over P ranks: slice count and rank of slice 0 per table, and the rows [start, end)
+    of every table that `rank` holds.  partitions: None = every table cut into P slices, slice r on rank r; "reference" = the reference
+    partitioner's slice-count rule (partitions_for with max_partitions = P), the slices dealt round-robin (place_slices); or an explicit
+    list of slice counts, dealt the same way."""
+    if partitions is None:
+        parts, first = [P] * len(vocab), [0] * len(vocab)
+    else:
+        parts = [partitions_for(v, K, P) for v in vocab] if partitions == "reference" else [int(p) for p in partitions]
+        if len(parts) != len(vocab) or any(p < 1 or p > P for p in parts):
+            raise ValueError("partitions: one slice count in [1, P=%d] per table" % P)
+        first = place_slices(parts, P)
+    return parts, first, [local_slice(v, parts[f], first[f], P, rank) for f, v in enumerate(vocab)]
+
+
 def _round_up(x, m):
     return (int(x) + m - 1) // m * m
+
+
+def _host_staged(t, group):
+    """Whether a collective on `t` goes through host memory: the development transport (several ranks on ONE GPU over gloo), never on a
+    multi-GPU node."""
+    return _HOST_STAGED or (t.is_cuda and dist.get_backend(group) == "gloo")
+
+
+def _wait(work):
+    if work is not None:
+        work.wait()
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
 
 
 class HipBackend:
@@ -91,8 +127,8 @@ class HipBackend:
         self.P = P
         self.parts_dev, self.first_dev = parts_dev, first_dev
         self._back = None
-        self._back_ts = None
-        self._finish_ts = {}
+        self._back_key = None         # rows_as_tables' key of the exact path's last row buffer
+        self.lin_ts, self._ftrl = None, None          # attach_linear
 
     # ---- variable-size (exact) path -----------------------------------------------------------------------
     def bucket(self, flat_ids):
@@ -110,16 +146,14 @@ class HipBackend:
     def back_buffer(self, n, K, device):
         if self._back is None or self._back.shape[0] != n:
             self._back = torch.empty((n, K), dtype=torch.float32, device=device)
-            self._back_ts = None
         return self._back
 
     def finish(self, back, inv, B, F, want_fm, out=None, fm=None):
-        if self._back_ts is None or self._back_ts.tables[0].data_ptr() != back.data_ptr() or self._back_ts.vocab[0] != back.shape[0]:
-            self._back_ts = ops.TableSet([back] * F)
-            self._back_ts.row_policy = "reuse"   # just received: largely cache-resident
-        if want_fm:
-            return ops.gather_fm(self._back_ts, inv.view(B, F), out=out, fm=fm)
-        return ops.embedding_bag(self._back_ts, inv.view(B, F), out=out), None
+        key = _rows_key(back, F)
+        if key != self._back_key:     # the exact path's buffer moved (training: a fresh one per lookup): the view of the last one goes
+            _ROWS_TS.pop(self._back_key, None)     # with it, or the cache would pin every buffer it has ever seen
+            self._back_key = key
+        return self.finish_chunk(back, inv.view(B, F), want_fm, out, fm)
 
     # ---- fixed-capacity path ------------------------------------------------------------------------------
     def new_workspace(self, device):
@@ -145,18 +179,11 @@ class HipBackend:
     def gather_slabs(self, recv, cap, out):
         ops.gather_slabs(self.ts, recv, self.P, cap, out)
 
-    def finish_chunk(self, back, inv2d, want_fm, out, fm):
-        key = (back.data_ptr(), back.shape[0], inv2d.shape[1])
-        ts = self._finish_ts.get(key)
-        if ts is None:
-            if len(self._finish_ts) > 64:
-                self._finish_ts.clear()
-            ts = self._finish_ts[key] = ops.TableSet([back] * inv2d.shape[1])
-            ts.row_policy = "reuse"
+    def finish_chunk(self, back, inv2d, want_fm, out=None, fm=None):
+        ts = rows_as_tables(back, inv2d.shape[1])
         if want_fm:
-            ops.gather_fm(ts, inv2d, out=out, fm=fm)
-        else:
-            ops.embedding_bag(ts, inv2d, out=out)
+            return ops.gather_fm(ts, inv2d, out=out, fm=fm)
+        return ops.embedding_bag(ts, inv2d, out=out), None
 
     # ---- multi-hot bags, pooled on the owner (lookup_bags) ------------------------------------------------
     def new_bags_workspace(self, device):
@@ -223,22 +250,28 @@ class HipBackend:
 _ROWS_TS = {}
 
 
+def _rows_key(rows, F):
+    return rows.data_ptr(), rows.shape[0], rows.shape[1], F
+
+
 def rows_as_tables(rows, F, absmax=None):
-    """The received row buffer of a lookup_consume() micro-batch as a TableSet of F identical "tables" (one per slot), cached by
-    address: what ops.gather_fm / ops.tower(gather=...) take as their tables, with the inverse positions as ids.
+    """A received row buffer -- of a lookup_consume() micro-batch, or of the lookup's own finish pass (HipBackend.finish / finish_chunk) --
+    as a TableSet of F identical "tables" (one per slot), cached by address: what ops.gather_fm / ops.embedding_bag /
+    ops.tower(gather=...) take as their tables, with the inverse positions as ids.  (The gathers never read TableSet.absmax -- only
+    TableSet.range_ok and ops.tower do -- so an absmax= left on an entry by one caller changes nothing a finish pass computes.)
     absmax: the largest |value| of the SHARDED tables (ShardedTables.absmax()): the magnitude bound a kernel that picks its split
     arithmetic by the tables' range (ops.tower(split=None)) must see -- the buffer's own contents change with every lookup, behind the
     back of TableSet.absmax()'s version-keyed cache."""
-    key = (rows.data_ptr(), rows.shape[0], rows.shape[1], F)
+    key = _rows_key(rows, F)
     ts = _ROWS_TS.get(key)
     if ts is None:
-        if len(_ROWS_TS) > 64:
+        if len(_ROWS_TS) > 192:      # (room for the views of every live plan's buffers, the finish passes' and the consumers' alike)
             _ROWS_TS.clear()
         ts = _ROWS_TS[key] = ops.TableSet([rows] * F)
         ts.row_policy = "reuse"      # just received: largely cache-resident
     if absmax is not None:
         ts.absmax = lambda every=1, _v=float(absmax): _v
-    return ts
+    return ops.held(ts)              # a graph captured now reads its pointer array: the capture's hold keeps it past the clear() above
 
 
 class _Plan:
@@ -246,9 +279,10 @@ class _Plan:
     so nothing is allocated per lookup and a lookup can be captured in a HIP graph.  Only the slab capacity has to agree across
     the ranks (equal-split exchanges); everything sized by the batch is local."""
 
-    def __init__(self, st, B, cap):
+    def __init__(self, st, B, cap, train=False):
         dev, P, F, K = st.device, st.P, st.F, st.K
         self.B, self.cap = B, cap
+        self.train = train            # the training pipeline's plan: its verdicts move _cap_train, not _cap (_learn)
         self.P, self.device, self.lrows = P, dev, None
         C = self.C = st._C()
         per = -(-B // C) if B else 0
@@ -285,11 +319,14 @@ class _Plan:
 
 class _BagPlan:
     """Persistent buffers of lookup_bags for one (local batch size, entry capacity, pair capacity): stable addresses, so that a lookup can
-    be captured in a HIP graph after one eager call.  Only the two capacities have to agree across the ranks."""
+    be captured in a HIP graph after one eager call.  Only the two capacities have to agree across the ranks.
+    train: a plan of lookup_bags_train -- `busy` from a forward to its backward, and pinned host words of its own for the verdict."""
 
-    def __init__(self, st, B, cap_e, cap_b):
+    def __init__(self, st, B, cap_e, cap_b, train=False):
         dev, P, F, K = st.device, st.P, st.F, st.K
         self.cap_e, self.cap_b = cap_e, cap_b
+        self.busy = False
+        self.host = torch.empty(3, dtype=torch.int64, pin_memory=True) if train and dev.type == "cuda" else None
         i64 = dict(dtype=torch.int64, device=dev)
         alias = not st._collective()                     # one rank, no collectives: receive buffers ARE the send buffers
         self.send = torch.empty(P * (cap_e + 1) * 2, **i64)         # P slabs of (cap_e + 1) 16-byte records
@@ -309,14 +346,14 @@ class _Lookup:
     applies the overflow policy and returns emb (or (emb, fm)).  Issue the NEXT lookup before calling result() -- or before the
     compute that consumes this one -- and the exchange runs under that compute."""
 
-    def __init__(self, st, plan, ids, want_fm, out, fm, done, exact=None, consumer=None, lin=None):
+    def __init__(self, st, plan, ids, want_fm, out, fm, done, consumer=None, lin=None):
+        """plan None: the lookup ran on the exact path, on the caller's stream -- out / fm / lin are complete, nothing is left to check."""
         self.st, self.plan, self.ids, self.want_fm, self.out, self.fm, self.done = st, plan, ids, want_fm, out, fm, done
-        self.exact = exact
         self.consumer = consumer
         self.lin = lin                # None, or (lin [B, 1], bias | None): the first-order term rides along (want_lin)
         self.fin = plan.fin if plan is not None else None      # this lookup's completion events on the side streams
-        self.joined = exact is not None
-        self.checked = exact is not None or done is False
+        self.joined = plan is None
+        self.checked = plan is None or done is False
 
     def join(self):
         """The caller's stream waits for THIS lookup's last kernels (events recorded when it was enqueued), not for whatever else has
@@ -331,19 +368,15 @@ class _Lookup:
     def result(self):
         st = self.st
         self.join()
-        if self.exact is not None:
-            return self.exact
-        if not self.checked:
-            if st.check == "eager":
-                self.checked = True
-                over, demand = st._read_flags(self.plan, self.done)
-                st._learn(self.plan, over, demand)
-                if over:                                      # rare: repeat on the exact path (results overwrite out / fm in stream order)
-                    st.stats["fallbacks"] += 1
-                    st._lookup_exact(self.ids, self.want_fm, out=self.out, fm=self.fm, consumer=self.consumer, lin=self.lin)
-        if self.lin is not None:
-            return (self.out, self.fm, self.lin[0]) if self.want_fm else (self.out, self.lin[0])
-        return (self.out, self.fm) if self.want_fm else self.out
+        if not self.checked and st.check == "eager":
+            self.checked = True
+            over, demand = st._read_flags(self.plan, self.done)
+            st._learn(self.plan, over, demand)
+            if over:                                          # rare: repeat on the exact path (results overwrite out / fm in stream order)
+                st.stats["fallbacks"] += 1
+                st._lookup_exact(self.ids, self.want_fm, out=self.out, fm=self.fm, consumer=self.consumer, lin=self.lin)
+        res = (self.out,) + ((self.fm,) if self.want_fm else ()) + ((self.lin[0],) if self.lin is not None else ())
+        return res if len(res) > 1 else self.out              # emb | (emb, fm) | (emb, lin) | (emb, fm, lin); emb = None under a consumer
 
 
 class _RowsLookup:
@@ -392,16 +425,8 @@ class ShardedTables:
         self.local_tables = list(local_tables)
         self.K = self.local_tables[0].shape[1]
         P = self.P
-        if partitions is None:
-            self.parts, self.first = [P] * self.F, [0] * self.F
-        else:
-            self.parts = ([partitions_for(v, self.K, P) for v in self.vocab] if partitions == "reference"
-                          else [int(p) for p in partitions])
-            if len(self.parts) != self.F or any(p < 1 or p > P for p in self.parts):
-                raise ValueError("partitions: one slice count in [1, P=%d] per table" % P)
-            self.first = place_slices(self.parts, P)
-        for f, t in enumerate(self.local_tables):
-            s, e = local_slice(self.vocab[f], self.parts[f], self.first[f], P, self.rank)
+        self.parts, self.first, self.slices = partition_layout(self.vocab, self.K, P, self.rank, partitions)   # slices: this rank's [start, end)
+        for f, (t, (s, e)) in enumerate(zip(self.local_tables, self.slices)):
             if t.shape[0] != e - s:
                 raise ValueError("table %d: rank %d must hold rows [%d,%d) (%d rows), got %d" % (f, self.rank, s, e, e - s, t.shape[0]))
         self.device = self.local_tables[0].device
@@ -419,11 +444,14 @@ class ShardedTables:
         self._cap = None              # the agreed slab capacity (collective mode); _cap0: its first value (the no-skew demand)
         self._cap_train = None        # the training pipeline's own capacity (never shrunk by de-duplicated inference verdicts)
         self._cap0 = None
+        self._share0 = None           # an owner's share of a micro-batch without skew (_agree_cap)
         self._use_exact = mode == "exact"
         self._unchecked = []          # lookups whose overflow verdict has not been read yet (check = lazy / never)
         self._slot = 0
         self._inflight = {}
-        self._streams = None
+        self._streams = None          # the two side streams of the pipeline and the verdict's stream (_ensure_streams)
+        self._chk_stream = None
+        self.optimizer = None         # enable_training: the owner-side sparse Adagrad
         self.stats = {"lookups": 0, "fallbacks": 0, "cap": None}
         self._updates = 0             # owner-side optimiser steps applied so far (the same on every rank: absmax()'s collective decision)
         self._absmax_all = None
@@ -434,6 +462,7 @@ class ShardedTables:
         self._bag_train_plans = {}    # lookup_bags_train's own plans: an inference lookup_bags between a forward and its backward never
                                       # touches the slabs, pos, mask and denom that backward reads
         self.lin_rows = None          # attach_linear: this rank's packed first-order rows [local rows, 4] = [w | n | z | -], one per slot
+        self._lin_arena = None        # ... and the one allocation they are blocks of
         self._lin_hp = None           # enable_linear_training: (lr, l1, l2) of the owner-side FTRL
 
     @classmethod
@@ -442,18 +471,8 @@ class ShardedTables:
         P = dist.get_world_size(group) if dist.is_initialized() else 1
         rank = dist.get_rank(group) if dist.is_initialized() else 0
         vocab = [t.shape[0] for t in full_tables]
-        K = full_tables[0].shape[1]
-        partitions = kw.get("partitions")
-        if partitions is None:
-            parts, first = [P] * len(vocab), [0] * len(vocab)
-        else:
-            parts = [partitions_for(v, K, P) for v in vocab] if partitions == "reference" else [int(p) for p in partitions]
-            first = place_slices(parts, P)
-        loc = []
-        for f, t in enumerate(full_tables):
-            s, e = local_slice(vocab[f], parts[f], first[f], P, rank)
-            loc.append(t[s:e].contiguous())
-        return cls(loc, vocab, group=group, **kw)
+        _, _, slices = partition_layout(vocab, full_tables[0].shape[1], P, rank, kw.get("partitions"))
+        return cls([t[s:e].contiguous() for t, (s, e) in zip(full_tables, slices)], vocab, group=group, **kw)
 
     # ---- the first-order (linear) term: slot f's weights live beside slot f's embedding rows ---------------------------
     def attach_linear(self, local_weights, initial_accumulator_value=0.1):
@@ -487,11 +506,7 @@ class ShardedTables:
 
     def attach_linear_from_full(self, full_weights, initial_accumulator_value=0.1):
         """attach_linear from replicated full weight vectors ([vocab_f] or [vocab_f, 1]), sliced as from_full slices the tables."""
-        loc = []
-        for f, w in enumerate(full_weights):
-            s, e = local_slice(self.vocab[f], self.parts[f], self.first[f], self.P, self.rank)
-            loc.append(w.reshape(-1)[s:e])
-        return self.attach_linear(loc, initial_accumulator_value)
+        return self.attach_linear([w.reshape(-1)[s:e] for w, (s, e) in zip(full_weights, self.slices)], initial_accumulator_value)
 
     def _need_linear(self, what):
         if self.lin_rows is None:
@@ -526,30 +541,37 @@ class ShardedTables:
         number of collectives)."""
         return self.chunks if self._collective() else 1
 
-    def _host_staged(self, t):
-        return _HOST_STAGED or (t.is_cuda and dist.get_backend(self.group) == "gloo")
+    def _a2a_staged(self, out, inp, out_splits=None, in_splits=None):
+        o = torch.empty(out.shape, dtype=out.dtype)
+        dist.all_to_all_single(o, inp.cpu(), out_splits, in_splits, group=self.group)
+        out.copy_(o)
 
     def _a2a(self, out, inp, out_splits, in_splits):
-        if self._collective():
-            if self._host_staged(out):     # development transport (several ranks on ONE GPU over gloo): never on a multi-GPU node
-                o = torch.empty(out.shape, dtype=out.dtype)
-                dist.all_to_all_single(o, inp.cpu(), out_splits, in_splits, group=self.group)
-                out.copy_(o)
-            else:
-                dist.all_to_all_single(out, inp, out_splits, in_splits, group=self.group)
-        else:
+        if not self._collective():
             out.copy_(inp)
+        elif _host_staged(out, self.group):
+            self._a2a_staged(out, inp, out_splits, in_splits)
+        else:
+            dist.all_to_all_single(out, inp, out_splits, in_splits, group=self.group)
 
     def _a2a_equal(self, out, inp):
         """Equal-split all-to-all, asynchronous where the transport allows: -> a work handle (or None when done / aliased)."""
         if not self._collective():
             return None                                   # out IS inp (see _Plan)
-        if self._host_staged(out):
-            o = torch.empty(out.shape, dtype=out.dtype)
-            dist.all_to_all_single(o, inp.cpu(), group=self.group)
-            out.copy_(o)
-            return None
+        if _host_staged(out, self.group):
+            return self._a2a_staged(out, inp)
         return dist.all_to_all_single(out, inp, group=self.group, async_op=True)
+
+    def _max_over_ranks(self, values):
+        """MAX over the ranks of a few host integers (a capacity agreement): on the host for gloo, through the device otherwise."""
+        t = torch.tensor(values, dtype=torch.int64)
+        if dist.get_backend(self.group) == "gloo":
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        else:
+            td = t.to(self.device)
+            dist.all_reduce(td, op=dist.ReduceOp.MAX, group=self.group)
+            t = td.cpu()
+        return [int(v) for v in t]
 
     # ---- training: the gradient rows travel the forward's row exchange backwards and the OWNER updates its shard -------
     def enable_training(self, lr, initial_accumulator_value=0.1):
@@ -569,37 +591,37 @@ class ShardedTables:
         bias is a replicated dense variable of the caller's).  Its backward receives both gradients: the row gradients and d lin travel
         the same equal-split exchange, then every owner applies Adagrad to its embedding rows and FTRL to its first-order rows (in that
         order: the FTRL step reuses the Adagrad step's sort of the payload) -- one optimiser step."""
-        if getattr(self, "optimizer", None) is None:
+        if self.optimizer is None:
             raise RuntimeError("call enable_training(lr) first")
-        anchor = torch.zeros((), dtype=torch.float32, device=ids.device, requires_grad=True)
         if with_linear:
             self._need_linear("lookup_train(with_linear=True)")
             if self._lin_hp is None:
                 raise RuntimeError("call enable_linear_training(lr) first")
-            return _ShardedLookupLinear.apply(self, ids, anchor)
-        return _ShardedLookup.apply(self, ids, anchor)
+        anchor = torch.zeros((), dtype=torch.float32, device=ids.device, requires_grad=True)
+        return _ShardedLookup.apply(self, ids, bool(with_linear), anchor)
 
-    def _forward_saved(self, ids, with_lin=False):
+    def _forward_train(self, ids, with_lin):
+        """The forward of a training lookup -> (emb, what the backward needs, lin [B, 1] | None).  On the fixed-capacity pipeline (never
+        de-duplicated: the backward needs one slab position per entry) unless mode == "exact", "auto" has given up on slabs, or a slab
+        overflows.  The overflow verdict is read here (the one host wait of a training lookup; it covers work that is long done when
+        the dense part of the model has been enqueued in between); the exact path keeps a row buffer of its own."""
         B, F = ids.shape
-        K, be = self.K, self.backend
-        flat = ids.reshape(-1).contiguous()
-        n = flat.numel()
-        payload, inv, send_counts, _ = be.bucket(flat)
-        recv_counts = torch.empty_like(send_counts)
-        self._a2a(recv_counts, send_counts, None, None)
-        both = torch.stack([send_counts, recv_counts]).tolist()
-        sc, rc = [int(v) for v in both[0]], [int(v) for v in both[1]]
-        recv = torch.empty(sum(rc), dtype=torch.int64, device=flat.device)
-        self._a2a(recv, payload, rc, sc)
-        rows = be.gather_packed(recv)
-        back = torch.empty((n, K), dtype=torch.float32, device=flat.device)       # private: kept alive by autograd users
-        self._a2a(back.view(-1), rows.reshape(-1), [c * K for c in sc], [c * K for c in rc])
-        emb, _ = be.finish(back, inv, B, F, False)
-        if with_lin:
-            lin = torch.empty((B, 1), dtype=torch.float32, device=flat.device)
-            self._linear_exact(recv, inv.view(B, F), sc, rc, (lin, None))
-            return emb, ("exact", inv, sc, rc, recv), lin
-        return emb, ("exact", inv, sc, rc, recv)
+        lin = (torch.empty((B, 1), dtype=torch.float32, device=ids.device), None) if with_lin else None
+        if not (self._use_exact or B == 0 and not self._collective()):
+            out = torch.empty((B, F * self.K), dtype=torch.float32, device=ids.device)
+            plan = self._plan(B, "train")
+            done = self._enqueue(plan, ids, False, out, None, dedup=False, lin=lin)
+            _Lookup(self, plan, ids, False, out, None, done).join()
+            over = False
+            if done is not False:
+                over, demand = self._read_flags(plan, done)
+                self._learn(plan, over, demand)
+            if not over:
+                return out, ("fixed", plan), lin[0] if with_lin else None
+            self.stats["fallbacks"] += 1
+        back, inv, sc, rc, recv = self._exchange_exact(ids, lin, private=True)
+        emb, _ = self.backend.finish(back, inv, B, F, False)
+        return emb, ("exact", inv, sc, rc, recv), lin[0] if with_lin else None
 
     def _linear_exact(self, recv, inv2d, sc, rc, lin):
         """The linear term on the exact path: one weight per received payload word, sent back with the row exchange's splits (one float
@@ -611,25 +633,6 @@ class ShardedTables:
         lback = torch.empty(n, dtype=torch.float32, device=recv.device)
         self._a2a(lback, lw, sc, rc)
         be.linear_finish(lback, inv2d, lin[1], lin[0])
-
-    def _forward_saved_fixed(self, ids, with_lin=False):
-        """Training forward on the fixed-capacity pipeline (never de-duplicated: the backward needs one slab position per entry).
-        The overflow verdict is read here (the one host wait of a training lookup; it covers work that is long done when the
-        dense part of the model has been enqueued in between)."""
-        B, F = ids.shape
-        out = torch.empty((B, F * self.K), dtype=torch.float32, device=ids.device)
-        plan = self._plan(B, "train")
-        lin = (torch.empty((B, 1), dtype=torch.float32, device=ids.device), None) if with_lin else None
-        done = self._enqueue(plan, ids, False, out, None, dedup=False, lin=lin)
-        lk = _Lookup(self, plan, ids, False, out, None, done)
-        lk.join()
-        if done is not False:
-            over, demand = self._read_flags(plan, done)
-            self._learn(plan, over, demand)
-            if over:
-                self.stats["fallbacks"] += 1
-                return self._forward_saved(ids, with_lin)
-        return (out, ("fixed", plan), lin[0]) if with_lin else (out, ("fixed", plan))
 
     def _backward_apply(self, saved, g_emb, g_lin=None):
         """g_lin (lookup_train(with_linear=True)): d loss / d lin [B_local, 1].  Its values go where the weights came back from and travel
@@ -690,7 +693,11 @@ class ShardedTables:
             be.apply_ftrl(recv, lrecv, hp[0], hp[1], hp[2], sorted_by=self.optimizer)
 
     # ---- the exact, variable-size lookup (one host read of the split sizes) --------------------------------
-    def _lookup_exact(self, ids, want_fm, out=None, fm=None, consumer=None, lin=None):
+    def _exchange_exact(self, ids, lin=None, private=False):
+        """Bucket, exchange the ids, gather on the owner, exchange the rows (and the linear term behind them).  -> (back [n, K]: the rows
+        in exchange order, inv [n]: every entry's position in it, send counts, receive counts, the payload received).
+        private: a fresh row buffer instead of the backend's cached one (training: an inference lookup between a forward and its backward
+        must not touch it)."""
         B, F = ids.shape
         K, be = self.K, self.backend
         flat = ids.reshape(-1).contiguous()
@@ -703,14 +710,19 @@ class ShardedTables:
         recv = torch.empty(sum(rc), dtype=torch.int64, device=flat.device)
         self._a2a(recv, payload, rc, sc)
         rows = be.gather_packed(recv)                                       # HIP (owner side)
-        back = be.back_buffer(n, K, flat.device)
+        back = torch.empty((n, K), dtype=torch.float32, device=flat.device) if private else be.back_buffer(n, K, flat.device)
         self._a2a(back.view(-1), rows.reshape(-1), [c * K for c in sc], [c * K for c in rc])
         if lin is not None:
             self._linear_exact(recv, inv.view(B, F), sc, rc, lin)
+        return back, inv, sc, rc, recv
+
+    def _lookup_exact(self, ids, want_fm, out=None, fm=None, consumer=None, lin=None):
+        B, F = ids.shape
+        back, inv = self._exchange_exact(ids, lin)[:2]
         if consumer is not None:                                            # (lookup_consume: the caller's kernel reads the rows where they are)
             consumer(0, B, back, inv.view(B, F))
             return None, None
-        return be.finish(back, inv, B, F, want_fm, out=out, fm=fm)          # HIP: un-permute (+ FM)
+        return self.backend.finish(back, inv, B, F, want_fm, out=out, fm=fm)    # HIP: un-permute (+ FM)
 
     # ---- the fixed-capacity, pipelined lookup ---------------------------------------------------------------
     def _default_cap(self, n_chunk):
@@ -727,15 +739,9 @@ class ShardedTables:
         Bm = max(int(B), int(self.max_batch or 0))
         n_chunk = max(1, -(-Bm // self._C())) * self.F
         cap = self._default_cap(n_chunk)
-        t = torch.tensor([cap, n_chunk], dtype=torch.int64)
-        if dist.get_backend(self.group) == "gloo":
-            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
-        else:
-            td = t.to(self.device)
-            dist.all_reduce(td, op=dist.ReduceOp.MAX, group=self.group)
-            t = td.cpu()
-        self._cap = self._cap_train = self._cap0 = int(t[0])
-        self._share0 = float(t[1]) / self.P               # an owner's share of a micro-batch without skew
+        cap, n_chunk = self._max_over_ranks([cap, n_chunk])
+        self._cap = self._cap_train = self._cap0 = cap
+        self._share0 = float(n_chunk) / self.P            # an owner's share of a micro-batch without skew
 
     def _plan(self, B, slot=0):
         if self._collective():
@@ -757,8 +763,7 @@ class ShardedTables:
             self._plans = {k: v for k, v in self._plans.items() if live(k)}
             if len(self._plans) > 8:
                 self._plans.clear()
-            plan = self._plans[key] = _Plan(self, B, cap)
-            plan.train = slot == "train"
+            plan = self._plans[key] = _Plan(self, B, cap, train=slot == "train")
         self.stats["cap"] = cap
         return plan
 
@@ -809,14 +814,10 @@ class ShardedTables:
             be.bucket_cap(ids[s:e], cap, plan.send[c], plan.inv[c], plan.counts[c], plan.flags[c], plan.ws[c], stat=plan.cstat[c], dedup=dedup)
             return self._a2a_equal(plan.recv[c], plan.send[c])
 
-        def wait(w):
-            if w is not None:
-                w.wait()
-
         def finish(c):
             s, e = plan.bounds[c]
             if lin is not None:
-                wait(wl[c])
+                _wait(wl[c])
                 if e > s:
                     be.linear_finish(lback[c], be.inv2d(plan.inv[c], e - s, F, dedup), lin[1], lin[0][s:e])
             if e > s and consumer is not None:
@@ -833,7 +834,7 @@ class ShardedTables:
                 with on(c + 1):
                     wi[c + 1] = bucket(c + 1)
             with on(c):
-                wait(wi[c])
+                _wait(wi[c])
                 if S:
                     ev_ids.append(S[c % 2].record_event())
                 be.gather_slabs(plan.recv[c], cap, plan.rows[c])
@@ -843,7 +844,7 @@ class ShardedTables:
                     wl[c] = self._a2a_equal(lback[c], lrows[c])
             if c >= 1:
                 with on(c - 1):
-                    wait(wr[c - 1])
+                    _wait(wr[c - 1])
                     finish(c - 1)
         # every micro-batch's slabs have arrived: their headers carry every sender's demand -> the verdict all ranks agree on
         done = None
@@ -857,7 +858,7 @@ class ShardedTables:
                 plan.host.copy_(plan.stat, non_blocking=True)
                 done = self._chk_stream.record_event()
         with on(C - 1):
-            wait(wr[C - 1])
+            _wait(wr[C - 1])
             finish(C - 1)
         plan.fin = [s.record_event() for s in S] if S else None
         return done
@@ -877,7 +878,7 @@ class ShardedTables:
         """Capacity policy after a checked lookup (inputs identical on every rank): grow to the observed demand after an overflow;
         with dedup, shrink to what de-duplication left; give up on fixed slabs (mode auto) when one owner wants more than twice
         the no-skew share -- padding every slab to that size would cost more link bytes than the exact path's host read."""
-        train = getattr(plan, "train", False)
+        train = plan.train
         if plan.cap != (self._cap_train if train else self._cap):
             return                                         # a verdict about slabs that are no longer in use
         cap = plan.cap
@@ -935,11 +936,7 @@ class ShardedTables:
             lt = (lin if lin is not None else torch.empty((B, 1), dtype=torch.float32, device=ids.device), lin_bias)
         if self._use_exact or (B == 0 and not self._collective()):
             emb, fmo = self._lookup_exact(ids, want_fm, out=out, fm=fm, consumer=consumer, lin=lt)
-            if lt is not None:
-                exact = (emb, fmo, lt[0]) if want_fm else (emb, lt[0])
-            else:
-                exact = (emb, fmo) if want_fm else (emb if consumer is None else ())
-            return _Lookup(self, None, ids, want_fm, emb, fmo, None, exact=exact, consumer=consumer, lin=lt)
+            return _Lookup(self, None, ids, want_fm, emb, fmo, None, consumer=consumer, lin=lt)
         if out is None and consumer is None:
             out = torch.empty((B, F * self.K), dtype=torch.float32, device=ids.device)
         if want_fm and fm is None:
@@ -992,21 +989,17 @@ class ShardedTables:
                 return e
             return time.perf_counter()
 
-        def wait(w):
-            if w is not None:
-                w.wait()
-
         for it in range(iters + 1):
             marks = []
             for c, (s, e) in enumerate(plan.bounds):
                 m = [mark()]
                 be.bucket_cap(ids[s:e], cap, plan.send[c], plan.inv[c], plan.counts[c], plan.flags[c], plan.ws[c], stat=plan.cstat[c], dedup=self.dedup)
                 m.append(mark())
-                wait(self._a2a_equal(plan.recv[c], plan.send[c]))
+                _wait(self._a2a_equal(plan.recv[c], plan.send[c]))
                 m.append(mark())
                 be.gather_slabs(plan.recv[c], cap, plan.rows[c])
                 m.append(mark())
-                wait(self._a2a_equal(plan.back[c], plan.rows[c]))
+                _wait(self._a2a_equal(plan.back[c], plan.rows[c]))
                 m.append(mark())
                 if e > s:
                     be.finish_chunk(plan.back[c], be.inv2d(plan.inv[c], e - s, F, self.dedup), want_fm, out[s:e], fm[s:e] if want_fm else None)
@@ -1035,7 +1028,7 @@ class ShardedTables:
         val = float(ts.absmax()) if ts is not None else 0.0
         if self._collective():
             t = torch.tensor([val], dtype=torch.float32, device=self.device)
-            if self._host_staged(t):
+            if _host_staged(t, self.group):
                 t = t.cpu()
             dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
             val = float(t[0])
@@ -1089,14 +1082,7 @@ class ShardedTables:
         if self._bag_cap is None:
             ce = self._default_cap(max(1, nnz))
             cb = min(ce, _round_up(max(B * self.F, 16), 16))           # every partial row has at least one entry
-            t = torch.tensor([ce, cb], dtype=torch.int64)
-            if dist.get_backend(self.group) == "gloo":
-                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
-            else:
-                td = t.to(self.device)
-                dist.all_reduce(td, op=dist.ReduceOp.MAX, group=self.group)
-                t = td.cpu()
-            self._bag_cap = (int(t[0]), int(t[1]))
+            self._bag_cap = tuple(self._max_over_ranks([ce, cb]))
         return self._bag_cap
 
     def _bag_plan(self, B, cap_e, cap_b):
@@ -1151,40 +1137,15 @@ class ShardedTables:
         after the whole lookup has been enqueued and repeats an overflowing lookup; "lazy" reads it after the NEXT lookup_bags has been
         enqueued (no host wait on a lookup's own work; an overflow raises there, the result it reports on was incomplete); "never" leaves
         it to check_overflow().  Every rank must call it the same number of times (SPMD)."""
-        F, K, be = self.F, self.K, self.backend
-        if values.dim() != 1 or offsets.dim() != 1 or (offsets.numel() - 1) % F:
-            raise ValueError("lookup_bags: values [nnz], offsets [B*F+1] with F=%d" % F)
-        B = (offsets.numel() - 1) // F
-        if weights is not None and weights.numel() != values.numel():
-            raise ValueError("lookup_bags: weights must be [nnz]")
-        sb, sf = (1, B) if field_major else (F, 1)
-        nnz = values.numel()
+        B = self._bag_args(values, offsets, weights, "lookup_bags")
         self.stats["bag_lookups"] = self.stats.get("bag_lookups", 0) + 1
-        dev = values.device
+        check = self._collective()
         while True:
-            cap_e, cap_b = self._bag_caps(B, nnz)
+            cap_e, cap_b = self._bag_caps(B, values.numel())
             plan = self._bag_plan(B, cap_e, cap_b)
             self.stats["bag_cap"] = (cap_e, cap_b)
-            be.bags_bucket(values, offsets, weights, B, sb, sf, combiner, flags, cap_e, cap_b, plan.send, plan.pos, plan.mask, plan.denom,
-                           plan.ws)
-            w = self._a2a_equal(plan.recv, plan.send)
-            if w is not None:
-                w.wait()
-            check = self._collective()
-            be.bags_pool(plan.recv, cap_e, cap_b, max_norm, plan.rows, stat=plan.stat if check else None)
-            pend = None
-            if check and dev.type == "cuda":
-                host = self._bag_host()
-                host.copy_(plan.stat, non_blocking=True)
-                pend = (torch.cuda.current_stream(dev).record_event(), host)
-            elif check:
-                pend = (None, plan.stat.clone())
-            w = self._a2a_equal(plan.back, plan.rows)
-            if w is not None:
-                w.wait()
-            out = torch.empty((B, F * K), dtype=torch.float32, device=dev)
-            fm = torch.empty((B, 1), dtype=torch.float32, device=dev) if want_fm else None
-            be.bags_combine(plan.back, cap_b, plan.pos, plan.mask, plan.denom, B, combiner, out, fm)
+            host = self._bag_host() if check and values.device.type == "cuda" else None
+            out, fm, pend = self._bags_pipeline(plan, host, values, offsets, weights, B, combiner, max_norm, field_major, flags, want_fm)
             if not check:
                 return out, fm
             if self.check != "eager":
@@ -1197,6 +1158,31 @@ class ShardedTables:
                 return out, fm
             if not self._bag_verdict(pend):       # the verdict, read after the whole lookup has been enqueued
                 return out, fm
+
+    def _bags_pipeline(self, plan, host, values, offsets, weights, B, combiner, max_norm, field_major, flags, want_fm):
+        """One pass of the bag lookup over `plan`'s buffers: bucket, exchange, pool on the owner, exchange, combine.  -> (emb, fm | None,
+        pending verdict | None).  With several ranks the pooling pass leaves [overflow, demands] off the received headers in plan.stat;
+        the pending verdict is (event, host) after which the pinned `host` words hold them, or (None, a copy) on a CPU backend.  What is
+        done with it is the caller's policy."""
+        F, K, be = self.F, self.K, self.backend
+        cap_e, cap_b = plan.cap_e, plan.cap_b
+        sb, sf = (1, B) if field_major else (F, 1)
+        dev = values.device
+        check = self._collective()
+        be.bags_bucket(values, offsets, weights, B, sb, sf, combiner, flags, cap_e, cap_b, plan.send, plan.pos, plan.mask, plan.denom, plan.ws)
+        _wait(self._a2a_equal(plan.recv, plan.send))
+        be.bags_pool(plan.recv, cap_e, cap_b, max_norm, plan.rows, stat=plan.stat if check else None)
+        pend = None
+        if check and host is not None:
+            host.copy_(plan.stat, non_blocking=True)
+            pend = (torch.cuda.current_stream(dev).record_event(), host)
+        elif check:
+            pend = (None, plan.stat.clone())
+        _wait(self._a2a_equal(plan.back, plan.rows))
+        out = torch.empty((B, F * K), dtype=torch.float32, device=dev)
+        fm = torch.empty((B, 1), dtype=torch.float32, device=dev) if want_fm else None
+        be.bags_combine(plan.back, cap_b, plan.pos, plan.mask, plan.denom, B, combiner, out, fm)
+        return out, fm, pend
 
     def _bag_args(self, values, offsets, weights, what):
         F = self.F
@@ -1220,7 +1206,7 @@ class ShardedTables:
         verdict (every rank the same words) and repeats with grown capacities; verdicts pending from check="lazy" / "never" lookup_bags
         calls stay pending.  As with lookup_train, where duplicate contributions sit in the slabs depends on atomic order: once a row has
         duplicates, results agree to fp32 rounding, not bit for bit, from run to run.  Every rank must call it (SPMD)."""
-        if getattr(self, "optimizer", None) is None:
+        if self.optimizer is None:
             raise RuntimeError("call enable_training(lr) first")
         self._bag_args(values, offsets, weights, "lookup_bags_train")
         anchor = torch.zeros((), dtype=torch.float32, device=values.device, requires_grad=True)
@@ -1231,9 +1217,7 @@ class ShardedTables:
         plan = self._bag_train_plans.get(key)
         if plan is not None and not plan.busy:
             return plan
-        fresh = _BagPlan(self, B, cap_e, cap_b)
-        fresh.busy = False
-        fresh.host = torch.empty(3, dtype=torch.int64, pin_memory=True) if self.device.type == "cuda" else None
+        fresh = _BagPlan(self, B, cap_e, cap_b, train=True)
         if plan is None:                    # (a plan still held by a forward whose backward has not run is left to it)
             if len(self._bag_train_plans) >= 4:
                 self._bag_train_plans = {k: v for k, v in self._bag_train_plans.items() if v.busy}
@@ -1241,33 +1225,11 @@ class ShardedTables:
         return fresh
 
     def _bags_forward_train(self, values, offsets, weights, combiner, max_norm, field_major, flags, hold):
-        F, K, be = self.F, self.K, self.backend
         B = self._bag_args(values, offsets, weights, "lookup_bags_train")
-        sb, sf = (1, B) if field_major else (F, 1)
-        nnz = values.numel()
         self.stats["bag_train_lookups"] = self.stats.get("bag_train_lookups", 0) + 1
-        dev = values.device
-        check = self._collective()
         while True:
-            cap_e, cap_b = self._bag_caps(B, nnz)
-            plan = self._bag_train_plan(B, cap_e, cap_b)
-            be.bags_bucket(values, offsets, weights, B, sb, sf, combiner, flags, cap_e, cap_b, plan.send, plan.pos, plan.mask, plan.denom,
-                           plan.ws)
-            w = self._a2a_equal(plan.recv, plan.send)
-            if w is not None:
-                w.wait()
-            be.bags_pool(plan.recv, cap_e, cap_b, max_norm, plan.rows, stat=plan.stat if check else None)
-            pend = None
-            if check and dev.type == "cuda":
-                plan.host.copy_(plan.stat, non_blocking=True)
-                pend = (torch.cuda.current_stream(dev).record_event(), plan.host)
-            elif check:
-                pend = (None, plan.stat.clone())
-            w = self._a2a_equal(plan.back, plan.rows)
-            if w is not None:
-                w.wait()
-            out = torch.empty((B, F * K), dtype=torch.float32, device=dev)
-            be.bags_combine(plan.back, cap_b, plan.pos, plan.mask, plan.denom, B, combiner, out, None)
+            plan = self._bag_train_plan(B, *self._bag_caps(B, values.numel()))
+            out, _, pend = self._bags_pipeline(plan, plan.host, values, offsets, weights, B, combiner, max_norm, field_major, flags, False)
             # this lookup's own verdict only (the same words on every rank: all ranks repeat together); pending lazy verdicts stay pending
             if pend is None or not self._bag_verdict(pend):
                 plan.busy = bool(hold)
@@ -1281,9 +1243,7 @@ class ShardedTables:
             g2 = g if g.dim() == 2 and (B == 0 or g.stride(1) == 1) else g.contiguous()
             # the partial rows' buffers are the gradient's: rows = what this rank sends, back = what it receives (the same at world 1)
             be.bags_grad(g2, plan.cap_b, plan.pos, plan.mask, plan.denom, B, combiner, plan.rows)
-            w = self._a2a_equal(plan.back, plan.rows)
-            if w is not None:
-                w.wait()
+            _wait(self._a2a_equal(plan.back, plan.rows))
             be.bags_adagrad(self.optimizer, plan.recv, plan.cap_e, plan.cap_b, plan.back, max_norm)
         finally:
             plan.busy = False
@@ -1324,41 +1284,20 @@ def _masked_stream(device, n_cus, which):
 
 
 class _ShardedLookup(torch.autograd.Function):
-    """emb = ShardedTables.lookup(ids) with a backward that routes the row gradients to their owners and lets each owner
-    apply the sparse Adagrad update to its shard (no gradient tensor is returned for the tables)."""
+    """emb (or, with_lin, (emb, lin): the lookup and the first-order term from ONE node) = ShardedTables.lookup(ids) with a backward that
+    routes the row gradients (and d lin along the same exchange) to their owners and lets each owner apply the sparse Adagrad update to its
+    embedding rows, then FTRL to its first-order rows -- one optimiser step; no gradient tensor is returned for the tables."""
 
     @staticmethod
-    def forward(ctx, st, ids, anchor):
-        if st._use_exact or ids.shape[0] == 0 and not st._collective():
-            emb, saved = st._forward_saved(ids)
-        else:
-            emb, saved = st._forward_saved_fixed(ids)
-        ctx.st, ctx.saved = st, saved
-        return emb
+    def forward(ctx, st, ids, with_lin, anchor):
+        emb, ctx.saved, lin = st._forward_train(ids, with_lin)
+        ctx.st = st
+        return (emb, lin) if with_lin else emb
 
     @staticmethod
-    def backward(ctx, g):
-        ctx.st._backward_apply(ctx.saved, g)
-        return None, None, None
-
-
-class _ShardedLookupLinear(torch.autograd.Function):
-    """(emb, lin) = the lookup and the first-order term from ONE node: its backward receives both gradients, sends them along the same
-    exchange and lets each owner apply Adagrad to its embedding rows, then FTRL to its first-order rows -- one optimiser step."""
-
-    @staticmethod
-    def forward(ctx, st, ids, anchor):
-        if st._use_exact or ids.shape[0] == 0 and not st._collective():
-            emb, saved, lin = st._forward_saved(ids, with_lin=True)
-        else:
-            emb, saved, lin = st._forward_saved_fixed(ids, with_lin=True)
-        ctx.st, ctx.saved = st, saved
-        return emb, lin
-
-    @staticmethod
-    def backward(ctx, g, g_lin):
-        ctx.st._backward_apply(ctx.saved, g, g_lin.contiguous())
-        return None, None, None
+    def backward(ctx, g, g_lin=None):
+        ctx.st._backward_apply(ctx.saved, g, None if g_lin is None else g_lin.contiguous())
+        return None, None, None, None
 
 
 class _ShardedBagLookup(torch.autograd.Function):
@@ -1388,7 +1327,7 @@ def allreduce_grads(params, group=None, bucket_bytes=64 << 20, average=False):
     grads = [p.grad for p in params if p.grad is not None]
     if not grads:
         return
-    host_staged = _HOST_STAGED or (dist.get_backend(group) == "gloo" and grads[0].is_cuda)
+    host_staged = _host_staged(grads[0], group)
     buckets, cur, size = [], [], 0
     for g in grads:
         if g.is_sparse:
@@ -1430,12 +1369,10 @@ def xdeepfm_predict(model, tables, ids, linear_logit=None):
     `model`'s linear_bias if it has one."""
     amax = tables.absmax()
     B = ids.shape[0]
-    was_training = model.training
-    model.eval()
-    from_tables = linear_logit is None and getattr(tables, "lin_rows", None) is not None
+    from_tables = linear_logit is None and tables.lin_rows is not None
     bias = getattr(model, "linear_bias", None) if from_tables else None
     bias = bias.data.reshape(-1)[:1] if bias is not None else None
-    try:
+    with _eval_mode(model):
         if tables.check == "eager":
             out = torch.empty((B, 1), dtype=torch.float32, device=ids.device)
             if from_tables:
@@ -1451,8 +1388,6 @@ def xdeepfm_predict(model, tables, ids, linear_logit=None):
             emb, linear_logit = tables.lookup(ids, want_lin=True, lin_bias=bias)
             return model.forward_embedded(emb, linear_logit, range_ok=ops.f16_range_ok(amax))
         return model.forward_embedded(tables.lookup(ids), linear_logit, range_ok=ops.f16_range_ok(amax))
-    finally:
-        model.train(was_training)
 
 
 class ShardedDeepFMTrainer:
@@ -1477,7 +1412,7 @@ class ShardedDeepFMTrainer:
         tables.enable_training(lr_sparse, initial_accumulator_value)
         self.linear = None
         if linear is not None:
-            if getattr(tables, "lin_rows", None) is None:
+            if tables.lin_rows is None:
                 raise ValueError("ShardedDeepFMTrainer(linear=...): the tables have no first-order weights (ShardedTables.attach_linear)")
             bias = model.linear_bias
             if any(p is bias for grp in dense_optimizer.param_groups for p in grp["params"]):
@@ -1504,14 +1439,20 @@ class ShardedDeepFMTrainer:
         else:
             emb = self.tables.lookup_train(ids)                               # tables update inside backward()
             logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb)         # fm_logit_fn + dnn_logit_fn, deepFM.py:337-338
-        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, labels, reduction="sum")
-        loss.backward()
-        allreduce_grads(self.dense_params, self.group)
-        self.dense_optimizer.step()
+        loss = self._loss_backward_dense_step(logits, labels)
         if self.linear is not None:                                           # the bias: FTRL with the GLOBAL gradient
             b = m.linear_bias
             with torch.no_grad():
                 self.tables.backend.ftrl_dense(b.data, self.bias_accum, self.bias_linear, b.grad.contiguous(), *self.linear)
+        return loss
+
+    def _loss_backward_dense_step(self, logits, labels):
+        """The tail of a step: the SUM loss, backward (every owner's shard takes its step inside), the dense gradients summed over the
+        ranks, the dense step.  -> this rank's summed loss (detached)."""
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, labels, reduction="sum")
+        loss.backward()
+        allreduce_grads(self.dense_params, self.group)
+        self.dense_optimizer.step()
         return loss.detach()
 
     def step_bags(self, values, offsets, labels, weights=None, field_major=False):
@@ -1526,12 +1467,7 @@ class ShardedDeepFMTrainer:
         self.dense_optimizer.zero_grad(set_to_none=True)
         comb = [c.combiner for c in m.dnn_feature_columns]
         emb = self.tables.lookup_bags_train(values, offsets, weights, combiner=comb, max_norm=m._max_norm(), field_major=field_major)
-        logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb)
-        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, labels, reduction="sum")
-        loss.backward()
-        allreduce_grads(self.dense_params, self.group)
-        self.dense_optimizer.step()
-        return loss.detach()
+        return self._loss_backward_dense_step(ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb), labels)
 
     @torch.no_grad()
     def predict(self, ids):
@@ -1541,9 +1477,7 @@ class ShardedDeepFMTrainer:
         term -- the [B, F*K] concatenation is never written; otherwise lookup(want_fm=True) + dnn_logit_fn.  Bit for bit the same logits."""
         from .dense import tower_infer
         m = self.model
-        was_training = m.training
-        m.eval()
-        try:
+        with _eval_mode(m):
             B = ids.shape[0]
             out = torch.empty((B, 1), dtype=torch.float32, device=ids.device)
             amax = self.tables.absmax()
@@ -1569,8 +1503,6 @@ class ShardedDeepFMTrainer:
                 return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(amax)) + lin
             emb, fm = self.tables.lookup(ids, want_fm=True)
             return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(amax))      # the SHARDED tables' magnitude, not the model's own
-        finally:
-            m.train(was_training)
 
     @torch.no_grad()
     def predict_bags(self, values, offsets, weights=None, field_major=False):
@@ -1580,12 +1512,8 @@ class ShardedDeepFMTrainer:
         if self.linear is not None:
             raise NotImplementedError(self._NO_BAG_LINEAR)
         m = self.model
-        was_training = m.training
-        m.eval()
-        try:
+        with _eval_mode(m):
             comb = [c.combiner for c in m.dnn_feature_columns]
             emb, fm = self.tables.lookup_bags(values, offsets, weights, combiner=comb, max_norm=m._max_norm(), field_major=field_major,
                                               want_fm=True)
             return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(self.tables.absmax()))
-        finally:
-            m.train(was_training)

@@ -7,21 +7,10 @@ rows, the requester's combine, the overflow verdict read off the received header
 steps cannot run without a GPU, so NumPy stand-ins take their place through the `backend` injection point -- writing the same slab
 format (include/dir_hip.h: dir_shard_bags_bucket) into the same buffers.  Reference: a float64 restatement of the bag semantics
 (ops.embedding_bag / [TF-upstream] embedding_lookup_sparse with max_norm) over the FULL tables, the same on every rank."""
-import os
-
 import numpy as np
-import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_CODES = {"sum": 0, "mean": 1, "sqrtn": 2}
-
-
-def _store():
-    import tempfile
-    return os.path.join(tempfile.mkdtemp(prefix="dir_pg_"), "store")
+from tests.shard_standin import NumpyBackend, per_slot, run_checked
 
 
 # ---- bags, layouts and the float64 reference (also used by tests/test_gpu_shard_bags.py) --------------------------------------------
@@ -66,10 +55,6 @@ def to_csr(bags, F, field_major):
     return v, np.asarray(offs, np.int64), w
 
 
-def per_slot(x, F):
-    return list(x) if isinstance(x, (list, tuple)) else [x] * F
-
-
 def bags_ref(full, bags, combiner, max_norm, prune):
     """float64 restatement: -> (emb [B, F*K], scale [B, F*K]) where scale bounds the fp32 rounding (the same combine over |w * row|)."""
     F, K = len(full), full[0].shape[1]
@@ -112,122 +97,6 @@ def fm_ref(emb, F, K):
     return 0.5 * ((e.sum(1) ** 2) - (e ** 2).sum(1)).sum(1)
 
 
-# ---- NumPy stand-ins for the three HIP steps ---------------------------------------------------------------------------------------
-def numpy_bags_backend(local, vocab, parts, first, P, K):
-    """The three lookup_bags steps of shard.HipBackend in NumPy, on the slab format of include/dir_hip.h (fp32 arithmetic in the
-    kernels' order: entries in entry order inside a partial, partials in ascending owner order)."""
-    from oracle import np_ref as R
-    F = len(vocab)
-
-    def codes(combiner):
-        return [_CODES[c] for c in per_slot(combiner, F)]
-
-    class Backend:
-        def new_bags_workspace(self, device):
-            return torch.zeros(256, dtype=torch.int32)
-
-        def bags_bucket(self, values, offsets, weights, B, sb, sf, combiner, flags, cap_e, cap_b, slabs, pos, mask, denom, workspace):
-            vals, offs = values.numpy(), offsets.numpy()
-            wts = None if weights is None else weights.numpy()
-            prune = wts is not None and bool(flags & 1)
-            cb_ = codes(combiner)
-            sl = slabs.numpy().reshape(P, cap_e + 1, 2)
-            ps, mk, dn = pos.numpy(), mask.numpy(), denom.numpy()
-            ne, nb = np.zeros(P, np.int64), np.zeros(P, np.int64)
-            for b in range(B):
-                for f in range(F):
-                    g = b * F + f
-                    s0, s1 = offs[b * sb + f * sf], offs[b * sb + f * sf + 1]
-                    runs = {}
-                    wsum, w2sum, n = np.float32(0), np.float32(0), 0
-                    for e in range(s0, s1):
-                        i = vals[e]
-                        w = np.float32(1) if wts is None else np.float32(wts[e])
-                        if i < 0 or i >= vocab[f] or (prune and not w > 0):
-                            continue
-                        o, l = R.shard_div_owner([i], vocab[f], parts[f])
-                        o = (int(o[0]) + first[f]) % P
-                        runs.setdefault(o, []).append((int(l[0]) * F + f, w))
-                        wsum = np.float32(wsum + w)
-                        w2sum = np.float32(w2sum + np.float32(w * w))
-                        n += 1
-                    if cb_[f] == 1:
-                        dn[g] = wsum if wts is not None else np.float32(n)
-                    elif cb_[f] == 2:
-                        dn[g] = np.sqrt(w2sum) if wts is not None else np.sqrt(np.float32(n))
-                    else:
-                        dn[g] = 1.0
-                    m = 0
-                    for o in sorted(runs):
-                        m |= 1 << o
-                        q = nb[o]
-                        nb[o] += 1
-                        ps[g * P + o] = o * cap_b + q if q < cap_b else -1
-                        for packed, w in runs[o]:
-                            if ne[o] < cap_e:
-                                ret = q if q < cap_b else -1
-                                sl[o, 1 + ne[o], 0] = packed
-                                sl[o, 1 + ne[o], 1] = int(np.float32(w).view(np.uint32)) | (int(np.uint32(ret & 0xffffffff)) << 32)
-                            ne[o] += 1
-                    mk[g] = np.int64(np.uint64(m).astype(np.int64)) if m < (1 << 63) else np.int64(m - (1 << 64))
-            de, db = int(ne.max()), int(nb.max())
-            for o in range(P):
-                sl[o, 0, 0] = min(ne[o], cap_e) | (min(nb[o], cap_b) << 32)
-                sl[o, 0, 1] = de | (db << 32)
-
-        def bags_pool(self, recv, cap_e, cap_b, max_norm, rows, stat=None):
-            sl = recv.numpy().reshape(P, cap_e + 1, 2)
-            mn = per_slot(max_norm, F)
-            out = rows.numpy()
-            for s in range(P):
-                ne = int(sl[s, 0, 0] & 0xffffffff)
-                prev, acc = None, None
-                for j in range(ne + 1):
-                    ret = int(np.int64(sl[s, 1 + j, 1]) >> 32) if j < ne else None
-                    if ret != prev and prev is not None and prev >= 0:
-                        out[s * cap_b + prev] = acc
-                    if j == ne:
-                        break
-                    if ret != prev:
-                        acc = np.zeros(K, np.float32)
-                    prev = ret
-                    packed = int(sl[s, 1 + j, 0])
-                    w = np.array([sl[s, 1 + j, 1] & 0xffffffff], np.uint64).astype(np.uint32).view(np.float32)[0]
-                    f, l = packed % F, packed // F
-                    r = local[f][l].numpy().astype(np.float32)
-                    if mn[f]:
-                        l2 = np.float32(0)
-                        for x in r:
-                            l2 = np.float32(l2 + np.float32(x * x))
-                        nrm = np.sqrt(l2) if l2 > 0 else l2
-                        r = (r * np.float32(mn[f])) / np.float32(max(nrm, np.float32(mn[f])))
-                    acc = (acc + r * w).astype(np.float32)
-            if stat is not None:
-                de = max(int(sl[s, 0, 1] & 0xffffffff) for s in range(P))
-                db = max(int(sl[s, 0, 1] >> 32) for s in range(P))
-                stat.copy_(torch.tensor([int(de > cap_e or db > cap_b), de, db]))
-
-        def bags_combine(self, back, cap_b, pos, mask, denom, B, combiner, out, fm=None):
-            cb_ = codes(combiner)
-            bk, ps, mk, dn = back.numpy(), pos.numpy(), mask.numpy(), denom.numpy()
-            o_ = out.numpy()
-            for b in range(B):
-                for f in range(F):
-                    g = b * F + f
-                    m = int(mk[g]) & ((1 << 64) - 1)
-                    acc = np.zeros(K, np.float32)
-                    for o in range(P):
-                        if (m >> o) & 1 and ps[g * P + o] >= 0:
-                            acc = (acc + bk[ps[g * P + o]]).astype(np.float32)
-                    if m and cb_[f] != 0:
-                        acc = (acc / dn[g]).astype(np.float32)
-                    o_[b, f * K:(f + 1) * K] = acc
-            if fm is not None:
-                fm.copy_(torch.from_numpy(fm_ref(o_, F, K).astype(np.float32)[:, None]))
-
-    return Backend()
-
-
 # ---- the ranks --------------------------------------------------------------------------------------------------------------------
 CASES = [   # (weights, combiner, max_norm, field_major, prune)
     (None, "mean", None, False, False),
@@ -238,32 +107,15 @@ CASES = [   # (weights, combiner, max_norm, field_major, prune)
 ]
 
 
-def _worker(rank, world, store, spec, q):
-    try:
-        import sys
-        sys.path.insert(0, ROOT)
-        os.environ.setdefault("GLOO_SOCKET_IFNAME", "lo")
-        import datetime
-        dist.init_process_group("gloo", init_method="file://" + store, rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-        try:
-            q.put((rank, _scenarios(rank, world, spec)))
-        finally:
-            dist.destroy_process_group()
-    except Exception:
-        import traceback
-        q.put((rank, traceback.format_exc()))
-
-
 def _scenarios(rank, world, spec):
-    from dir_amd.shard import ShardedTables, local_slice, place_slices
+    from dir_amd.shard import ShardedTables, partition_layout
     vocab, K = spec["vocab"], spec["K"]
     F = len(vocab)
-    parts = spec.get("partitions") or [world] * F
-    first = place_slices(parts, world) if spec.get("partitions") else [0] * F
+    parts, first, slices = partition_layout(vocab, K, world, rank, spec.get("partitions"))
     rng = np.random.default_rng(7)                                  # the same full tables on every rank
     full = [(rng.standard_normal((v, K)) * 0.5).astype(np.float32) for v in vocab]
-    local = [torch.from_numpy(full[f][slice(*local_slice(v, parts[f], first[f], world, rank))].copy()) for f, v in enumerate(vocab)]
-    be = numpy_bags_backend(local, vocab, parts, first, world, K)
+    local = [torch.from_numpy(full[f][s:e].copy()) for f, (s, e) in enumerate(slices)]
+    be = NumpyBackend(local, vocab, parts, first, world, K)
     kw = {k: spec[k] for k in ("partitions", "slack", "check") if k in spec}
     st = ShardedTables(local, vocab, backend=be, **kw)
     rng_b = np.random.default_rng(1000 + rank)                      # every rank draws its own bags
@@ -315,23 +167,7 @@ def _lazy_overflow(st, full, rng_b, spec):
 
 
 def _run(world, spec):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    store = _store()
-    procs = [ctx.Process(target=_worker, args=(r, world, store, spec, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=300) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    out = {}
-    for rank, got in res:
-        assert not isinstance(got, str), "rank %d raised:\n%s" % (rank, got)
-        bad = [(n, d) for n, ok, d in got[0] if not ok]
-        assert not bad, "rank %d: %s" % (rank, bad)
-        out[rank] = got
-    return out
+    return run_checked(world, _scenarios, spec)
 
 
 def test_bags_world2_matrix():
@@ -369,11 +205,9 @@ def test_bags_lazy_verdict_raises_at_the_next_lookup():
 
 def test_bags_world1_capacity_buckets():
     """One rank: the entry capacity is rounded up to an eighth of its power of two, so batches of similar nnz share one plan."""
-    import sys
-    sys.path.insert(0, ROOT)
     from dir_amd.shard import ShardedTables
     local = [torch.zeros((10, 4)), torch.zeros((7, 4))]
-    st = ShardedTables(local, [10, 7], backend=numpy_bags_backend(local, [10, 7], [1, 1], [0, 0], 1, 4))
+    st = ShardedTables(local, [10, 7], backend=NumpyBackend(local, [10, 7], [1, 1], [0, 0], 1, 4))
     assert st._bag_caps(50, 1000) == st._bag_caps(50, 1010) == (1024, 112)
     for n in (0, 1, 17, 1000, 5000, 123457, 4980736):
         ce, _ = st._bag_caps(50, n)

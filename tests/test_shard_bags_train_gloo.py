@@ -7,154 +7,13 @@ shared with the one-hot lookup_train.  The HIP steps cannot run without a GPU, s
 injection point, writing and reading the same buffers (include/dir_hip.h: dir_shard_bags_grad_f32, dir_sparse_adagrad_sorted_bags_f32).
 Reference: float64 torch autograd of the bag forward over the FULL tables on the GLOBAL batch, then [TF-upstream] Adagrad on every table
 (duplicates summed before the accumulator moves) -- the same on every rank."""
-import datetime
-import os
-
 import numpy as np
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-from tests.test_shard_bags_gloo import _store, draw_bags, numpy_bags_backend, per_slot, to_csr
+from tests.shard_standin import NumpyBackend, per_slot, run_checked
+from tests.test_shard_bags_gloo import CASES, draw_bags, to_csr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LR, ACC0 = 0.3, 0.1
-_CODES = {"sum": 0, "mean": 1, "sqrtn": 2}
-
-
-# ---- NumPy stand-ins for the training steps ----------------------------------------------------------------------------------------
-def add_training(be, local, vocab, parts, first, P, K):
-    """Give numpy_bags_backend the two backward steps of the bags, the optimiser (float64 accumulators) and the fixed-capacity one-hot
-    lookup_train steps that share it."""
-    from oracle import np_ref as R
-    F = len(vocab)
-
-    def make_optimizer(lr, init):
-        return {"lr": lr, "acc": [np.full(tuple(t.shape), init, np.float64) for t in local]}
-
-    def adagrad(opt, f, rows, g):
-        """One Adagrad step of table f: rows (unique) take their summed gradient rows g (float64)."""
-        if not len(rows):
-            return
-        w = local[f].numpy().astype(np.float64)
-        acc = opt["acc"][f]
-        acc[rows] += g * g
-        w[rows] -= opt["lr"] * g / np.sqrt(acc[rows])
-        local[f].copy_(torch.from_numpy(w.astype(np.float32)))
-
-    def bags_grad(g, cap_b, pos, mask, denom, B, combiner, send):
-        comb = [_CODES[c] for c in per_slot(combiner, F)]
-        gg, ps, mk, dn, sd = g.numpy(), pos.numpy(), mask.numpy(), denom.numpy(), send.numpy()
-        for b in range(B):
-            for f in range(F):
-                gi = b * F + f
-                m = int(mk[gi]) & ((1 << 64) - 1)
-                if not m:
-                    continue
-                v = gg[b, f * K:(f + 1) * K].astype(np.float32)
-                if comb[f] != 0:
-                    v = (v / dn[gi]).astype(np.float32)
-                for o in range(P):
-                    p = int(ps[gi * P + o])
-                    if (m >> o) & 1 and 0 <= p < P * cap_b:
-                        sd[p] = v
-
-    def bags_adagrad(opt, recv, cap_e, cap_b, grad_rows, max_norm):
-        sl = recv.numpy().reshape(P, cap_e + 1, 2)
-        gr = grad_rows.numpy().astype(np.float64)
-        mn = per_slot(max_norm, F)
-        ent = []
-        for s in range(P):
-            ne = int(sl[s, 0, 0] & 0xffffffff)
-            rec = sl[s, 1:1 + ne]
-            packed = rec[:, 0]
-            ret = rec[:, 1] >> 32
-            w = (rec[:, 1] & 0xffffffff).astype(np.uint32).view(np.float32).astype(np.float64)
-            ok = (packed >= 0) & (ret >= 0) & (ret < cap_b)
-            ent.append((packed[ok], ret[ok] + s * cap_b, w[ok]))
-        packed = np.concatenate([e[0] for e in ent]) if ent else np.zeros(0, np.int64)
-        gidx = np.concatenate([e[1] for e in ent]) if ent else np.zeros(0, np.int64)
-        w = np.concatenate([e[2] for e in ent]) if ent else np.zeros(0)
-        for f in range(F):
-            sel = (packed % F == f) & (packed // F < local[f].shape[0])
-            rows_all = packed[sel] // F
-            G = np.zeros(tuple(local[f].shape))
-            np.add.at(G, rows_all, w[sel][:, None] * gr[gidx[sel]])
-            rows = np.unique(rows_all)
-            g = G[rows]
-            if mn[f] and len(rows):                         # clip_by_norm's derivative at the pre-update row
-                r = local[f].numpy().astype(np.float64)[rows]
-                n = np.sqrt((r * r).sum(1, keepdims=True))
-                gc = mn[f] * (g / np.maximum(n, 1e-30) - r * ((r * g).sum(1, keepdims=True) / np.maximum(n, 1e-30) ** 3))
-                g = np.where(n > mn[f], gc, g)
-            adagrad(opt, f, rows, g)
-
-    # ---- the one-hot fixed-capacity pipeline (lookup_train), for the shared-accumulator scenario ----
-    def route(a):
-        n = a.size
-        own, loc = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
-        for f in range(F):
-            sel = np.arange(f, n, F)
-            ok = (a[sel] >= 0) & (a[sel] < vocab[f])
-            o, l = R.shard_div_owner(np.where(ok, a[sel], 0), vocab[f], parts[f])
-            own[sel] = np.where(ok, (np.asarray(o) + first[f]) % P, -1)
-            loc[sel] = np.where(ok, l, -1)
-        return own, loc
-
-    def new_workspace(device):
-        return torch.zeros(64, dtype=torch.int32)
-
-    def bucket_cap(ids2d, cap, payload, inv, counts, overflow, workspace, stat=None, dedup=False):
-        a = ids2d.numpy().reshape(-1)
-        own, loc = route(a)
-        pay = payload.numpy().reshape(P, cap + 1)
-        iv = inv.numpy()
-        iv[:] = -1
-        fill = np.zeros(P, np.int64)
-        for i in range(a.size):
-            o = own[i]
-            if o < 0:
-                continue
-            if fill[o] < cap:
-                pay[o, 1 + fill[o]] = loc[i] * F + (i % F)
-                iv[i] = o * cap + fill[o]
-            fill[o] += 1
-        pay[:, 0] = np.minimum(fill, cap) | (int(fill.max()) << 32)
-        counts.copy_(torch.from_numpy(fill))
-        overflow.fill_(int((fill > cap).any()))
-        if stat is not None:
-            stat[0], stat[1] = int((fill > cap).any()), int(fill.max())
-
-    def slab_stat(recv_all, n_slabs, cap, stat):
-        h = recv_all.numpy().reshape(n_slabs, cap + 1)[:, 0] >> 32
-        stat[0], stat[1] = int(h.max() > cap), int(h.max())
-
-    def gather_slabs(recv, cap, out):
-        r, o = recv.numpy().reshape(P, cap + 1), out.numpy()
-        for s in range(P):
-            for j in range(int(r[s, 0] & 0xffffffff)):
-                v = r[s, 1 + j]
-                o[s * cap + j] = local[v % F].numpy()[v // F]
-
-    def finish_chunk(back, inv2d, want_fm, out, fm):
-        iv = inv2d.reshape(-1).numpy()
-        emb = np.where((iv >= 0)[:, None], back.numpy()[np.maximum(iv, 0)], 0).astype(np.float32)
-        out.copy_(torch.from_numpy(emb.reshape(out.shape)))
-
-    def apply_adagrad(opt, payload, grad_rows):
-        p, g = payload.numpy(), grad_rows.numpy().astype(np.float64)
-        for f in range(F):
-            sel = (p >= 0) & (p % F == f)
-            rows_all = p[sel] // F
-            G = np.zeros(tuple(local[f].shape))
-            np.add.at(G, rows_all, g[sel])
-            rows = np.unique(rows_all)
-            adagrad(opt, f, rows, G[rows])
-
-    for fn in (make_optimizer, bags_grad, bags_adagrad, new_workspace, bucket_cap, slab_stat, gather_slabs, finish_chunk, apply_adagrad):
-        setattr(be, fn.__name__, fn)
-    be.inv2d = lambda inv, Bc, F_, dedup: inv.view(Bc, F_)
-    return be
 
 
 # ---- the float64 reference ---------------------------------------------------------------------------------------------------------
@@ -214,46 +73,20 @@ def ref_step(full, acc, bags, G, combiner, max_norm, prune, lr):
 
 
 # ---- the ranks --------------------------------------------------------------------------------------------------------------------
-CASES = [   # (weights, combiner, max_norm, field_major, prune)
-    (None, "mean", None, False, False),
-    ("pos", "sqrtn", 0.9, True, False),
-    ("signed", ["sum", "mean", "sqrtn"], [None, 1.1, 0.6], False, True),
-    ("pos", ["mean", "sum", "mean"], None, True, False),
-    (None, ["sqrtn", "sqrtn", "sum"], [0.7, None, None], True, False),
-]
-
-
-def _worker(rank, world, store, spec, q):
-    try:
-        import sys
-        sys.path.insert(0, ROOT)
-        os.environ.setdefault("GLOO_SOCKET_IFNAME", "lo")
-        dist.init_process_group("gloo", init_method="file://" + store, rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-        try:
-            q.put((rank, _scenario(rank, world, spec)))
-        finally:
-            dist.destroy_process_group()
-    except Exception:
-        import traceback
-        q.put((rank, traceback.format_exc()))
-
-
 def _close(got, ref):
     return float((np.abs(got.astype(np.float64) - ref) / (1.0 + np.abs(ref))).max()) if got.size else 0.0
 
 
 def _scenario(rank, world, spec):
-    from dir_amd.shard import ShardedTables, local_slice, partitions_for, place_slices
+    from dir_amd.shard import ShardedTables, partition_layout
     vocab, K = spec["vocab"], spec["K"]
     F = len(vocab)
-    pspec = spec.get("partitions")
-    parts = ([partitions_for(v, K, world) for v in vocab] if pspec == "reference" else list(pspec)) if pspec else [world] * F
-    first = place_slices(parts, world) if pspec else [0] * F
+    parts, first, slices = partition_layout(vocab, K, world, rank, spec.get("partitions"))
     rng = np.random.default_rng(7)                                  # the same full tables on every rank
     full = [(rng.standard_normal((v, K)) * 0.5).astype(np.float32) for v in vocab]
-    mine = [slice(*local_slice(v, parts[f], first[f], world, rank)) for f, v in enumerate(vocab)]
+    mine = [slice(s, e) for s, e in slices]
     local = [torch.from_numpy(full[f][mine[f]].copy()) for f in range(F)]
-    be = add_training(numpy_bags_backend(local, vocab, parts, first, world, K), local, vocab, parts, first, world, K)
+    be = NumpyBackend(local, vocab, parts, first, world, K)
     kw = {k: spec[k] for k in ("partitions", "slack", "check") if k in spec}
     st = ShardedTables(local, vocab, backend=be, **kw).enable_training(LR, ACC0)
     ref = [t.astype(np.float64) for t in full]
@@ -316,23 +149,7 @@ def _scenario(rank, world, spec):
 
 
 def _run(world, spec):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    store = _store()
-    procs = [ctx.Process(target=_worker, args=(r, world, store, spec, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=300) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    out = {}
-    for rank, got in res:
-        assert not isinstance(got, str), "rank %d raised:\n%s" % (rank, got)
-        bad = [(n, d) for n, ok, d in got[0] if not ok]
-        assert not bad, "rank %d: %s" % (rank, bad)
-        out[rank] = got
-    return out
+    return run_checked(world, _scenario, spec)
 
 
 def test_bags_train_world1():

@@ -9,228 +9,22 @@ dir_shard_linear_finish_f32, dir_shard_linear_grad_f32, dir_sparse_ftrl_rows_sor
 Reference: the FULL, unsharded weights in float64 on the GLOBAL batch -- oracle.np_ref.sparse_ftrl_step once per step for the first-order
 weights, [TF-upstream] Adagrad (duplicates summed before the accumulator moves) for the embedding tables -- the same on every rank.
 Error measure (tests/test_gpu_shard_bags_train.py::_close): max |got - ref| / (1 + |ref|) <= 1e-5."""
-import datetime
-import os
-
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.shard_standin import NumpyBackend, run_ranks
+
 LR, ACC0 = 0.3, 0.1
 FTRL = dict(lr=0.2, l1=0.0, l2=0.0)
 SCENARIOS = ("forward", "train3", "l1_zero", "partitions", "overflow", "lazy_chunks", "trainer")
 TOL = 1e-5
 
 
-def _store():
-    import tempfile
-    return os.path.join(tempfile.mkdtemp(prefix="dir_pg_"), "store")
-
-
 def _err(got, ref):
     got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
     return float(np.max(np.abs(got - ref) / (1 + np.abs(ref)))) if got.size else 0.0
-
-
-# ---- NumPy stand-ins for the HIP steps ---------------------------------------------------------------------------------------------
-class NumpyBackend:
-    """Both lookup paths of the one-hot lookup, its owner-side Adagrad (float64 accumulators), and the four steps of the linear term."""
-
-    def __init__(self, local, vocab, parts, first, P, K):
-        self.local, self.vocab, self.parts, self.first, self.P, self.K, self.F = local, vocab, parts, first, P, K, len(vocab)
-        self.lin = None
-        self.ftrl_calls = 0
-
-    def route(self, a):
-        """owner rank / local row of every entry of a flat [.., F] id array (-1: pruned or out of range)."""
-        from oracle import np_ref as R
-        F, n = self.F, a.size
-        own, loc = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
-        for f in range(F):
-            sel = np.arange(f, n, F)
-            ok = (a[sel] >= 0) & (a[sel] < self.vocab[f])
-            o, l = R.shard_div_owner(np.where(ok, a[sel], 0), self.vocab[f], self.parts[f])
-            own[sel] = np.where(ok, (np.asarray(o) + self.first[f]) % self.P, -1)
-            loc[sel] = np.where(ok, l, -1)
-        return own, loc
-
-    # ---- exact path ----
-    def bucket(self, flat):
-        a = flat.numpy()
-        n, F, P = a.size, self.F, self.P
-        own, loc = self.route(a)
-        own = np.where(own < 0, np.arange(n) % P, own)          # pruned entries travel as -1 payloads
-        order = np.argsort(own, kind="stable")
-        inv = np.empty(n, np.int64)
-        inv[order] = np.arange(n)
-        packed = np.where(loc < 0, -1, loc * F + (np.arange(n) % F))[order]
-        counts = np.bincount(own, minlength=P).astype(np.int64)
-        starts = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
-        return torch.from_numpy(packed), torch.from_numpy(inv), torch.from_numpy(counts), torch.from_numpy(starts)
-
-    def gather_packed(self, payload):
-        p = payload.numpy()
-        out = np.zeros((p.size, self.K), np.float32)
-        for i, v in enumerate(p):
-            if v >= 0:
-                out[i] = self.local[v % self.F].numpy()[v // self.F]
-        return torch.from_numpy(out)
-
-    def back_buffer(self, n, K, device):
-        return torch.empty((n, K), dtype=torch.float32)
-
-    def finish(self, back, inv, B, F, want_fm, out=None, fm=None):
-        iv = inv.numpy()
-        emb = np.where((iv >= 0)[:, None], back.numpy()[np.maximum(iv, 0)], 0).astype(np.float32).reshape(B, F * self.K)
-        fmv = None
-        if want_fm:
-            e = emb.reshape(B, F, self.K).astype(np.float64)
-            fmv = torch.from_numpy((0.5 * ((e.sum(1) ** 2) - (e ** 2).sum(1)).sum(1, keepdims=True)).astype(np.float32))
-            if fm is not None:
-                fm.copy_(fmv)
-                fmv = fm
-        emb = torch.from_numpy(emb)
-        if out is not None:
-            out.copy_(emb)
-            emb = out
-        return emb, fmv
-
-    # ---- fixed-capacity path ----
-    def new_workspace(self, device):
-        return torch.zeros(64, dtype=torch.int32)
-
-    def bucket_cap(self, ids2d, cap, payload, inv, counts, overflow, workspace, stat=None, dedup=False):
-        a = ids2d.numpy().reshape(-1)
-        F, P = self.F, self.P
-        own, loc = self.route(a)
-        pay = payload.numpy().reshape(P, cap + 1)
-        iv = inv.numpy()
-        iv[:] = -1
-        fill = np.zeros(P, np.int64)
-        seen = {}
-        for i in range(a.size):
-            o = own[i]
-            if o < 0:
-                continue
-            p = loc[i] * F + (i % F)
-            if dedup and (o, p) in seen:
-                iv[i] = seen[(o, p)]
-                continue
-            if fill[o] < cap:
-                pay[o, 1 + fill[o]] = p
-                iv[i] = o * cap + fill[o]
-            if dedup:
-                seen[(o, p)] = iv[i]
-            fill[o] += 1
-        pay[:, 0] = np.minimum(fill, cap) | (int(fill.max()) << 32)   # header: valid slots | this sender's largest demand
-        counts.copy_(torch.from_numpy(fill))
-        overflow.fill_(int((fill > cap).any()))
-        if stat is not None:
-            stat[0], stat[1] = int((fill > cap).any()), int(fill.max())
-
-    @staticmethod
-    def inv2d(inv, Bc, F, dedup):
-        return inv.view(Bc, F)
-
-    def slab_stat(self, recv_all, n_slabs, cap, stat):
-        h = recv_all.numpy().reshape(n_slabs, cap + 1)[:, 0] >> 32
-        stat[0], stat[1] = int(h.max() > cap), int(h.max())
-
-    def gather_slabs(self, recv, cap, out):
-        r, o = recv.numpy().reshape(self.P, cap + 1), out.numpy()
-        for s in range(self.P):
-            for j in range(int(r[s, 0] & 0xffffffff)):
-                v = r[s, 1 + j]
-                o[s * cap + j] = self.local[v % self.F].numpy()[v // self.F]
-
-    def finish_chunk(self, back, inv2d, want_fm, out, fm):
-        b, f = inv2d.shape
-        self.finish(back, inv2d.reshape(-1), b, f, want_fm, out=out, fm=fm)
-
-    def make_optimizer(self, lr, init):
-        return {"lr": lr, "acc": [np.full(tuple(t.shape), init, np.float64) for t in self.local]}
-
-    def apply_adagrad(self, opt, payload, grad_rows):
-        p, g = payload.numpy(), grad_rows.numpy().astype(np.float64)
-        for f in range(self.F):
-            sel = (p >= 0) & (p % self.F == f)
-            rows = p[sel] // self.F
-            gsum = np.zeros(tuple(self.local[f].shape))
-            np.add.at(gsum, rows, g[sel])
-            t = np.zeros(self.local[f].shape[0], bool)
-            t[rows] = True
-            opt["acc"][f][t] += gsum[t] ** 2
-            w = self.local[f].numpy().astype(np.float64)
-            w[t] -= opt["lr"] * gsum[t] / np.sqrt(opt["acc"][f][t])
-            self.local[f].copy_(torch.from_numpy(w.astype(np.float32)))
-
-    # ---- the linear term (the four new steps) ----
-    def attach_linear(self, rows, arena):
-        self.lin = rows                                # [local rows, 4] float32 torch tensors = [w | n | z | -]: the kernels' buffers
-
-    def _weights_of(self, p):
-        """One weight per payload word (0.0 for p < 0 and for rows outside the slot's local rows)."""
-        out = np.zeros(p.size, np.float32)
-        for i, v in enumerate(p):
-            if v >= 0 and v // self.F < self.lin[v % self.F].shape[0]:
-                out[i] = self.lin[v % self.F].numpy()[v // self.F, 0]
-        return out
-
-    def linear_gather(self, recv, cap, out):
-        o = out.numpy()
-        if cap is None:
-            o[:recv.numel()] = self._weights_of(recv.numpy())
-            return
-        r = recv.numpy().reshape(self.P, cap + 1)
-        o[:self.P * cap] = 0.0                         # every word is written: nothing uninitialised crosses the wire
-        for s in range(self.P):
-            nv = int(r[s, 0] & 0xffffffff)
-            o[s * cap:s * cap + nv] = self._weights_of(r[s, 1:1 + nv])
-
-    def linear_finish(self, wback, inv2d, bias, out):
-        iv, wb = inv2d.numpy(), wback.numpy()
-        acc = np.zeros(iv.shape[0], np.float32)
-        for f in range(iv.shape[1]):                   # float32, slot order: dir_linear_onehot_rows_f32's sum
-            acc = acc + np.where(iv[:, f] >= 0, wb[np.maximum(iv[:, f], 0)], np.float32(0)).astype(np.float32)
-        acc = acc + (np.float32(bias.numpy().reshape(-1)[0]) if bias is not None else np.float32(0))
-        out.copy_(torch.from_numpy(acc.reshape(-1, 1)))
-
-    def linear_grad(self, g, inv2d, send):
-        iv, gg, sd = inv2d.numpy(), g.detach().numpy().reshape(-1), send.numpy()
-        sd[:] = 0.0
-        for b in range(iv.shape[0]):
-            for f in range(iv.shape[1]):
-                if iv[b, f] >= 0:
-                    sd[iv[b, f]] = gg[b]
-
-    def apply_ftrl(self, payload, grad, lr, l1, l2, sorted_by=None):
-        self.ftrl_calls += 1
-        p, g = payload.numpy(), grad.numpy().astype(np.float64)
-        assert g.size == p.size
-        for f in range(self.F):
-            sel = (p >= 0) & (p % self.F == f)
-            rows = p[sel] // self.F
-            r = self.lin[f].numpy()
-            gs = np.zeros(r.shape[0])
-            np.add.at(gs, rows, g[sel])                # ALL duplicates of a row are summed before n, z and w move
-            t = np.zeros(r.shape[0], bool)
-            t[rows] = True
-            w, n, z = (r[t, c].astype(np.float64) for c in range(3))
-            n_new = n + gs[t] ** 2
-            z_new = z + gs[t] - (np.sqrt(n_new) - np.sqrt(n)) / lr * w
-            r[t, 0] = np.where(np.abs(z_new) > l1, (np.sign(z_new) * l1 - z_new) / (np.sqrt(n_new) / lr + 2 * l2), 0.0)
-            r[t, 1], r[t, 2] = n_new, z_new
-
-    def ftrl_dense(self, w, accum, linear, grad, lr, l1, l2):
-        wv, n, z, g = (t.numpy().astype(np.float64) for t in (w, accum, linear, grad))
-        n_new = n + g * g
-        z_new = z + g - (np.sqrt(n_new) - np.sqrt(n)) / lr * wv
-        w.copy_(torch.from_numpy(np.where(np.abs(z_new) > l1, (np.sign(z_new) * l1 - z_new) / (np.sqrt(n_new) / lr + 2 * l2), 0.0).astype(np.float32)))
-        accum.copy_(torch.from_numpy(n_new.astype(np.float32)))
-        linear.copy_(torch.from_numpy(z_new.astype(np.float32)))
 
 
 # ---- the float64 reference over the FULL weights and the GLOBAL batch ---------------------------------------------------------------
@@ -271,24 +65,15 @@ def _batch(vocab, B, seed, rank, step=0, hot=False):
 
 
 def _tables(rank, world, vocab, K, seed, **kw):
-    from dir_amd.shard import ShardedTables, local_slice, partitions_for, place_slices
-    F = len(vocab)
+    from dir_amd.shard import ShardedTables, partition_layout
     full, full_w = _draw(vocab, K, seed)
-    partitions = kw.get("partitions")
-    if partitions is None:
-        parts, first = [world] * F, [0] * F
-    else:
-        parts = [partitions_for(v, K, world) for v in vocab] if partitions == "reference" else list(partitions)
-        first = place_slices(parts, world)
-    local, local_w = [], []
-    for f, v in enumerate(vocab):
-        s, e = local_slice(v, parts[f], first[f], world, rank)
-        local.append(torch.from_numpy(full[f][s:e].copy()))
-        local_w.append(torch.from_numpy(full_w[f][s:e].copy()))
+    parts, first, slices = partition_layout(vocab, K, world, rank, kw.get("partitions"))
+    local = [torch.from_numpy(full[f][s:e].copy()) for f, (s, e) in enumerate(slices)]
+    local_w = [torch.from_numpy(full_w[f][s:e].copy()) for f, (s, e) in enumerate(slices)]
     be = NumpyBackend(local, vocab, parts, first, world, K)
     st = ShardedTables(local, vocab, backend=be, **kw)
     st.attach_linear(local_w, initial_accumulator_value=ACC0)
-    return st, be, full, full_w, [local_slice(v, parts[f], first[f], world, rank) for f, v in enumerate(vocab)]
+    return st, be, full, full_w, slices
 
 
 def _compare_shards(st, be, ref, slices, what):
@@ -535,40 +320,15 @@ _FUNCS = dict(forward=sc_forward, train3=sc_train3, l1_zero=sc_l1_zero, partitio
               lazy_chunks=sc_lazy_chunks, trainer=sc_trainer)
 
 
-def _worker(rank, world, store, names, q):
-    try:
-        import sys
-        sys.path.insert(0, ROOT)
-        os.environ.setdefault("GLOO_SOCKET_IFNAME", "lo")
-        torch.set_num_threads(1)
-        dist.init_process_group("gloo", init_method="file://" + store, rank=rank, world_size=world, timeout=datetime.timedelta(seconds=180))
-        try:
-            out = []
-            for n in names:                     # an assertion that fails on one rank ends that rank's run: its peers time out and say so
-                out.append((n, _FUNCS[n](rank, world)))
-            q.put((rank, out))
-        finally:
-            dist.destroy_process_group()
-    except Exception:
-        import traceback
-        q.put((rank, traceback.format_exc()))
+def _scenarios(rank, world, names):
+    return [(n, _FUNCS[n](rank, world)) for n in names]
 
 
 def _run(world, names):
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    store = _store()
-    procs = [ctx.Process(target=_worker, args=(r, world, store, names, q)) for r in range(world)]
-    for p in procs:
-        p.start()
-    res = [q.get(timeout=600) for _ in range(world)]
-    for p in procs:
-        p.join(timeout=60)
-        assert p.exitcode == 0
-    for rank, got in sorted(res):
-        assert not isinstance(got, str), "rank %d raised:\n%s" % (rank, got)
+    res = run_ranks(world, _scenarios, names, timeout=600)
+    for rank, got in sorted(res.items()):
         assert [n for n, _ in got] == list(names), "rank %d ran %s" % (rank, got)       # every scenario, on every rank
-    return dict(res)
+    return res
 
 
 @pytest.mark.parametrize("world", [1, 2, 3, 8])
