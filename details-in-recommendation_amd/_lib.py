@@ -222,6 +222,12 @@ SIGNATURES = {
     "dir_shard_linear_grad_f32": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp]),
     "dir_sparse_ftrl_rows_sorted_payload_f32": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp,
                                                         c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "dir_shard_bags_linear_pool_f32": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp]),
+    "dir_shard_bags_linear_combine_f32": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i64, c_i32,
+                                                  c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "dir_shard_bags_linear_grad_f32": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "dir_sparse_ftrl_rows_sorted_bags_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                     c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
 }
 
 DIR_OK, DIR_E_BADARG, DIR_E_RANGE, DIR_E_HIP, DIR_E_UNSUPPORTED = 0, -1, -2, -3, -4

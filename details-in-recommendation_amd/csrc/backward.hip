@@ -620,6 +620,13 @@ __device__ __forceinline__ void bag_apply(const AdagradUpd& upd, const BagSrc& b
     V::st(wp, wv);
 }
 
+// ... and for FTRL on the packed first-order rows (dir_sparse_ftrl_rows_sorted_bags_f32: K = 1, one lane per run): the first-order
+// weights have no max_norm, so the run's sum goes straight into FtrlUpd::apply
+template <int LPS, int VEC>
+__device__ __forceinline__ void bag_apply(const FtrlUpd& upd, const BagSrc&, int f, int64_t id, int c, int kv, typename BV<VEC>::T sum) {
+    if (c < kv) upd.template apply<VEC>(f, id, c * VEC, sum);
+}
+
 // every row of table f NOT stepped by AdamUpd this step (mark == 0): zero gradient -> m *= b1, v *= b2, var -= lr_t * m / (sqrt(v) + eps);
 // marked rows are skipped and their mark cleared.  LPS = K / 4 adjacent lanes own a row (all of them read the mark before lane 0 of
 // the group clears it: one wave instruction apart).
@@ -1562,6 +1569,69 @@ extern "C" int dir_sparse_adagrad_sorted_bags_f32(float* const* tables, float* c
         }
     }
 #undef DIR_CASE
+    DIR_CHECK_LAUNCH(name);
+    return DIR_OK;
+}
+
+// The owner side of ShardedTables.lookup_bags_train(with_linear=True)'s backward: FTRL on the packed first-order rows [w | n | z | -] over
+// the bag records the owner kept.  Entry e's gradient is w_e * grecv[src * cap_b + ret_e]; all entries of a (slot, row) -- of any bag, of
+// any rank, inside one bag -- are summed before n, z and w move, and every row is written once.  Built as
+// dir_sparse_adagrad_sorted_bags_f32 is: adagrad_keys_bags_k, the radix sort, then adagrad_tile_k / adagrad_fix_k in bag mode with
+// FtrlUpd{rows = true}, K = 1.  sorted_from (optional): the workspace of the Adagrad bag step that has just sorted the SAME slabs (same P,
+// cap_e, cap_b, row_base, total_rows) on this stream: its sorted (row, entry) pairs are read and the key pass and the sort are skipped
+// (the pair arrays sit at offsets that depend on the entry count only, not on K) -- the same pairs, so the same rows bit for bit.
+extern "C" int dir_sparse_ftrl_rows_sorted_bags_f32(float* const* rows, int F, const int64_t* recv, int P, int64_t cap_e, int64_t cap_b,
+                                                    const float* grecv, float lr, float l1, float l2, const int64_t* row_base,
+                                                    int64_t total_rows, void* workspace, int64_t workspace_bytes, const void* sorted_from,
+                                                    dir_stream_t stream) {
+    const char* name = "dir_sparse_ftrl_rows_sorted_bags_f32";
+    DIR_CHECK_ARG(F > 0 && P > 0 && P <= 64, "%s: F=%d P=%d (1 <= P <= 64)", name, F, P);
+    DIR_CHECK_ARG(cap_e > 0 && cap_b > 0 && cap_e < ((int64_t)1 << 31) && (int64_t)P * cap_b < ((int64_t)1 << 31),
+                  "%s: cap_e=%lld cap_b=%lld (each in (0, 2^31), P*cap_b < 2^31)", name, (long long)cap_e, (long long)cap_b);
+    DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
+    DIR_CHECK_ARG(rows && recv && grecv && row_base && workspace, "%s: null pointer", name);
+    const int64_t n = (int64_t)P * cap_e;
+    if (n >= ((int64_t)1 << 30)) return fail(DIR_E_UNSUPPORTED, "%s: P*cap_e=%lld entry slots (the sort takes < 2^30)", name, (long long)n);
+    if (total_rows < 0 || total_rows >= 0xffffffffll) return fail(DIR_E_UNSUPPORTED, "%s: total_rows must be in [0, 2^32-1)", name);
+    if (total_rows == 0) return DIR_OK;          // this rank holds no rows: no record can name one
+    AdaSortedPlan p;
+    if (!adagrad_sorted_plan(n, 1, total_rows, p)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
+    if ((int64_t)p.total > workspace_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(DIR_E_BADARG, "%s: workspace needs %lld bytes, 256-byte aligned", name, (long long)p.total);
+    if (reinterpret_cast<uintptr_t>(sorted_from) & 255u) return fail(DIR_E_BADARG, "%s: sorted_from must be a 256-byte aligned workspace", name);
+    hipStream_t st = as_stream(stream);
+    char* ws = static_cast<char*>(workspace);
+    uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + p.off_keys[1]);
+    uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + p.off_vals[1]);
+    float* carry = reinterpret_cast<float*>(ws + p.off_carry);
+    const int4* r = reinterpret_cast<const int4*>(recv);
+    if (sorted_from) {
+        char* src = const_cast<char*>(static_cast<const char*>(sorted_from));
+        k1 = reinterpret_cast<uint32_t*>(src + p.off_keys[1]);
+        v1 = reinterpret_cast<uint32_t*>(src + p.off_vals[1]);
+    } else {
+        uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + p.off_keys[0]);
+        uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + p.off_vals[0]);
+        const bool second = radix_sort_input_buffer((size_t)n, p.bits) == 1;
+        hipLaunchKernelGGL(adagrad_keys_bags_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, r, n, cap_e, cap_b, F, row_base,
+                           (uint32_t)total_rows, second ? k1 : k0, second ? v1 : v0);
+        DIR_CHECK_LAUNCH(name);
+        if (radix_sort_pairs_u32(ws + p.off_tmp, k0, k1, v0, v1, (size_t)n, p.bits, st) != hipSuccess) return fail(DIR_E_HIP, "%s: radix sort failed", name);
+    }
+    FtrlUpd upd{rows, rows, rows, lr, l1, l2, (int64_t)4};
+    upd.rows = true;
+    BagSrc bag;
+    bag.recv = r;
+    bag.grecv = grecv;
+    bag.cap_e = cap_e;
+    bag.cap_b = cap_b;
+    const int64_t ntiles = (int64_t)p.ntiles;
+    static const int stage_min = dev_env_int("DIR_ADA_STAGE_MIN", 8);       // development A/B switch
+    // one "slot" per entry for the sort (F = 1); the slot is found from the key among the F row blocks (nt = F), as in the Adagrad form
+    hipLaunchKernelGGL((adagrad_tile_k<1, 1, FtrlUpd, false, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, 1, 1, n, k1, v1, nullptr,
+                       (int64_t)0, (int64_t)0, row_base, (uint32_t)total_rows, F, carry, nullptr, nullptr, stage_min, bag);
+    hipLaunchKernelGGL((adagrad_fix_k<1, 1, FtrlUpd, true>), dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, st, upd, 1, 1, n, ntiles, k1,
+                       v1, row_base, (uint32_t)total_rows, F, carry, bag);
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
 }

@@ -126,6 +126,209 @@ __global__ __launch_bounds__(256) void linear_grad_k(const float* __restrict__ g
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// the term over multi-hot bags (ShardedTables.lookup_bags(want_lin=True) / lookup_bags_train(with_linear=True))
+// ------------------------------------------------------------------------------------------------
+// The bag lookup's owner holds every entry's 16-byte record (shard_bags.hip: x, y = local_row * F + slot, z = weight, w = return position),
+// so it pools the first-order weights of each run beside the embedding rows: one float per partial-row position travels back behind the
+// partial rows, the requester adds a bag's partials in ascending owner order, applies the model's ONE linear_sparse_combiner (independent of
+// the per-slot embedding combiners: its denominators are computed from the CSR entries with the lookup's liveness rule) and sums the
+// sample's F bags in slot order -- linear_csr_k's operations in its order (linear_cross.hip), so with one owner per bag and flags = 0
+// the result is dir_linear_sparse_sum_f32's bit for bit.
+//   bags_linear_pool_k     owner:      lout[src * cap_b + ret] = sum over the run of w_e * lw[row_e], in entry order, from 0.0f
+//   bags_linear_denom_k    requester:  lden[g] of every bag (mean / sqrtn only), kept in the plan for the backward
+//   bags_linear_combine_k  requester:  lin[b] = sum_f (sum_o partial) [/ lden] + bias
+//   bags_linear_grad_k     requester:  the transpose of the combine: send[pos[g * P + o]] = d lin[b] [/ lden[g]]
+// The owner's update is dir_sparse_ftrl_rows_sorted_bags_f32 (backward.hip).
+constexpr int SBL_U = 8;      // entry slots per lane (bags_pool_k's chunk)
+
+// Owner side.  ONE lane takes a chunk of SBL_U entry slots of the received slabs -- bags_pool_k's walk with a lane where that kernel has a
+// lane group: the chunk's records (consecutive lanes read consecutive 128-byte pieces of the slab: every line a wave touches is used whole)
+// and then its SBL_U weights are in flight together; the lane pools every run that STARTS inside its chunk, acc + w * lw in entry order,
+// and writes each position once; a run that goes on past the chunk is walked to its end, SBL_U records at a time, and a leading run that
+// began in the previous chunk is left to that chunk's lane.  bags_pool_k's record checks: count from the header, slot < F (by the
+// decode), row < the slot's local rows, 0 <= return position < cap_b -- an entry that kernel drops is dropped here.  Positions no run
+// names keep the zero the C entry filled lout with.
+__global__ __launch_bounds__(256) void bags_linear_pool_k(const float* const* __restrict__ rows, int64_t ld, const int64_t* __restrict__ lvocab,
+                                                          int F, const int4* __restrict__ recv, int P, int64_t cap_e, int64_t cap_b,
+                                                          float* __restrict__ lout) {
+    constexpr int U = SBL_U;
+    const int64_t cpb = (cap_e + U - 1) / U;                          // chunks per slab
+    const int64_t n = (int64_t)P * cpb;
+    // record j of a slab -> return position, the address of its weight (nullptr: none / outside the local rows), entry weight
+    auto load = [&](const int4* slab, int64_t j, int64_t ne, int& ret, const float*& src, float& w) {
+        ret = -2;
+        src = nullptr;
+        w = 0.f;
+        if (j < ne) {
+            const int4 r = slab[1 + j];
+            ret = r.w;
+            const int64_t p = (int64_t)(((uint64_t)(uint32_t)r.y << 32) | (uint32_t)r.x);
+            w = __int_as_float(r.z);
+            if (p >= 0 && ret >= 0 && (int64_t)ret < cap_b) {
+                const int64_t rr = p < 0x7fffffff ? (int64_t)((uint32_t)p / (uint32_t)F) : p / F;
+                const int sl = (int)(p - rr * F);
+                if (rr < lvocab[sl]) src = rows[sl] + rr * ld;
+            }
+        }
+    };
+    for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < n; it += (int64_t)gridDim.x * 256) {
+        const int s = n < ((int64_t)1 << 31) ? (int)((uint32_t)it / (uint32_t)cpb) : (int)(it / cpb);
+        const int64_t c0 = (it - (int64_t)s * cpb) * U;
+        const int4* slab = recv + (int64_t)s * (cap_e + 1);
+        const int64_t ne = min((int64_t)(unsigned int)slab[0].x, cap_e);
+        if (c0 >= ne) continue;
+        const int prev = c0 > 0 ? slab[c0].w : -3;
+        int ret[U];
+        const float* src[U];
+        float w[U], v[U];
+        bool cont = true;
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            load(slab, c0 + u, ne, ret[u], src[u], w[u]);
+            cont = cont && ret[u] == prev;
+            if (cont) {
+                ret[u] = -2;
+                src[u] = nullptr;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = src[u] ? *src[u] : 0.f;        // U independent 4-byte reads in flight
+        float acc = 0.f;
+        int cur = -2;
+        auto store = [&](int r, float a) {
+            if (r >= 0 && (int64_t)r < cap_b) lout[(int64_t)s * cap_b + r] = a;
+        };
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (ret[u] == -2) continue;
+            if (ret[u] != cur) {
+                store(cur, acc);
+                acc = 0.f;
+                cur = ret[u];
+            }
+            if (src[u]) acc = acc + w[u] * v[u];
+        }
+        if (cur >= 0 && (int64_t)cur < cap_b) {                            // the chunk's last run may go on past it
+            for (int64_t j0 = c0 + U; j0 < ne && slab[1 + j0].w == cur; j0 += U) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    load(slab, j0 + u, ne, ret[u], src[u], w[u]);
+                    if (ret[u] != cur) src[u] = nullptr;
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) v[u] = src[u] ? *src[u] : 0.f;
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (src[u]) acc = acc + w[u] * v[u];
+                if (ret[U - 1] != cur) break;
+            }
+        }
+        store(cur, acc);
+    }
+}
+
+// Requester side: the linear combiner's denominator of every bag g = b * F + f, from the CSR entries with bags_bucket_k's liveness rule (id
+// inside [0, vocab_f); weight > 0 under PRUNE_NONPOSITIVE_WEIGHTS) and linear_csr_k's arithmetic: wsum and w2sum in entry order, the
+// entry count without weights, sqrtf for sqrtn.  A bag without a live entry gets a value nobody divides by.
+__global__ __launch_bounds__(256) void bags_linear_denom_k(const int64_t* __restrict__ ids, const int64_t* __restrict__ offsets,
+                                                           const float* __restrict__ weights, int64_t sb, int64_t sf, int64_t nb, int F,
+                                                           const int64_t* __restrict__ vocab, int flags, int combiner,
+                                                           float* __restrict__ lden) {
+    const bool prune_w = weights && (flags & DIR_BAG_PRUNE_NONPOSITIVE_WEIGHTS);
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < nb; g += (int64_t)gridDim.x * 256) {
+        const int64_t b = (int64_t)((uint32_t)g / (uint32_t)F);          // nb < 2^31
+        const int f = (int)(g - b * F);
+        const int64_t bag = b * sb + (int64_t)f * sf;
+        const int64_t beg = offsets[bag], end = offsets[bag + 1];
+        const uint64_t V = (uint64_t)vocab[f];
+        float wsum = 0.f, w2sum = 0.f;
+        int cnt = 0;
+        for (int64_t e = beg; e < end; ++e) {
+            const int64_t id = ids[e];
+            const float w = weights ? weights[e] : 1.0f;
+            if (!((uint64_t)id < V)) continue;
+            if (prune_w && !(w > 0.0f)) continue;
+            wsum = wsum + w;
+            w2sum = w2sum + w * w;
+            ++cnt;
+        }
+        lden[g] = combiner == DIR_COMBINER_MEAN ? (weights ? wsum : (float)cnt) : (weights ? sqrtf(w2sum) : sqrtf((float)cnt));
+    }
+}
+
+// Requester side: linear_finish_k's quads -- lane c of a sample's four computes the bags of slots 4 j + c (v = 0; v += the partial of every
+// owner in mask[g], ascending; v /= lden[g] when the bag had a live entry and the combiner is mean or sqrtn), and the quad adds them up in
+// SLOT order through quad broadcasts: acc = 0; acc += v_f for f = 0..F-1; r = acc + (bias ? bias[0] : 0.0f).  lden == nullptr: sum.
+template <int UFL>
+__global__ __launch_bounds__(256) void bags_linear_combine_k(const float* __restrict__ lback, int64_t n_back, int P,
+                                                             const int32_t* __restrict__ pos, const uint64_t* __restrict__ mask,
+                                                             const float* __restrict__ lden, int F, const float* __restrict__ bias, int64_t B,
+                                                             float* __restrict__ out, int64_t out_ld) {
+    const int c = threadIdx.x & 3;
+    const int64_t per_grid = ((int64_t)gridDim.x * blockDim.x) >> 2;
+    for (int64_t b0 = ((int64_t)blockIdx.x * blockDim.x) >> 2; b0 < B; b0 += per_grid) {      // (block-uniform trip count: the DPP reads see live lanes)
+        const int64_t b = b0 + (threadIdx.x >> 2);
+        const bool live = b < B;
+        float acc = 0.f;
+        for (int f0 = 0; f0 < F; f0 += 4 * UFL) {
+            uint64_t m[UFL];
+            float v[UFL];
+#pragma unroll
+            for (int j = 0; j < UFL; ++j) {
+                const int f = f0 + 4 * j + c;
+                m[j] = (live && f < F) ? mask[b * F + f] : 0ull;
+            }
+#pragma unroll
+            for (int j = 0; j < UFL; ++j) {
+                v[j] = 0.f;
+                if (m[j]) {
+                    const int64_t g = b * F + f0 + 4 * j + c;
+                    for (uint64_t mm = m[j]; mm; mm &= mm - 1ull) {
+                        const int32_t p = pos[g * P + (__ffsll((long long)mm) - 1)];
+                        if (p >= 0 && (int64_t)p < n_back) v[j] = v[j] + lback[p];
+                    }
+                    if (lden) v[j] = v[j] / lden[g];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < UFL; ++j) {
+                const int vi = __builtin_bit_cast(int, v[j]);
+                const float q0 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x00, 0xf, 0xf, true));   // quad_perm [0,0,0,0]
+                const float q1 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x55, 0xf, 0xf, true));   // [1,1,1,1]
+                const float q2 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xaa, 0xf, 0xf, true));   // [2,2,2,2]
+                const float q3 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xff, 0xf, 0xf, true));   // [3,3,3,3]
+                const int f = f0 + 4 * j;
+                if (f < F) acc = acc + q0;
+                if (f + 1 < F) acc = acc + q1;
+                if (f + 2 < F) acc = acc + q2;
+                if (f + 3 < F) acc = acc + q3;
+            }
+        }
+        if (live && c == 0) out[b * out_ld] = acc + (bias ? bias[0] : 0.f);
+    }
+}
+
+// Requester side of the backward, one lane per bag: every owner o in mask[g] gets c_g * d lin[b] (c_g = 1 / lden[g] for mean and sqrtn:
+// lden != nullptr) at position pos[g * P + o] of `send` -- where the forward received that partial.  bags_grad_k's rule: positions no
+// partial came back from are not written (the owners never read them).
+__global__ __launch_bounds__(256) void bags_linear_grad_k(const float* __restrict__ g, int64_t g_ld, int P, const int32_t* __restrict__ pos,
+                                                          const uint64_t* __restrict__ mask, const float* __restrict__ lden, int64_t nb, int F,
+                                                          float* __restrict__ send, int64_t n_send) {
+    for (int64_t gi = (int64_t)blockIdx.x * 256 + threadIdx.x; gi < nb; gi += (int64_t)gridDim.x * 256) {
+        const uint64_t m = mask[gi];
+        if (!m) continue;
+        const int64_t b = (int64_t)((uint32_t)gi / (uint32_t)F);         // nb < 2^31
+        float d = g[b * g_ld];
+        if (lden) d = d / lden[gi];
+        for (uint64_t mm = m; mm; mm &= mm - 1ull) {
+            const int32_t p = pos[gi * P + (__ffsll((long long)mm) - 1)];
+            if (p >= 0 && (int64_t)p < n_send) send[p] = d;
+        }
+    }
+}
+
 }  // namespace dir
 
 using namespace dir;
@@ -181,6 +384,71 @@ extern "C" int dir_shard_linear_grad_f32(const float* g, int64_t g_ld, const int
     if (B == 0 || n_send == 0) return DIR_OK;
     const int64_t n = B * F;
     hipLaunchKernelGGL(linear_grad_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, g, g_ld, inv, stride_b, stride_f, F, n, send, n_send);
+    DIR_CHECK_LAUNCH(name);
+    return DIR_OK;
+}
+
+// ---- the term over multi-hot bags ---------------------------------------------------------------------------------------------------
+extern "C" int dir_shard_bags_linear_pool_f32(const float* const* rows, int64_t row_ld, const int64_t* local_rows, int F, const int64_t* recv,
+                                              int P, int64_t cap_e, int64_t cap_b, float* lout, dir_stream_t stream) {
+    const char* name = "dir_shard_bags_linear_pool_f32";
+    DIR_CHECK_ARG(F > 0 && row_ld >= 1, "%s: F=%d row_ld=%lld", name, F, (long long)row_ld);
+    DIR_CHECK_ARG(P > 0 && P <= 64, "%s: P=%d (1 <= P <= 64)", name, P);
+    DIR_CHECK_ARG(cap_e > 0 && cap_e < ((int64_t)1 << 31), "%s: cap_e=%lld (0 < cap_e < 2^31)", name, (long long)cap_e);
+    DIR_CHECK_ARG(cap_b > 0 && (int64_t)P * cap_b < ((int64_t)1 << 31), "%s: cap_b=%lld (cap_b > 0, P*cap_b < 2^31)", name, (long long)cap_b);
+    DIR_CHECK_ARG(rows && local_rows && recv && lout, "%s: null pointer", name);
+    hipStream_t st = as_stream(stream);
+    // every word crosses the wire: a kernel's zero-fill (a memset node would end the world-1 lookup's graph capture: DESIGN 7.1)
+    if (zero_async(lout, (size_t)P * (size_t)cap_b * sizeof(float), st) != hipSuccess) return fail(DIR_E_HIP, "%s: zero-fill of lout failed", name);
+    const int64_t n = (int64_t)P * ((cap_e + SBL_U - 1) / SBL_U);      // one lane per chunk of SBL_U entry slots
+    hipLaunchKernelGGL(bags_linear_pool_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, rows, row_ld, local_rows, F,
+                       reinterpret_cast<const int4*>(recv), P, cap_e, cap_b, lout);
+    DIR_CHECK_LAUNCH(name);
+    return DIR_OK;
+}
+
+extern "C" int dir_shard_bags_linear_combine_f32(const float* lback, int P, int64_t cap_b, const int32_t* pos, const int64_t* mask,
+                                                 const int64_t* ids, const int64_t* offsets, const float* weights, int64_t nnz,
+                                                 int64_t stride_b, int64_t stride_f, const int64_t* vocab, int flags, int64_t B, int F,
+                                                 int combiner, float* lden, const float* bias, float* out, int64_t out_ld,
+                                                 dir_stream_t stream) {
+    const char* name = "dir_shard_bags_linear_combine_f32";
+    DIR_CHECK_ARG(F > 0 && B >= 0 && B * F < ((int64_t)1 << 31), "%s: F=%d B=%lld (B*F < 2^31)", name, F, (long long)B);
+    DIR_CHECK_ARG(P > 0 && P <= 64, "%s: P=%d (1 <= P <= 64)", name, P);
+    DIR_CHECK_ARG(cap_b > 0 && (int64_t)P * cap_b < ((int64_t)1 << 31), "%s: cap_b=%lld (cap_b > 0, P*cap_b < 2^31)", name, (long long)cap_b);
+    DIR_CHECK_ARG(combiner >= DIR_COMBINER_SUM && combiner <= DIR_COMBINER_SQRTN, "%s: combiner=%d", name, combiner);
+    DIR_CHECK_ARG(nnz >= 0 && out_ld >= 1, "%s: nnz=%lld out_ld=%lld", name, (long long)nnz, (long long)out_ld);
+    if (B == 0) return DIR_OK;                                 // an empty batch carries no buffers
+    DIR_CHECK_ARG(lback && pos && mask && out, "%s: null pointer", name);
+    const bool div = combiner != DIR_COMBINER_SUM;
+    DIR_CHECK_ARG(!div || (lden && offsets && vocab && (ids || nnz == 0)), "%s: null pointer (mean / sqrtn: ids, offsets, vocab, lden)", name);
+    hipStream_t st = as_stream(stream);
+    if (div) {
+        const int64_t nb = B * F;
+        hipLaunchKernelGGL(bags_linear_denom_k, dim3(grid_for((nb + 255) / 256)), dim3(256), 0, st, ids, offsets, weights, stride_b, stride_f,
+                           nb, F, vocab, flags, combiner, lden);
+    }
+    hipLaunchKernelGGL((bags_linear_combine_k<4>), dim3(grid_for((B + 63) / 64)), dim3(256), 0, st, lback, (int64_t)P * cap_b, P, pos,
+                       reinterpret_cast<const uint64_t*>(mask), div ? lden : nullptr, F, bias, B, out, out_ld);
+    DIR_CHECK_LAUNCH(name);
+    return DIR_OK;
+}
+
+extern "C" int dir_shard_bags_linear_grad_f32(const float* g, int64_t g_ld, int P, int64_t cap_b, const int32_t* pos, const int64_t* mask,
+                                              const float* lden, int64_t B, int F, int combiner, float* send, dir_stream_t stream) {
+    const char* name = "dir_shard_bags_linear_grad_f32";
+    DIR_CHECK_ARG(F > 0 && B >= 0 && B * F < ((int64_t)1 << 31), "%s: F=%d B=%lld (B*F < 2^31)", name, F, (long long)B);
+    DIR_CHECK_ARG(P > 0 && P <= 64, "%s: P=%d (1 <= P <= 64)", name, P);
+    DIR_CHECK_ARG(cap_b > 0 && (int64_t)P * cap_b < ((int64_t)1 << 31), "%s: cap_b=%lld (cap_b > 0, P*cap_b < 2^31)", name, (long long)cap_b);
+    DIR_CHECK_ARG(combiner >= DIR_COMBINER_SUM && combiner <= DIR_COMBINER_SQRTN, "%s: combiner=%d", name, combiner);
+    DIR_CHECK_ARG(g_ld >= 1, "%s: g_ld=%lld", name, (long long)g_ld);
+    DIR_CHECK_ARG(send, "%s: null pointer", name);
+    const bool div = combiner != DIR_COMBINER_SUM;
+    DIR_CHECK_ARG(B == 0 || (g && pos && mask && (lden || !div)), "%s: null pointer", name);
+    if (B == 0) return DIR_OK;
+    const int64_t nb = B * F;
+    hipLaunchKernelGGL(bags_linear_grad_k, dim3(grid_for((nb + 255) / 256)), dim3(256), 0, as_stream(stream), g, g_ld, P, pos,
+                       reinterpret_cast<const uint64_t*>(mask), div ? lden : nullptr, nb, F, send, (int64_t)P * cap_b);
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
 }

@@ -2511,6 +2511,61 @@ def shard_linear_grad(g, inv2d, send):
     return send
 
 
+def _lin_combiner(combiner):
+    if isinstance(combiner, (list, tuple)) or combiner not in _COMBINERS:
+        raise ValueError("the linear combiner is ONE of sum / mean / sqrtn (the model's linear_sparse_combiner), got %r" % (combiner,))
+    return _COMBINERS[combiner]
+
+
+def shard_bags_linear_pool(lin_ts, recv, P, cap_e, cap_b, out):
+    """Owner side of the first-order term over sharded bags (include/dir_hip.h: dir_shard_bags_linear_pool_f32): lin_ts = this rank's
+    packed linear rows (TableSet.ftrl_rows' layout), recv = the P received bag slabs -> out [P*cap_b] fp32: the run of every partial-row
+    position pooled as sum w_e * weight, in entry order (0.0 where no run returns: every word is written)."""
+    _dev(recv, torch.int64, "recv")
+    _dev(out, torch.float32, "out")
+    if lin_ts.K != 1 or lin_ts.ld == lin_ts.K:
+        raise ValueError("shard_bags_linear_pool: packed linear training rows (TableSet.ftrl_rows)")
+    if not recv.is_contiguous() or not out.is_contiguous() or recv.numel() < P * (cap_e + 1) * 2 or out.numel() < P * cap_b:
+        raise ValueError("shard_bags_linear_pool: recv [P*(cap_e+1)*2] int64 slabs, out a contiguous [P*cap_b] buffer")
+    _lib.check(_lib.load().dir_shard_bags_linear_pool_f32(_ptr(lin_ts._ptrs), lin_ts.ld, _ptr(lin_ts.vocab_dev), lin_ts.F, _ptr(recv), P, cap_e,
+                                                          cap_b, _ptr(out), _stream()))
+    return out
+
+
+def shard_bags_linear_combine(lback, P, cap_b, pos, mask, values, offsets, weights, sb, sf, vocab_dev, flags, B, F, combiner, lden, bias=None,
+                              out=None):
+    """Requester side (dir_shard_bags_linear_combine_f32): lback [P*cap_b] = the pooled weights as the exchange returned them, pos / mask
+    of the bucket pass -> out [B, 1] = sum_f combiner(sum of bag (b, f)'s partials in ascending owner order) + bias, ops.linear_logit's
+    CSR arithmetic in its order.  mean / sqrtn: lden [B*F] fp32 is written first, from the CSR entries (values, offsets, weights, the
+    layout strides and flags of the bucket call) -- keep it for shard_bags_linear_grad; sum: lden may be None."""
+    _dev(lback, torch.float32, "lback")
+    code = _lin_combiner(combiner)
+    if out is None:
+        out = torch.empty((B, 1), dtype=torch.float32, device=lback.device)
+    _dev(out, torch.float32, "out")
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+    if not lback.is_contiguous() or lback.numel() < P * cap_b or out.shape[0] != B or (code and (lden is None or lden.numel() < B * F)):
+        raise ValueError("shard_bags_linear_combine: lback a contiguous [P*cap_b] buffer, out [B, 1], lden [B*F] for mean / sqrtn")
+    _lib.check(_lib.load().dir_shard_bags_linear_combine_f32(_ptr(lback), P, cap_b, _ptr(pos), _ptr(mask), _ptr(values), _ptr(offsets),
+                                                             _ptr(weights), values.numel(), sb, sf, _ptr(vocab_dev), flags, B, F, code,
+                                                             _ptr(lden), _ptr(bias), _ptr(out), out.stride(0) if B > 1 else 1, _stream()))
+    return out
+
+
+def shard_bags_linear_grad(g, P, cap_b, pos, mask, lden, B, F, combiner, send):
+    """Requester side of the backward (dir_shard_bags_linear_grad_f32): g [B, 1] (or [B]) = d loss / d lin -> send [P*cap_b]: the position
+    of every partial the forward received set to g[b] (/ lden[g] for mean and sqrtn); other positions are left as they are."""
+    _dev(g, torch.float32, "g")
+    _dev(send, torch.float32, "send")
+    code = _lin_combiner(combiner)
+    if g.numel() != B or not send.is_contiguous() or send.numel() < P * cap_b or (code and lden is None):
+        raise ValueError("shard_bags_linear_grad: g [B, 1], send a contiguous [P*cap_b] buffer, lden for mean / sqrtn")
+    _lib.check(_lib.load().dir_shard_bags_linear_grad_f32(_ptr(g), g.stride(0) if B > 1 else 1, P, cap_b, _ptr(pos), _ptr(mask), _ptr(lden), B, F,
+                                                          code, _ptr(send), _stream()))
+    return send
+
+
 # ---- backward of the interaction ops (SURVEY 8f rank 2) --------------------------------------------------
 def fm_logit_backward(emb, g, F, K, add_in=None, out=None):
     """d fm_logit / d emb: demb[b,f,:] = g[b] * (sum_f' e[b,f',:] - e[b,f,:]) (+ add_in).  g: [B] or [B,1]."""
@@ -3216,6 +3271,33 @@ class SparseFtrl:
             src = ctypes.c_void_p(sorted_by._ws.data_ptr() + (-sorted_by._ws.data_ptr()) % 256)
         _lib.check(lib.dir_sparse_ftrl_rows_sorted_payload_f32(_ptr(ts._ptrs), ts.F, _ptr(payload), n, _ptr(grad), self.lr, self.l1, self.l2,
                                                                _ptr(self.row_base), self.total_rows, ws, need, src, _stream()))
+        ts.written(*self.accums, *self.linears)
+
+
+    def step_bags(self, recv, P, cap_e, cap_b, grad, sorted_by=None):
+        """Owner side of the first-order term's backward over sharded bags (shard.ShardedTables.lookup_bags_train(with_linear=True);
+        include/dir_hip.h: dir_sparse_ftrl_rows_sorted_bags_f32): recv = the P bag slabs the forward received, grad [P*cap_b] fp32 = d lin
+        of every partial-row position as received.  Entry (s, j) adds w * grad[s*cap_b + ret] to its (slot, row); every touched row takes
+        one FTRL step with its summed gradient.  sorted_by: the SparseAdagrad whose step_bags has JUST run over the same slabs on this
+        stream with the same local vocabularies: its sorted (row, entry) pairs are read and the key pass and the sort are skipped."""
+        ts = self.ts
+        if not self.packed:
+            raise ValueError("step_bags: packed linear training rows (TableSet.ftrl_rows)")
+        _dev(recv, torch.int64, "recv")
+        _dev(grad, torch.float32, "grad")
+        if recv.numel() < P * (cap_e + 1) * 2 or grad.numel() != P * cap_b or not grad.is_contiguous() or not recv.is_contiguous():
+            raise ValueError("step_bags: recv [P*(cap_e+1)*2] int64, grad a contiguous [P*cap_b] tensor")
+        if self.total_rows == 0:
+            return
+        lib = _lib.load()
+        ws, need = _sorted_ws(self, lib, P * cap_e, 1, 1, self.total_rows, ts.device)
+        src = None
+        if sorted_by is not None:
+            if sorted_by.total_rows != self.total_rows or list(sorted_by.ts.vocab) != list(ts.vocab) or sorted_by._ws is None:
+                raise ValueError("step_bags: sorted_by must have just sorted the same slabs over the same local vocabularies")
+            src = ctypes.c_void_p(sorted_by._ws.data_ptr() + (-sorted_by._ws.data_ptr()) % 256)
+        _lib.check(lib.dir_sparse_ftrl_rows_sorted_bags_f32(_ptr(ts._ptrs), ts.F, _ptr(recv), P, cap_e, cap_b, _ptr(grad), self.lr, self.l1,
+                                                            self.l2, _ptr(self.row_base), self.total_rows, ws, need, src, _stream()))
         ts.written(*self.accums, *self.linears)
 
 

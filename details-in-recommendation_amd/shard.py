@@ -24,6 +24,9 @@ DeepFM's first-order weights can live on the shards too (attach_linear: slot f's
 [w | n | z | -] rows).  The linear term then rides on the same id exchange -- owner: one weight per received payload word; one float
 per slab slot travels back behind the rows; requester: the sample's F weights summed in slot order -- and lookup_train(with_linear=True)
 sends d logit back the same way for an owner-side FTRL step on the Adagrad step's sort of the payload.
+Over multi-hot bags (lookup_bags(want_lin=True), lookup_bags_train(with_linear=True)) it rides on the bag lookup instead: the owner pools
+the first-order weights of each run beside the embedding rows, one float per partial-row position travels back behind the partial rows,
+and the requester applies the model's one linear_sparse_combiner.
 
 The collectives are torch.distributed.all_to_all_single (backend "nccl" = RCCL on ROCm; "gloo" in the CPU tests).
 world_size == 1 skips the collectives (unless force_collective) but still runs the three HIP steps.  The HIP steps sit
@@ -93,6 +96,13 @@ def partition_layout(vocab, K, P, rank, partitions=None):
 
 def _round_up(x, m):
     return (int(x) + m - 1) // m * m
+
+
+def _lin_combiner(c):
+    """The first-order term's combiner over bags: ONE name for every slot (the model's linear_sparse_combiner, deepFM.py:59)."""
+    if c not in ("sum", "mean", "sqrtn"):
+        raise ValueError("lin_combiner: 'sum' | 'mean' | 'sqrtn' (one for every slot), got %r" % (c,))
+    return c
 
 
 def _host_staged(t, group):
@@ -237,14 +247,37 @@ class HipBackend:
     def apply_ftrl(self, payload, grad, lr, l1, l2, sorted_by=None):
         """Owner, backward: the sorted FTRL over the payload it kept; sorted_by = the Adagrad optimiser that has just sorted the same
         payload (apply_adagrad): its sorted pairs are reused and the second key pass and sort are skipped."""
+        self._ftrl_opt(lr, l1, l2).step_payload(payload, grad, sorted_by=sorted_by)
+
+    def _ftrl_opt(self, lr, l1, l2):
         o = self._ftrl
         if o is None or (o.lr, o.l1, o.l2) != (float(lr), float(l1), float(l2)):
             o = self._ftrl = ops.SparseFtrl(self.lin_ts, lr, l1=l1, l2=l2)
-        o.step_payload(payload, grad, sorted_by=sorted_by)
+        return o
 
     def ftrl_dense(self, w, accum, linear, grad, lr, l1, l2):
         """FTRL step of a replicated dense variable (the linear bias) with its summed gradient."""
         ops.ftrl_dense_(w, accum, linear, grad, lr, l1, l2)
+
+    # ---- ... over multi-hot bags: it rides on the bag lookup (lookup_bags(want_lin=True), lookup_bags_train(with_linear=True)) ------
+    def bags_linear_pool(self, recv, cap_e, cap_b, out):
+        """Owner: out [P*cap_b] = the first-order weights of every run pooled as sum w_e * weight, in entry order; every word is written."""
+        ops.shard_bags_linear_pool(self.lin_ts, recv, self.P, cap_e, cap_b, out)
+
+    def bags_linear_combine(self, lback, cap_b, pos, mask, values, offsets, weights, B, sb, sf, flags, combiner, lden, bias, out):
+        """Requester: out [B, 1] = sum_f combiner(bag (b, f)'s partials in ascending owner order) + bias; mean / sqrtn write lden [B*F]
+        (the linear combiner's denominators, from the CSR entries with the lookup's liveness rule) on the way."""
+        ops.shard_bags_linear_combine(lback, self.P, cap_b, pos, mask, values, offsets, weights, sb, sf, self.vocab_dev, flags, B, self.ts.F,
+                                      combiner, lden, bias, out)
+
+    def bags_linear_grad(self, g, cap_b, pos, mask, lden, B, combiner, send):
+        """Requester, backward: send[pos of every partial the forward received] = g[b] (/ lden for mean and sqrtn)."""
+        ops.shard_bags_linear_grad(g, self.P, cap_b, pos, mask, lden, B, self.ts.F, combiner, send)
+
+    def bags_ftrl(self, recv, cap_e, cap_b, grad, lr, l1, l2, sorted_by=None):
+        """Owner, backward: the sorted FTRL over the bag records it kept, entry gradient w * grad[src*cap_b + ret]; sorted_by = the Adagrad
+        optimiser that has just sorted the same slabs (bags_adagrad): its sorted pairs are reused."""
+        self._ftrl_opt(lr, l1, l2).step_bags(recv, self.P, cap_e, cap_b, grad, sorted_by=sorted_by)
 
 
 _ROWS_TS = {}
@@ -339,6 +372,17 @@ class _BagPlan:
         self.back = self.rows if alias else torch.empty_like(self.rows)
         self.ws = st.backend.new_bags_workspace(dev)
         self.stat = torch.zeros(3, **i64)                 # [overflow, largest entry demand, largest pair demand], off the received headers
+        self.P, self.nb, self.device, self.lrows = P, nb, dev, None
+
+    def lin_buffers(self):
+        """The first-order term's buffers, made at the first lookup that wants it: one float per partial-row position, sent (lrows) and
+        received (lback; the same at world 1), and the linear combiner's denominator per bag (lden: written by mean / sqrtn forwards, read
+        by their backward).  -> (lrows, lback, lden)"""
+        if self.lrows is None:
+            self.lrows = torch.zeros(self.P * self.cap_b, dtype=torch.float32, device=self.device)
+            self.lback = self.lrows if self.recv is self.send else torch.zeros_like(self.lrows)
+            self.lden = torch.ones(max(1, self.nb), dtype=torch.float32, device=self.device)
+        return self.lrows, self.lback, self.lden
 
 
 class _Lookup:
@@ -1121,7 +1165,8 @@ class ShardedTables:
             raise RuntimeError("ShardedTables: a slab of an earlier lookup_bags overflowed: that result was incomplete (the capacities have "
                                "grown to %s)" % (self._bag_cap,))
 
-    def lookup_bags(self, values, offsets, weights=None, combiner="mean", max_norm=None, field_major=False, flags=0, want_fm=False):
+    def lookup_bags(self, values, offsets, weights=None, combiner="mean", max_norm=None, field_major=False, flags=0, want_fm=False,
+                    want_lin=False, lin_combiner="sum", lin_bias=None):
         """Multi-hot bags over the row-sharded tables, pooled on the owning rank: the sharded form of ops.embedding_bag(values, offsets,
         weights, combiner, field_major, flags, max_norm=) (values [nnz] global row ids, offsets [B_local*F+1], bag (b, f) = b*F+f, or f*B+b
         when field_major; weights [nnz] or None; combiner / max_norm: one value or one per slot).  -> (emb [B_local, F*K], fm [B_local, 1]
@@ -1136,8 +1181,24 @@ class ShardedTables:
         every rank) and the capacities grow to the demands the headers carry; the constructor's `check` decides when: "eager" reads it
         after the whole lookup has been enqueued and repeats an overflowing lookup; "lazy" reads it after the NEXT lookup_bags has been
         enqueued (no host wait on a lookup's own work; an overflow raises there, the result it reports on was incomplete); "never" leaves
-        it to check_overflow().  Every rank must call it the same number of times (SPMD)."""
+        it to check_overflow().  Every rank must call it the same number of times (SPMD).
+
+        want_lin: -> (emb, fm, lin); lin [B_local, 1] = the first-order term over the same bags (attach_linear) + lin_bias (a [1] device
+        tensor, or None), ops.linear_logit(values, offsets, weights, combiner=lin_combiner, field_major=) over the unsharded weights.  It
+        rides on this lookup: the owner pools the first-order weights of each run beside the embedding rows (w * weight summed in entry
+        order), ONE float per partial-row position travels back behind the partial rows, and the requester adds a bag's partials in
+        ascending owner order, applies lin_combiner -- the model's one linear_sparse_combiner ("sum" | "mean" | "sqrtn"), independent of
+        the per-slot `combiner` -- and sums the sample's F bags in slot order.  With one owner per bag and flags = 0 the result is
+        ops.linear_logit's bit for bit.  The term sees the lookup's live entries: under PRUNE_NONPOSITIVE_WEIGHTS the pruned entries
+        contribute to neither term.  An overflow repeat carries it; without want_lin nothing here changes."""
         B = self._bag_args(values, offsets, weights, "lookup_bags")
+        lin = None
+        if want_lin:
+            self._need_linear("lookup_bags(want_lin=True)")
+            lin = (_lin_combiner(lin_combiner), lin_bias)
+
+        def res(out, fm, lo):
+            return (out, fm, lo) if want_lin else (out, fm)
         self.stats["bag_lookups"] = self.stats.get("bag_lookups", 0) + 1
         check = self._collective()
         while True:
@@ -1145,9 +1206,10 @@ class ShardedTables:
             plan = self._bag_plan(B, cap_e, cap_b)
             self.stats["bag_cap"] = (cap_e, cap_b)
             host = self._bag_host() if check and values.device.type == "cuda" else None
-            out, fm, pend = self._bags_pipeline(plan, host, values, offsets, weights, B, combiner, max_norm, field_major, flags, want_fm)
+            out, fm, pend, lo = self._bags_pipeline(plan, host, values, offsets, weights, B, combiner, max_norm, field_major, flags, want_fm,
+                                                    lin)
             if not check:
-                return out, fm
+                return res(out, fm, lo)
             if self.check != "eager":
                 prev, self._bag_unchecked = self._bag_unchecked, (self._bag_unchecked + [pend])[-2:]
                 if self.check == "lazy":          # the earlier lookups' verdicts: their header scans finished long ago
@@ -1155,15 +1217,18 @@ class ShardedTables:
                     if any([self._bag_verdict(p) for p in prev]):
                         raise RuntimeError("ShardedTables: a slab of the previous lookup_bags overflowed: that result was incomplete "
                                            "(the capacities have grown to %s)" % (self._bag_cap,))
-                return out, fm
+                return res(out, fm, lo)
             if not self._bag_verdict(pend):       # the verdict, read after the whole lookup has been enqueued
-                return out, fm
+                return res(out, fm, lo)
 
-    def _bags_pipeline(self, plan, host, values, offsets, weights, B, combiner, max_norm, field_major, flags, want_fm):
+    def _bags_pipeline(self, plan, host, values, offsets, weights, B, combiner, max_norm, field_major, flags, want_fm, lin=None):
         """One pass of the bag lookup over `plan`'s buffers: bucket, exchange, pool on the owner, exchange, combine.  -> (emb, fm | None,
-        pending verdict | None).  With several ranks the pooling pass leaves [overflow, demands] off the received headers in plan.stat;
-        the pending verdict is (event, host) after which the pinned `host` words hold them, or (None, a copy) on a CPU backend.  What is
-        done with it is the caller's policy."""
+        pending verdict | None, lin | None).  With several ranks the pooling pass leaves [overflow, demands] off the received headers in
+        plan.stat; the pending verdict is (event, host) after which the pinned `host` words hold them, or (None, a copy) on a CPU backend.
+        What is done with it is the caller's policy.
+        lin = (linear combiner, bias | None): the first-order term rides along -- the owner pools the first-order weights of each run
+        right after the rows, one float per partial-row position goes back behind the partial rows (a second equal-split all-to-all), and
+        the requester combines them beside the rows; without it nothing here changes."""
         F, K, be = self.F, self.K, self.backend
         cap_e, cap_b = plan.cap_e, plan.cap_b
         sb, sf = (1, B) if field_major else (F, 1)
@@ -1178,11 +1243,21 @@ class ShardedTables:
             pend = (torch.cuda.current_stream(dev).record_event(), host)
         elif check:
             pend = (None, plan.stat.clone())
-        _wait(self._a2a_equal(plan.back, plan.rows))
+        wr, wl = self._a2a_equal(plan.back, plan.rows), None
+        if lin is not None:                      # (the owner's second pass runs under the row exchange where the transport is asynchronous)
+            lrows, lback, lden = plan.lin_buffers()
+            be.bags_linear_pool(plan.recv, cap_e, cap_b, lrows)
+            wl = self._a2a_equal(lback, lrows)
+        _wait(wr)
         out = torch.empty((B, F * K), dtype=torch.float32, device=dev)
         fm = torch.empty((B, 1), dtype=torch.float32, device=dev) if want_fm else None
         be.bags_combine(plan.back, cap_b, plan.pos, plan.mask, plan.denom, B, combiner, out, fm)
-        return out, fm, pend
+        lo = None
+        if lin is not None:
+            _wait(wl)
+            lo = torch.empty((B, 1), dtype=torch.float32, device=dev)
+            be.bags_linear_combine(lback, cap_b, plan.pos, plan.mask, values, offsets, weights, B, sb, sf, flags, lin[0], lden, lin[1], lo)
+        return out, fm, pend, lo
 
     def _bag_args(self, values, offsets, weights, what):
         F = self.F
@@ -1192,7 +1267,8 @@ class ShardedTables:
             raise ValueError("%s: weights must be [nnz]" % what)
         return (offsets.numel() - 1) // F
 
-    def lookup_bags_train(self, values, offsets, weights=None, combiner="mean", max_norm=None, field_major=False, flags=0):
+    def lookup_bags_train(self, values, offsets, weights=None, combiner="mean", max_norm=None, field_major=False, flags=0,
+                          with_linear=False, lin_combiner="sum"):
         """Differentiable lookup_bags (the same arguments but want_fm): emb [B_local, F*K] with a grad_fn, equal to lookup_bags(...)[0] bit
         for bit; the tables get no .grad.  emb.backward(g) performs ONE synchronous sparse Adagrad step over the global batch on every
         rank's shard (the optimiser of enable_training, shared with lookup_train): entry e of bag (b, f) contributes w_e * c_bag *
@@ -1205,12 +1281,25 @@ class ShardedTables:
         Training uses its own plans: inference lookups in between leave the backward's buffers alone.  The forward reads its own overflow
         verdict (every rank the same words) and repeats with grown capacities; verdicts pending from check="lazy" / "never" lookup_bags
         calls stay pending.  As with lookup_train, where duplicate contributions sit in the slabs depends on atomic order: once a row has
-        duplicates, results agree to fp32 rounding, not bit for bit, from run to run.  Every rank must call it (SPMD)."""
+        duplicates, results agree to fp32 rounding, not bit for bit, from run to run.  Every rank must call it (SPMD).
+        with_linear: -> (emb, lin) from ONE autograd node; lin [B_local, 1] = lookup_bags(want_lin=True, lin_combiner=)'s term without a
+        bias (the bias is a replicated dense variable of the caller's).  Its backward receives both gradients: the requester scatters both
+        (d lin[b] times 1 / the linear denominator for mean and sqrtn, to the position of every partial), the rows travel back, then the
+        floats, and every owner applies Adagrad to its embedding rows, then FTRL (enable_linear_training) to its first-order rows over
+        the same bag records on the Adagrad step's sort: entry e contributes w_e * c_bag * d lin[b], all contributions to a row summed
+        before n, z and w move -- one optimiser step."""
         if self.optimizer is None:
             raise RuntimeError("call enable_training(lr) first")
+        lin_comb = None
+        if with_linear:
+            self._need_linear("lookup_bags_train(with_linear=True)")
+            if self._lin_hp is None:
+                raise RuntimeError("call enable_linear_training(lr) first")
+            lin_comb = _lin_combiner(lin_combiner)
         self._bag_args(values, offsets, weights, "lookup_bags_train")
         anchor = torch.zeros((), dtype=torch.float32, device=values.device, requires_grad=True)
-        return _ShardedBagLookup.apply(self, values, offsets, weights, combiner, max_norm, field_major, flags, torch.is_grad_enabled(), anchor)
+        return _ShardedBagLookup.apply(self, values, offsets, weights, combiner, max_norm, field_major, flags, torch.is_grad_enabled(), lin_comb,
+                                       anchor)
 
     def _bag_train_plan(self, B, cap_e, cap_b):
         key = (B, cap_e, cap_b)
@@ -1224,27 +1313,37 @@ class ShardedTables:
             self._bag_train_plans[key] = fresh
         return fresh
 
-    def _bags_forward_train(self, values, offsets, weights, combiner, max_norm, field_major, flags, hold):
+    def _bags_forward_train(self, values, offsets, weights, combiner, max_norm, field_major, flags, hold, lin_comb=None):
         B = self._bag_args(values, offsets, weights, "lookup_bags_train")
         self.stats["bag_train_lookups"] = self.stats.get("bag_train_lookups", 0) + 1
         while True:
             plan = self._bag_train_plan(B, *self._bag_caps(B, values.numel()))
-            out, _, pend = self._bags_pipeline(plan, plan.host, values, offsets, weights, B, combiner, max_norm, field_major, flags, False)
+            out, _, pend, lo = self._bags_pipeline(plan, plan.host, values, offsets, weights, B, combiner, max_norm, field_major, flags, False,
+                                                   None if lin_comb is None else (lin_comb, None))
             # this lookup's own verdict only (the same words on every rank: all ranks repeat together); pending lazy verdicts stay pending
             if pend is None or not self._bag_verdict(pend):
                 plan.busy = bool(hold)
-                return out, plan
+                return out, plan, lo
 
-    def _bags_backward_apply(self, saved, g):
-        plan, B, combiner, max_norm = saved
+    def _bags_backward_apply(self, saved, g, g_lin=None):
+        """g_lin (with_linear): d loss / d lin [B_local, 1].  The forward's float buffers carry it back behind the gradient rows; the
+        owner's FTRL runs after its Adagrad, over the same bag records, on that step's sort."""
+        plan, B, combiner, max_norm, lin_comb = saved
         be = self.backend
         self._updates += 1
         try:
             g2 = g if g.dim() == 2 and (B == 0 or g.stride(1) == 1) else g.contiguous()
             # the partial rows' buffers are the gradient's: rows = what this rank sends, back = what it receives (the same at world 1)
             be.bags_grad(g2, plan.cap_b, plan.pos, plan.mask, plan.denom, B, combiner, plan.rows)
+            if g_lin is not None:
+                lrows, lback, lden = plan.lin_buffers()
+                be.bags_linear_grad(g_lin, plan.cap_b, plan.pos, plan.mask, lden, B, lin_comb, lrows)
             _wait(self._a2a_equal(plan.back, plan.rows))
+            if g_lin is not None:
+                _wait(self._a2a_equal(lback, lrows))
             be.bags_adagrad(self.optimizer, plan.recv, plan.cap_e, plan.cap_b, plan.back, max_norm)
+            if g_lin is not None:
+                be.bags_ftrl(plan.recv, plan.cap_e, plan.cap_b, lback, *self._lin_hp, sorted_by=self.optimizer)
         finally:
             plan.busy = False
 
@@ -1301,19 +1400,21 @@ class _ShardedLookup(torch.autograd.Function):
 
 
 class _ShardedBagLookup(torch.autograd.Function):
-    """emb = ShardedTables.lookup_bags(...)[0] with a backward that sends every bag's gradient back along its partial rows and lets each
-    owner apply the sparse Adagrad update to its shard from the bag records it kept (no gradient tensor is returned for the tables)."""
+    """emb (or, lin_comb given, (emb, lin): the bags and the first-order term over them from ONE node) = ShardedTables.lookup_bags(...) with a
+    backward that sends every bag's gradient (and d lin behind it) back along its partial rows and lets each owner apply the sparse Adagrad
+    update to its shard, then FTRL to its first-order rows, from the bag records it kept -- one optimiser step; no gradient tensor is
+    returned for the tables."""
 
     @staticmethod
-    def forward(ctx, st, values, offsets, weights, combiner, max_norm, field_major, flags, hold, anchor):
-        emb, plan = st._bags_forward_train(values, offsets, weights, combiner, max_norm, field_major, flags, hold)
-        ctx.st, ctx.saved = st, (plan, emb.shape[0], combiner, max_norm)
-        return emb
+    def forward(ctx, st, values, offsets, weights, combiner, max_norm, field_major, flags, hold, lin_comb, anchor):
+        emb, plan, lin = st._bags_forward_train(values, offsets, weights, combiner, max_norm, field_major, flags, hold, lin_comb)
+        ctx.st, ctx.saved = st, (plan, emb.shape[0], combiner, max_norm, lin_comb)
+        return emb if lin_comb is None else (emb, lin)
 
     @staticmethod
-    def backward(ctx, g):
-        ctx.st._bags_backward_apply(ctx.saved, g)
-        return (None,) * 10
+    def backward(ctx, g, g_lin=None):
+        ctx.st._bags_backward_apply(ctx.saved, g, None if g_lin is None else g_lin.contiguous())
+        return (None,) * 11
 
 
 # ---- the dense (replicated) side of multi-GPU training -----------------------------------------------------------------
@@ -1401,8 +1502,10 @@ class ShardedDeepFMTrainer:
     (:58).  The first-order weights live on the shards (tables.attach_linear: co-located with the embedding rows, owner-side FTRL over the
     global batch); `model`.linear_bias is replicated and takes a dense FTRL step with its gradient summed over the ranks (FTRL is not
     linear in the gradient: the all-reduce comes first), so it must not be among dense_optimizer's parameters.  step() and predict() then
-    compute fm + dnn + lin; the multi-hot forms do not carry the term (a first-order term over bags needs linear_sparse_combiner on the
-    owner).  linear = None: the FM + DNN model, as before."""
+    compute fm + dnn + lin, and so do step_bags() and predict_bags() over multi-hot bags: the owners pool the first-order weights of
+    each bag beside its embedding rows and `model`.linear_sparse_combiner is applied on the requester (lookup_bags(want_lin=True),
+    lookup_bags_train(with_linear=True)); a backend without the bag forms of the term raises NotImplementedError there.
+    linear = None: the FM + DNN model, as before."""
 
     def __init__(self, model, tables, lr_sparse, dense_optimizer, group=None, initial_accumulator_value=0.1, linear=None):
         self.model, self.tables, self.group = model, tables, group
@@ -1424,8 +1527,16 @@ class ShardedDeepFMTrainer:
             self.bias_accum = torch.full_like(bias.data, float(linear.get("initial_accumulator_value", 0.1)))
             self.bias_linear = torch.zeros_like(bias.data)
 
-    _NO_BAG_LINEAR = ("ShardedDeepFMTrainer(linear=...): the first-order term is not carried over multi-hot bags (it needs "
-                      "linear_sparse_combiner on the owning rank); use step() / predict() or linear=None")
+    _BAG_LINEAR = ("bags_linear_pool", "bags_linear_combine", "bags_linear_grad", "bags_ftrl")
+
+    def _bag_linear(self):
+        """Whether the multi-hot forms carry the first-order term (linear=...); checked BEFORE anything is read off the model."""
+        if self.linear is None:
+            return False
+        if not all(hasattr(self.tables.backend, n) for n in self._BAG_LINEAR):
+            raise NotImplementedError("ShardedDeepFMTrainer(linear=...): this backend has no first-order term over multi-hot bags "
+                                      "(bags_linear_pool / _combine / _grad, bags_ftrl); use step() / predict() or linear=None")
+        return True
 
     def step(self, ids, labels):
         """ids [B_local, F] global row ids, labels [B_local, 1] -> this rank's summed loss (detached)."""
@@ -1440,11 +1551,15 @@ class ShardedDeepFMTrainer:
             emb = self.tables.lookup_train(ids)                               # tables update inside backward()
             logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb)         # fm_logit_fn + dnn_logit_fn, deepFM.py:337-338
         loss = self._loss_backward_dense_step(logits, labels)
-        if self.linear is not None:                                           # the bias: FTRL with the GLOBAL gradient
-            b = m.linear_bias
-            with torch.no_grad():
-                self.tables.backend.ftrl_dense(b.data, self.bias_accum, self.bias_linear, b.grad.contiguous(), *self.linear)
+        if self.linear is not None:
+            self._bias_ftrl_step()
         return loss
+
+    def _bias_ftrl_step(self):
+        """The replicated bias: FTRL with the GLOBAL gradient (allreduce_grads has summed it: linear_bias is among dense_params)."""
+        b = self.model.linear_bias
+        with torch.no_grad():
+            self.tables.backend.ftrl_dense(b.data, self.bias_accum, self.bias_linear, b.grad.contiguous(), *self.linear)
 
     def _loss_backward_dense_step(self, logits, labels):
         """The tail of a step: the SUM loss, backward (every owner's shard takes its step inside), the dense gradients summed over the
@@ -1459,15 +1574,22 @@ class ShardedDeepFMTrainer:
         """step() over multi-hot bags (a history column of the reference's DeepFM, deepFM.py:53,77,84): lookup_bags_train with every
         column's combiner and max_norm, the FM + DNN logits, the SUM loss, backward (every owner's shard takes its Adagrad step), the
         dense gradients summed over the ranks and the dense step.  values / offsets / weights as lookup_bags; labels [B_local, 1] ->
-        this rank's summed loss (detached)."""
+        this rank's summed loss (detached).  linear=...: + (lin + linear_bias) with the model's linear_sparse_combiner over the same bags
+        (deepFM.py:89-95, 255-275); the owners' first-order rows take their FTRL step inside backward, the bias its dense one, as in step()."""
         from . import autograd as ag
-        if self.linear is not None:
-            raise NotImplementedError(self._NO_BAG_LINEAR)
+        with_lin = self._bag_linear()
         m = self.model
         self.dense_optimizer.zero_grad(set_to_none=True)
         comb = [c.combiner for c in m.dnn_feature_columns]
-        emb = self.tables.lookup_bags_train(values, offsets, weights, combiner=comb, max_norm=m._max_norm(), field_major=field_major)
-        return self._loss_backward_dense_step(ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb), labels)
+        kw = dict(combiner=comb, max_norm=m._max_norm(), field_major=field_major)
+        if not with_lin:
+            emb = self.tables.lookup_bags_train(values, offsets, weights, **kw)
+            return self._loss_backward_dense_step(ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb), labels)
+        m.linear_bias.grad = None
+        emb, lin = self.tables.lookup_bags_train(values, offsets, weights, with_linear=True, lin_combiner=m.linear_sparse_combiner, **kw)
+        loss = self._loss_backward_dense_step(ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb) + (lin + m.linear_bias), labels)
+        self._bias_ftrl_step()
+        return loss
 
     @torch.no_grad()
     def predict(self, ids):
@@ -1508,12 +1630,16 @@ class ShardedDeepFMTrainer:
     def predict_bags(self, values, offsets, weights=None, field_major=False):
         """Inference logits [B_local, 1] of the same FM + DNN model over multi-hot bags of the row-sharded tables (a history column of the
         reference's DeepFM, deepFM.py:53,77,84): lookup_bags(want_fm=True) with every column's combiner and max_norm, then the tower with
-        the FM term added -- what predict() does for one-hot ids."""
-        if self.linear is not None:
-            raise NotImplementedError(self._NO_BAG_LINEAR)
+        the FM term added -- what predict() does for one-hot ids.  linear=...: the first-order term (the model's linear_sparse_combiner,
+        + linear_bias) rides on the same lookup and is added to the logits."""
+        with_lin = self._bag_linear()
         m = self.model
         with _eval_mode(m):
             comb = [c.combiner for c in m.dnn_feature_columns]
-            emb, fm = self.tables.lookup_bags(values, offsets, weights, combiner=comb, max_norm=m._max_norm(), field_major=field_major,
-                                              want_fm=True)
-            return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(self.tables.absmax()))
+            kw = dict(combiner=comb, max_norm=m._max_norm(), field_major=field_major, want_fm=True)
+            if not with_lin:
+                emb, fm = self.tables.lookup_bags(values, offsets, weights, **kw)
+                return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(self.tables.absmax()))
+            emb, fm, lin = self.tables.lookup_bags(values, offsets, weights, want_lin=True, lin_combiner=m.linear_sparse_combiner,
+                                                   lin_bias=m.linear_bias.data.reshape(-1)[:1], **kw)
+            return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(self.tables.absmax())) + lin

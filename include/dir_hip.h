@@ -572,6 +572,45 @@ int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F, const int
                                             float l2, const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
                                             const void* sorted_from, dir_stream_t stream);
 
+/* The first-order term over MULTI-HOT bags on row-sharded weights (ShardedTables.lookup_bags(want_lin=) / lookup_bags_train(with_linear=);
+ * reference: the linear model's categorical columns with linear_sparse_combiner, deepFM.py:59,89-95,255-275).  It rides on the bag
+ * lookup (dir_shard_bags_bucket / _pool / _combine): no second bucket pass, no second entry exchange; one float per partial-row position
+ * travels back behind the partial rows (1/K of their bytes).  combiner is the model's ONE linear_sparse_combiner (DIR_COMBINER_*),
+ * independent of the per-slot embedding combiners.
+ * dir_shard_bags_linear_pool_f32 (owner): rows / row_ld / local_rows = this rank's packed [w | n | z | -] rows as
+ *   dir_shard_linear_gather_f32 takes them (local_rows required), recv = the P received bag slabs of cap_e + 1 16-byte records.
+ *   lout [P * cap_b] is zero-filled (by a kernel: graph-capturable), then lout[src * cap_b + ret] = sum over the run of w_e *
+ *   rows[slot_e][row_e * row_ld], in entry order, from 0.0f.  dir_shard_bags_pool_f32's record checks: count from the header, row < the
+ *   slot's local rows, 0 <= ret < cap_b.  P <= 64, 0 < cap_e < 2^31, P * cap_b < 2^31.
+ * dir_shard_bags_linear_combine_f32 (requester): lback [P * cap_b] = the floats as the exchange returned them; pos / mask of the bucket
+ *   pass.  Per bag g = b * F + f: v = the partials of the owners in mask[g] in ascending order, from 0; mean / sqrtn and mask[g] != 0:
+ *   v / lden[g].  out[b * out_ld] = (sum_f v, slot order, from 0) + (bias ? bias[0] : 0) -- dir_linear_sparse_sum_f32's operations in its
+ *   order: with one owner per bag and flags = 0, its result bit for bit.  mean / sqrtn: lden [B * F] is WRITTEN first, from the CSR
+ *   entries (ids [nnz], offsets, weights or NULL, bag (b, f) at offsets[b * stride_b + f * stride_f], vocab [F], flags: the bucket
+ *   call's) with the lookup's liveness rule: wsum / sqrtf(w2sum) in entry order with weights, the live count / its sqrtf without; keep it
+ *   for the backward.  sum: ids, offsets, weights, vocab, lden are not read (NULL is fine).  B * F < 2^31.
+ * dir_shard_bags_linear_grad_f32 (requester, the transpose of the combine): every owner o in mask[g] gets send[pos[g * P + o]] =
+ *   g[b * g_ld] (/ lden[g] for mean and sqrtn; lden as the combine call wrote it, NULL for sum).  Positions no partial came back from are
+ *   not written.  send is [P * cap_b].
+ * dir_sparse_ftrl_rows_sorted_bags_f32 (owner): FTRL-Proximal on the packed rows over the bag records the owner kept: entry e adds
+ *   w_e * grecv[src * cap_b + ret_e] to its (slot, row); all entries of a row -- of any bag, any rank, inside one bag -- are summed BEFORE
+ *   n, z and w move, and every row is written once (lr > 0, l1, l2 >= 0).  The key pass applies the pool kernel's checks.  Workspace:
+ *   dir_sparse_adagrad_sorted_workspace_bytes(P * cap_e, 1, 1, total_rows) device bytes, 256-byte aligned; P * cap_e < 2^30.  sorted_from
+ *   (or NULL): the workspace of the dir_sparse_adagrad_sorted_bags_f32 call that has just sorted the SAME slabs (P, cap_e, cap_b,
+ *   row_base, total_rows) on this stream: its sorted pairs are read, the key pass and the sort are skipped; the rows come out bit for
+ *   bit as without it. */
+int dir_shard_bags_linear_pool_f32(const float* const* rows, int64_t row_ld, const int64_t* local_rows, int F, const int64_t* recv, int P,
+                                   int64_t cap_e, int64_t cap_b, float* lout, dir_stream_t stream);
+int dir_shard_bags_linear_combine_f32(const float* lback, int P, int64_t cap_b, const int32_t* pos, const int64_t* mask, const int64_t* ids,
+                                      const int64_t* offsets, const float* weights, int64_t nnz, int64_t stride_b, int64_t stride_f,
+                                      const int64_t* vocab, int flags, int64_t B, int F, int combiner, float* lden, const float* bias,
+                                      float* out, int64_t out_ld, dir_stream_t stream);
+int dir_shard_bags_linear_grad_f32(const float* g, int64_t g_ld, int P, int64_t cap_b, const int32_t* pos, const int64_t* mask,
+                                   const float* lden, int64_t B, int F, int combiner, float* send, dir_stream_t stream);
+int dir_sparse_ftrl_rows_sorted_bags_f32(float* const* rows, int F, const int64_t* recv, int P, int64_t cap_e, int64_t cap_b,
+                                         const float* grecv, float lr, float l1, float l2, const int64_t* row_base, int64_t total_rows,
+                                         void* workspace, int64_t workspace_bytes, const void* sorted_from, dir_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * A5 / A9  hidden layers of the DNN towers: Y[M, N] = act(X[M, Kd] . Wt[N, Kd]^T + bias[N])   (row strides x_ld, w_ld, y_ld).
  *   reference: dnn_logit_fn, models/DeepFM/deepFM.py:295-300; _deep_architecture,
