@@ -61,7 +61,7 @@ if os.environ.get("DIR_ABLATE"):
 
 
 def _deps_mtime():
-    hdrs = [os.path.join(CSRC, h) for h in ("common.hpp", "bag_row.hpp", "shard_route.hpp")] + [os.path.join(HERE, "..", "include", "dir_hip.h")]
+    hdrs = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp")] + [os.path.join(HERE, "..", "include", "dir_hip.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

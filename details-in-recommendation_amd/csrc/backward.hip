@@ -20,6 +20,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #endif
 #include "common.hpp"
+#include "shard_wire.hpp"
 #include <type_traits>
 
 namespace dir {
@@ -411,8 +412,9 @@ __global__ __launch_bounds__(256) void adagrad_keys_payload_k(const int64_t* __r
                                                               uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         const int64_t p = payload[e];
-        const int f = p >= 0 ? (int)(p % F) : 0;
-        const int64_t row = p >= 0 ? p / F : -1;
+        int f = 0;
+        int64_t row = -1;
+        if (p >= 0) unpack_payload(p, F, f, row);
         const int64_t vf = (f + 1 < F ? row_base[f + 1] : (int64_t)total_rows) - row_base[f];
         keys[e] = (uint64_t)row < (uint64_t)vf ? (uint32_t)(row_base[f] + row) : total_rows;
         vals[e] = (uint32_t)e;
@@ -420,23 +422,20 @@ __global__ __launch_bounds__(256) void adagrad_keys_payload_k(const int64_t* __r
 }
 
 // bag entries of the sharded multi-hot backward (ShardedTables.lookup_bags_train, owner side): entry e = record e % cap_e of received
-// slab e / cap_e (shard_bags.hip's 16-byte records).  Records past the slab header's count, and records that fail bags_pool_k's checks
-// (row < the local table's rows, return position in [0, cap_b)), sort behind every row.  The record is read unconditionally: j < cap_e
-// always lies inside the slab.
+// slab e / cap_e (shard_wire.hpp's 16-byte records).  Records past the slab header's count, and records the pool drops
+// (read_bag_record, row < the local table's rows), sort behind every row.
 __global__ __launch_bounds__(256) void adagrad_keys_bags_k(const int4* __restrict__ recv, int64_t n, int64_t cap_e, int64_t cap_b, int F,
                                                            const int64_t* __restrict__ row_base, uint32_t total_rows,
                                                            uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         const int64_t src = (uint32_t)e / (uint32_t)cap_e;                 // n < 2^30
         const int64_t j = e - src * cap_e;
-        const int4* slab = recv + src * (cap_e + 1);
-        const int64_t ne = min((int64_t)(unsigned int)slab[0].x, cap_e);
-        const int4 r = slab[1 + j];
-        const int64_t p = (int64_t)(((uint64_t)(uint32_t)r.y << 32) | (uint32_t)r.x);
+        const int4* slab = bag_slab_of(recv, src, cap_e);
         uint32_t key = total_rows;
-        if (j < ne && p >= 0 && r.w >= 0 && (int64_t)r.w < cap_b) {
-            const int64_t rr = p / F;
-            const int sl = (int)(p - rr * F);
+        int ret, sl;
+        float w;
+        int64_t rr;
+        if (read_bag_record(slab, j, bag_entries(slab, cap_e), F, cap_b, ret, w, sl, rr)) {
             const int64_t vf = (sl + 1 < F ? row_base[sl + 1] : (int64_t)total_rows) - row_base[sl];
             if (rr < vf) key = (uint32_t)(row_base[sl] + rr);
         }
@@ -721,9 +720,10 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
         if constexpr (BAG) {
             // the record's weight times the gradient of its partial row (the key pass checked the return position; clamped anyway)
             const uint32_t src = ent / (uint32_t)bag.cap_e;
-            const int4 r = bag.recv[(int64_t)src * (bag.cap_e + 1) + 1 + (ent - (int64_t)src * bag.cap_e)];
-            const int64_t ret = r.w < 0 ? 0 : ((int64_t)r.w < bag.cap_b ? r.w : bag.cap_b - 1);
-            return V::scale(V::ld(bag.grecv + ((int64_t)src * bag.cap_b + ret) * K + (c < kv ? c : 0) * VEC), __int_as_float(r.z));
+            const int4 r = bag_slab_of(bag.recv, src, bag.cap_e)[1 + (ent - (int64_t)src * bag.cap_e)];
+            const int rr = bag_record_ret(r);
+            const int64_t ret = rr < 0 ? 0 : ((int64_t)rr < bag.cap_b ? rr : bag.cap_b - 1);
+            return V::scale(V::ld(bag.grecv + ((int64_t)src * bag.cap_b + ret) * K + (c < kv ? c : 0) * VEC), bag_record_weight(r));
         }
         const uint32_t b = ent / (uint32_t)F;
         const int f = (int)(ent - b * (uint32_t)F);
@@ -952,6 +952,25 @@ static bool adagrad_sorted_plan(int64_t n, int K, int64_t total_rows, AdaSortedP
     return true;
 }
 
+// The workspace of a sorted update carved by its plan: the two (key, value) buffer pairs of the sort (sorted pairs land in k1 / v1), the
+// tiles' carry rows and the sort's scratch.  sorted_from != nullptr: the workspace of an earlier sorted update of the SAME entries on
+// this stream -- its sorted pairs are borrowed as k1 / v1 (the pair arrays sit at offsets that depend on the entry count only).
+struct SortedBufs { uint32_t *k0, *k1, *v0, *v1; float* carry; char* tmp; };
+static int sorted_carve(const char* name, const AdaSortedPlan& p, void* workspace, int64_t workspace_bytes, const void* sorted_from, SortedBufs& b) {
+    if ((int64_t)p.total > workspace_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(DIR_E_BADARG, "%s: workspace needs %lld bytes, 256-byte aligned", name, (long long)p.total);
+    if (reinterpret_cast<uintptr_t>(sorted_from) & 255u) return fail(DIR_E_BADARG, "%s: sorted_from must be a 256-byte aligned workspace", name);
+    char* ws = static_cast<char*>(workspace);
+    char* pairs = sorted_from ? const_cast<char*>(static_cast<const char*>(sorted_from)) : ws;
+    b.k0 = reinterpret_cast<uint32_t*>(ws + p.off_keys[0]);
+    b.v0 = reinterpret_cast<uint32_t*>(ws + p.off_vals[0]);
+    b.k1 = reinterpret_cast<uint32_t*>(pairs + p.off_keys[1]);
+    b.v1 = reinterpret_cast<uint32_t*>(pairs + p.off_vals[1]);
+    b.carry = reinterpret_cast<float*>(ws + p.off_carry);
+    b.tmp = ws + p.off_tmp;
+    return DIR_OK;
+}
+
 // FTRL on a dense variable (the linear model's bias under linear_optimizer='Ftrl', deepFM.py:58,268-275): FtrlUpd::one per element
 __global__ __launch_bounds__(256) void ftrl_dense_k(float* __restrict__ w, float* __restrict__ n, float* __restrict__ z, const float* __restrict__ g,
                                                      int64_t count, float lr, float l1, float l2) {
@@ -1054,24 +1073,15 @@ static int sparse_sorted_update(const char* name, U upd, int F, int K, const int
     if (!adagrad_sorted_plan(n, K, total_rows, p, payload ? 0 : B, payload ? 0 : F)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
     // ids [B, F]: the slot-major sort (csrc/radix_sort.hip: the slot is known from the entry's position, the sort runs on local rows)
     const bool slot_sort = !payload && !sorted_from && !use_rocprim_sort() && radix_slot_sort_ok(B, F, p.bits);
-    if ((int64_t)p.total > workspace_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return fail(DIR_E_BADARG, "%s: workspace needs %lld bytes, 256-byte aligned", name, (long long)p.total);
+    SortedBufs bufs;
+    if (int rc = sorted_carve(name, p, workspace, workspace_bytes, sorted_from, bufs)) return rc;
+    uint32_t *const k0 = bufs.k0, *const k1 = bufs.k1, *const v0 = bufs.v0, *const v1 = bufs.v1;
+    float* const carry = bufs.carry;
     hipStream_t st = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + p.off_keys[0]);
-    uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + p.off_keys[1]);
-    uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + p.off_vals[0]);
-    uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + p.off_vals[1]);
-    float* carry = reinterpret_cast<float*>(ws + p.off_carry);
-    if (sorted_from) {                     // the pair arrays sit at offsets that depend on the entry count only
-        if (reinterpret_cast<uintptr_t>(sorted_from) & 255u) return fail(DIR_E_BADARG, "%s: sorted_from must be a 256-byte aligned workspace", name);
-        char* src = const_cast<char*>(static_cast<const char*>(sorted_from));
-        k1 = reinterpret_cast<uint32_t*>(src + p.off_keys[1]);
-        v1 = reinterpret_cast<uint32_t*>(src + p.off_vals[1]);
-    } else if (slot_sort) {
-        if (radix_slot_sort_entries(ws + p.off_tmp, ids, stride_b, stride_f, F, B, row_base, (uint32_t)total_rows, p.bits, k0, k1, v0, v1, st) != hipSuccess)
+    if (slot_sort) {
+        if (radix_slot_sort_entries(bufs.tmp, ids, stride_b, stride_f, F, B, row_base, (uint32_t)total_rows, p.bits, k0, k1, v0, v1, st) != hipSuccess)
             return fail(DIR_E_HIP, "%s: radix sort failed", name);
-    } else {
+    } else if (!sorted_from) {
         // the key pass writes where the sort wants its input (an even number of digit passes starts from the second pair of buffers)
         const bool second = !use_rocprim_sort() && radix_sort_input_buffer((size_t)n, p.bits) == 1;
         uint32_t* kin = second ? k1 : k0;
@@ -1088,11 +1098,11 @@ static int sparse_sorted_update(const char* name, U upd, int F, int K, const int
 #if defined(DIR_WITH_ROCPRIM_SORT)
         if (use_rocprim_sort()) {
             size_t tmp = p.tmp_bytes;
-            if (rocprim_sort_pairs(ws + p.off_tmp, tmp, k0, k1, v0, v1, (size_t)n, p.bits, st) != hipSuccess)
+            if (rocprim_sort_pairs(bufs.tmp, tmp, k0, k1, v0, v1, (size_t)n, p.bits, st) != hipSuccess)
                 return fail(DIR_E_HIP, "%s: radix sort failed", name);
         } else
 #endif
-        if (radix_sort_pairs_u32(ws + p.off_tmp, k0, k1, v0, v1, (size_t)n, p.bits, st) != hipSuccess)
+        if (radix_sort_pairs_u32(bufs.tmp, k0, k1, v0, v1, (size_t)n, p.bits, st) != hipSuccess)
             return fail(DIR_E_HIP, "%s: radix sort failed", name);
     }
     const bool vec = (K % 4 == 0) && (grad_ld % 4 == 0) && (grad_fs % 4 == 0) && aligned16(grad) && (!fm_sum || aligned16(fm_sum));
@@ -1102,41 +1112,19 @@ static int sparse_sorted_update(const char* name, U upd, int F, int K, const int
     const int64_t ntiles = (int64_t)p.ntiles;
     static const int stage_min = dev_env_int("DIR_ADA_STAGE_MIN", 8);       // development A/B switch
     dim3 gfix((unsigned)((ntiles * lps + 255) / 256));
-#define DIR_CASE(L, V)                                                                                                         \
-    do {                                                                                                                       \
-        if constexpr (std::is_same<U, AdagradUpd>::value) {                                                                    \
-            if (fm_g)                                                                                                          \
-                hipLaunchKernelGGL((adagrad_tile_k<L, V, U, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, F, K, n, k1, v1, grad, \
-                                   grad_ld, grad_fs, row_base, (uint32_t)total_rows, nt, carry, fm_g, fm_sum, stage_min);       \
-        }                                                                                                                      \
-        if (!fm_g)                                                                                                             \
-            hipLaunchKernelGGL((adagrad_tile_k<L, V, U>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, F, K, n, k1, v1, grad, grad_ld, \
-                               grad_fs, row_base, (uint32_t)total_rows, nt, carry, nullptr, nullptr, stage_min);                \
-        hipLaunchKernelGGL((adagrad_fix_k<L, V, U>), gfix, dim3(256), 0, st, upd, F, K, n, ntiles, k1, v1, row_base,             \
-                           (uint32_t)total_rows, nt, carry);                                                                    \
-    } while (0)
-    if (vec) {
-        switch (lps) {
-            case 1: DIR_CASE(1, 4); break;
-            case 2: DIR_CASE(2, 4); break;
-            case 4: DIR_CASE(4, 4); break;
-            case 8: DIR_CASE(8, 4); break;
-            case 16: DIR_CASE(16, 4); break;
-            case 32: DIR_CASE(32, 4); break;
-            default: DIR_CASE(64, 4); break;
+    dispatch_lps(vec, lps, [&](auto L, auto V) {
+        constexpr int LPS = decltype(L)::value, VEC = decltype(V)::value;
+        if constexpr (std::is_same<U, AdagradUpd>::value) {
+            if (fm_g)
+                hipLaunchKernelGGL((adagrad_tile_k<LPS, VEC, U, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, F, K, n, k1, v1, grad,
+                                   grad_ld, grad_fs, row_base, (uint32_t)total_rows, nt, carry, fm_g, fm_sum, stage_min);
         }
-    } else {
-        switch (lps) {
-            case 1: DIR_CASE(1, 1); break;
-            case 2: DIR_CASE(2, 1); break;
-            case 4: DIR_CASE(4, 1); break;
-            case 8: DIR_CASE(8, 1); break;
-            case 16: DIR_CASE(16, 1); break;
-            case 32: DIR_CASE(32, 1); break;
-            default: DIR_CASE(64, 1); break;
-        }
-    }
-#undef DIR_CASE
+        if (!fm_g)
+            hipLaunchKernelGGL((adagrad_tile_k<LPS, VEC, U>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, F, K, n, k1, v1, grad, grad_ld,
+                               grad_fs, row_base, (uint32_t)total_rows, nt, carry, nullptr, nullptr, stage_min);
+        hipLaunchKernelGGL((adagrad_fix_k<LPS, VEC, U>), gfix, dim3(256), 0, st, upd, F, K, n, ntiles, k1, v1, row_base,
+                           (uint32_t)total_rows, nt, carry);
+    });
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
 }
@@ -1236,29 +1224,10 @@ extern "C" int dir_fm_second_order_backward_f32(const float* emb, int64_t emb_ld
     const int64_t waves = (B + spw - 1) / spw;
     dim3 grid(grid_for((waves + 3) / 4));
     hipStream_t st = as_stream(stream);
-#define DIR_CASE(L, V) hipLaunchKernelGGL((fm_bwd_k<L, V>), grid, dim3(256), 0, st, emb, emb_ld, g, add_in, add_ld, B, F, K, demb, demb_ld)
-    if (vec) {
-        switch (lps) {
-            case 1: DIR_CASE(1, 4); break;
-            case 2: DIR_CASE(2, 4); break;
-            case 4: DIR_CASE(4, 4); break;
-            case 8: DIR_CASE(8, 4); break;
-            case 16: DIR_CASE(16, 4); break;
-            case 32: DIR_CASE(32, 4); break;
-            default: DIR_CASE(64, 4); break;
-        }
-    } else {
-        switch (lps) {
-            case 1: DIR_CASE(1, 1); break;
-            case 2: DIR_CASE(2, 1); break;
-            case 4: DIR_CASE(4, 1); break;
-            case 8: DIR_CASE(8, 1); break;
-            case 16: DIR_CASE(16, 1); break;
-            case 32: DIR_CASE(32, 1); break;
-            default: DIR_CASE(64, 1); break;
-        }
-    }
-#undef DIR_CASE
+    dispatch_lps(vec, lps, [&](auto L, auto V) {
+        hipLaunchKernelGGL((fm_bwd_k<decltype(L)::value, decltype(V)::value>), grid, dim3(256), 0, st, emb, emb_ld, g, add_in, add_ld, B, F, K,
+                           demb, demb_ld);
+    });
     DIR_CHECK_LAUNCH("fm_second_order_backward");
     return DIR_OK;
 }
@@ -1359,29 +1328,10 @@ extern "C" int dir_sparse_adagrad_f32(float* const* tables, float* const* accums
     while (lps < (vec ? K / 4 : K)) lps <<= 1;
     if (lps > 64) return fail(DIR_E_UNSUPPORTED, "dir_sparse_adagrad_f32: K=%d too wide", K);
     dim3 grid(grid_for((n * lps + 255) / 256));
-#define DIR_CASE(L, V) hipLaunchKernelGGL((adagrad_apply_k<L, V>), grid, dim3(256), 0, st, tables, accums, ids, stride_b, stride_f, F, K, n, grad, grad_ld, lr, head_base, total_rows, head, next)
-    if (vec) {
-        switch (lps) {
-            case 1: DIR_CASE(1, 4); break;
-            case 2: DIR_CASE(2, 4); break;
-            case 4: DIR_CASE(4, 4); break;
-            case 8: DIR_CASE(8, 4); break;
-            case 16: DIR_CASE(16, 4); break;
-            case 32: DIR_CASE(32, 4); break;
-            default: DIR_CASE(64, 4); break;
-        }
-    } else {
-        switch (lps) {
-            case 1: DIR_CASE(1, 1); break;
-            case 2: DIR_CASE(2, 1); break;
-            case 4: DIR_CASE(4, 1); break;
-            case 8: DIR_CASE(8, 1); break;
-            case 16: DIR_CASE(16, 1); break;
-            case 32: DIR_CASE(32, 1); break;
-            default: DIR_CASE(64, 1); break;
-        }
-    }
-#undef DIR_CASE
+    dispatch_lps(vec, lps, [&](auto L, auto V) {
+        hipLaunchKernelGGL((adagrad_apply_k<decltype(L)::value, decltype(V)::value>), grid, dim3(256), 0, st, tables, accums, ids, stride_b,
+                           stride_f, F, K, n, grad, grad_ld, lr, head_base, total_rows, head, next);
+    });
     DIR_CHECK_LAUNCH("sparse_adagrad");
     return DIR_OK;
 }
@@ -1489,19 +1439,16 @@ extern "C" int dir_adagrad_dense_f32(float* w, float* accum, const float* grad, 
     return DIR_OK;
 }
 
-// The owner side of ShardedTables.lookup_bags_train's backward: the sorted Adagrad over the received bag records (see adagrad_keys_bags_k,
-// BagSrc, bag_apply).  The sort runs on all P * cap_e entry slots (the dead ones sort behind every row); the workspace is the payload
-// form's for n = P * cap_e entries.
-extern "C" int dir_sparse_adagrad_sorted_bags_f32(float* const* tables, float* const* accums, int F, int K, const int64_t* recv, int P,
-                                                  int64_t cap_e, int64_t cap_b, const float* grecv, const float* slot_max_norm,
-                                                  float max_norm, float lr, const int64_t* row_base, int64_t total_rows, void* workspace,
-                                                  int64_t workspace_bytes, dir_stream_t stream) {
-    const char* name = "dir_sparse_adagrad_sorted_bags_f32";
-    DIR_CHECK_ARG(F > 0 && K > 0 && P > 0 && P <= 64, "%s: F=%d K=%d P=%d (P <= 64)", name, F, K, P);
-    DIR_CHECK_ARG(cap_e > 0 && cap_b > 0 && cap_e < ((int64_t)1 << 31) && (int64_t)P * cap_b < ((int64_t)1 << 31),
-                  "%s: cap_e=%lld cap_b=%lld (each < 2^31, P*cap_b too)", name, (long long)cap_e, (long long)cap_b);
-    DIR_CHECK_ARG(!(max_norm < 0.f), "%s: max_norm=%g", name, max_norm);
-    DIR_CHECK_ARG(tables && accums && recv && grecv && row_base && workspace, "%s: null pointer", name);
+// The owner side of the bag backward, one body for both update rules: the sorted update over the received bag records (see
+// adagrad_keys_bags_k, BagSrc, bag_apply).  The sort runs on all P * cap_e entry slots (the dead ones sort behind every row); the
+// workspace is the payload form's for n = P * cap_e entries.  One "slot" per entry for the sort (F = 1); the table is found from the key
+// among the F tables (nt = F), as in the payload form.  sorted_from (optional): the workspace of a bag update that has just sorted the
+// SAME slabs (same P, cap_e, cap_b, row_base, total_rows) on this stream: the key pass and the sort are skipped -- the same pairs, so
+// the same rows bit for bit.
+template <class U>
+static int sorted_bags_update(const char* name, U upd, int K, int F, const int64_t* recv, int P, int64_t cap_e, int64_t cap_b, const float* grecv,
+                              const float* slot_mn, float mn, const int64_t* row_base, int64_t total_rows, void* workspace,
+                              int64_t workspace_bytes, const void* sorted_from, dir_stream_t stream) {
     const bool vec = (K % 4 == 0) && aligned16(grecv);
     int lps = 1;
     while (lps < (vec ? K / 4 : K)) lps <<= 1;
@@ -1512,126 +1459,68 @@ extern "C" int dir_sparse_adagrad_sorted_bags_f32(float* const* tables, float* c
     if (total_rows == 0) return DIR_OK;          // this rank holds no rows: no record can name one
     AdaSortedPlan p;
     if (!adagrad_sorted_plan(n, K, total_rows, p)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
-    if ((int64_t)p.total > workspace_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return fail(DIR_E_BADARG, "%s: workspace needs %lld bytes, 256-byte aligned", name, (long long)p.total);
+    SortedBufs b;
+    if (int rc = sorted_carve(name, p, workspace, workspace_bytes, sorted_from, b)) return rc;
     hipStream_t st = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + p.off_keys[0]);
-    uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + p.off_keys[1]);
-    uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + p.off_vals[0]);
-    uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + p.off_vals[1]);
-    float* carry = reinterpret_cast<float*>(ws + p.off_carry);
-    const bool second = radix_sort_input_buffer((size_t)n, p.bits) == 1;
-    const int4* r = reinterpret_cast<const int4*>(recv);
-    hipLaunchKernelGGL(adagrad_keys_bags_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, r, n, cap_e, cap_b, F, row_base,
-                       (uint32_t)total_rows, second ? k1 : k0, second ? v1 : v0);
-    DIR_CHECK_LAUNCH(name);
-    if (radix_sort_pairs_u32(ws + p.off_tmp, k0, k1, v0, v1, (size_t)n, p.bits, st) != hipSuccess) return fail(DIR_E_HIP, "%s: radix sort failed", name);
-    const AdagradUpd upd{tables, accums, lr, (int64_t)K};
     BagSrc bag;
-    bag.recv = r;
+    bag.recv = reinterpret_cast<const int4*>(recv);
     bag.grecv = grecv;
     bag.cap_e = cap_e;
     bag.cap_b = cap_b;
-    bag.slot_mn = slot_max_norm;
-    bag.mn = max_norm;
+    bag.slot_mn = slot_mn;
+    bag.mn = mn;
+    if (!sorted_from) {
+        const bool second = radix_sort_input_buffer((size_t)n, p.bits) == 1;
+        hipLaunchKernelGGL(adagrad_keys_bags_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, bag.recv, n, cap_e, cap_b, F, row_base,
+                           (uint32_t)total_rows, second ? b.k1 : b.k0, second ? b.v1 : b.v0);
+        DIR_CHECK_LAUNCH(name);
+        if (radix_sort_pairs_u32(b.tmp, b.k0, b.k1, b.v0, b.v1, (size_t)n, p.bits, st) != hipSuccess) return fail(DIR_E_HIP, "%s: radix sort failed", name);
+    }
     const int64_t ntiles = (int64_t)p.ntiles;
     static const int stage_min = dev_env_int("DIR_ADA_STAGE_MIN", 8);       // development A/B switch
-    dim3 gfix((unsigned)((ntiles * lps + 255) / 256));
-    // one "slot" per entry for the sort (F = 1); the table is found from the key among the F tables (nt = F), as in the payload form
-#define DIR_CASE(L, V)                                                                                                                  \
-    do {                                                                                                                                \
-        hipLaunchKernelGGL((adagrad_tile_k<L, V, AdagradUpd, false, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, 1, K, n, k1, \
-                           v1, nullptr, (int64_t)0, (int64_t)0, row_base, (uint32_t)total_rows, F, carry, nullptr, nullptr, stage_min,   \
-                           bag);                                                                                                        \
-        hipLaunchKernelGGL((adagrad_fix_k<L, V, AdagradUpd, true>), gfix, dim3(256), 0, st, upd, 1, K, n, ntiles, k1, v1, row_base,     \
-                           (uint32_t)total_rows, F, carry, bag);                                                                        \
-    } while (0)
-    if (vec) {
-        switch (lps) {
-            case 1: DIR_CASE(1, 4); break;
-            case 2: DIR_CASE(2, 4); break;
-            case 4: DIR_CASE(4, 4); break;
-            case 8: DIR_CASE(8, 4); break;
-            case 16: DIR_CASE(16, 4); break;
-            case 32: DIR_CASE(32, 4); break;
-            default: DIR_CASE(64, 4); break;
-        }
-    } else {
-        switch (lps) {
-            case 1: DIR_CASE(1, 1); break;
-            case 2: DIR_CASE(2, 1); break;
-            case 4: DIR_CASE(4, 1); break;
-            case 8: DIR_CASE(8, 1); break;
-            case 16: DIR_CASE(16, 1); break;
-            case 32: DIR_CASE(32, 1); break;
-            default: DIR_CASE(64, 1); break;
-        }
-    }
-#undef DIR_CASE
+    auto launch = [&](auto L, auto V) {
+        constexpr int LPS = decltype(L)::value, VEC = decltype(V)::value;
+        hipLaunchKernelGGL((adagrad_tile_k<LPS, VEC, U, false, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, 1, K, n, b.k1, b.v1, nullptr,
+                           (int64_t)0, (int64_t)0, row_base, (uint32_t)total_rows, F, b.carry, nullptr, nullptr, stage_min, bag);
+        hipLaunchKernelGGL((adagrad_fix_k<LPS, VEC, U, true>), dim3((unsigned)((ntiles * LPS + 255) / 256)), dim3(256), 0, st, upd, 1, K, n, ntiles,
+                           b.k1, b.v1, row_base, (uint32_t)total_rows, F, b.carry, bag);
+    };
+    if constexpr (std::is_same<U, FtrlUpd>::value) launch(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});     // packed rows: K = 1
+    else dispatch_lps(vec, lps, launch);
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
 }
 
+// The owner side of ShardedTables.lookup_bags_train's backward: Adagrad on the embedding rows over the received bag records; the run's
+// sum goes through the slot's max_norm clip derivative before the step.
+extern "C" int dir_sparse_adagrad_sorted_bags_f32(float* const* tables, float* const* accums, int F, int K, const int64_t* recv, int P,
+                                                  int64_t cap_e, int64_t cap_b, const float* grecv, const float* slot_max_norm,
+                                                  float max_norm, float lr, const int64_t* row_base, int64_t total_rows, void* workspace,
+                                                  int64_t workspace_bytes, dir_stream_t stream) {
+    const char* name = "dir_sparse_adagrad_sorted_bags_f32";
+    DIR_CHECK_ARG(F > 0 && K > 0, "%s: F=%d K=%d", name, F, K);
+    if (int rc = check_slab_geometry(name, P, cap_e, cap_b)) return rc;
+    DIR_CHECK_ARG(!(max_norm < 0.f), "%s: max_norm=%g", name, max_norm);
+    DIR_CHECK_ARG(tables && accums && recv && grecv && row_base && workspace, "%s: null pointer", name);
+    return sorted_bags_update(name, AdagradUpd{tables, accums, lr, (int64_t)K}, K, F, recv, P, cap_e, cap_b, grecv, slot_max_norm, max_norm,
+                              row_base, total_rows, workspace, workspace_bytes, nullptr, stream);
+}
+
 // The owner side of ShardedTables.lookup_bags_train(with_linear=True)'s backward: FTRL on the packed first-order rows [w | n | z | -] over
 // the bag records the owner kept.  Entry e's gradient is w_e * grecv[src * cap_b + ret_e]; all entries of a (slot, row) -- of any bag, of
-// any rank, inside one bag -- are summed before n, z and w move, and every row is written once.  Built as
-// dir_sparse_adagrad_sorted_bags_f32 is: adagrad_keys_bags_k, the radix sort, then adagrad_tile_k / adagrad_fix_k in bag mode with
-// FtrlUpd{rows = true}, K = 1.  sorted_from (optional): the workspace of the Adagrad bag step that has just sorted the SAME slabs (same P,
-// cap_e, cap_b, row_base, total_rows) on this stream: its sorted (row, entry) pairs are read and the key pass and the sort are skipped
-// (the pair arrays sit at offsets that depend on the entry count only, not on K) -- the same pairs, so the same rows bit for bit.
+// any rank, inside one bag -- are summed before n, z and w move, and every row is written once.  sorted_from (optional): the workspace
+// of the Adagrad bag step that has just sorted the same slabs.
 extern "C" int dir_sparse_ftrl_rows_sorted_bags_f32(float* const* rows, int F, const int64_t* recv, int P, int64_t cap_e, int64_t cap_b,
                                                     const float* grecv, float lr, float l1, float l2, const int64_t* row_base,
                                                     int64_t total_rows, void* workspace, int64_t workspace_bytes, const void* sorted_from,
                                                     dir_stream_t stream) {
     const char* name = "dir_sparse_ftrl_rows_sorted_bags_f32";
-    DIR_CHECK_ARG(F > 0 && P > 0 && P <= 64, "%s: F=%d P=%d (1 <= P <= 64)", name, F, P);
-    DIR_CHECK_ARG(cap_e > 0 && cap_b > 0 && cap_e < ((int64_t)1 << 31) && (int64_t)P * cap_b < ((int64_t)1 << 31),
-                  "%s: cap_e=%lld cap_b=%lld (each in (0, 2^31), P*cap_b < 2^31)", name, (long long)cap_e, (long long)cap_b);
+    DIR_CHECK_ARG(F > 0, "%s: F=%d", name, F);
+    if (int rc = check_slab_geometry(name, P, cap_e, cap_b)) return rc;
     DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
     DIR_CHECK_ARG(rows && recv && grecv && row_base && workspace, "%s: null pointer", name);
-    const int64_t n = (int64_t)P * cap_e;
-    if (n >= ((int64_t)1 << 30)) return fail(DIR_E_UNSUPPORTED, "%s: P*cap_e=%lld entry slots (the sort takes < 2^30)", name, (long long)n);
-    if (total_rows < 0 || total_rows >= 0xffffffffll) return fail(DIR_E_UNSUPPORTED, "%s: total_rows must be in [0, 2^32-1)", name);
-    if (total_rows == 0) return DIR_OK;          // this rank holds no rows: no record can name one
-    AdaSortedPlan p;
-    if (!adagrad_sorted_plan(n, 1, total_rows, p)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
-    if ((int64_t)p.total > workspace_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255u))
-        return fail(DIR_E_BADARG, "%s: workspace needs %lld bytes, 256-byte aligned", name, (long long)p.total);
-    if (reinterpret_cast<uintptr_t>(sorted_from) & 255u) return fail(DIR_E_BADARG, "%s: sorted_from must be a 256-byte aligned workspace", name);
-    hipStream_t st = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + p.off_keys[1]);
-    uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + p.off_vals[1]);
-    float* carry = reinterpret_cast<float*>(ws + p.off_carry);
-    const int4* r = reinterpret_cast<const int4*>(recv);
-    if (sorted_from) {
-        char* src = const_cast<char*>(static_cast<const char*>(sorted_from));
-        k1 = reinterpret_cast<uint32_t*>(src + p.off_keys[1]);
-        v1 = reinterpret_cast<uint32_t*>(src + p.off_vals[1]);
-    } else {
-        uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + p.off_keys[0]);
-        uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + p.off_vals[0]);
-        const bool second = radix_sort_input_buffer((size_t)n, p.bits) == 1;
-        hipLaunchKernelGGL(adagrad_keys_bags_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, r, n, cap_e, cap_b, F, row_base,
-                           (uint32_t)total_rows, second ? k1 : k0, second ? v1 : v0);
-        DIR_CHECK_LAUNCH(name);
-        if (radix_sort_pairs_u32(ws + p.off_tmp, k0, k1, v0, v1, (size_t)n, p.bits, st) != hipSuccess) return fail(DIR_E_HIP, "%s: radix sort failed", name);
-    }
     FtrlUpd upd{rows, rows, rows, lr, l1, l2, (int64_t)4};
     upd.rows = true;
-    BagSrc bag;
-    bag.recv = r;
-    bag.grecv = grecv;
-    bag.cap_e = cap_e;
-    bag.cap_b = cap_b;
-    const int64_t ntiles = (int64_t)p.ntiles;
-    static const int stage_min = dev_env_int("DIR_ADA_STAGE_MIN", 8);       // development A/B switch
-    // one "slot" per entry for the sort (F = 1); the slot is found from the key among the F row blocks (nt = F), as in the Adagrad form
-    hipLaunchKernelGGL((adagrad_tile_k<1, 1, FtrlUpd, false, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, 1, 1, n, k1, v1, nullptr,
-                       (int64_t)0, (int64_t)0, row_base, (uint32_t)total_rows, F, carry, nullptr, nullptr, stage_min, bag);
-    hipLaunchKernelGGL((adagrad_fix_k<1, 1, FtrlUpd, true>), dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, st, upd, 1, 1, n, ntiles, k1,
-                       v1, row_base, (uint32_t)total_rows, F, carry, bag);
-    DIR_CHECK_LAUNCH(name);
-    return DIR_OK;
+    return sorted_bags_update(name, upd, 1, F, recv, P, cap_e, cap_b, grecv, nullptr, 0.f, row_base, total_rows, workspace, workspace_bytes,
+                              sorted_from, stream);
 }

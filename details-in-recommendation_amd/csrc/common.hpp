@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/dir_hip.h"
 
@@ -127,6 +128,25 @@ inline bool lds_limit(LdsOnce& o, int bytes, Ks... kernels) {
     ((ok = (hipFuncSetAttribute(reinterpret_cast<const void*>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) && ok), ...);
     if (ok) o.done.fetch_or(bit, std::memory_order_release);
     return ok;
+}
+
+// The (lanes per row, floats per lane) instantiation of a row kernel: f(integral_constant<int, LPS>, integral_constant<int, VEC>) with
+// VEC = vec ? 4 : 1 and LPS = lps, a power of two in 1..64 (checked by the caller).
+template <class Fn>
+inline void dispatch_lps(bool vec, int lps, Fn&& f) {
+    auto by_lps = [&](auto v) {
+        switch (lps) {
+            case 1: f(std::integral_constant<int, 1>{}, v); break;
+            case 2: f(std::integral_constant<int, 2>{}, v); break;
+            case 4: f(std::integral_constant<int, 4>{}, v); break;
+            case 8: f(std::integral_constant<int, 8>{}, v); break;
+            case 16: f(std::integral_constant<int, 16>{}, v); break;
+            case 32: f(std::integral_constant<int, 32>{}, v); break;
+            default: f(std::integral_constant<int, 64>{}, v); break;
+        }
+    };
+    if (vec) by_lps(std::integral_constant<int, 4>{});
+    else by_lps(std::integral_constant<int, 1>{});
 }
 
 inline int grid_resident(int64_t work_blocks, int resident) {
@@ -253,6 +273,22 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 __device__ __forceinline__ float wave_max_dpp(float v) {
     v = row16_max(v);
     return fmaxf(fmaxf(lane_bcast(v, 0), lane_bcast(v, 16)), fmaxf(lane_bcast(v, 32), lane_bcast(v, 48)));
+}
+
+// The ordered sum of a quad: lane c of a quad holds the value v of item f + c; acc += v_f, v_f+1, v_f+2, v_f+3 in that order (items at
+// or past F add nothing) through four quad broadcasts -- the sequential fp32 sum, the same bits in every lane of the quad.  The one-hot
+// linear term, its sharded finish and the sharded bags' combine all call this, so their sums agree bit for bit.  All four lanes active.
+__device__ __forceinline__ float quad_add_in_order(float v, int f, int F, float acc) {
+    const int vi = __builtin_bit_cast(int, v);
+    const float q0 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x00, 0xf, 0xf, true));   // quad_perm [0,0,0,0]
+    const float q1 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x55, 0xf, 0xf, true));   // [1,1,1,1]
+    const float q2 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xaa, 0xf, 0xf, true));   // [2,2,2,2]
+    const float q3 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xff, 0xf, 0xf, true));   // [3,3,3,3]
+    if (f < F) acc = acc + q0;
+    if (f + 1 < F) acc = acc + q1;
+    if (f + 2 < F) acc = acc + q2;
+    if (f + 3 < F) acc = acc + q3;
+    return acc;
 }
 
 __device__ __forceinline__ float wave_max(float v) {

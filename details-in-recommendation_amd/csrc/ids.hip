@@ -9,7 +9,9 @@
 // Fingerprint64 is farmhashna::Hash64 of FarmHash 1.1, restated from the public algorithm; checked
 // against published known answers in tests/ (lengths <= 16; longer branches have no published vector).
 #include "common.hpp"
+#include "bag_row.hpp"
 #include "shard_route.hpp"
+#include "shard_wire.hpp"
 #include <type_traits>
 
 namespace dir {
@@ -340,7 +342,7 @@ __device__ __forceinline__ int wave_agg_rank(int* cnt, int o, bool active) {
     unsigned long long todo = __ballot(active);
     int rank = 0;
     while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
+        const int leader = lowest_bit(todo);
         const int oo = __shfl(o, leader, 64);
         const unsigned long long same = __ballot(active && o == oo) & todo;
         int basev = 0;
@@ -447,27 +449,22 @@ __global__ __launch_bounds__(256) void bucket_scatter_k(const int64_t* __restric
         const int rank = wave_agg_rank(cnt, o, active);
         if (active) {
             const int64_t dst = basev[o] + rank;
-            payload[dst] = ll < 0 ? (int64_t)-1 : ll * F + fsl;
+            payload[dst] = ll < 0 ? (int64_t)-1 : pack_payload(ll, F, fsl);
             inv[ii] = dst;
         }
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Fixed-capacity bucketing (the sync-free lookup): owner o gets a SLAB of cap payload slots behind a one-word header,
-//   payload[o*(cap+1)] = number of valid slots (written by bucket_cap_fin_k), payload[o*(cap+1) + 1 + pos] = local*F + slot.
+// Fixed-capacity bucketing (the sync-free lookup) into the ONE-HOT SLABS of shard_wire.hpp (headers written by bucket_cap_fin_k).
 // One pass: every workgroup routes its 4096 elements keeping (owner, rank-in-workgroup, payload) in registers, reserves a
-// contiguous range of every owner's slab with ONE global atomic per owner, and scatters.  inv[i] = o*cap + pos is the row of
-// element i in the [P*cap, K] row buffer that comes back; pruned / out-of-range ids and elements that do not fit the slab
-// get inv = -1 (the finish gather turns that into a zero row; an overflow is reported through the flag and the caller
-// repeats the lookup on the exact variable-size path).  The order inside a slab is arbitrary (atomics); inv is its exact
-// inverse, so the looked-up values do not depend on it.  gcount: P int32 counters, zero on entry, zeroed again by fin.
+// contiguous range of every owner's slab with ONE global atomic per owner, and scatters.  inv = -1 becomes a zero row in the finish
+// gather; an overflow is reported through the flag and the caller repeats the lookup on the exact variable-size path.
+// gcount: P int32 counters, zero on entry, zeroed again by fin.
 // ------------------------------------------------------------------------------------------------
 // Elements per workgroup of the one-pass kernel = 256 * EPT.  Two opposing costs: few workgroups leave CUs idle (4096 elements
 // per workgroup on a 16 384 x 26 micro-batch: 104 workgroups, 24 us), many workgroups queue up on the P slab counters (same-address
 // atomics retire at ~90 per us: 1 664 workgroups on the whole 65 536 x 26 batch: 28 us).  The host picks EPT for ~400-800 workgroups.
-typedef float f32x4_ids __attribute__((ext_vector_type(4)));
-
 template <int BK_EPT>
 __global__ __launch_bounds__(256) void bucket_cap_k(const int64_t* __restrict__ ids, int64_t n,
                                                     const int64_t* __restrict__ vocab, const int32_t* __restrict__ parts,
@@ -498,7 +495,7 @@ __global__ __launch_bounds__(256) void bucket_cap_k(const int64_t* __restrict__ 
             (void)i;
             o = oo_;
             keep = l >= 0;
-            pv[k] = l * F + f;
+            pv[k] = pack_payload(l, F, f);
         }
         const int rank = wave_agg_rank(cnt, o, keep);
         orank[k] = keep ? (o << 16) | rank : -1;
@@ -515,18 +512,13 @@ __global__ __launch_bounds__(256) void bucket_cap_k(const int64_t* __restrict__ 
             const int o = orank[k] >> 16;
             const int64_t pos = (int64_t)basev[o] + (orank[k] & 0xffff);
             if (pos < cap) {
-                payload[(int64_t)o * (cap + 1) + 1 + pos] = pv[k];
+                slab_of(payload, o, cap)[1 + pos] = pv[k];
                 dst = (int64_t)o * cap + pos;
             }
         }
         inv[base + e] = dst;
     }
 }
-
-// Slab header word: low 32 bits = number of valid slots (<= cap); high 32 bits = the SENDER's largest per-owner demand in this
-// micro-batch.  Every rank therefore learns every other rank's demand from the id exchange itself (slab_stat_k below): the global
-// overflow verdict needs no collective of its own.
-__device__ __forceinline__ int64_t slab_count(int64_t header) { return (int64_t)(uint32_t)header; }
 
 __global__ void bucket_cap_fin_k(int32_t* __restrict__ gcount, int P, int64_t cap, int64_t* __restrict__ payload,
                                  int64_t* __restrict__ counts, int32_t* __restrict__ overflow, int64_t* __restrict__ stat) {
@@ -544,7 +536,7 @@ __global__ void bucket_cap_fin_k(int32_t* __restrict__ gcount, int P, int64_t ca
     const unsigned long long any = __ballot(over);
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) c32 = max(c32, __shfl_xor(c32, d, 64));
-    if (o < P) payload[(int64_t)o * (cap + 1)] = (c < cap ? c : cap) | ((int64_t)c32 << 32);
+    if (o < P) slab_of(payload, o, cap)[0] = make_slab_header(c, cap, c32);
     if (o == 0) {
         overflow[0] = any ? 1 : 0;
         if (stat) {          // [overflow, largest per-owner demand]: what the caller reduces over chunks and ranks
@@ -571,7 +563,7 @@ __device__ __forceinline__ void bucket_cap_finalize(int32_t* __restrict__ gcount
     const unsigned long long any = __ballot(over);
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) c32 = max(c32, __shfl_xor(c32, d, 64));
-    if (o < P) payload[(int64_t)o * (cap + 1)] = (c < cap ? c : cap) | ((int64_t)c32 << 32);
+    if (o < P) slab_of(payload, o, cap)[0] = make_slab_header(c, cap, c32);
     if (o == 0) {
         overflow[0] = any ? 1 : 0;
         if (stat) {
@@ -624,7 +616,7 @@ __global__ __launch_bounds__(NT) void bucket_cap2_k(const int64_t* __restrict__ 
             (void)i;
             o = oo_;
             keep = l >= 0;
-            pv[k] = l * F + f;
+            pv[k] = pack_payload(l, F, f);
         }
         const int rank = wave_agg_rank(cnt, o, keep);
         orank[k] = keep ? (o << 16) | rank : -1;
@@ -641,7 +633,7 @@ __global__ __launch_bounds__(NT) void bucket_cap2_k(const int64_t* __restrict__ 
             const int o = orank[k] >> 16;
             const int64_t pos = (int64_t)basev[o] + (orank[k] & 0xffff);
             if (pos < cap) {
-                payload[(int64_t)o * (cap + 1) + 1 + pos] = pv[k];
+                slab_of(payload, o, cap)[1 + pos] = pv[k];
                 dst = (int64_t)o * cap + pos;
             }
         }
@@ -660,7 +652,7 @@ __global__ __launch_bounds__(NT) void bucket_cap2_k(const int64_t* __restrict__ 
 // stat = {1 iff some sender's demand exceeded cap, the largest demand}: the same two numbers on every rank.
 __global__ void slab_stat_k(const int64_t* __restrict__ recv, int n_slabs, int64_t cap, int64_t* __restrict__ stat) {
     int m = 0;
-    for (int i = threadIdx.x; i < n_slabs; i += 64) m = max(m, (int)(recv[(int64_t)i * (cap + 1)] >> 32));
+    for (int i = threadIdx.x; i < n_slabs; i += 64) m = max(m, slab_demand(slab_of(recv, i, cap)[0]));
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) m = max(m, __shfl_xor(m, d, 64));
     if (threadIdx.x == 0) {
@@ -716,7 +708,7 @@ __global__ __launch_bounds__(256) void bucket_cap_dedup_k(const int64_t* __restr
                 o += fd.first;
                 if (o >= P) o -= P;
                 own[k] = o;
-                const int64_t p = l * F + f;
+                const int64_t p = pack_payload(l, F, f);
                 pv[k] = p;
                 if (id < (int64_t)EMPTY) {                  // the tile is ONE slot: the row id itself identifies the value (owner included)
                     const uint32_t p32 = (uint32_t)id;
@@ -748,7 +740,7 @@ __global__ __launch_bounds__(256) void bucket_cap_dedup_k(const int64_t* __restr
             const int o = own[k];
             const int64_t pos = (int64_t)basev[o] + rank[k];
             if (pos < cap) {
-                payload[(int64_t)o * (cap + 1) + 1 + pos] = pv[k];
+                slab_of(payload, o, cap)[1 + pos] = pv[k];
                 dst[k] = (int64_t)o * cap + pos;
             }
             if (slot[k] >= 0) hpos[slot[k]] = (int32_t)dst[k];
@@ -765,14 +757,15 @@ __global__ __launch_bounds__(256) void bucket_cap_dedup_k(const int64_t* __restr
     }
 }
 
-// owner side of the fixed-capacity exchange: recv = P slabs [header | cap slots] as received (slab s from rank s);
-// out[(s*cap + j), :] = tables[p % F][p / F, :] for j < header_s.  Slots behind the header are neither read nor written
+// owner side of the fixed-capacity exchange: recv = P one-hot slabs (shard_wire.hpp) as received (slab s from rank s);
+// out[(s*cap + j), :] = tables[slot][row, :] of the payload word for j < the header's count.  Slots behind the header are neither read nor written
 // (the requester never looks at them); with sanitize the slot itself is overwritten with -1 so that the slab can later be
 // walked as a flat pruned-aware payload (the owner side of the sharded backward).
 template <int VEC, bool NT>
 __global__ __launch_bounds__(256) void gather_slabs_k(const float* const* __restrict__ tables, int K, int lps, int F,
                                                       int64_t* __restrict__ recv, int P, int64_t cap, int sanitize,
                                                       float* __restrict__ out) {
+    using V = typename VecT<VEC>::T;
     const int kv = K / VEC;
     const int64_t total = (int64_t)P * cap;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -781,7 +774,7 @@ __global__ __launch_bounds__(256) void gather_slabs_k(const float* const* __rest
         const int64_t i = q / lps;
         const int c = (int)(q - i * lps);
         const int64_t sl = i / cap, j = i - sl * cap;
-        int64_t* slab = recv + sl * (cap + 1);
+        int64_t* slab = slab_of(recv, sl, cap);
         const int64_t valid = slab_count(slab[0]);
         if (j >= valid) {
             if (sanitize && c == 0) slab[1 + j] = -1;
@@ -791,28 +784,9 @@ __global__ __launch_bounds__(256) void gather_slabs_k(const float* const* __rest
         const int64_t p = slab[1 + j];
         int slot;
         int64_t row;
-        if (p < (int64_t)0x7fffffff) {   // 32-bit division when it fits
-            const uint32_t r32 = (uint32_t)p / (uint32_t)F;
-            slot = (int)((uint32_t)p - r32 * (uint32_t)F);
-            row = r32;
-        } else {
-            row = p / F;
-            slot = (int)(p - row * F);
-        }
-        float* o = out + i * K + c * VEC;
+        unpack_payload(p, F, slot, row);
         const float* src = tables[slot] + row * K + c * VEC;
-        if (VEC == 4) {
-            float4 v;
-            if (NT) {
-                const f32x4_ids t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_ids*>(src));
-                v = make_float4(t.x, t.y, t.z, t.w);
-            } else {
-                v = *reinterpret_cast<const float4*>(src);
-            }
-            *reinterpret_cast<float4*>(o) = v;
-        } else {
-            *o = NT ? __builtin_nontemporal_load(src) : *src;
-        }
+        stv(out + i * K + c * VEC, NT ? ldv_nt(src, (V*)nullptr) : ldv(src, (V*)nullptr));
     }
 }
 #undef BK_ROUTE_ELEMENT
@@ -822,6 +796,7 @@ template <int VEC, bool NT>
 __global__ __launch_bounds__(256) void gather_packed_k(const float* const* __restrict__ tables, int K, int lps, int F,
                                                        const int64_t* __restrict__ payload, int64_t n,
                                                        float* __restrict__ out) {
+    using V = typename VecT<VEC>::T;
     const int kv = K / VEC;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t nthr = (int64_t)gridDim.x * blockDim.x;
@@ -833,33 +808,13 @@ __global__ __launch_bounds__(256) void gather_packed_k(const float* const* __res
         float* o = out + i * K + c * VEC;
         int slot = 0;
         int64_t row = 0;
+        if (p >= 0) unpack_payload(p, F, slot, row);
+        V v = vzero((V*)nullptr);
         if (p >= 0) {
-            if (p < (int64_t)0x7fffffff) {   // 32-bit division when it fits
-                const uint32_t r32 = (uint32_t)p / (uint32_t)F;
-                slot = (int)((uint32_t)p - r32 * (uint32_t)F);
-                row = r32;
-            } else {
-                row = p / F;
-                slot = (int)(p - row * F);
-            }
+            const float* src = tables[slot] + row * K + c * VEC;
+            v = NT ? ldv_nt(src, (V*)nullptr) : ldv(src, (V*)nullptr);
         }
-        if (VEC == 4) {
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (p >= 0) {
-                const float* src = tables[slot] + row * K + c * 4;
-                if (NT) {
-                    const f32x4_ids t = __builtin_nontemporal_load(reinterpret_cast<const f32x4_ids*>(src));
-                    v = make_float4(t.x, t.y, t.z, t.w);
-                } else {
-                    v = *reinterpret_cast<const float4*>(src);
-                }
-            }
-            *reinterpret_cast<float4*>(o) = v;
-        } else {
-            float v = 0.f;
-            if (p >= 0) v = NT ? __builtin_nontemporal_load(tables[slot] + row * K + c) : tables[slot][row * K + c];
-            *o = v;
-        }
+        stv(o, v);
     }
 }
 

@@ -84,18 +84,7 @@ __global__ __launch_bounds__(256) void linear_onehot4_k(const float* const* __re
                 }
             }
 #pragma unroll
-            for (int j = 0; j < UFL; ++j) {
-                const int vi = __builtin_bit_cast(int, v[j]);
-                const float q0 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x00, 0xf, 0xf, true));   // quad_perm [0,0,0,0]
-                const float q1 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x55, 0xf, 0xf, true));   // [1,1,1,1]
-                const float q2 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xaa, 0xf, 0xf, true));   // [2,2,2,2]
-                const float q3 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xff, 0xf, 0xf, true));   // [3,3,3,3]
-                const int f = f0 + 4 * j;
-                if (f < F) acc = acc + q0;
-                if (f + 1 < F) acc = acc + q1;
-                if (f + 2 < F) acc = acc + q2;
-                if (f + 3 < F) acc = acc + q3;
-            }
+            for (int j = 0; j < UFL; ++j) acc = quad_add_in_order(v[j], f0 + 4 * j, F, acc);
         }
         if (live && c == 0) {
             const float r = acc + (bias ? bias[0] : 0.f);

@@ -17,13 +17,11 @@
 #include "common.hpp"
 #include "bag_row.hpp"
 #include "shard_route.hpp"
+#include "shard_wire.hpp"
 
 namespace dir {
 
-// A slab is (cap_e + 1) records of 16 bytes: record 0 = header, records 1..cap_e = entries.
-//   entry  : x, y = local_row * F + slot (int64, little-endian halves), z = weight (fp32 bits), w = return position (-1: none)
-//   header : x = entries in this slab (<= cap_e), y = partial rows asked for (<= cap_b), z, w = the SENDER's largest per-owner demand
-//            of entries / partial rows (may exceed the capacities): every receiver reads every sender's demand off the exchange itself
+// The slabs of 16-byte records that travel: shard_wire.hpp (BAG SLAB).
 constexpr int SB_NT = 128;       // threads of the bucketing kernel's workgroup (one bag per thread per step)
 constexpr int SB_MAXF = 256;     // slots whose 'div' constants are staged in LDS
 
@@ -68,12 +66,11 @@ __global__ __launch_bounds__(SB_NT) void bags_bucket_k(const int64_t* __restrict
     const int64_t nbags = B * F;
     const int64_t g0 = (int64_t)blockIdx.x * SB_NT * bpt;
     const bool prune_w = weights && (flags & DIR_BAG_PRUNE_NONPOSITIVE_WEIGHTS);
-    // entry e of a bag of slot f: live (bag_csr_k's pruning: id outside [0, vocab_f), weight <= 0 under PRUNE) -> owner o, local row l
+    // entry e of a bag of slot f: live (bag_csr_k's pruning: bag_entry_live) -> owner o, local row l
     auto route = [&](int64_t e, const FieldDiv& d, int& o, int64_t& l, float& w) -> bool {
         const int64_t id = ids[e];
         w = weights ? weights[e] : 1.0f;
-        if (!((uint64_t)id < (uint64_t)d.V)) return false;
-        if (prune_w && !(w > 0.0f)) return false;
+        if (!bag_entry_live(id, w, d.V, prune_w)) return false;
         route_fd(id, d, &o, &l);
         o += d.first;
         if (o >= P) o -= P;
@@ -124,8 +121,7 @@ __global__ __launch_bounds__(SB_NT) void bags_bucket_k(const int64_t* __restrict
         bag_of(g, f, beg, end);
         const FieldDiv d = f < SB_MAXF ? fd[f] : bag_fielddiv(vocab, parts, first, P, f);
         uint64_t m = 0;
-        float wsum = 0.f, w2sum = 0.f;
-        int n = 0;
+        BagDenom den;                      // bag_csr_k's sums, in entry order (w = 1 without weights)
         for (int64_t e = beg; e < end; ++e) {
             int o;
             int64_t l;
@@ -133,23 +129,17 @@ __global__ __launch_bounds__(SB_NT) void bags_bucket_k(const int64_t* __restrict
             if (!route(e, d, o, l, w)) continue;
             cnt[o * SB_NT + t] += 1;
             m |= 1ull << o;
-            wsum = wsum + w;               // bag_csr_k's sums, in entry order (w = 1 without weights)
-            w2sum = w2sum + w * w;
-            ++n;
+            den.add(w);
         }
-        const int comb = slot_combiner ? slot_combiner[f] : combiner;
-        float den = 1.f;                   // (applied by the combine step only when the bag has a live entry and comb != SUM)
-        if (comb == DIR_COMBINER_MEAN) den = weights ? wsum : (float)n;
-        else if (comb == DIR_COMBINER_SQRTN) den = weights ? sqrtf(w2sum) : sqrtf((float)n);
         mask[g] = m;
-        denom[g] = den;
-        for (uint64_t mm = m; mm; mm &= mm - 1ull) {
-            const int o = __ffsll((long long)mm) - 1;
+        // (applied by the combine step only when the bag has a live entry and the combiner is not SUM)
+        denom[g] = den.value(slot_combiner ? slot_combiner[f] : combiner, weights != nullptr);
+        for_each_owner(m, [&](int o) {
             const unsigned int start = atomicAdd(&wg_e[o], (unsigned int)cnt[o * SB_NT + t]);
             const unsigned int q = atomicAdd(&wg_b[o], 1u);
             cnt[o * SB_NT + t] = (int)start;
             pos[g * P + o] = (int64_t)q < cap_b ? (int32_t)((int64_t)o * cap_b + q) : -1;
-        }
+        });
         if (m) {
             for (int64_t e = beg; e < end; ++e) {
                 int o;
@@ -160,16 +150,10 @@ __global__ __launch_bounds__(SB_NT) void bags_bucket_k(const int64_t* __restrict
                 cnt[o * SB_NT + t] = (int)(p + 1);
                 if (p < cap_e) {
                     const int32_t r = pos[g * P + o];
-                    const int64_t packed = l * F + f;
-                    int4 rec;
-                    rec.x = (int)(uint32_t)(uint64_t)packed;
-                    rec.y = (int)(uint32_t)((uint64_t)packed >> 32);
-                    rec.z = __float_as_int(w);
-                    rec.w = r >= 0 ? (int)(r - (int64_t)o * cap_b) : -1;
-                    slabs[(int64_t)o * (cap_e + 1) + 1 + p] = rec;
+                    bag_slab_of(slabs, o, cap_e)[1 + p] = make_bag_record(pack_payload(l, F, f), w, r >= 0 ? (int)(r - (int64_t)o * cap_b) : -1);
                 }
             }
-            for (uint64_t mm = m; mm; mm &= mm - 1ull) cnt[(__ffsll((long long)mm) - 1) * SB_NT + t] = 0;
+            for_each_owner(m, [&](int o) { cnt[o * SB_NT + t] = 0; });
         }
     }
     // arrival: the last workgroup writes the headers (no fence: the counters are device-scope atomics whose results every workgroup
@@ -181,27 +165,9 @@ __global__ __launch_bounds__(SB_NT) void bags_bucket_k(const int64_t* __restrict
         const unsigned long long c = t < P ? atomicExch(&gcount[t], 0ull) : 0ull;
         const unsigned int ce = (unsigned int)c, cb = (unsigned int)(c >> 32);
         unsigned int me = ce, mb = cb;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            me = max(me, (unsigned int)__shfl_xor((int)me, o, 64));
-            mb = max(mb, (unsigned int)__shfl_xor((int)mb, o, 64));
-        }
-        if (t < P) {
-            int4 h;
-            h.x = (int)((int64_t)ce < cap_e ? ce : (unsigned int)cap_e);
-            h.y = (int)((int64_t)cb < cap_b ? cb : (unsigned int)cap_b);
-            h.z = (int)me;
-            h.w = (int)mb;
-            slabs[(int64_t)t * (cap_e + 1)] = h;
-        }
-        if (t == 0) {
-            if (stat) {
-                stat[0] = ((int64_t)me > cap_e || (int64_t)mb > cap_b) ? 1 : 0;
-                stat[1] = me;
-                stat[2] = mb;
-            }
-            __hip_atomic_store(reinterpret_cast<unsigned int*>(gcount + 64), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        bag_demand_stat(me, mb, cap_e, cap_b, stat);
+        if (t < P) bag_slab_of(slabs, t, cap_e)[0] = make_bag_header(ce, cb, cap_e, cap_b, me, mb);
+        if (t == 0) __hip_atomic_store(reinterpret_cast<unsigned int*>(gcount + 64), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -212,8 +178,8 @@ __global__ __launch_bounds__(SB_NT) void bags_bucket_k(const int64_t* __restrict
 // row): its U records and U rows are in flight together, and it pools every run that starts inside the chunk -- clip_row with the slot's
 // max_norm, acc + w * row in entry order, the per-entry operations of bag_csr_k -- writing each partial row once; a run that goes on past
 // the chunk is walked to its end, U records at a time, and a run that began in the previous chunk is left to that chunk's group.
-// Received records are checked (slot < F, row < the local table's rows, return position < cap_b) before they are used.
-// Block 0 also reads the P received headers: stat = {some sender's demand > a capacity, largest entry demand, largest pair demand}.
+// Received records are checked (read_bag_record, then row < the local table's rows) before they are used.
+// Block 0 also reads the P received headers into stat (bag_demand_stat).
 template <int LPS, int VEC, bool CLIP>
 __global__ __launch_bounds__(256) void bags_pool_k(const float* const* __restrict__ tables, const int64_t* __restrict__ lvocab, int F,
                                                    int K, const int4* __restrict__ recv, int P, int64_t cap_e, int64_t cap_b,
@@ -238,41 +204,21 @@ __global__ __launch_bounds__(256) void bags_pool_k(const float* const* __restric
     if (stat && blockIdx.x == 0 && threadIdx.x < 64) {
         unsigned int me = 0, mb = 0;
         for (int o = threadIdx.x; o < P; o += 64) {
-            const int4 h = recv[(int64_t)o * (cap_e + 1)];
+            const int4 h = bag_slab_of(recv, o, cap_e)[0];
             me = max(me, (unsigned int)h.z);
             mb = max(mb, (unsigned int)h.w);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            me = max(me, (unsigned int)__shfl_xor((int)me, o, 64));
-            mb = max(mb, (unsigned int)__shfl_xor((int)mb, o, 64));
-        }
-        if (threadIdx.x == 0) {
-            stat[0] = ((int64_t)me > cap_e || (int64_t)mb > cap_b) ? 1 : 0;
-            stat[1] = me;
-            stat[2] = mb;
-        }
+        bag_demand_stat(me, mb, cap_e, cap_b, stat);
     }
     const int64_t cpb = (cap_e + U - 1) / U;                          // chunks of U entry slots per slab
     const int64_t n = (int64_t)P * cpb;
     const int64_t nwave = (int64_t)gridDim.x * (blockDim.x >> 6);
     // record j of a slab -> return position, row (-1: none / outside the local table), slot, weight
     auto load = [&](const int4* slab, int64_t j, int64_t ne, int& ret, int64_t& row, int& sl, float& w) {
-        ret = -2;
         row = -1;
         sl = 0;
-        w = 0.f;
-        if (j < ne) {
-            const int4 r = slab[1 + j];
-            ret = r.w;
-            const int64_t p = (int64_t)(((uint64_t)(uint32_t)r.y << 32) | (uint32_t)r.x);
-            w = __int_as_float(r.z);
-            if (p >= 0 && ret >= 0 && (int64_t)ret < cap_b) {
-                const int64_t rr = p < 0x7fffffff ? (int64_t)((uint32_t)p / (uint32_t)F) : p / F;
-                sl = (int)(p - rr * F);
-                if (rr < (sl < SB_MAXF ? s_rows[sl] : lvocab[sl])) row = rr;
-            }
-        }
+        int64_t rr;
+        if (read_bag_record(slab, j, ne, F, cap_b, ret, w, sl, rr) && rr < (sl < SB_MAXF ? s_rows[sl] : lvocab[sl])) row = rr;
     };
     // U rows in flight, then clip_row with the slot's max_norm and acc + w * row in entry order (bag_csr_k's per-entry operations)
     auto rows_of = [&](const int64_t (&row)[U], const int (&sl)[U], V (&v)[U]) {
@@ -300,11 +246,11 @@ __global__ __launch_bounds__(256) void bags_pool_k(const float* const* __restric
         if (it >= n) continue;
         const int src = n < ((int64_t)1 << 31) ? (int)((uint32_t)it / (uint32_t)cpb) : (int)(it / cpb);     // 32-bit division when it fits
         const int64_t c0 = (it - (int64_t)src * cpb) * U;
-        const int4* slab = recv + (int64_t)src * (cap_e + 1);
-        const int64_t ne = min((int64_t)(unsigned int)slab[0].x, cap_e);
+        const int4* slab = bag_slab_of(recv, src, cap_e);
+        const int64_t ne = bag_entries(slab, cap_e);
         if (c0 >= ne) continue;
         // the chunk's U records; a leading run that began in the previous chunk belongs to that chunk's group
-        const int prev = c0 > 0 ? slab[c0].w : -3;
+        const int prev = c0 > 0 ? bag_record_ret(slab[c0]) : -3;
         int ret[U], sl[U];
         int64_t row[U];
         float w[U];
@@ -334,7 +280,7 @@ __global__ __launch_bounds__(256) void bags_pool_k(const float* const* __restric
         }
         // the chunk's last run may go on past it: walk the rest of it, U records at a time
         if (cur >= 0 && (int64_t)cur < cap_b) {
-            for (int64_t j0 = c0 + U; j0 < ne && slab[1 + j0].w == cur; j0 += U) {
+            for (int64_t j0 = c0 + U; j0 < ne && bag_record_ret(slab[1 + j0]) == cur; j0 += U) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     load(slab, j0 + u, ne, ret[u], row[u], sl[u], w[u]);
@@ -380,10 +326,10 @@ __global__ __launch_bounds__(256) void bags_combine_k(const float* __restrict__ 
             if (sact) {
                 const int64_t g = b * F + f;
                 const uint64_t m = mask[g];
-                for (uint64_t mm = m; mm; mm &= mm - 1ull) {
-                    const int32_t p = pos[g * P + (__ffsll((long long)mm) - 1)];
+                for_each_owner(m, [&](int o) {
+                    const int32_t p = pos[g * P + o];
                     if (p >= 0 && cact) acc = vadd(acc, ldv(back + (int64_t)p * K + c * VEC, (V*)nullptr));
-                }
+                });
                 const int comb = slot_combiner ? slot_combiner[f] : combiner;
                 if (m && comb != DIR_COMBINER_SUM) acc = vdiv(acc, denom[g]);
                 if (act) stv(out + b * out_ld + (int64_t)f * K + c * VEC, acc);
@@ -429,10 +375,10 @@ __global__ __launch_bounds__(256) void bags_grad_k(const float* __restrict__ g, 
             const int comb = slot_combiner ? slot_combiner[f] : combiner;
             V gv = ldv(g + b * g_ld + (int64_t)f * K + (cact ? c * VEC : 0), (V*)nullptr);
             if (comb != DIR_COMBINER_SUM) gv = vdiv(gv, denom[gi]);
-            for (uint64_t mm = m; mm; mm &= mm - 1ull) {
-                const int32_t p = pos[gi * P + (__ffsll((long long)mm) - 1)];
+            for_each_owner(m, [&](int o) {
+                const int32_t p = pos[gi * P + o];
                 if (p >= 0 && (int64_t)p < n_rows && cact) stv(send + (int64_t)p * K + c * VEC, gv);
-            }
+            });
         }
     }
 }
@@ -455,11 +401,9 @@ extern "C" int dir_shard_bags_bucket(const int64_t* ids, const int64_t* offsets,
                                      int P, const int32_t* slot_combiner, int combiner, int flags, int64_t cap_e, int64_t cap_b,
                                      int64_t* slabs, int32_t* pos, int64_t* mask, float* denom, int64_t* stat, void* workspace,
                                      dir_stream_t stream) {
-    DIR_CHECK_ARG(F > 0 && P > 0 && P <= 64 && B >= 0 && nnz >= 0, "dir_shard_bags_bucket: F=%d P=%d B=%lld nnz=%lld (P <= 64)", F, P,
+    DIR_CHECK_ARG(F > 0 && B >= 0 && nnz >= 0 && nnz < ((int64_t)1 << 31), "dir_shard_bags_bucket: F=%d B=%lld nnz=%lld (nnz < 2^31)", F,
                   (long long)B, (long long)nnz);
-    DIR_CHECK_ARG(cap_e > 0 && cap_b > 0 && cap_e < ((int64_t)1 << 31) && (int64_t)P * cap_b < ((int64_t)1 << 31) && nnz < ((int64_t)1 << 31),
-                  "dir_shard_bags_bucket: cap_e=%lld cap_b=%lld nnz=%lld (each < 2^31, P*cap_b too)", (long long)cap_e, (long long)cap_b,
-                  (long long)nnz);
+    if (int rc = check_slab_geometry("dir_shard_bags_bucket", P, cap_e, cap_b)) return rc;
     DIR_CHECK_ARG(combiner >= DIR_COMBINER_SUM && combiner <= DIR_COMBINER_SQRTN, "dir_shard_bags_bucket: combiner=%d", combiner);
     DIR_CHECK_ARG(vocab && slabs && workspace, "dir_shard_bags_bucket: null pointer");
     DIR_CHECK_ARG(B == 0 || (offsets && pos && mask && denom && (nnz == 0 || ids)), "dir_shard_bags_bucket: null pointer");
@@ -480,8 +424,9 @@ extern "C" int dir_shard_bags_bucket(const int64_t* ids, const int64_t* offsets,
 extern "C" int dir_shard_bags_pool_f32(const float* const* tables, const int64_t* local_vocab, int F, int K, const int64_t* recv, int P,
                                        int64_t cap_e, int64_t cap_b, const float* slot_max_norm, float max_norm, int flags, float* out,
                                        int64_t* stat, dir_stream_t stream) {
-    DIR_CHECK_ARG(F > 0 && K > 0 && P > 0 && P <= 64 && cap_e > 0 && cap_b > 0, "dir_shard_bags_pool_f32: F=%d K=%d P=%d cap_e=%lld cap_b=%lld",
-                  F, K, P, (long long)cap_e, (long long)cap_b);
+    DIR_CHECK_ARG(F > 0 && K > 0 && cap_e > 0 && cap_b > 0, "dir_shard_bags_pool_f32: F=%d K=%d cap_e=%lld cap_b=%lld", F, K, (long long)cap_e,
+                  (long long)cap_b);
+    if (int rc = check_owners("dir_shard_bags_pool_f32", P)) return rc;
     DIR_CHECK_ARG(!(max_norm < 0.f), "dir_shard_bags_pool_f32: max_norm=%g", max_norm);
     DIR_CHECK_ARG(tables && local_vocab && recv && out, "dir_shard_bags_pool_f32: null pointer");
     const bool vec = (K % 4 == 0) && aligned16(out);
@@ -493,37 +438,10 @@ extern "C" int dir_shard_bags_pool_f32(const float* const* tables, const int64_t
     hipStream_t st = as_stream(stream);
     const int4* r = reinterpret_cast<const int4*>(recv);
     const bool clip = max_norm > 0.f || slot_max_norm;
-#define DIR_CASE(L, V)                                                                                                                  \
-    do {                                                                                                                                \
-        if (clip)                                                                                                                       \
-            hipLaunchKernelGGL((bags_pool_k<L, V, true>), grid, dim3(256), 0, st, tables, local_vocab, F, K, r, P, cap_e, cap_b,          \
-                               slot_max_norm, max_norm, flags, out, stat);                                                              \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((bags_pool_k<L, V, false>), grid, dim3(256), 0, st, tables, local_vocab, F, K, r, P, cap_e, cap_b,         \
-                               slot_max_norm, max_norm, flags, out, stat);                                                              \
-    } while (0)
-    if (vec) {
-        switch (lps) {
-            case 1: DIR_CASE(1, 4); break;
-            case 2: DIR_CASE(2, 4); break;
-            case 4: DIR_CASE(4, 4); break;
-            case 8: DIR_CASE(8, 4); break;
-            case 16: DIR_CASE(16, 4); break;
-            case 32: DIR_CASE(32, 4); break;
-            default: DIR_CASE(64, 4); break;
-        }
-    } else {
-        switch (lps) {
-            case 1: DIR_CASE(1, 1); break;
-            case 2: DIR_CASE(2, 1); break;
-            case 4: DIR_CASE(4, 1); break;
-            case 8: DIR_CASE(8, 1); break;
-            case 16: DIR_CASE(16, 1); break;
-            case 32: DIR_CASE(32, 1); break;
-            default: DIR_CASE(64, 1); break;
-        }
-    }
-#undef DIR_CASE
+    dispatch_lps(vec, lps, [&](auto L, auto V) {
+        auto k = clip ? bags_pool_k<decltype(L)::value, decltype(V)::value, true> : bags_pool_k<decltype(L)::value, decltype(V)::value, false>;
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, st, tables, local_vocab, F, K, r, P, cap_e, cap_b, slot_max_norm, max_norm, flags, out, stat);
+    });
     DIR_CHECK_LAUNCH("shard_bags_pool");
     return DIR_OK;
 }
@@ -531,7 +449,8 @@ extern "C" int dir_shard_bags_pool_f32(const float* const* tables, const int64_t
 extern "C" int dir_shard_bags_combine_f32(const float* back, int K, int P, const int32_t* pos, const int64_t* mask, const float* denom,
                                           int64_t B, int F, const int32_t* slot_combiner, int combiner, float* out, int64_t out_ld,
                                           float* fm, dir_stream_t stream) {
-    DIR_CHECK_ARG(F > 0 && K > 0 && P > 0 && P <= 64 && B >= 0, "dir_shard_bags_combine_f32: F=%d K=%d P=%d B=%lld", F, K, P, (long long)B);
+    DIR_CHECK_ARG(F > 0 && K > 0 && B >= 0, "dir_shard_bags_combine_f32: F=%d K=%d B=%lld", F, K, (long long)B);
+    if (int rc = check_owners("dir_shard_bags_combine_f32", P)) return rc;
     DIR_CHECK_ARG(combiner >= DIR_COMBINER_SUM && combiner <= DIR_COMBINER_SQRTN, "dir_shard_bags_combine_f32: combiner=%d", combiner);
     DIR_CHECK_ARG(out_ld >= (int64_t)F * K, "dir_shard_bags_combine_f32: out_ld=%lld < F*K=%lld", (long long)out_ld, (long long)F * K);
     // the FM step's lane layout follows dir_fm_second_order_f32's choice on `out`, so that the fused logit is that kernel's bit for bit
@@ -546,37 +465,10 @@ extern "C" int dir_shard_bags_combine_f32(const float* back, int K, int P, const
     dim3 grid(grid_for((waves + 3) / 4));
     hipStream_t st = as_stream(stream);
     const uint64_t* m = reinterpret_cast<const uint64_t*>(mask);
-#define DIR_CASE(L, V)                                                                                                                  \
-    do {                                                                                                                                \
-        if (fm)                                                                                                                         \
-            hipLaunchKernelGGL((bags_combine_k<L, V, true>), grid, dim3(256), 0, st, back, K, P, pos, m, denom, slot_combiner, combiner, \
-                               B, F, out, out_ld, fm);                                                                                  \
-        else                                                                                                                            \
-            hipLaunchKernelGGL((bags_combine_k<L, V, false>), grid, dim3(256), 0, st, back, K, P, pos, m, denom, slot_combiner,         \
-                               combiner, B, F, out, out_ld, fm);                                                                        \
-    } while (0)
-    if (vec) {
-        switch (lps) {
-            case 1: DIR_CASE(1, 4); break;
-            case 2: DIR_CASE(2, 4); break;
-            case 4: DIR_CASE(4, 4); break;
-            case 8: DIR_CASE(8, 4); break;
-            case 16: DIR_CASE(16, 4); break;
-            case 32: DIR_CASE(32, 4); break;
-            default: DIR_CASE(64, 4); break;
-        }
-    } else {
-        switch (lps) {
-            case 1: DIR_CASE(1, 1); break;
-            case 2: DIR_CASE(2, 1); break;
-            case 4: DIR_CASE(4, 1); break;
-            case 8: DIR_CASE(8, 1); break;
-            case 16: DIR_CASE(16, 1); break;
-            case 32: DIR_CASE(32, 1); break;
-            default: DIR_CASE(64, 1); break;
-        }
-    }
-#undef DIR_CASE
+    dispatch_lps(vec, lps, [&](auto L, auto V) {
+        auto k = fm ? bags_combine_k<decltype(L)::value, decltype(V)::value, true> : bags_combine_k<decltype(L)::value, decltype(V)::value, false>;
+        hipLaunchKernelGGL(k, grid, dim3(256), 0, st, back, K, P, pos, m, denom, slot_combiner, combiner, B, F, out, out_ld, fm);
+    });
     DIR_CHECK_LAUNCH("shard_bags_combine");
     return DIR_OK;
 }
@@ -585,8 +477,8 @@ extern "C" int dir_shard_bags_grad_f32(const float* g, int64_t g_ld, int K, int 
                                        int64_t B, int F, const int32_t* slot_combiner, int combiner, int64_t cap_b, float* send,
                                        dir_stream_t stream) {
     const char* name = "dir_shard_bags_grad_f32";
-    DIR_CHECK_ARG(F > 0 && K > 0 && P > 0 && P <= 64 && B >= 0, "%s: F=%d K=%d P=%d B=%lld (P <= 64)", name, F, K, P, (long long)B);
-    DIR_CHECK_ARG(cap_b > 0 && (int64_t)P * cap_b < ((int64_t)1 << 31), "%s: cap_b=%lld (P*cap_b < 2^31)", name, (long long)cap_b);
+    DIR_CHECK_ARG(F > 0 && K > 0 && B >= 0, "%s: F=%d K=%d B=%lld", name, F, K, (long long)B);
+    if (int rc = check_partial_geometry(name, P, cap_b)) return rc;
     DIR_CHECK_ARG(combiner >= DIR_COMBINER_SUM && combiner <= DIR_COMBINER_SQRTN, "%s: combiner=%d", name, combiner);
     DIR_CHECK_ARG(g_ld >= (int64_t)F * K, "%s: g_ld=%lld < F*K=%lld", name, (long long)g_ld, (long long)F * K);
     DIR_CHECK_ARG(send, "%s: null pointer", name);
@@ -601,30 +493,10 @@ extern "C" int dir_shard_bags_grad_f32(const float* g, int64_t g_ld, int K, int 
     hipStream_t st = as_stream(stream);
     const uint64_t* m = reinterpret_cast<const uint64_t*>(mask);
     const int64_t n_rows = (int64_t)P * cap_b;
-#define DIR_CASE(L, V)                                                                                                                  \
-    hipLaunchKernelGGL((bags_grad_k<L, V>), grid, dim3(256), 0, st, g, g_ld, K, P, pos, m, denom, slot_combiner, combiner, B, F, send, n_rows)
-    if (vec) {
-        switch (lps) {
-            case 1: DIR_CASE(1, 4); break;
-            case 2: DIR_CASE(2, 4); break;
-            case 4: DIR_CASE(4, 4); break;
-            case 8: DIR_CASE(8, 4); break;
-            case 16: DIR_CASE(16, 4); break;
-            case 32: DIR_CASE(32, 4); break;
-            default: DIR_CASE(64, 4); break;
-        }
-    } else {
-        switch (lps) {
-            case 1: DIR_CASE(1, 1); break;
-            case 2: DIR_CASE(2, 1); break;
-            case 4: DIR_CASE(4, 1); break;
-            case 8: DIR_CASE(8, 1); break;
-            case 16: DIR_CASE(16, 1); break;
-            case 32: DIR_CASE(32, 1); break;
-            default: DIR_CASE(64, 1); break;
-        }
-    }
-#undef DIR_CASE
+    dispatch_lps(vec, lps, [&](auto L, auto V) {
+        hipLaunchKernelGGL((bags_grad_k<decltype(L)::value, decltype(V)::value>), grid, dim3(256), 0, st, g, g_ld, K, P, pos, m, denom,
+                           slot_combiner, combiner, B, F, send, n_rows);
+    });
     DIR_CHECK_LAUNCH("shard_bags_grad");
     return DIR_OK;
 }

@@ -13,14 +13,13 @@
 // All three are request-rate-bound (one 4-byte read or write per entry, no reuse): one lane per entry, the payload read coalesced, several
 // independent loads in flight per lane, nothing staged through LDS.
 #include "common.hpp"
+#include "shard_wire.hpp"
 
 namespace dir {
 
-__device__ __forceinline__ int64_t lin_slab_count(int64_t header) { return (int64_t)(uint32_t)header; }
-
-// Owner side.  Slab form (cap > 0): recv = P slabs of [header | cap slots] (header: low 32 bits = valid slots), out[s * cap + j].  Flat form
-// (cap == 0): recv = n payload words, out[i].  p = local_row * F + slot; p < 0, a slot behind the header, or a row outside the slot's
-// local rows (local_rows, optional) writes 0.0f: every output word is written, nothing uninitialised goes back over the wire.
+// Owner side.  Slab form (cap > 0): recv = P one-hot slabs (shard_wire.hpp), out[s * cap + j].  Flat form (cap == 0): recv = n payload
+// words, out[i].  p < 0, a slot behind the header, or a row outside the slot's local rows (local_rows, optional) writes 0.0f: every
+// output word is written, nothing uninitialised goes back over the wire.
 template <int EPT>
 __global__ __launch_bounds__(256) void linear_gather_k(const float* const* __restrict__ rows, int64_t ld, const int64_t* __restrict__ local_rows,
                                                        int F, const int64_t* __restrict__ recv, int64_t cap, int64_t total,
@@ -38,27 +37,20 @@ __global__ __launch_bounds__(256) void linear_gather_k(const float* const* __res
                 if (cap > 0) {
                     const int64_t sl = (int64_t)((uint32_t)i / (uint32_t)cap);       // total < 2^31
                     const int64_t j = i - sl * cap;
-                    const int64_t* slab = recv + sl * (cap + 1);
-                    if (j < lin_slab_count(slab[0])) p[u] = slab[1 + j];
+                    const int64_t* slab = slab_of(recv, sl, cap);
+                    if (j < slab_count(slab[0])) p[u] = slab[1 + j];
                 } else {
                     p[u] = recv[i];
                 }
             }
         }
 #pragma unroll
-        for (int u = 0; u < EPT; ++u) {                        // decode as gather_slabs_k does (32-bit division when it fits)
+        for (int u = 0; u < EPT; ++u) {
             src[u] = nullptr;
             if (p[u] >= 0) {
                 int slot;
                 int64_t row;
-                if (p[u] < (int64_t)0x7fffffff) {
-                    const uint32_t r32 = (uint32_t)p[u] / (uint32_t)F;
-                    slot = (int)((uint32_t)p[u] - r32 * (uint32_t)F);
-                    row = r32;
-                } else {
-                    row = p[u] / F;
-                    slot = (int)(p[u] - row * F);
-                }
+                unpack_payload(p[u], F, slot, row);
                 if (!local_rows || row < local_rows[slot]) src[u] = rows[slot] + row * ld;
             }
         }
@@ -97,18 +89,7 @@ __global__ __launch_bounds__(256) void linear_finish_k(const float* __restrict__
 #pragma unroll
             for (int j = 0; j < UFL; ++j) v[j] = (uint64_t)pos[j] < (uint64_t)n_back ? wback[pos[j]] : 0.f;     // inv < 0: pruned
 #pragma unroll
-            for (int j = 0; j < UFL; ++j) {
-                const int vi = __builtin_bit_cast(int, v[j]);
-                const float q0 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x00, 0xf, 0xf, true));   // quad_perm [0,0,0,0]
-                const float q1 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x55, 0xf, 0xf, true));   // [1,1,1,1]
-                const float q2 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xaa, 0xf, 0xf, true));   // [2,2,2,2]
-                const float q3 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xff, 0xf, 0xf, true));   // [3,3,3,3]
-                const int f = f0 + 4 * j;
-                if (f < F) acc = acc + q0;
-                if (f + 1 < F) acc = acc + q1;
-                if (f + 2 < F) acc = acc + q2;
-                if (f + 3 < F) acc = acc + q3;
-            }
+            for (int j = 0; j < UFL; ++j) acc = quad_add_in_order(v[j], f0 + 4 * j, F, acc);
         }
         if (live && c == 0) out[b * out_ld] = acc + (bias ? bias[0] : 0.f);
     }
@@ -130,12 +111,12 @@ __global__ __launch_bounds__(256) void linear_grad_k(const float* __restrict__ g
 // ------------------------------------------------------------------------------------------------
 // the term over multi-hot bags (ShardedTables.lookup_bags(want_lin=True) / lookup_bags_train(with_linear=True))
 // ------------------------------------------------------------------------------------------------
-// The bag lookup's owner holds every entry's 16-byte record (shard_bags.hip: x, y = local_row * F + slot, z = weight, w = return position),
-// so it pools the first-order weights of each run beside the embedding rows: one float per partial-row position travels back behind the
-// partial rows, the requester adds a bag's partials in ascending owner order, applies the model's ONE linear_sparse_combiner (independent of
-// the per-slot embedding combiners: its denominators are computed from the CSR entries with the lookup's liveness rule) and sums the
-// sample's F bags in slot order -- linear_csr_k's operations in its order (linear_cross.hip), so with one owner per bag and flags = 0
-// the result is dir_linear_sparse_sum_f32's bit for bit.
+// The bag lookup's owner holds every entry's 16-byte record (shard_wire.hpp), so it pools the first-order weights of each run beside the
+// embedding rows: one float per partial-row position travels back behind the partial rows, the requester adds a bag's partials in
+// ascending owner order, applies the model's ONE linear_sparse_combiner (independent of the per-slot embedding combiners: its
+// denominators are computed from the CSR entries with the lookup's liveness rule) and sums the sample's F bags in slot order --
+// linear_csr_k's operations in its order (linear_cross.hip), so with one owner per bag and flags = 0 the result is
+// dir_linear_sparse_sum_f32's bit for bit.
 //   bags_linear_pool_k     owner:      lout[src * cap_b + ret] = sum over the run of w_e * lw[row_e], in entry order, from 0.0f
 //   bags_linear_denom_k    requester:  lden[g] of every bag (mean / sqrtn only), kept in the plan for the backward
 //   bags_linear_combine_k  requester:  lin[b] = sum_f (sum_o partial) [/ lden] + bias
@@ -147,9 +128,8 @@ constexpr int SBL_U = 8;      // entry slots per lane (bags_pool_k's chunk)
 // lane group: the chunk's records (consecutive lanes read consecutive 128-byte pieces of the slab: every line a wave touches is used whole)
 // and then its SBL_U weights are in flight together; the lane pools every run that STARTS inside its chunk, acc + w * lw in entry order,
 // and writes each position once; a run that goes on past the chunk is walked to its end, SBL_U records at a time, and a leading run that
-// began in the previous chunk is left to that chunk's lane.  bags_pool_k's record checks: count from the header, slot < F (by the
-// decode), row < the slot's local rows, 0 <= return position < cap_b -- an entry that kernel drops is dropped here.  Positions no run
-// names keep the zero the C entry filled lout with.
+// began in the previous chunk is left to that chunk's lane.  bags_pool_k's record checks (read_bag_record, row < the slot's local
+// rows): an entry that kernel drops is dropped here.  Positions no run names keep the zero the C entry filled lout with.
 __global__ __launch_bounds__(256) void bags_linear_pool_k(const float* const* __restrict__ rows, int64_t ld, const int64_t* __restrict__ lvocab,
                                                           int F, const int4* __restrict__ recv, int P, int64_t cap_e, int64_t cap_b,
                                                           float* __restrict__ lout) {
@@ -158,28 +138,18 @@ __global__ __launch_bounds__(256) void bags_linear_pool_k(const float* const* __
     const int64_t n = (int64_t)P * cpb;
     // record j of a slab -> return position, the address of its weight (nullptr: none / outside the local rows), entry weight
     auto load = [&](const int4* slab, int64_t j, int64_t ne, int& ret, const float*& src, float& w) {
-        ret = -2;
         src = nullptr;
-        w = 0.f;
-        if (j < ne) {
-            const int4 r = slab[1 + j];
-            ret = r.w;
-            const int64_t p = (int64_t)(((uint64_t)(uint32_t)r.y << 32) | (uint32_t)r.x);
-            w = __int_as_float(r.z);
-            if (p >= 0 && ret >= 0 && (int64_t)ret < cap_b) {
-                const int64_t rr = p < 0x7fffffff ? (int64_t)((uint32_t)p / (uint32_t)F) : p / F;
-                const int sl = (int)(p - rr * F);
-                if (rr < lvocab[sl]) src = rows[sl] + rr * ld;
-            }
-        }
+        int sl;
+        int64_t rr;
+        if (read_bag_record(slab, j, ne, F, cap_b, ret, w, sl, rr) && rr < lvocab[sl]) src = rows[sl] + rr * ld;
     };
     for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < n; it += (int64_t)gridDim.x * 256) {
         const int s = n < ((int64_t)1 << 31) ? (int)((uint32_t)it / (uint32_t)cpb) : (int)(it / cpb);
         const int64_t c0 = (it - (int64_t)s * cpb) * U;
-        const int4* slab = recv + (int64_t)s * (cap_e + 1);
-        const int64_t ne = min((int64_t)(unsigned int)slab[0].x, cap_e);
+        const int4* slab = bag_slab_of(recv, s, cap_e);
+        const int64_t ne = bag_entries(slab, cap_e);
         if (c0 >= ne) continue;
-        const int prev = c0 > 0 ? slab[c0].w : -3;
+        const int prev = c0 > 0 ? bag_record_ret(slab[c0]) : -3;
         int ret[U];
         const float* src[U];
         float w[U], v[U];
@@ -211,7 +181,7 @@ __global__ __launch_bounds__(256) void bags_linear_pool_k(const float* const* __
             if (src[u]) acc = acc + w[u] * v[u];
         }
         if (cur >= 0 && (int64_t)cur < cap_b) {                            // the chunk's last run may go on past it
-            for (int64_t j0 = c0 + U; j0 < ne && slab[1 + j0].w == cur; j0 += U) {
+            for (int64_t j0 = c0 + U; j0 < ne && bag_record_ret(slab[1 + j0]) == cur; j0 += U) {
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     load(slab, j0 + u, ne, ret[u], src[u], w[u]);
@@ -229,9 +199,8 @@ __global__ __launch_bounds__(256) void bags_linear_pool_k(const float* const* __
     }
 }
 
-// Requester side: the linear combiner's denominator of every bag g = b * F + f, from the CSR entries with bags_bucket_k's liveness rule (id
-// inside [0, vocab_f); weight > 0 under PRUNE_NONPOSITIVE_WEIGHTS) and linear_csr_k's arithmetic: wsum and w2sum in entry order, the
-// entry count without weights, sqrtf for sqrtn.  A bag without a live entry gets a value nobody divides by.
+// Requester side: the linear combiner's denominator of every bag g = b * F + f, from the CSR entries: bags_bucket_k's liveness rule and
+// sums (bag_entry_live, BagDenom), which are linear_csr_k's arithmetic.  A bag without a live entry gets a value nobody divides by.
 __global__ __launch_bounds__(256) void bags_linear_denom_k(const int64_t* __restrict__ ids, const int64_t* __restrict__ offsets,
                                                            const float* __restrict__ weights, int64_t sb, int64_t sf, int64_t nb, int F,
                                                            const int64_t* __restrict__ vocab, int flags, int combiner,
@@ -242,19 +211,13 @@ __global__ __launch_bounds__(256) void bags_linear_denom_k(const int64_t* __rest
         const int f = (int)(g - b * F);
         const int64_t bag = b * sb + (int64_t)f * sf;
         const int64_t beg = offsets[bag], end = offsets[bag + 1];
-        const uint64_t V = (uint64_t)vocab[f];
-        float wsum = 0.f, w2sum = 0.f;
-        int cnt = 0;
+        const int64_t V = vocab[f];
+        BagDenom den;
         for (int64_t e = beg; e < end; ++e) {
-            const int64_t id = ids[e];
             const float w = weights ? weights[e] : 1.0f;
-            if (!((uint64_t)id < V)) continue;
-            if (prune_w && !(w > 0.0f)) continue;
-            wsum = wsum + w;
-            w2sum = w2sum + w * w;
-            ++cnt;
+            if (bag_entry_live(ids[e], w, V, prune_w)) den.add(w);
         }
-        lden[g] = combiner == DIR_COMBINER_MEAN ? (weights ? wsum : (float)cnt) : (weights ? sqrtf(w2sum) : sqrtf((float)cnt));
+        lden[g] = den.value(combiner, weights != nullptr);
     }
 }
 
@@ -285,26 +248,15 @@ __global__ __launch_bounds__(256) void bags_linear_combine_k(const float* __rest
                 v[j] = 0.f;
                 if (m[j]) {
                     const int64_t g = b * F + f0 + 4 * j + c;
-                    for (uint64_t mm = m[j]; mm; mm &= mm - 1ull) {
-                        const int32_t p = pos[g * P + (__ffsll((long long)mm) - 1)];
+                    for_each_owner(m[j], [&](int o) {
+                        const int32_t p = pos[g * P + o];
                         if (p >= 0 && (int64_t)p < n_back) v[j] = v[j] + lback[p];
-                    }
+                    });
                     if (lden) v[j] = v[j] / lden[g];
                 }
             }
 #pragma unroll
-            for (int j = 0; j < UFL; ++j) {
-                const int vi = __builtin_bit_cast(int, v[j]);
-                const float q0 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x00, 0xf, 0xf, true));   // quad_perm [0,0,0,0]
-                const float q1 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0x55, 0xf, 0xf, true));   // [1,1,1,1]
-                const float q2 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xaa, 0xf, 0xf, true));   // [2,2,2,2]
-                const float q3 = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(vi, 0xff, 0xf, 0xf, true));   // [3,3,3,3]
-                const int f = f0 + 4 * j;
-                if (f < F) acc = acc + q0;
-                if (f + 1 < F) acc = acc + q1;
-                if (f + 2 < F) acc = acc + q2;
-                if (f + 3 < F) acc = acc + q3;
-            }
+            for (int j = 0; j < UFL; ++j) acc = quad_add_in_order(v[j], f0 + 4 * j, F, acc);
         }
         if (live && c == 0) out[b * out_ld] = acc + (bias ? bias[0] : 0.f);
     }
@@ -322,10 +274,10 @@ __global__ __launch_bounds__(256) void bags_linear_grad_k(const float* __restric
         const int64_t b = (int64_t)((uint32_t)gi / (uint32_t)F);         // nb < 2^31
         float d = g[b * g_ld];
         if (lden) d = d / lden[gi];
-        for (uint64_t mm = m; mm; mm &= mm - 1ull) {
-            const int32_t p = pos[gi * P + (__ffsll((long long)mm) - 1)];
+        for_each_owner(m, [&](int o) {
+            const int32_t p = pos[gi * P + o];
             if (p >= 0 && (int64_t)p < n_send) send[p] = d;
-        }
+        });
     }
 }
 
@@ -339,7 +291,7 @@ extern "C" int dir_shard_linear_gather_f32(const float* const* rows, int64_t row
     DIR_CHECK_ARG(F > 0 && row_ld >= 1, "%s: F=%d row_ld=%lld", name, F, (long long)row_ld);
     int64_t total;
     if (cap > 0) {                                             // the P fixed-capacity slabs
-        DIR_CHECK_ARG(P > 0 && P <= 64, "%s: P=%d (1 <= P <= 64)", name, P);
+        if (int rc = check_owners(name, P)) return rc;
         DIR_CHECK_ARG((int64_t)P * cap < ((int64_t)1 << 31), "%s: cap=%lld (P*cap < 2^31)", name, (long long)cap);
         total = (int64_t)P * cap;
     } else {                                                   // a flat payload of n words
@@ -393,9 +345,7 @@ extern "C" int dir_shard_bags_linear_pool_f32(const float* const* rows, int64_t 
                                               int P, int64_t cap_e, int64_t cap_b, float* lout, dir_stream_t stream) {
     const char* name = "dir_shard_bags_linear_pool_f32";
     DIR_CHECK_ARG(F > 0 && row_ld >= 1, "%s: F=%d row_ld=%lld", name, F, (long long)row_ld);
-    DIR_CHECK_ARG(P > 0 && P <= 64, "%s: P=%d (1 <= P <= 64)", name, P);
-    DIR_CHECK_ARG(cap_e > 0 && cap_e < ((int64_t)1 << 31), "%s: cap_e=%lld (0 < cap_e < 2^31)", name, (long long)cap_e);
-    DIR_CHECK_ARG(cap_b > 0 && (int64_t)P * cap_b < ((int64_t)1 << 31), "%s: cap_b=%lld (cap_b > 0, P*cap_b < 2^31)", name, (long long)cap_b);
+    if (int rc = check_slab_geometry(name, P, cap_e, cap_b)) return rc;
     DIR_CHECK_ARG(rows && local_rows && recv && lout, "%s: null pointer", name);
     hipStream_t st = as_stream(stream);
     // every word crosses the wire: a kernel's zero-fill (a memset node would end the world-1 lookup's graph capture: DESIGN 7.1)
@@ -414,8 +364,7 @@ extern "C" int dir_shard_bags_linear_combine_f32(const float* lback, int P, int6
                                                  dir_stream_t stream) {
     const char* name = "dir_shard_bags_linear_combine_f32";
     DIR_CHECK_ARG(F > 0 && B >= 0 && B * F < ((int64_t)1 << 31), "%s: F=%d B=%lld (B*F < 2^31)", name, F, (long long)B);
-    DIR_CHECK_ARG(P > 0 && P <= 64, "%s: P=%d (1 <= P <= 64)", name, P);
-    DIR_CHECK_ARG(cap_b > 0 && (int64_t)P * cap_b < ((int64_t)1 << 31), "%s: cap_b=%lld (cap_b > 0, P*cap_b < 2^31)", name, (long long)cap_b);
+    if (int rc = check_partial_geometry(name, P, cap_b)) return rc;
     DIR_CHECK_ARG(combiner >= DIR_COMBINER_SUM && combiner <= DIR_COMBINER_SQRTN, "%s: combiner=%d", name, combiner);
     DIR_CHECK_ARG(nnz >= 0 && out_ld >= 1, "%s: nnz=%lld out_ld=%lld", name, (long long)nnz, (long long)out_ld);
     if (B == 0) return DIR_OK;                                 // an empty batch carries no buffers
@@ -438,8 +387,7 @@ extern "C" int dir_shard_bags_linear_grad_f32(const float* g, int64_t g_ld, int 
                                               const float* lden, int64_t B, int F, int combiner, float* send, dir_stream_t stream) {
     const char* name = "dir_shard_bags_linear_grad_f32";
     DIR_CHECK_ARG(F > 0 && B >= 0 && B * F < ((int64_t)1 << 31), "%s: F=%d B=%lld (B*F < 2^31)", name, F, (long long)B);
-    DIR_CHECK_ARG(P > 0 && P <= 64, "%s: P=%d (1 <= P <= 64)", name, P);
-    DIR_CHECK_ARG(cap_b > 0 && (int64_t)P * cap_b < ((int64_t)1 << 31), "%s: cap_b=%lld (cap_b > 0, P*cap_b < 2^31)", name, (long long)cap_b);
+    if (int rc = check_partial_geometry(name, P, cap_b)) return rc;
     DIR_CHECK_ARG(combiner >= DIR_COMBINER_SUM && combiner <= DIR_COMBINER_SQRTN, "%s: combiner=%d", name, combiner);
     DIR_CHECK_ARG(g_ld >= 1, "%s: g_ld=%lld", name, (long long)g_ld);
     DIR_CHECK_ARG(send, "%s: null pointer", name);

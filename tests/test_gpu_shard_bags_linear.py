@@ -12,6 +12,8 @@ dir_shard_bags_linear_combine_f32, dir_shard_bags_linear_grad_f32, dir_sparse_ft
   6. a captured world-1 lookup_bags(want_fm, want_lin) replays to the eager result, also after the first-order rows moved;
   7. step_bags / predict_bags with linear= on a real DeepFM with a history column, against the float64 three-term model;
   8. two ranks on cuda:0 over host-staged gloo (and over RCCL with one rank per GPU; skipped with a reason on a one-GPU box).
+  9. payload words at and past 2^31 (F = 2048 slots, a slot of 2^20 + 16 rows): the 64-bit branch of the decode that the one-hot
+     gathers, both pools and both key passes share (csrc/shard_wire.hpp), on all four world-1 calls.
 Error measure: the sibling tests' _close, max |got - ref| / (1 + |ref|)."""
 import os
 
@@ -290,6 +292,74 @@ def test_world1_graph_replay_equals_eager(built_lib):
     torch.cuda.synchronize()
     assert torch.equal(step.out[0], e1) and torch.equal(step.out[1], f1) and torch.equal(step.out[2], l1)
     assert not torch.equal(l1, l0) and torch.equal(e1, e0)
+
+
+# ---- 9. the 64-bit branch of the payload decode ------------------------------------------------------------------------------------------
+def test_world1_wide_payload(built_lib):
+    """F = 2048 slots of one row each, except slot 2047 with 2^20 + 16 rows; every id of that slot lies in its last 16 rows, so its
+    payload word local_row * F + slot is >= 2^31: lookup(want_lin), lookup_bags(want_lin), one lookup_train(with_linear) step and one
+    lookup_bags_train(with_linear) step decode it in 64 bits.  A gather copies rows, so the one-hot emb is the rows themselves; the
+    one-hot and the bag term are ops.linear_logit's and the bag rows ops.embedding_bag's bit for bit (the neighbouring world-1 tests'
+    contract); both training steps within 1e-5 of the float64 references (theirs too)."""
+    from dir_amd import ops
+    from dir_amd.shard import ShardedTables
+    dev = torch.device("cuda", 0)
+    F, K, B, big = 2048, 4, 8, (1 << 20) + 16
+    vocab = [1] * (F - 1) + [big]
+    rng = np.random.default_rng(71)
+    small = torch.from_numpy((rng.standard_normal((F - 1, K)) * 0.4).astype(np.float32)).to(dev)
+    wide = torch.from_numpy((rng.standard_normal((big, K)) * 0.4).astype(np.float32)).to(dev)
+    small_w = torch.from_numpy((0.3 * rng.standard_normal(F - 1)).astype(np.float32)).to(dev)
+    wide_w = torch.from_numpy((0.3 * rng.standard_normal(big)).astype(np.float32)).to(dev)
+    views = lambda a, b: [a[f:f + 1] for f in range(F - 1)] + [b]      # noqa: E731   2047 one-row views of one tensor + the wide table
+    full, full_w = views(small.clone(), wide.clone()), views(small_w, wide_w)      # `full` stays untouched: st trains its own copy
+    ftrl = dict(lr=0.2, l1=0.01, l2=0.02)
+    st = ShardedTables.from_full(views(small, wide)).attach_linear_from_full(full_w, ACC0)
+    st.enable_training(LR, ACC0).enable_linear_training(**ftrl)
+    lref = Reference([t.cpu().numpy() for t in full], [w.cpu().numpy() for w in full_w])
+    last = lambda n: rng.integers(big - 16, big, size=n).astype(np.int64)          # noqa: E731
+    assert (big - 16) * F + F - 1 >= 1 << 31
+    # one-hot
+    ids_np = np.zeros((B, F), np.int64)
+    ids_np[:, F - 1] = last(B)
+    ids = torch.from_numpy(ids_np).to(dev)
+    emb, lin = st.lookup(ids, want_lin=True)
+    assert torch.equal(emb, torch.cat([small.reshape(1, -1).expand(B, -1), wide[ids[:, F - 1]]], dim=1))
+    assert torch.equal(lin, ops.linear_logit(ops.TableSet.ftrl_rows(full_w), ids))
+    # bags of 0..3 entries in the wide slot, 0..2 in the others
+    bags = []
+    for b in range(B):
+        row = []
+        for f in range(F):
+            L = (0, 1, 2, 3, 3, 2, 1, 3)[b] if f == F - 1 else int(rng.integers(0, 3))
+            row.append((last(L) if f == F - 1 else np.zeros(L, np.int64), rng.uniform(0.1, 2.0, size=L).astype(np.float32)))
+        bags.append(row)
+    v, o, w = _dev(*to_csr(bags, F, False), dev)
+    kw = dict(combiner="mean", max_norm=0.9)
+    embb, _, linb = st.lookup_bags(v, o, w, want_lin=True, lin_combiner="sqrtn", **kw)
+    assert torch.equal(embb, ops.embedding_bag(full, v, o, w, **kw))
+    assert torch.equal(linb, ops.linear_logit(full_w, v, o, w, combiner="sqrtn"))
+    # one one-hot step, then one bag step, against float64
+    G = torch.from_numpy(rng.standard_normal((B, F * K)).astype(np.float32)).to(dev)
+    g = torch.from_numpy(rng.standard_normal((B, 1)).astype(np.float32)).to(dev)
+    e1, l1 = st.lookup_train(ids, with_linear=True)
+    assert torch.equal(e1.detach(), emb) and torch.equal(l1.detach(), lin)
+    ((e1 * G).sum() + (l1 * g).sum()).backward()
+    lref.step(ids_np, G.cpu().numpy(), g.cpu().numpy(), ftrl)
+
+    def errs(what):
+        ew, en, ez = _state_err(st, lref)
+        et = max(_close(st.local_tables[f], lref.T[f]) for f in range(F))
+        ea = max(_close(st.optimizer.accums[f], lref.acc[f]) for f in range(F))
+        assert max(ew, en, ez, et, ea) <= 1e-5, "%s: w %.2e n %.2e z %.2e tables %.2e accums %.2e" % (what, ew, en, ez, et, ea)
+    errs("one-hot step")
+    moved = lref.n[F - 1][:, 0] != ACC0
+    assert moved[big - 16:].any() and not moved[:big - 16].any()                   # the rows named by the wide payloads took the step
+    e2, l2 = st.lookup_bags_train(v, o, w, with_linear=True, lin_combiner="sqrtn", **kw)
+    ((e2 * G).sum() + (l2 * g).sum()).backward()
+    ref_step(lref.T, lref.acc, bags, G.cpu().numpy(), "mean", 0.9, False, LR)
+    lin_ftrl64(lref.w, lref.n, lref.z, lin_entries(bags, vocab, "sqrtn", False), g.cpu().numpy(), **ftrl)
+    errs("bag step")
 
 
 # ---- 7. / 8. the trainer -----------------------------------------------------------------------------------------------------------------
