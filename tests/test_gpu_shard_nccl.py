@@ -304,3 +304,9 @@ def test_sharded_lookup_scenarios_two_ranks_on_one_gpu(built_lib):
     if res is None or any(isinstance(g, str) and ("onnect" in g or "imeout" in g) for _, g in res):
         res = _run(2, "gloo_same_device")            # one retry for a failed rendezvous (transport hiccup, not the code under test)
     _check(res, 2)
+
+
+def test_sharded_lookup_scenarios_eight_ranks_on_one_gpu(built_lib):
+    """The same scenarios, unchanged, at the world size the sharded path exists for: eight fresh ranks on cuda:0 (gloo, host-staged
+    exchanges) -- the dress rehearsal of an 8-GPU node that a one-GPU box can run.  Once, without a rendezvous retry."""
+    _check(_run(8, "gloo_same_device"), 8)

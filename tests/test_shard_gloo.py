@@ -214,6 +214,10 @@ def _run(world, vocab, K, B, seed, train=False, opts=None):
     (3, [50, 20, 33, 7], {"stages": True, "chunks": 2}),
     (2, [50, 20, 33, 7], {"stages": True, "dedup": True, "id_hi": 9}),
     (3, [50, 20, 33], {"async": True, "dedup": True, "chunks": 3, "check": "lazy"}),
+    # world 8 (the size the sharded path exists for): tables with fewer rows than ranks, uneven local batches with empty ones
+    (8, [100, 5, 64, 9], {"uneven": [[5, 0, 11, 3, 1, 9, 0, 5], [2, 7, 0, 4, 8, 1, 3, 6]], "consume": True}),
+    (8, [100, 5, 64, 9], {"dedup": True, "id_hi": 12, "uneven": [[6, 0, 11, 3, 1, 9, 0, 5]]}),
+    (8, [40, 90, 64, 9, 17], {"partitions": [1, 8, 3, 1, 2], "consume": True, "uneven": [[0, 4, 9, 1, 0, 12, 3, 7]]}),
 ])
 def test_sharded_lookup_matches_full_tables(world, vocab, opts):
     K, B = 8, opts.get("B", 37)
@@ -223,7 +227,8 @@ def test_sharded_lookup_matches_full_tables(world, vocab, opts):
 
 
 @pytest.mark.parametrize("world,vocab,opts", [(2, [10, 7, 33], None), (3, [40, 5, 64, 9], None), (3, [40, 5, 64, 9], {"partitions": [2, 1, 3, 1]}),
-                                              (2, [200, 300, 100], {"dedup": True, "id_hi": 12, "chunks": 2, "B": 600, "infer_first": 3})])
+                                              (2, [200, 300, 100], {"dedup": True, "id_hi": 12, "chunks": 2, "B": 600, "infer_first": 3}),
+                                              (8, [40, 5, 64, 9], None), (8, [40, 5, 64, 9], {"partitions": [2, 1, 8, 3]})])
 def test_sharded_training_step_matches_full_table_adagrad(world, vocab, opts):
     """lookup_train + backward over gloo: every rank's row gradients reach the owners (the forward exchange reversed) and
     the owners' shards end up equal to one synchronous Adagrad step on the full tables over all ranks' batches."""
