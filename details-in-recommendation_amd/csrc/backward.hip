@@ -487,7 +487,8 @@ struct FtrlUpd {      // FTRL-Proximal, learning_rate_power = -0.5 ([TF-upstream
     float* const* linears;   // z
     float lr, l1, l2;
     int64_t ld;
-    bool rows = false;       // tables[f] are packed [vocab, 4] rows [w | n | z | -] (K = 1): one 16-byte read and write per touched id
+    bool rows = false;       // tables[f] are packed [vocab, 4 * units] rows, [w | n | z | -] per unit: one 16-byte read and write per touched (id, unit)
+    int units = 1;           // rows: first-order terms per row (K = units: `col` selects the unit)
     __device__ __forceinline__ void one(float g, float& n, float& z, float& w) const {
         const float n_new = n + g * g;
         const float sigma = (sqrtf(n_new) - sqrtf(n)) / lr;
@@ -498,17 +499,22 @@ struct FtrlUpd {      // FTRL-Proximal, learning_rate_power = -0.5 ([TF-upstream
         n = n_new;
         z = z_new;
     }
+    __device__ __forceinline__ void one_block(float4* rp, float g) const {
+        float4 r = *rp;
+        one(g, r.y, r.z, r.x);
+        *rp = r;
+    }
     template <int VEC>
     __device__ __forceinline__ void apply(int f, int64_t id, int col, typename BV<VEC>::T g) const {
         using V = BV<VEC>;
-        if constexpr (VEC == 1) {
-            if (rows) {                                    // (uniform)
-                float4* rp = reinterpret_cast<float4*>(tables[f] + id * 4);
-                float4 r = *rp;
-                one(g, r.y, r.z, r.x);
-                *rp = r;
-                return;
+        if (rows) {                                        // (uniform)
+            float4* rp = reinterpret_cast<float4*>(tables[f] + (id * units + col) * 4);
+            if constexpr (VEC == 1) {
+                one_block(rp, g);
+            } else {                                       // units % 4 == 0: this lane's four units
+                one_block(rp, g.x); one_block(rp + 1, g.y); one_block(rp + 2, g.z); one_block(rp + 3, g.w);
             }
+            return;
         }
         const int64_t off = id * ld + col;
         float* np_ = accums[f] + off;
@@ -575,6 +581,16 @@ struct AdamUpd {
         if (col == 0) mark[row_base[f] + id] = 1;
     }
 };
+// FtrlUpd with COMPENSATED run sums (Kahan): the update of the units = U first-order rows.  The tile pass adds a run's gradients one after
+// the other in fp32; for a row hit by hundreds of entries of one step (a 7-row table under a batch of 1500: ~140 hits) that sum is off by
+// 1-2e-5 absolute in an order-dependent way, and z = z_prev + g can cancel to O(0.1) against summands of O(10) -- z then misses 1e-5 of
+// float64.  With the compensation a tile's run sum is good to an ulp whatever the order (adagrad_fix_k still adds the partial sums of a
+// run that crosses tiles plainly: one rounding per further tile).  Only the new units export uses it: the units = 1
+// exports keep FtrlUpd and their results bit for bit.
+struct FtrlUnitsUpd : FtrlUpd { static constexpr bool kCompensated = true; };
+template <class U, class = void> struct IsCompensated { static constexpr bool value = false; };
+template <class U> struct IsCompensated<U, std::void_t<decltype(U::kCompensated)>> { static constexpr bool value = U::kCompensated; };
+
 template <class U, class = void> struct IsNorm { static constexpr bool value = false; };
 template <class U> struct IsNorm<U, std::void_t<decltype(U::kNorm)>> { static constexpr bool value = U::kNorm; };
 
@@ -821,9 +837,19 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
         const uint32_t rk = skey[s];
         if (rk >= total_rows || (!BAG && c >= kv)) continue;  // pruned ids / idle lanes of a padded group (BAG: they join bag_apply)
         T sum = V::zero();
+        [[maybe_unused]] T comp = V::zero();               // IsCompensated: the low-order part the adds so far have lost
+        auto kahan = [&](T x) {
+            const T y = V::sub(x, comp), t = V::add(sum, y);
+            comp = V::sub(V::sub(t, sum), y);
+            sum = t;
+        };
         int f = (int)(sval[s] % (uint32_t)F);
         if (staged) {
-            for (int i = s; i < e; ++i) sum = V::add(sum, V::ld(sd + i * (LPS * VEC) + c * VEC));
+            for (int i = s; i < e; ++i) {
+                const T x = V::ld(sd + i * (LPS * VEC) + c * VEC);
+                if constexpr (IsCompensated<U>::value) kahan(x);
+                else sum = V::add(sum, x);
+            }
         } else {
             T wv = V::zero();
             if constexpr (FM) wv = V::ld(upd.tables[f] + ((int64_t)rk - row_base[f]) * upd.ld + c * VEC);
@@ -831,9 +857,16 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
             for (; i + 4 <= e; i += 4) {                    // four entries' loads in flight before their (ordered) adds
                 const T d0 = entry_grad(i, wv, true), d1 = entry_grad(i + 1, wv, true), d2 = entry_grad(i + 2, wv, true),
                         d3 = entry_grad(i + 3, wv, true);
-                sum = V::add(V::add(V::add(V::add(sum, d0), d1), d2), d3);
+                if constexpr (IsCompensated<U>::value) {
+                    kahan(d0); kahan(d1); kahan(d2); kahan(d3);
+                } else {
+                    sum = V::add(V::add(V::add(V::add(sum, d0), d1), d2), d3);
+                }
             }
-            for (; i < e; ++i) sum = V::add(sum, entry_grad(i, wv, true));
+            for (; i < e; ++i) {
+                if constexpr (IsCompensated<U>::value) kahan(entry_grad(i, wv, true));
+                else sum = V::add(sum, entry_grad(i, wv, true));
+            }
         }
         if (nt > 0) {                                      // payload mode: entries carry no slot; row_base is ascending
             f = 0;
@@ -1361,6 +1394,28 @@ extern "C" int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F
     upd.rows = true;
     return sparse_sorted_update(name, upd, F, 1, nullptr, 0, 0, grad, (int64_t)1, 0, n, row_base, total_rows, workspace, workspace_bytes, stream,
                                 payload, nullptr, nullptr, sorted_from);
+}
+
+// dir_sparse_ftrl_rows_sorted_payload_f32 with units = U first-order terms per row (ShardedTables.attach_linear([rows, U])): rows[f] is
+// [local rows, 4 U] = U blocks [w | n | z | -], grad is [n, U] in payload order.  Driven through sparse_sorted_update with K = U and
+// grad_ld = U; FtrlUpd's `col` selects the unit's block; the run sums are compensated (FtrlUnitsUpd).  sorted_from works as in the units = 1 form: the pair arrays of a sorted
+// workspace sit at offsets that depend on n only -- not on K -- so the Adagrad step's sort of the same payload at width G * K is
+// reusable here, and the row order (hence every sum) is the one a sort of its own would give.
+extern "C" int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows, int F, int units, const int64_t* payload, int64_t n,
+                                                             const float* grad, float lr, float l1, float l2, const int64_t* row_base,
+                                                             int64_t total_rows, void* workspace, int64_t workspace_bytes,
+                                                             const void* sorted_from, dir_stream_t stream) {
+    const char* name = "dir_sparse_ftrl_rows_units_sorted_payload_f32";
+    DIR_CHECK_ARG(F > 0 && n >= 0, "%s: F=%d n=%lld", name, F, (long long)n);
+    DIR_CHECK_ARG(units >= 1 && units <= 8, "%s: units=%d (1 <= units <= 8)", name, units);
+    DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
+    DIR_CHECK_ARG(rows && (payload || n == 0), "%s: null pointer", name);
+    FtrlUnitsUpd upd;                                      // (compensated run sums: see the struct)
+    static_cast<FtrlUpd&>(upd) = FtrlUpd{rows, rows, rows, lr, l1, l2, (int64_t)4 * units};
+    upd.rows = true;
+    upd.units = units;
+    return sparse_sorted_update(name, upd, F, units, nullptr, 0, 0, grad, (int64_t)units, 0, n, row_base, total_rows, workspace, workspace_bytes,
+                                stream, payload, nullptr, nullptr, sorted_from);
 }
 
 // ---- tf.train.AdamOptimizer on the embedding tables ------------------------------------------------------------------------------

@@ -818,6 +818,89 @@ __global__ __launch_bounds__(256) void gather_packed_k(const float* const* __res
     }
 }
 
+// ---- row groups: G rows of K floats stored side by side per (slot, local row) (ShardedTables(groups=G): ESMM's [ctr row | cvr row]) ----
+// The received buffer holds rows of W = G*K floats; bucket, both exchanges and the owner gather above are width-generic.  What is new
+// is the requester's finish pass, which un-permutes through inv AND de-interleaves: group g's K floats of position inv[b, f] go to
+// outs[g][b, f*K : (f+1)*K], the [B, F*K] layout a tower expects -- every received row is read ONCE, 16 bytes per lane (two gather
+// passes over strided views of the buffer would fetch each 128-byte row twice) -- and its transpose for the training backward.
+// One lane per 16-byte chunk of a row; consecutive lanes take consecutive chunks, so a row's W/4 lanes read it whole and the K/4 lanes
+// of a group write one contiguous piece of that group's output.  FG_EPT chunks per lane: their positions are loaded first, then the row
+// chunks (independent loads in flight), then the stores.
+constexpr int DIR_MAX_GROUPS = 16;
+constexpr int FG_EPT = 4;
+struct GroupPtrs { float* p[DIR_MAX_GROUPS]; };
+struct GroupCPtrs { const float* p[DIR_MAX_GROUPS]; };
+
+// chunk q of the [B*F, W/4] chunk grid -> the entry's inverse position (or -1), its group's row offset in outs / grads, its offset in a W row
+struct GroupChunk { int64_t pos, row_off; int g, wc; };
+__device__ __forceinline__ GroupChunk group_chunk(uint32_t q, uint32_t kv, uint32_t kvg, int F, int K, const int64_t* __restrict__ inv,
+                                                  int64_t sb, int64_t sf, int64_t ld) {
+    const uint32_t e = q / kv, c = q - e * kv;                 // entry (b, f), chunk of its W-float row
+    const uint32_t b = e / (uint32_t)F, f = e - b * (uint32_t)F;
+    const uint32_t g = c / kvg, cc = c - g * kvg;              // group, chunk inside the group's K floats
+    GroupChunk r;
+    r.pos = inv[(int64_t)b * sb + (int64_t)f * sf];
+    r.row_off = (int64_t)b * ld + (int64_t)f * K + cc * 4;
+    r.g = (int)g;
+    r.wc = (int)c * 4;
+    return r;
+}
+
+__global__ __launch_bounds__(256) void finish_groups_k(const float* __restrict__ back, int64_t n_back, int W, int K, int F,
+                                                       const int64_t* __restrict__ inv, int64_t sb, int64_t sf, uint32_t total /* B*F*W/4 */,
+                                                       GroupPtrs outs, int64_t out_ld) {
+    const uint32_t kv = (uint32_t)W / 4, kvg = (uint32_t)K / 4;
+    const uint32_t per_grid = gridDim.x * 256u * FG_EPT;
+    for (uint32_t q0 = blockIdx.x * 256u * FG_EPT; q0 < total; q0 += per_grid) {
+        GroupChunk ch[FG_EPT];
+        float4 v[FG_EPT];
+#pragma unroll
+        for (int u = 0; u < FG_EPT; ++u) {
+            const uint32_t q = q0 + u * 256u + threadIdx.x;
+            ch[u].pos = -1;
+            ch[u].g = -1;
+            if (q < total) ch[u] = group_chunk(q, kv, kvg, F, K, inv, sb, sf, out_ld);
+        }
+#pragma unroll
+        for (int u = 0; u < FG_EPT; ++u) {
+            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);                // pruned (inv < 0): a zero row in every group
+            if ((uint64_t)ch[u].pos < (uint64_t)n_back) v[u] = *reinterpret_cast<const float4*>(back + ch[u].pos * W + ch[u].wc);
+        }
+#pragma unroll
+        for (int u = 0; u < FG_EPT; ++u)
+            if (ch[u].g >= 0) *reinterpret_cast<float4*>(outs.p[ch[u].g] + ch[u].row_off) = v[u];
+    }
+}
+
+// the transpose: entry (b, f) writes its G gradient pieces, interleaved, to row inv[b, f] of `send` (zero-filled by the C entry; training
+// lookups are never de-duplicated: one writer per position, plain stores; pruned entries write nothing)
+__global__ __launch_bounds__(256) void grad_groups_k(GroupCPtrs grads, int64_t g_ld, int W, int K, int F, const int64_t* __restrict__ inv,
+                                                     int64_t sb, int64_t sf, uint32_t total, float* __restrict__ send, int64_t n_send) {
+    const uint32_t kv = (uint32_t)W / 4, kvg = (uint32_t)K / 4;
+    const uint32_t per_grid = gridDim.x * 256u * FG_EPT;
+    for (uint32_t q0 = blockIdx.x * 256u * FG_EPT; q0 < total; q0 += per_grid) {
+        GroupChunk ch[FG_EPT];
+        float4 v[FG_EPT];
+#pragma unroll
+        for (int u = 0; u < FG_EPT; ++u) {
+            const uint32_t q = q0 + u * 256u + threadIdx.x;
+            ch[u].pos = -1;
+            ch[u].g = -1;
+            if (q < total) ch[u] = group_chunk(q, kv, kvg, F, K, inv, sb, sf, g_ld);
+        }
+#pragma unroll
+        for (int u = 0; u < FG_EPT; ++u) {
+            const bool live = ch[u].g >= 0 && (uint64_t)ch[u].pos < (uint64_t)n_send;
+            v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!live) ch[u].g = -1;
+            else v[u] = *reinterpret_cast<const float4*>(grads.p[ch[u].g] + ch[u].row_off);
+        }
+#pragma unroll
+        for (int u = 0; u < FG_EPT; ++u)
+            if (ch[u].g >= 0) *reinterpret_cast<float4*>(send + ch[u].pos * W + ch[u].wc) = v[u];
+    }
+}
+
 }  // namespace dir
 
 using namespace dir;
@@ -1053,5 +1136,61 @@ extern "C" int dir_gather_packed_f32(const float* const* tables, int F, int K, c
     else if (nt) hipLaunchKernelGGL((gather_packed_k<1, true>), grid, dim3(256), 0, st, tables, K, lps, F, payload, n, out);
     else hipLaunchKernelGGL((gather_packed_k<1, false>), grid, dim3(256), 0, st, tables, K, lps, F, payload, n, out);
     DIR_CHECK_LAUNCH("gather_packed");
+    return DIR_OK;
+}
+
+// ---- row groups (ShardedTables(groups=G)): the requester's finish pass and its transpose ----
+// the shape checks the two entries share: -> DIR_OK and total = B * F * (G*K / 4) chunks, or the failure code
+static int check_groups_shape(const char* name, int G, int K, int F, int64_t B, int64_t ld, const char* ld_name, int64_t* total) {
+    DIR_CHECK_ARG(F > 0 && B >= 0, "%s: F=%d B=%lld", name, F, (long long)B);
+    DIR_CHECK_ARG(G > 0 && G <= DIR_MAX_GROUPS, "%s: G=%d (1 <= G <= %d)", name, G, DIR_MAX_GROUPS);
+    DIR_CHECK_ARG(K > 0 && K % 4 == 0, "%s: K=%d (K %% 4 == 0: 16-byte pieces)", name, K);
+    DIR_CHECK_ARG(ld >= (int64_t)F * K && ld % 4 == 0, "%s: %s=%lld (>= F*K, a multiple of 4)", name, ld_name, (long long)ld);
+    *total = B * F * ((int64_t)G * K / 4);
+    DIR_CHECK_ARG(*total < ((int64_t)1 << 31), "%s: B=%lld (B*F*G*K/4 < 2^31)", name, (long long)B);
+    return DIR_OK;
+}
+
+extern "C" int dir_shard_finish_groups_f32(const float* back, int64_t n_back, int G, int K, const int64_t* inv, int64_t stride_b,
+                                           int64_t stride_f, int F, int64_t B, float* const* outs, int64_t out_ld, dir_stream_t stream) {
+    const char* name = "dir_shard_finish_groups_f32";
+    int64_t total;
+    if (int rc = check_groups_shape(name, G, K, F, B, out_ld, "out_ld", &total)) return rc;
+    DIR_CHECK_ARG(n_back >= 0 && n_back < ((int64_t)1 << 31), "%s: n_back=%lld (0 <= n_back < 2^31)", name, (long long)n_back);
+    if (B == 0) return DIR_OK;
+    DIR_CHECK_ARG(inv && outs && (back || n_back == 0), "%s: null pointer", name);
+    GroupPtrs o;
+    for (int g = 0; g < DIR_MAX_GROUPS; ++g) {
+        o.p[g] = g < G ? outs[g] : nullptr;                        // outs: a HOST array of G device pointers
+        DIR_CHECK_ARG(g >= G || (o.p[g] && aligned16(o.p[g])), "%s: outs[%d]: null pointer or not 16-byte aligned", name, g);
+    }
+    DIR_CHECK_ARG(aligned16(back), "%s: back must be 16-byte aligned", name);
+    hipLaunchKernelGGL(finish_groups_k, dim3(grid_for((total + 256 * FG_EPT - 1) / (256 * FG_EPT))), dim3(256), 0, as_stream(stream), back,
+                       n_back, G * K, K, F, inv, stride_b, stride_f, (uint32_t)total, o, out_ld);
+    DIR_CHECK_LAUNCH(name);
+    return DIR_OK;
+}
+
+extern "C" int dir_shard_grad_groups_f32(const float* const* grads, int64_t g_ld, int G, int K, const int64_t* inv, int64_t stride_b,
+                                         int64_t stride_f, int F, int64_t B, float* send, int64_t n_send, dir_stream_t stream) {
+    const char* name = "dir_shard_grad_groups_f32";
+    int64_t total;
+    if (int rc = check_groups_shape(name, G, K, F, B, g_ld, "g_ld", &total)) return rc;
+    DIR_CHECK_ARG(n_send >= 0 && n_send < ((int64_t)1 << 31), "%s: n_send=%lld (0 <= n_send < 2^31)", name, (long long)n_send);
+    DIR_CHECK_ARG((send && aligned16(send)) || n_send == 0, "%s: send: null pointer or not 16-byte aligned", name);
+    DIR_CHECK_ARG(B == 0 || (grads && inv), "%s: null pointer", name);
+    GroupCPtrs gp;
+    for (int g = 0; g < DIR_MAX_GROUPS; ++g) {
+        gp.p[g] = (B > 0 && g < G) ? grads[g] : nullptr;          // grads: a HOST array of G device pointers
+        DIR_CHECK_ARG(B == 0 || g >= G || (gp.p[g] && aligned16(gp.p[g])), "%s: grads[%d]: null pointer or not 16-byte aligned", name, g);
+    }
+    hipStream_t st = as_stream(stream);
+    // every position no entry names is zero when the slabs leave (a kernel's fill: a memset node would end a graph capture)
+    if (n_send > 0 && zero_async(send, (size_t)n_send * (size_t)G * K * sizeof(float), st) != hipSuccess)
+        return fail(DIR_E_HIP, "%s: zero-fill of send failed", name);
+    if (B == 0 || n_send == 0) return DIR_OK;
+    hipLaunchKernelGGL(grad_groups_k, dim3(grid_for((total + 256 * FG_EPT - 1) / (256 * FG_EPT))), dim3(256), 0, st, gp, g_ld, G * K, K, F, inv,
+                       stride_b, stride_f, (uint32_t)total, send, n_send);
+    DIR_CHECK_LAUNCH(name);
     return DIR_OK;
 }

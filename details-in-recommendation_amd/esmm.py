@@ -53,6 +53,12 @@ class _BaseModel(nn.Module):
         # the input is a concatenation of embedding rows (ESMM.py:135 over embedding columns); in inference (the fused tower kernel splits its
         # input unscaled) the tables' magnitudes are checked as well
         emb_in = self.input_layer.embedding_only and (torch.is_grad_enabled() or self.input_layer.embedding_range_ok())
+        return self.tower(net, emb_in)
+
+    def tower(self, net, emb_in=False):
+        """The hidden layers and the logit layer on a given input [B, column_num] (what follows the input layer in forward; a caller that
+        looks the rows up elsewhere -- shard.ShardedESMMTrainer over row-sharded tables -- feeds them here).  emb_in: the input is a
+        concatenation of embedding rows whose magnitudes the unscaled fp16 x 2 kernels accept (always so under autograd)."""
         fused = tower_infer(self.hidden, net, self.activation, head=self.logits, embedding_input=emb_in)      # inference: tower + logit layer in one launch
         if fused is not None:
             return fused
@@ -131,6 +137,17 @@ class _BaseModelWD(nn.Module):
         return logits
 
 
+def ctcvr_logits_of(ctr_logits, cvr_logits):
+    """ctcvr_logits = logit(clip(sigmoid(ctr) * sigmoid(cvr), 1e-7, 1 - 1e-7)) (ESMM.py:69-74): one launch in inference on the GPU, the
+    differentiable library ops otherwise."""
+    if (not torch.is_grad_enabled() and ctr_logits.is_cuda and ctr_logits.dtype == torch.float32 and ctr_logits.is_contiguous()
+            and cvr_logits.is_contiguous() and ctr_logits.shape == cvr_logits.shape):
+        return ops.esmm_head(ctr_logits, cvr_logits, _EPSILON)                  # inference: :69-74 in one launch (seven library launches otherwise)
+    ctcvr_logistic = torch.sigmoid(ctr_logits) * torch.sigmoid(cvr_logits)      # :69-71
+    p = ctcvr_logistic.clamp(_EPSILON, 1 - _EPSILON)                             # :73-74
+    return torch.log(p / (1 - p))
+
+
 class ESMM(nn.Module):
     def __init__(self, model_dir=None, columns=None, ctr_weight_column=None, ctcvr_weight_column=None,
                  dnn_hidden_units=None, dnn_dropout=None, config=None, dnn_activation_fn=torch.relu, optimizer=None):
@@ -148,13 +165,7 @@ class ESMM(nn.Module):
         memo = {}                                                                # both towers read the same columns: one id matrix
         ctr_logits = self.ctr_model(features, memo)
         cvr_logits = self.cvr_model(features, memo)
-        if (not torch.is_grad_enabled() and ctr_logits.is_cuda and ctr_logits.dtype == torch.float32 and ctr_logits.is_contiguous()
-                and cvr_logits.is_contiguous() and ctr_logits.shape == cvr_logits.shape):
-            ctcvr_logits = ops.esmm_head(ctr_logits, cvr_logits, _EPSILON)      # inference: :69-74 in one launch (seven library launches otherwise)
-        else:
-            ctcvr_logistic = torch.sigmoid(ctr_logits) * torch.sigmoid(cvr_logits)  # :69-71
-            p = ctcvr_logistic.clamp(_EPSILON, 1 - _EPSILON)                         # :73-74
-            ctcvr_logits = torch.log(p / (1 - p))
+        ctcvr_logits = ctcvr_logits_of(ctr_logits, cvr_logits)
         out = {"ctr_logits": ctr_logits, "ctcvr_logits": ctcvr_logits, "cvr_logits": cvr_logits}
         from ._input import raise_pending
         raise_pending()                                                          # id-range verdicts of both towers' input layers

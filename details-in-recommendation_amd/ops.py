@@ -2511,6 +2511,100 @@ def shard_linear_grad(g, inv2d, send):
     return send
 
 
+def _host_ptrs(tensors):
+    """A HOST array of device pointers (the entries that take a few buffers by value: include/dir_hip.h says which)."""
+    return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def shard_finish_groups(back, inv2d, K, outs):
+    """Requester side of a lookup over row groups (include/dir_hip.h: dir_shard_finish_groups_f32): back [n, G*K] = the received rows,
+    inv2d [B, F] int64 (any strides; < 0: pruned), outs = G preallocated [B, F*K] tensors (unit inner stride, one common row stride) ->
+    outs[g][b, f*K:(f+1)*K] = back[inv2d[b, f], g*K:(g+1)*K]; every received row is read once."""
+    _dev(back, torch.float32, "back")
+    _dev(inv2d, torch.int64, "inv")
+    B, F = inv2d.shape
+    G = len(outs)
+    for o in outs:
+        _dev(o, torch.float32, "out")
+        if o.shape != (B, F * K) or (B and o.stride(1) != 1) or (B > 1 and o.stride(0) != outs[0].stride(0)):
+            raise ValueError("shard_finish_groups: G outputs [B, F*K] with unit inner stride and one row stride")
+    if back.dim() != 2 or back.shape[1] != G * K or not back.is_contiguous():
+        raise ValueError("shard_finish_groups: back must be a contiguous [n, G*K] buffer")
+    ld = outs[0].stride(0) if B > 1 else F * K
+    _lib.check(_lib.load().dir_shard_finish_groups_f32(_ptr(back), back.shape[0], G, K, _ptr(inv2d), inv2d.stride(0), inv2d.stride(1), F, B,
+                                                       _host_ptrs(outs), ld, _stream()))
+    return outs
+
+
+def shard_grad_groups(grads, inv2d, K, send):
+    """Requester side of the backward over row groups (dir_shard_grad_groups_f32): grads = G tensors [B, F*K] (unit inner stride, one row
+    stride) -> send [n, G*K] zero-filled, then row inv2d[b, f] = the entry's G gradient pieces side by side."""
+    _dev(inv2d, torch.int64, "inv")
+    _dev(send, torch.float32, "send")
+    B, F = inv2d.shape
+    G = len(grads)
+    for g in grads:
+        _dev(g, torch.float32, "grad")
+        if g.shape != (B, F * K) or (B and g.stride(1) != 1) or (B > 1 and g.stride(0) != grads[0].stride(0)):
+            raise ValueError("shard_grad_groups: G gradients [B, F*K] with unit inner stride and one row stride")
+    if send.dim() != 2 or send.shape[1] != G * K or not send.is_contiguous():
+        raise ValueError("shard_grad_groups: send must be a contiguous [n, G*K] buffer")
+    ld = grads[0].stride(0) if B > 1 else F * K
+    _lib.check(_lib.load().dir_shard_grad_groups_f32(_host_ptrs(grads), ld, G, K, _ptr(inv2d), inv2d.stride(0), inv2d.stride(1), F, B,
+                                                     _ptr(send), send.shape[0], _stream()))
+    return send
+
+
+def shard_linear_gather_units(lin_ts, recv, P, cap, out):
+    """shard_linear_gather over rows of lin_ts.units first-order terms (dir_shard_linear_gather_units_f32): -> out [P*cap*U] / [n*U],
+    U floats per payload word; every word is written."""
+    _dev(recv, torch.int64, "recv")
+    _dev(out, torch.float32, "out")
+    U = int(getattr(lin_ts, "units", 1))
+    if lin_ts.K != 1 or lin_ts.ld != 4 * U:
+        raise ValueError("shard_linear_gather_units: packed rows of 4 * units floats")
+    n = recv.numel()
+    if not recv.is_contiguous() or not out.is_contiguous() or (cap and n < P * (cap + 1)) or out.numel() < (P * cap if cap else n) * U:
+        raise ValueError("shard_linear_gather_units: recv [P*(cap+1)] slabs (or a flat payload), out `units` contiguous floats per payload word")
+    _lib.check(_lib.load().dir_shard_linear_gather_units_f32(_ptr(lin_ts._ptrs), U, _ptr(lin_ts.vocab_dev), lin_ts.F, _ptr(recv), P,
+                                                             cap or 0, 0 if cap else n, _ptr(out), _stream()))
+    return out
+
+
+def shard_linear_finish_units(wback, inv2d, U, bias=None, out=None):
+    """Requester side (dir_shard_linear_finish_units_f32): wback [n*U], inv2d [B, F] -> out [B, U], column u = sum_f wback[inv2d[b, f]*U + u]
+    + bias[u] in ops.linear_logit's order and arithmetic."""
+    _dev(wback, torch.float32, "wback")
+    _dev(inv2d, torch.int64, "inv")
+    B, F = inv2d.shape
+    if out is None:
+        out = torch.empty((B, U), dtype=torch.float32, device=wback.device)
+    _dev(out, torch.float32, "out")
+    if bias is not None:
+        _dev(bias, torch.float32, "bias")
+        if bias.numel() != U or not bias.is_contiguous():
+            raise ValueError("shard_linear_finish_units: bias [units], contiguous")
+    if not wback.is_contiguous() or wback.numel() % U or out.shape != (B, U) or (B and out.stride(1) != 1):
+        raise ValueError("shard_linear_finish_units: wback contiguous [n*units], out [B, units]")
+    _lib.check(_lib.load().dir_shard_linear_finish_units_f32(_ptr(wback), wback.numel() // U, U, _ptr(inv2d), inv2d.stride(0), inv2d.stride(1),
+                                                             F, _ptr(bias), B, _ptr(out), out.stride(0) if B > 1 else U, _stream()))
+    return out
+
+
+def shard_linear_grad_units(g, inv2d, U, send):
+    """Requester side of the backward (dir_shard_linear_grad_units_f32): g [B, U] -> send [n*U] zero-filled, then
+    send[inv2d[b, f]*U + u] = g[b, u]."""
+    _dev(g, torch.float32, "g")
+    _dev(inv2d, torch.int64, "inv")
+    _dev(send, torch.float32, "send")
+    B, F = inv2d.shape
+    if g.shape != (B, U) or (B and g.stride(1) != 1) or not send.is_contiguous() or send.numel() % U:
+        raise ValueError("shard_linear_grad_units: g [B, units] with unit inner stride, send a contiguous [n*units] buffer")
+    _lib.check(_lib.load().dir_shard_linear_grad_units_f32(_ptr(g), g.stride(0) if B > 1 else U, U, _ptr(inv2d), inv2d.stride(0),
+                                                           inv2d.stride(1), F, B, _ptr(send), send.numel() // U, _stream()))
+    return send
+
+
 def _lin_combiner(combiner):
     if isinstance(combiner, (list, tuple)) or combiner not in _COMBINERS:
         raise ValueError("the linear combiner is ONE of sum / mean / sqrtn (the model's linear_sparse_combiner), got %r" % (combiner,))
@@ -3273,6 +3367,31 @@ class SparseFtrl:
                                                                _ptr(self.row_base), self.total_rows, ws, need, src, _stream()))
         ts.written(*self.accums, *self.linears)
 
+
+    def step_payload_units(self, payload, grad, sorted_by=None):
+        """step_payload over rows of ts.units first-order terms (include/dir_hip.h: dir_sparse_ftrl_rows_units_sorted_payload_f32): grad
+        [n, units] in payload order; sorted_by as in step_payload -- the co-located embedding rows may be of any width."""
+        ts = self.ts
+        U = int(getattr(ts, "units", 1))
+        if not self.packed or ts.ld != 4 * U:
+            raise ValueError("step_payload_units: packed rows of 4 * units floats")
+        _dev(payload, torch.int64, "payload")
+        _dev(grad, torch.float32, "grad")
+        n = payload.numel()
+        if grad.numel() != n * U or not grad.is_contiguous() or not payload.is_contiguous():
+            raise ValueError("grad must be a contiguous [n, units] tensor matching the payload")
+        if n == 0 or self.total_rows == 0:
+            return
+        lib = _lib.load()
+        ws, need = _sorted_ws(self, lib, n, 1, U, self.total_rows, ts.device)
+        src = None
+        if sorted_by is not None:
+            if sorted_by.total_rows != self.total_rows or list(sorted_by.ts.vocab) != list(ts.vocab) or sorted_by._ws is None:
+                raise ValueError("step_payload_units: sorted_by must have just sorted the same payload over the same local vocabularies")
+            src = ctypes.c_void_p(sorted_by._ws.data_ptr() + (-sorted_by._ws.data_ptr()) % 256)
+        _lib.check(lib.dir_sparse_ftrl_rows_units_sorted_payload_f32(_ptr(ts._ptrs), ts.F, U, _ptr(payload), n, _ptr(grad), self.lr, self.l1,
+                                                                     self.l2, _ptr(self.row_base), self.total_rows, ws, need, src, _stream()))
+        ts.written(*self.accums, *self.linears)
 
     def step_bags(self, recv, P, cap_e, cap_b, grad, sorted_by=None):
         """Owner side of the first-order term's backward over sharded bags (shard.ShardedTables.lookup_bags_train(with_linear=True);

@@ -28,6 +28,12 @@ Over multi-hot bags (lookup_bags(want_lin=True), lookup_bags_train(with_linear=T
 the first-order weights of each run beside the embedding rows, one float per partial-row position travels back behind the partial rows,
 and the requester applies the model's one linear_sparse_combiner.
 
+Row groups (ShardedTables(groups=G)) store the G rows that sub-models keep for one id side by side -- the wide & deep ESMM's ctr_model and
+cvr_model look up the same (slot, row) pairs (ESMM_wide_deep.py:213-217) -- so one id exchange, one owner gather and one owner-side sort
+serve all of them; the finish pass de-interleaves into G outputs, the backward interleaves the G gradients again.  attach_linear([rows, U])
+is the same for the first-order term: U weights behind one payload word.  ShardedESMMTrainer trains ESMM / ESMM_W_D on them (DESIGN.md
+section 5.2).
+
 The collectives are torch.distributed.all_to_all_single (backend "nccl" = RCCL on ROCm; "gloo" in the CPU tests).
 world_size == 1 skips the collectives (unless force_collective) but still runs the three HIP steps.  The HIP steps sit
 behind a small backend object so that the CPU (gloo) tests can stand the oracle in for them; the default backend is the
@@ -44,6 +50,9 @@ from . import ops
 
 _HOST_STAGED = os.environ.get("DIR_SHARD_HOST_STAGED") == "1"
 MIN_SLICE_SIZE = 64 << 20     # deepFM.py:167
+MAX_GROUPS = 16               # include/dir_hip.h: dir_shard_finish_groups_f32
+MAX_ROW_FLOATS = 256          # the widest row the sorted Adagrad covers (64 lanes x 16 bytes)
+MAX_UNITS = 8                 # include/dir_hip.h: dir_shard_linear_gather_units_f32
 
 
 def div_range(vocab, P, rank):
@@ -195,6 +204,16 @@ class HipBackend:
             return ops.gather_fm(ts, inv2d, out=out, fm=fm)
         return ops.embedding_bag(ts, inv2d, out=out), None
 
+    # ---- row groups (ShardedTables(groups=G), G > 1): the finish pass that de-interleaves, and its transpose --------
+    def finish_groups(self, back, inv2d, K, outs):
+        """Requester: back [n, G*K], inv2d [Bc, F] -> outs[g][b, f*K:(f+1)*K] = group g's piece of row inv2d[b, f] (zeros where < 0);
+        every received row is read once."""
+        ops.shard_finish_groups(back, inv2d, K, outs)
+
+    def grad_groups(self, grads, inv2d, K, send):
+        """Requester, backward: send [n, G*K] zero-filled, then row inv2d[b, f] = the entry's G gradient pieces side by side."""
+        ops.shard_grad_groups(grads, inv2d, K, send)
+
     # ---- multi-hot bags, pooled on the owner (lookup_bags) ------------------------------------------------
     def new_bags_workspace(self, device):
         return torch.zeros(256, dtype=torch.int32, device=device)      # dir_shard_bags_workspace_bytes: 1024 bytes
@@ -226,10 +245,11 @@ class HipBackend:
     # ---- the first-order (linear) term, co-located with the embedding rows (ShardedTables.attach_linear) -------------
     def attach_linear(self, rows, arena):
         """rows[f]: this rank's packed [local rows, 4] = [w | n | z | -] blocks of one arena (TableSet.ftrl_rows' layout)."""
-        ts = ops.TableSet([r[:, 0:1] for r in rows], ld=4)
+        U = rows[0].shape[1] // 4                       # units > 1: U blocks [w | n | z | -] per row; the views below are unit 0's
+        ts = ops.TableSet([r[:, 0:1] for r in rows], ld=4 * U)
         ts.accums = [r[:, 1:2] for r in rows]
         ts.linears = [r[:, 2:3] for r in rows]
-        ts.arena, ts.rows = arena, rows
+        ts.arena, ts.rows, ts.units = arena, rows, U
         self.lin_ts, self._ftrl = ts, None
 
     def linear_gather(self, recv, cap, out):
@@ -258,6 +278,23 @@ class HipBackend:
     def ftrl_dense(self, w, accum, linear, grad, lr, l1, l2):
         """FTRL step of a replicated dense variable (the linear bias) with its summed gradient."""
         ops.ftrl_dense_(w, accum, linear, grad, lr, l1, l2)
+
+    # ---- ... with units = U > 1 terms per row (attach_linear([rows, U])): U floats per payload word -------------------
+    def linear_gather_units(self, recv, cap, out):
+        """Owner: out[i*U + u] = unit u's weight of payload word i (slab or flat form); every word of out is written."""
+        ops.shard_linear_gather_units(self.lin_ts, recv, self.P, cap, out)
+
+    def linear_finish_units(self, wback, inv2d, U, bias, out):
+        """Requester: out [Bc, U], column u = sum_f wback[inv2d[b, f]*U + u] + bias[u], ops.linear_logit's sum bit for bit."""
+        ops.shard_linear_finish_units(wback, inv2d, U, bias, out)
+
+    def linear_grad_units(self, g, inv2d, U, send):
+        """Requester, backward: send zero-filled, then send[inv2d[b, f]*U + u] = g[b, u]."""
+        ops.shard_linear_grad_units(g, inv2d, U, send)
+
+    def apply_ftrl_units(self, payload, grad, lr, l1, l2, sorted_by=None):
+        """Owner, backward: apply_ftrl over rows of U units; grad [n, U] in payload order."""
+        self._ftrl_opt(lr, l1, l2).step_payload_units(payload, grad, sorted_by=sorted_by)
 
     # ---- ... over multi-hot bags: it rides on the bag lookup (lookup_bags(want_lin=True), lookup_bags_train(with_linear=True)) ------
     def bags_linear_pool(self, recv, cap_e, cap_b, out):
@@ -313,7 +350,7 @@ class _Plan:
     the ranks (equal-split exchanges); everything sized by the batch is local."""
 
     def __init__(self, st, B, cap, train=False):
-        dev, P, F, K = st.device, st.P, st.F, st.K
+        dev, P, F, K = st.device, st.P, st.F, st.KW     # (KW: the stored row, G * K floats with row groups)
         self.B, self.cap = B, cap
         self.train = train            # the training pipeline's plan: its verdicts move _cap_train, not _cap (_learn)
         self.P, self.device, self.lrows = P, dev, None
@@ -338,11 +375,11 @@ class _Plan:
         self.host = torch.empty(2, dtype=torch.int64, pin_memory=dev.type == "cuda")
         self.fin = None                                   # events behind the last enqueued lookup's final kernels (one per side stream)
 
-    def lin_buffers(self):
-        """The linear term's buffers, made at the first lookup that wants it: one float per slab slot and micro-batch, sent (lrows) and
-        received (lback); [C, P*cap] each, so that the backward hands all micro-batches to the owner's update as one array in payload order."""
-        if self.lrows is None:
-            n = self.P * self.cap
+    def lin_buffers(self, U=1):
+        """The linear term's buffers, made at the first lookup that wants it: U floats (units) per slab slot and micro-batch, sent (lrows)
+        and received (lback); [C, P*cap*U] each, so that the backward hands all micro-batches to the owner's update as one array in payload order."""
+        if self.lrows is None or self.lrows_all.shape[1] != self.P * self.cap * U:
+            n = self.P * self.cap * U
             self.lrows_all = torch.zeros((self.C, n), dtype=torch.float32, device=self.device)
             self.lback_all = self.lrows_all if self.recv_all is self.send_all else torch.zeros_like(self.lrows_all)
             self.lrows = [self.lrows_all[c] for c in range(self.C)]
@@ -453,13 +490,17 @@ class ShardedTables:
       "never" (graph capture; call check_overflow() yourself);
     dedup: send each (slot, row) once per owner, chunk and 2048/4096-sample tile (csrc/ids.hip: bucket_cap_dedup_k);
     side_cus: confine the lookup's side streams to that many compute units each (for lookups prefetched under MFMA-bound compute).
+    groups: G rows of K floats stored side by side for every (slot, local row) -- local_tables[f] is [local rows, G*K], the wide & deep
+      ESMM's [ctr row | cvr row] (from_full_groups; DESIGN.md section 5.2).  One id exchange and one owner gather serve every group;
+      lookup / lookup_async / lookup_train return a TUPLE of G tensors [B_local, F*K] where they return one tensor at G = 1.  One-hot
+      lookups only: want_fm, lookup_consume, lookup_rows and the bag forms raise NotImplementedError.  K % 4 == 0, G <= 16, G*K <= 256.
 
     Ranks may look up DIFFERENT local batch sizes (an uneven last batch): the only quantity the equal-split exchanges need to agree
     on is the slab capacity, which is agreed once (first lookup: one host MAX) and afterwards changes only on statistics every rank
     reads identically off the slab headers.  Every rank must call lookup the same number of times (SPMD)."""
 
     def __init__(self, local_tables, vocab, group=None, backend=None, force_collective=False, partitions=None, chunks=2,
-                 slack=None, mode="auto", check="eager", dedup=False, max_batch=None, side_cus=None):
+                 slack=None, mode="auto", check="eager", dedup=False, max_batch=None, side_cus=None, groups=1):
         self.group = group
         self.force_collective = force_collective  # issue the all_to_all calls even when world_size == 1
         self.P = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -467,7 +508,18 @@ class ShardedTables:
         self.vocab = [int(v) for v in vocab]
         self.F = len(self.vocab)
         self.local_tables = list(local_tables)
-        self.K = self.local_tables[0].shape[1]
+        self.G = int(groups)
+        self.KW = int(self.local_tables[0].shape[1])     # floats of a stored row: G * K
+        if self.G < 1 or self.KW % self.G:
+            raise ValueError("groups=%d: the tables' rows of %d floats must hold `groups` rows of one width" % (self.G, self.KW))
+        self.K = self.KW // self.G
+        if self.G > 1:
+            if self.K % 4:
+                raise ValueError("groups=%d: K=%d must be a multiple of 4 (the grouped finish pass moves 16-byte pieces)" % (self.G, self.K))
+            if self.G > MAX_GROUPS or self.KW > MAX_ROW_FLOATS:
+                raise ValueError("groups=%d x K=%d: at most %d groups and rows of %d floats (what the owner gather and the sorted Adagrad "
+                                 "cover)" % (self.G, self.K, MAX_GROUPS, MAX_ROW_FLOATS))
+        self.U = 1                    # attach_linear: first-order terms (units) per row
         P = self.P
         self.parts, self.first, self.slices = partition_layout(self.vocab, self.K, P, self.rank, partitions)   # slices: this rank's [start, end)
         for f, (t, (s, e)) in enumerate(zip(self.local_tables, self.slices)):
@@ -518,6 +570,42 @@ class ShardedTables:
         _, _, slices = partition_layout(vocab, full_tables[0].shape[1], P, rank, kw.get("partitions"))
         return cls([t[s:e].contiguous() for t, (s, e) in zip(full_tables, slices)], vocab, group=group, **kw)
 
+    @classmethod
+    def from_full_groups(cls, full_tables_per_group, group=None, **kw):
+        """from_full for row groups: full_tables_per_group[g][f] is group g's replicated table [vocab_f, K] (for ESMM: [ctr_model's tables,
+        cvr_model's]); this rank's slices of the G tables of a slot are stored side by side, [local rows, G*K]."""
+        per = [list(t) for t in full_tables_per_group]
+        G, t0 = len(per), per[0]
+        for g, tg in enumerate(per):
+            if len(tg) != len(t0) or any(a.shape != b.shape for a, b in zip(tg, t0)):
+                raise ValueError("from_full_groups: group %d's tables must have group 0's shapes" % g)
+        P = dist.get_world_size(group) if dist.is_initialized() else 1
+        rank = dist.get_rank(group) if dist.is_initialized() else 0
+        vocab = [t.shape[0] for t in t0]
+        _, _, slices = partition_layout(vocab, t0[0].shape[1], P, rank, kw.get("partitions"))
+        local = [torch.cat([tg[f][s:e] for tg in per], dim=1).contiguous() for f, (s, e) in enumerate(slices)]
+        return cls(local, vocab, group=group, groups=G, **kw)
+
+    def group_tables(self, g):
+        """Group g's rows of this rank's shard: one [local rows, K] strided VIEW of local_tables[f] per slot."""
+        if not 0 <= g < self.G:
+            raise ValueError("group %d of %d" % (g, self.G))
+        return [t[:, g * self.K:(g + 1) * self.K] for t in self.local_tables]
+
+    def group_accums(self, g):
+        """Group g's Adagrad accumulators (enable_training first): [local rows, K] views, like group_tables."""
+        if self.optimizer is None:
+            raise RuntimeError("call enable_training(lr) first")
+        if not 0 <= g < self.G:
+            raise ValueError("group %d of %d" % (g, self.G))
+        accs = self.optimizer.accums if hasattr(self.optimizer, "accums") else self.backend.accums(self.optimizer)
+        return [a[:, g * self.K:(g + 1) * self.K] for a in accs]
+
+    def _no_groups(self, what):
+        if self.G > 1:
+            raise NotImplementedError("%s is not available on grouped tables (groups=%d): row groups cover the one-hot lookup, lookup_async and "
+                                      "lookup_train only" % (what, self.G))
+
     # ---- the first-order (linear) term: slot f's weights live beside slot f's embedding rows ---------------------------
     def attach_linear(self, local_weights, initial_accumulator_value=0.1):
         """Give the shards DeepFM's first-order weights (the reference creates them under the same partitioner as the embedding tables:
@@ -529,42 +617,56 @@ class ShardedTables:
         if len(local_weights) != self.F:
             raise ValueError("attach_linear: one weight vector per table (F=%d), got %d" % (self.F, len(local_weights)))
         n_rows = [int(t.shape[0]) for t in self.local_tables]
+        U = int(local_weights[0].shape[1]) if local_weights[0].dim() == 2 else 1
+        if not 1 <= U <= MAX_UNITS:
+            raise ValueError("attach_linear: units = %d (1 <= units <= %d)" % (U, MAX_UNITS))
         for f, w in enumerate(local_weights):
-            if w.numel() != n_rows[f] or w.dim() > 2:
-                raise ValueError("attach_linear: slot %d: rank %d holds %d rows, got weights of shape %s (units = 1)"
-                                 % (f, self.rank, n_rows[f], tuple(w.shape)))
-        arena = torch.zeros(sum(n_rows) * 4 + 4, dtype=torch.float32, device=self.device)
+            if w.numel() != n_rows[f] * U or w.dim() > 2 or (w.dim() == 2 and w.shape[1] != U):
+                raise ValueError("attach_linear: slot %d: rank %d holds %d rows, got weights of shape %s (units = %d)"
+                                 % (f, self.rank, n_rows[f], tuple(w.shape), U))
+        # units = U: U blocks [w | n | z | -] per row, side by side (16 U bytes; U = 1: TableSet.ftrl_rows' layout)
+        arena = torch.zeros(sum(n_rows) * 4 * U + 4, dtype=torch.float32, device=self.device)
         off = (-(arena.data_ptr() // 4)) % 4               # rows 16-byte aligned
         rows = []
         for w, v in zip(local_weights, n_rows):
-            blk = arena[off:off + v * 4].view(v, 4)
-            blk[:, 0] = w.detach().reshape(-1).to(device=self.device, dtype=torch.float32)
-            blk[:, 1] = float(initial_accumulator_value)
+            blk = arena[off:off + v * 4 * U].view(v, 4 * U)
+            blk[:, 0::4] = w.detach().reshape(v, U).to(device=self.device, dtype=torch.float32)
+            blk[:, 1::4] = float(initial_accumulator_value)
             rows.append(blk)
-            off += v * 4
-        self.lin_rows, self._lin_arena = rows, arena
+            off += v * 4 * U
+        self.lin_rows, self._lin_arena, self.U = rows, arena, U
+        if U > 1 and not hasattr(self.backend, "linear_gather_units"):
+            raise NotImplementedError("attach_linear: this backend has no first-order term with units > 1 (linear_gather_units / "
+                                      "_finish_units / _grad_units, apply_ftrl_units)")
         attach = getattr(self.backend, "attach_linear", None)
         if attach is not None:
             attach(rows, arena)
         return self
 
     def attach_linear_from_full(self, full_weights, initial_accumulator_value=0.1):
-        """attach_linear from replicated full weight vectors ([vocab_f] or [vocab_f, 1]), sliced as from_full slices the tables."""
-        return self.attach_linear([w.reshape(-1)[s:e] for w, (s, e) in zip(full_weights, self.slices)], initial_accumulator_value)
+        """attach_linear from replicated full weights ([vocab_f], [vocab_f, 1] or, units = U, [vocab_f, U]), sliced as from_full slices
+        the tables."""
+        return self.attach_linear([(w if w.dim() == 2 and w.shape[1] > 1 else w.reshape(-1))[s:e] for w, (s, e) in zip(full_weights, self.slices)],
+                                  initial_accumulator_value)
 
     def _need_linear(self, what):
         if self.lin_rows is None:
             raise RuntimeError("%s: the tables have no first-order weights (call attach_linear first)" % what)
 
+    def _units1(self, what):
+        if self.U > 1:
+            raise NotImplementedError("%s: the first-order term over bags carries units = 1 only (the rows hold %d)" % (what, self.U))
+
     def linear_weights(self):
-        """This rank's first-order weights, one [local rows] VIEW of the packed rows per slot."""
+        """This rank's first-order weights, one [local rows] VIEW of the packed rows per slot ([local rows, U] with units = U > 1)."""
         self._need_linear("linear_weights")
-        return [r[:, 0] for r in self.lin_rows]
+        return [r[:, 0] if self.U == 1 else r[:, 0::4] for r in self.lin_rows]
 
     def linear_state(self):
-        """(w, n, z): per slot the [local rows] views of the weights and of their FTRL accumulator and linear slots."""
+        """(w, n, z): per slot the [local rows] views ([local rows, U] with units = U > 1) of the weights and of their FTRL accumulator
+        and linear slots."""
         self._need_linear("linear_state")
-        return tuple([r[:, c] for r in self.lin_rows] for c in range(3))
+        return tuple([r[:, c] if self.U == 1 else r[:, c::4] for r in self.lin_rows] for c in range(3))
 
     def enable_linear_training(self, lr, l1=0.0, l2=0.0):
         """Attach the owner-side FTRL-Proximal of the first-order rows (the reference's linear_optimizer='Ftrl', deepFM.py:58, applied by
@@ -617,6 +719,36 @@ class ShardedTables:
             t = td.cpu()
         return [int(v) for v in t]
 
+    # ---- the steps that have a grouped / units form: today's backend call at G = 1 / U = 1, the new one otherwise ----------
+    def _new_out(self, B, device):
+        """The result buffer(s) of a lookup: [B, F*K], or a tuple of G of them over row groups."""
+        if self.G == 1:
+            return torch.empty((B, self.F * self.K), dtype=torch.float32, device=device)
+        return tuple(torch.empty((B, self.F * self.K), dtype=torch.float32, device=device) for _ in range(self.G))
+
+    def _finish_groups(self, back, inv2d, out, s=None, e=None):
+        """Row groups: the finish pass of samples [s, e) (None: all) from `back` through inv2d into the G outputs.  -> (out, None)"""
+        self.backend.finish_groups(back, inv2d, self.K, list(out) if s is None else [o[s:e] for o in out])
+        return out, None
+
+    def _lin_gather(self, recv, cap, out):
+        be = self.backend
+        return be.linear_gather(recv, cap, out) if self.U == 1 else be.linear_gather_units(recv, cap, out)
+
+    def _lin_finish(self, wback, inv2d, bias, out):
+        be = self.backend
+        return be.linear_finish(wback, inv2d, bias, out) if self.U == 1 else be.linear_finish_units(wback, inv2d, self.U, bias, out)
+
+    def _lin_grad(self, g, inv2d, send):
+        be = self.backend
+        return be.linear_grad(g, inv2d, send) if self.U == 1 else be.linear_grad_units(g, inv2d, self.U, send)
+
+    def _lin_ftrl(self, payload, grad, sorted_by):
+        be, hp = self.backend, self._lin_hp
+        if self.U == 1:
+            return be.apply_ftrl(payload, grad, hp[0], hp[1], hp[2], sorted_by=sorted_by)
+        return be.apply_ftrl_units(payload, grad, hp[0], hp[1], hp[2], sorted_by=sorted_by)
+
     # ---- training: the gradient rows travel the forward's row exchange backwards and the OWNER updates its shard -------
     def enable_training(self, lr, initial_accumulator_value=0.1):
         """Attach the owner-side sparse Adagrad (the reference's dnn_optimizer='Adagrad', deepFM.py:61, applied by the
@@ -642,7 +774,12 @@ class ShardedTables:
             if self._lin_hp is None:
                 raise RuntimeError("call enable_linear_training(lr) first")
         anchor = torch.zeros((), dtype=torch.float32, device=ids.device, requires_grad=True)
-        return _ShardedLookup.apply(self, ids, bool(with_linear), anchor)
+        res = _ShardedLookup.apply(self, ids, bool(with_linear), anchor)
+        if self.G == 1:
+            return res
+        # row groups: a tuple of G embedding matrices (one autograd node: their gradients go back interleaved in ONE row exchange and
+        # the owner takes ONE Adagrad step at width G*K), or (that tuple, lin [B_local, U])
+        return (tuple(res[:self.G]), res[self.G]) if with_linear else tuple(res)
 
     def _forward_train(self, ids, with_lin):
         """The forward of a training lookup -> (emb, what the backward needs, lin [B, 1] | None).  On the fixed-capacity pipeline (never
@@ -650,9 +787,9 @@ class ShardedTables:
         overflows.  The overflow verdict is read here (the one host wait of a training lookup; it covers work that is long done when
         the dense part of the model has been enqueued in between); the exact path keeps a row buffer of its own."""
         B, F = ids.shape
-        lin = (torch.empty((B, 1), dtype=torch.float32, device=ids.device), None) if with_lin else None
+        lin = (torch.empty((B, self.U), dtype=torch.float32, device=ids.device), None) if with_lin else None
         if not (self._use_exact or B == 0 and not self._collective()):
-            out = torch.empty((B, F * self.K), dtype=torch.float32, device=ids.device)
+            out = self._new_out(B, ids.device)
             plan = self._plan(B, "train")
             done = self._enqueue(plan, ids, False, out, None, dedup=False, lin=lin)
             _Lookup(self, plan, ids, False, out, None, done).join()
@@ -664,51 +801,62 @@ class ShardedTables:
                 return out, ("fixed", plan), lin[0] if with_lin else None
             self.stats["fallbacks"] += 1
         back, inv, sc, rc, recv = self._exchange_exact(ids, lin, private=True)
-        emb, _ = self.backend.finish(back, inv, B, F, False)
+        if self.G == 1:
+            emb, _ = self.backend.finish(back, inv, B, F, False)
+        else:
+            emb, _ = self._finish_groups(back, inv.view(B, F), self._new_out(B, ids.device))
         return emb, ("exact", inv, sc, rc, recv), lin[0] if with_lin else None
 
     def _linear_exact(self, recv, inv2d, sc, rc, lin):
         """The linear term on the exact path: one weight per received payload word, sent back with the row exchange's splits (one float
         per entry), summed per sample."""
-        be = self.backend
+        U = self.U                                       # floats per entry
         n = inv2d.numel()
-        lw = torch.empty(recv.numel(), dtype=torch.float32, device=recv.device)
-        be.linear_gather(recv, None, lw)
-        lback = torch.empty(n, dtype=torch.float32, device=recv.device)
-        self._a2a(lback, lw, sc, rc)
-        be.linear_finish(lback, inv2d, lin[1], lin[0])
+        lw = torch.empty(recv.numel() * U, dtype=torch.float32, device=recv.device)
+        self._lin_gather(recv, None, lw)
+        lback = torch.empty(n * U, dtype=torch.float32, device=recv.device)
+        self._a2a(lback, lw, sc if U == 1 else [c * U for c in sc], rc if U == 1 else [c * U for c in rc])
+        self._lin_finish(lback, inv2d, lin[1], lin[0])
 
     def _backward_apply(self, saved, g_emb, g_lin=None):
         """g_lin (lookup_train(with_linear=True)): d loss / d lin [B_local, 1].  Its values go where the weights came back from and travel
         the same exchange as the gradient rows; the owner's FTRL runs after its Adagrad, over the same payload, on that step's sort."""
-        K = self.K
+        K, G = self.K, self.G
         be = self.backend
-        hp = self._lin_hp
+        U = self.U
         self._updates += 1
+        if G > 1:                                        # row groups: g_emb = the G gradients; they travel interleaved, G*K floats per position
+            gs = [g.contiguous() for g in g_emb]
+            dev = gs[0].device
         if saved[0] == "fixed":
             plan = saved[1]
             P, cap = self.P, plan.cap
             C = plan.C
-            g2 = g_emb.contiguous()
+            g2 = g_emb.contiguous() if G == 1 else None
             works, grecv_l = [], []
             for c, (s, e) in enumerate(plan.bounds):
                 # entry i's gradient row goes to slab position inv[i] (row P*cap = a dump row for pruned entries); owners receive
                 # the slabs through the forward row exchange reversed (equal splits again)
-                gsend = torch.zeros((P * cap + 1, K), dtype=torch.float32, device=g2.device)
-                if e > s:
-                    inv = plan.inv[c]
-                    idx = torch.where(inv < 0, torch.full_like(inv, P * cap), inv)
-                    gsend.index_copy_(0, idx, g2[s:e].reshape(-1, K))
-                grecv = torch.empty((P * cap, K), dtype=torch.float32, device=g2.device)
-                if self._collective():
-                    self._a2a(grecv.view(-1), gsend[:P * cap].reshape(-1), None, None)
+                if G > 1:
+                    # ... by the HIP transpose of the grouped finish: zero-fill + one writer per position, no dump row
+                    gsend = torch.empty((P * cap, self.KW), dtype=torch.float32, device=dev)
+                    be.grad_groups([g[s:e] for g in gs], be.inv2d(plan.inv[c], e - s, self.F, False), K, gsend)
                 else:
-                    grecv = gsend[:P * cap]
+                    gsend = torch.zeros((P * cap + 1, K), dtype=torch.float32, device=g2.device)
+                    if e > s:
+                        inv = plan.inv[c]
+                        idx = torch.where(inv < 0, torch.full_like(inv, P * cap), inv)
+                        gsend.index_copy_(0, idx, g2[s:e].reshape(-1, K))
+                    gsend = gsend[:P * cap]
+                grecv = gsend
+                if self._collective():
+                    grecv = torch.empty((P * cap, self.KW), dtype=torch.float32, device=gsend.device)
+                    self._a2a(grecv.view(-1), gsend.reshape(-1), None, None)
                 grecv_l.append(grecv)
                 if g_lin is not None:
                     # the forward's linear buffers carry the gradient back: lrows = what this rank sends, lback = what it receives
-                    lrows, lback = plan.lin_buffers()
-                    be.linear_grad(g_lin[s:e], be.inv2d(plan.inv[c], e - s, self.F, False), lrows[c])
+                    lrows, lback = plan.lin_buffers(U)
+                    self._lin_grad(g_lin[s:e], be.inv2d(plan.inv[c], e - s, self.F, False), lrows[c])
                     if self._collective():
                         self._a2a(lback[c], lrows[c], None, None)
             # ONE update over all micro-batches (duplicates of a row -- from any chunk, any rank -- are summed before the accumulator
@@ -719,22 +867,28 @@ class ShardedTables:
             pay = torch.where(pos.unsqueeze(0) < hdr.unsqueeze(1), slabs[:, 1:], torch.full_like(slabs[:, 1:], -1)).reshape(-1)
             self.backend.apply_adagrad(self.optimizer, pay, grecv_l[0] if C == 1 else torch.cat(grecv_l, dim=0))
             if g_lin is not None:
-                be.apply_ftrl(pay, plan.lback_all.view(-1), hp[0], hp[1], hp[2], sorted_by=self.optimizer)
+                self._lin_ftrl(pay, plan.lback_all.view(-1), self.optimizer)
             return
         _, inv, sc, rc, recv = saved
         n = inv.numel()
-        g = g_emb.contiguous().view(n, K)
-        gsend = torch.empty_like(g)
-        gsend[inv] = g                                   # entry e's row sits at position inv[e] of the exchange order
-        grecv = torch.empty((recv.numel(), K), dtype=torch.float32, device=g.device)
-        self._a2a(grecv.view(-1), gsend.view(-1), [c * K for c in rc], [c * K for c in sc])   # the forward exchange, reversed
+        KW = self.KW
+        if G == 1:
+            g = g_emb.contiguous().view(n, K)
+            gsend = torch.empty_like(g)
+            gsend[inv] = g                               # entry e's row sits at position inv[e] of the exchange order
+        else:
+            gsend = torch.empty((n, KW), dtype=torch.float32, device=dev)
+            be.grad_groups(gs, inv.view(-1, self.F), K, gsend)
+        dev = gsend.device
+        grecv = torch.empty((recv.numel(), KW), dtype=torch.float32, device=dev)
+        self._a2a(grecv.view(-1), gsend.view(-1), [c * KW for c in rc], [c * KW for c in sc])   # the forward exchange, reversed
         self.backend.apply_adagrad(self.optimizer, recv, grecv)
         if g_lin is not None:
-            lsend = torch.empty(n, dtype=torch.float32, device=g.device)
-            be.linear_grad(g_lin, inv.view(-1, self.F), lsend)
-            lrecv = torch.empty(recv.numel(), dtype=torch.float32, device=g.device)
-            self._a2a(lrecv, lsend, rc, sc)
-            be.apply_ftrl(recv, lrecv, hp[0], hp[1], hp[2], sorted_by=self.optimizer)
+            lsend = torch.empty(n * U, dtype=torch.float32, device=dev)
+            self._lin_grad(g_lin, inv.view(-1, self.F), lsend)
+            lrecv = torch.empty(recv.numel() * U, dtype=torch.float32, device=dev)
+            self._a2a(lrecv, lsend, rc if U == 1 else [c * U for c in rc], sc if U == 1 else [c * U for c in sc])
+            self._lin_ftrl(recv, lrecv, self.optimizer)
 
     # ---- the exact, variable-size lookup (one host read of the split sizes) --------------------------------
     def _exchange_exact(self, ids, lin=None, private=False):
@@ -743,7 +897,7 @@ class ShardedTables:
         private: a fresh row buffer instead of the backend's cached one (training: an inference lookup between a forward and its backward
         must not touch it)."""
         B, F = ids.shape
-        K, be = self.K, self.backend
+        K, be = self.KW, self.backend
         flat = ids.reshape(-1).contiguous()
         n = flat.numel()
         payload, inv, send_counts, _ = be.bucket(flat)                      # HIP
@@ -766,6 +920,8 @@ class ShardedTables:
         if consumer is not None:                                            # (lookup_consume: the caller's kernel reads the rows where they are)
             consumer(0, B, back, inv.view(B, F))
             return None, None
+        if self.G > 1:
+            return self._finish_groups(back, inv.view(B, F), out if out is not None else self._new_out(B, ids.device))
         return self.backend.finish(back, inv, B, F, want_fm, out=out, fm=fm)    # HIP: un-permute (+ FM)
 
     # ---- the fixed-capacity, pipelined lookup ---------------------------------------------------------------
@@ -830,17 +986,19 @@ class ShardedTables:
         be, P = self.backend, self.P
         C = plan.C
         cap = plan.cap
-        lrows, lback = plan.lin_buffers() if lin is not None else (None, None)
+        lrows, lback = plan.lin_buffers(self.U) if lin is not None else (None, None)
         if not self._collective():
             # one rank, no exchange: the three kernels back to back on the caller's stream
             be.bucket_cap(ids, cap, plan.send[0], plan.inv[0], plan.counts[0], plan.flags[0], plan.ws[0], stat=plan.cstat[0], dedup=dedup)
             be.gather_slabs(plan.recv[0], cap, plan.rows[0])
             if lin is not None:
-                be.linear_gather(plan.recv[0], cap, lrows[0])
+                self._lin_gather(plan.recv[0], cap, lrows[0])
                 if B:
-                    be.linear_finish(lback[0], be.inv2d(plan.inv[0], B, F, dedup), lin[1], lin[0])
+                    self._lin_finish(lback[0], be.inv2d(plan.inv[0], B, F, dedup), lin[1], lin[0])
             if B and consumer is not None:
                 consumer(0, B, plan.back[0], be.inv2d(plan.inv[0], B, F, dedup))
+            elif B and self.G > 1:
+                self._finish_groups(plan.back[0], be.inv2d(plan.inv[0], B, F, dedup), out)
             elif B:
                 be.finish_chunk(plan.back[0], be.inv2d(plan.inv[0], B, F, dedup), want_fm, out, fm if want_fm else None)
             return False
@@ -863,9 +1021,11 @@ class ShardedTables:
             if lin is not None:
                 _wait(wl[c])
                 if e > s:
-                    be.linear_finish(lback[c], be.inv2d(plan.inv[c], e - s, F, dedup), lin[1], lin[0][s:e])
+                    self._lin_finish(lback[c], be.inv2d(plan.inv[c], e - s, F, dedup), lin[1], lin[0][s:e])
             if e > s and consumer is not None:
                 consumer(s, e, plan.back[c], be.inv2d(plan.inv[c], e - s, F, dedup))
+            elif e > s and self.G > 1:
+                self._finish_groups(plan.back[c], be.inv2d(plan.inv[c], e - s, F, dedup), out, s, e)
             elif e > s:
                 be.finish_chunk(plan.back[c], be.inv2d(plan.inv[c], e - s, F, dedup), want_fm, out[s:e], fm[s:e] if want_fm else None)
 
@@ -884,7 +1044,7 @@ class ShardedTables:
                 be.gather_slabs(plan.recv[c], cap, plan.rows[c])
                 wr[c] = self._a2a_equal(plan.back[c], plan.rows[c])
                 if lin is not None:
-                    be.linear_gather(plan.recv[c], cap, lrows[c])
+                    self._lin_gather(plan.recv[c], cap, lrows[c])
                     wl[c] = self._a2a_equal(lback[c], lrows[c])
             if c >= 1:
                 with on(c - 1):
@@ -973,16 +1133,23 @@ class ShardedTables:
         B, F = ids.shape
         if F != self.F:
             raise ValueError("ids must be [B, F=%d]" % self.F)
+        if self.G > 1:                # (before anything is launched)
+            if want_fm:
+                self._no_groups("want_fm (the FM term)")
+            if consumer is not None:
+                self._no_groups("lookup_consume / lookup_rows (a lookup without its finish pass)")
+            if out is not None and (len(out) != self.G or any(o.shape != (B, F * self.K) for o in out)):
+                raise ValueError("out: %d tensors [B, F*K], one per group" % self.G)
         self.stats["lookups"] += 1
         lt = None
         if want_lin:
             self._need_linear("lookup(want_lin=True)")
-            lt = (lin if lin is not None else torch.empty((B, 1), dtype=torch.float32, device=ids.device), lin_bias)
+            lt = (lin if lin is not None else torch.empty((B, self.U), dtype=torch.float32, device=ids.device), lin_bias)
         if self._use_exact or (B == 0 and not self._collective()):
             emb, fmo = self._lookup_exact(ids, want_fm, out=out, fm=fm, consumer=consumer, lin=lt)
             return _Lookup(self, None, ids, want_fm, emb, fmo, None, consumer=consumer, lin=lt)
         if out is None and consumer is None:
-            out = torch.empty((B, F * self.K), dtype=torch.float32, device=ids.device)
+            out = self._new_out(B, ids.device)
         if want_fm and fm is None:
             fm = torch.empty((B, 1), dtype=torch.float32, device=ids.device)
         slot = self._slot
@@ -1016,6 +1183,7 @@ class ShardedTables:
         slowest peer to arrive).  Every rank must call it (the exchanges are collectives).  The results of the last run are returned
         so that the caller can check them."""
         import time
+        self._no_groups("stage_times")
         B, F = ids.shape
         if F != self.F:
             raise ValueError("ids must be [B, F=%d]" % self.F)
@@ -1088,6 +1256,7 @@ class ShardedTables:
         never written or read: the rank-local passes of a lookup are bucket + owner gather only.
         On a slab overflow (check="eager") the lookup is repeated on the exact path and the consumer called again for the whole batch:
         its outputs must be plain overwrites.  Returns after the caller's stream has been made to wait for the consumer's kernels."""
+        self._no_groups("lookup_consume")
         if self.check != "eager":
             raise ValueError("lookup_consume needs check='eager' (the overflow repair calls the consumer again)")
         self.lookup_async(ids, want_fm=False, consumer=consumer).result()
@@ -1101,6 +1270,7 @@ class ShardedTables:
         them as (rows_as_tables(rows, F), inv); ops.cin_stack_gather and ops.tower(gather=) take them directly: the [B, F*K] concatenation
         is never written.  The buffers belong to the lookup's plan slot: valid until the lookup after the next one is enqueued (two slots).
         Needs check='eager' (an overflow is repaired on the exact path before the rows are handed out: then ONE entry for the whole batch)."""
+        self._no_groups("lookup_rows")
         if self.check != "eager":
             raise ValueError("lookup_rows needs check='eager' (an overflow is repaired before the rows are handed out)")
         chunks = []      # (want_lin: the handle's .lin holds the first-order term [B, 1] (+ lin_bias) after result())
@@ -1191,10 +1361,12 @@ class ShardedTables:
         the per-slot `combiner` -- and sums the sample's F bags in slot order.  With one owner per bag and flags = 0 the result is
         ops.linear_logit's bit for bit.  The term sees the lookup's live entries: under PRUNE_NONPOSITIVE_WEIGHTS the pruned entries
         contribute to neither term.  An overflow repeat carries it; without want_lin nothing here changes."""
+        self._no_groups("lookup_bags")
         B = self._bag_args(values, offsets, weights, "lookup_bags")
         lin = None
         if want_lin:
             self._need_linear("lookup_bags(want_lin=True)")
+            self._units1("lookup_bags(want_lin=True)")
             lin = (_lin_combiner(lin_combiner), lin_bias)
 
         def res(out, fm, lo):
@@ -1288,11 +1460,13 @@ class ShardedTables:
         floats, and every owner applies Adagrad to its embedding rows, then FTRL (enable_linear_training) to its first-order rows over
         the same bag records on the Adagrad step's sort: entry e contributes w_e * c_bag * d lin[b], all contributions to a row summed
         before n, z and w move -- one optimiser step."""
+        self._no_groups("lookup_bags_train")
         if self.optimizer is None:
             raise RuntimeError("call enable_training(lr) first")
         lin_comb = None
         if with_linear:
             self._need_linear("lookup_bags_train(with_linear=True)")
+            self._units1("lookup_bags_train(with_linear=True)")
             if self._lin_hp is None:
                 raise RuntimeError("call enable_linear_training(lr) first")
             lin_comb = _lin_combiner(lin_combiner)
@@ -1391,11 +1565,19 @@ class _ShardedLookup(torch.autograd.Function):
     def forward(ctx, st, ids, with_lin, anchor):
         emb, ctx.saved, lin = st._forward_train(ids, with_lin)
         ctx.st = st
+        if st.G > 1:                                     # row groups: G embedding matrices (+ lin) from the one node
+            return tuple(emb) + ((lin,) if with_lin else ())
         return (emb, lin) if with_lin else emb
 
     @staticmethod
-    def backward(ctx, g, g_lin=None):
-        ctx.st._backward_apply(ctx.saved, g, None if g_lin is None else g_lin.contiguous())
+    def backward(ctx, g, *more):
+        st = ctx.st
+        if st.G > 1:
+            gs, g_lin = (g,) + more[:st.G - 1], (more[st.G - 1] if len(more) >= st.G else None)
+            st._backward_apply(ctx.saved, gs, None if g_lin is None else g_lin.contiguous())
+            return None, None, None, None
+        g_lin = more[0] if more else None
+        st._backward_apply(ctx.saved, g, None if g_lin is None else g_lin.contiguous())
         return None, None, None, None
 
 
@@ -1643,3 +1825,161 @@ class ShardedDeepFMTrainer:
             emb, fm, lin = self.tables.lookup_bags(values, offsets, weights, want_lin=True, lin_combiner=m.linear_sparse_combiner,
                                                    lin_bias=m.linear_bias.data.reshape(-1)[:1], **kw)
             return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(self.tables.absmax())) + lin
+
+
+def _esmm_parts(model):
+    """(ctr tower, cvr tower, ctr linear model | None, cvr linear model | None) of an esmm.ESMM / esmm.ESMM_W_D whose columns the row-sharded
+    trainer covers; ValueError naming the column otherwise.  Table f of the sharded tables is the f-th embedding column in the input
+    layer's (name-sorted) order."""
+    from ._input import categorical_of
+    from .feature_column import EmbeddingColumn, HashedCategoricalColumn, IdentityCategoricalColumn
+    subs = (model.ctr_model, model.cvr_model)
+    wd = hasattr(subs[0], "dnn")                       # esmm._BaseModelWD: dnn tower + linear model
+    towers = tuple(s.dnn if wd else s for s in subs)
+    linears = tuple(s.linear if wd else None for s in subs)
+    if any(t is None for t in towers):
+        raise ValueError("ShardedESMMTrainer: both sub-models need a dnn tower (dnn_feature_columns)")
+    il = towers[0].input_layer
+    dim = None
+    for c in il.columns:
+        cat = categorical_of(c)
+        if not isinstance(c, EmbeddingColumn) or not isinstance(cat, (IdentityCategoricalColumn, HashedCategoricalColumn)):
+            raise ValueError("ShardedESMMTrainer: column %r: one-hot embedding columns over identity / hashed categorical columns only" % c.name)
+        if getattr(c, "max_norm", None):
+            raise ValueError("ShardedESMMTrainer: column %r: max_norm is not carried by the sharded one-hot lookup" % c.name)
+        dim = c.dimension if dim is None else dim
+        if c.dimension != dim:
+            raise ValueError("ShardedESMMTrainer: column %r: dimension %d, the other columns have %d (one common dimension)" % (c.name, c.dimension, dim))
+    for lm in linears:
+        if lm is None:
+            continue
+        cats = [categorical_of(c) for c in il.emb_cols]
+        for i, c in enumerate(lm.columns):
+            if i >= len(cats) or categorical_of(c) is not cats[i]:
+                raise ValueError("ShardedESMMTrainer: linear column %r (position %d): the linear columns must be the dnn columns' categorical "
+                                 "columns in the input layer's order (%s)" % (getattr(c, "name", c), i, [getattr(x, "name", x) for x in cats]))
+        if len(lm.columns) != len(cats):
+            raise ValueError("ShardedESMMTrainer: %d linear columns for %d dnn columns (linear-only columns are not covered): missing %r"
+                             % (len(lm.columns), len(cats), getattr(cats[len(lm.columns)], "name", cats[len(lm.columns)])))
+    return towers + linears
+
+
+class ShardedESMMTrainer:
+    """One synchronous multi-GPU training step of an esmm.ESMM / esmm.ESMM_W_D over row-sharded tables: the reference shards the wide &
+    deep ESMM's variables with the same partitioner as DeepFM's (ESMM_wide_deep.py:213-217, 258-261).  ctr_model and cvr_model look up
+    the same (slot, row) pairs, so their two embedding rows of an id live side by side on its owner (ShardedTables(groups=2)) and ONE id
+    exchange, owner gather, row exchange and finish pass -- and ONE owner-side sort and Adagrad step -- serve both; ESMM_W_D's two linear
+    models are a 2-unit first-order term riding on the same exchange (attach_linear([rows, 2]), owner-side FTRL on the Adagrad step's
+    sort).  The towers are replicated; their gradients are summed with bucketed all-reduces.
+    The loss is _get_loss's (ESMM.py:150-175): each task's cross entropy MEAN-reduced with its weight column.  The two weight sums (the
+    sample counts without weight columns) are all-reduced once per step and every rank back-propagates sum_local(w * ce) / W_global, so the
+    gradients that ADD over the ranks -- at the owners and in allreduce_grads -- are the global-batch mean loss's.
+    linear = dict(lr=, l1=, l2=) for ESMM_W_D: the two linear biases are replicated and take dense FTRL steps on their all-reduced
+    gradients here, so they must not be among dense_optimizer's parameters.  `model`'s own embedding tables and linear weights are not
+    used (tables_from_model copies them into the shards)."""
+
+    def __init__(self, model, tables, lr_sparse, dense_optimizer, group=None, linear=None, initial_accumulator_value=0.1):
+        self.model, self.tables, self.group = model, tables, group
+        self.ctr, self.cvr, self.ctr_lin, self.cvr_lin = _esmm_parts(model)
+        il = self.ctr.input_layer
+        if tables.G != 2 or tables.F != len(il.emb_cols) or tables.K != il.emb_cols[0].dimension:
+            raise ValueError("ShardedESMMTrainer: the tables must hold 2 row groups of F=%d slots of K=%d floats (tables_from_model), got G=%d F=%d K=%d"
+                             % (len(il.emb_cols), il.emb_cols[0].dimension, tables.G, tables.F, tables.K))
+        self.dense_params = [p for n, p in model.named_parameters() if not ("embedding_weights" in n or ".linear.weights" in n)]
+        self.dense_optimizer = dense_optimizer
+        tables.enable_training(lr_sparse, initial_accumulator_value)
+        self.linear = None
+        if linear is not None:
+            if self.ctr_lin is None:
+                raise ValueError("ShardedESMMTrainer(linear=...): the model has no linear models (esmm.ESMM_W_D with linear_feature_columns)")
+            if tables.lin_rows is None or tables.U != 2:
+                raise ValueError("ShardedESMMTrainer(linear=...): the tables need the 2-unit first-order rows (tables_from_model / attach_linear([rows, 2]))")
+            self.biases = [self.ctr_lin.bias, self.cvr_lin.bias]
+            if any(p is b for grp in dense_optimizer.param_groups for p in grp["params"] for b in self.biases):
+                raise ValueError("ShardedESMMTrainer(linear=...): the linear biases take the FTRL step here; leave them out of dense_optimizer")
+            hp = (float(linear["lr"]), float(linear.get("l1", 0.0)), float(linear.get("l2", 0.0)))
+            tables.enable_linear_training(*hp)
+            self.linear = hp
+            # the biases' FTRL slots ([TF-upstream] FtrlOptimizer: accumulator 0.1, linear 0)
+            self.bias_accum = [torch.full_like(b.data, float(linear.get("initial_accumulator_value", 0.1))) for b in self.biases]
+            self.bias_linear = [torch.zeros_like(b.data) for b in self.biases]
+        elif self.ctr_lin is not None:
+            raise ValueError("ShardedESMMTrainer: the model has linear models: pass linear=dict(lr=, l1=, l2=)")
+
+    @classmethod
+    def tables_from_model(cls, model, group=None, linear_initial_accumulator_value=0.1, **kw):
+        """The grouped ShardedTables of `model` (every rank holds the same replicated model): slot f = the f-th embedding column in the
+        input layer's order, group 0 = ctr_model's table, group 1 = cvr_model's; for ESMM_W_D also the 2-unit first-order rows, unit 0 =
+        ctr_model's linear weights, unit 1 = cvr_model's.  kw: ShardedTables' options (partitions=, chunks=, mode=, ...)."""
+        ctr, cvr, ctr_lin, cvr_lin = _esmm_parts(model)
+        per = [[p.data for p in ops.plain_list(t.input_layer.embedding_weights)] for t in (ctr, cvr)]
+        tables = ShardedTables.from_full_groups(per, group=group, **kw)
+        if ctr_lin is not None:
+            full_w = [torch.stack([a.data.reshape(-1), b.data.reshape(-1)], dim=1) for a, b in zip(ctr_lin.weights, cvr_lin.weights)]
+            tables.attach_linear_from_full(full_w, linear_initial_accumulator_value)
+        return tables
+
+    def _global_sums(self, sums):
+        """The per-task weight sums over ALL ranks (one all-reduce of two numbers, no host read)."""
+        if not dist.is_initialized() or dist.get_world_size(self.group) == 1:
+            return sums
+        t = sums.cpu() if _host_staged(sums, self.group) else sums.clone()
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t.to(sums.device)
+
+    def step(self, ids, labels, ctr_weights=None, ctcvr_weights=None):
+        """ids [B_local, F] global row ids (the input layer's column order); labels {'click_label', 'convert_label'} ([B_local, 1] each) or
+        a [B_local, 2] tensor in that order; ctr_weights / ctcvr_weights [B_local, 1]: the two weight columns, or None (weight 1).
+        -> this rank's (ctr_loss, ctcvr_loss) contributions to the global-batch mean losses (detached; they ADD over the ranks)."""
+        from .esmm import ctcvr_logits_of
+        from .train_spec import weighted_sigmoid_cross_entropy
+        B = ids.shape[0]
+        if isinstance(labels, dict):
+            click, convert = labels["click_label"], labels["convert_label"]
+        else:
+            click, convert = labels[:, 0:1], labels[:, 1:2]
+        self.dense_optimizer.zero_grad(set_to_none=True)
+        if self.linear is not None:
+            for b in self.biases:
+                b.grad = None
+            (emb_ctr, emb_cvr), lin = self.tables.lookup_train(ids, with_linear=True)      # every owner's rows update inside backward()
+        else:
+            emb_ctr, emb_cvr = self.tables.lookup_train(ids)
+        ctr_logits, cvr_logits = self.ctr.tower(emb_ctr, True), self.cvr.tower(emb_cvr, True)
+        if self.linear is not None:                                                        # dnn_logits + linear_logits, ESMM_wide_deep.py:265-270
+            ctr_logits = ctr_logits + (lin[:, 0:1] + self.biases[0])
+            cvr_logits = cvr_logits + (lin[:, 1:2] + self.biases[1])
+        ctcvr_logits = ctcvr_logits_of(ctr_logits, cvr_logits)
+        ctr_sum, _ = weighted_sigmoid_cross_entropy(ctr_logits, click.reshape(B, 1), ctr_weights, "sum")
+        ctcvr_sum, _ = weighted_sigmoid_cross_entropy(ctcvr_logits, convert.reshape(B, 1), ctcvr_weights, "sum")
+        dev = ctr_logits.device
+        local = torch.stack([w.to(device=dev, dtype=torch.float32).sum() if w is not None else torch.tensor(float(B), device=dev)
+                             for w in (ctr_weights, ctcvr_weights)])
+        den = self._global_sums(local)
+        parts = torch.where(den > 0, torch.stack([ctr_sum, ctcvr_sum]) / den.clamp_min(1e-30), torch.zeros_like(den))
+        parts.sum().backward()
+        allreduce_grads(self.dense_params, self.group)
+        self.dense_optimizer.step()
+        if self.linear is not None:                        # FTRL is not linear in the gradient: the all-reduce came first
+            with torch.no_grad():
+                for b, n, z in zip(self.biases, self.bias_accum, self.bias_linear):
+                    self.tables.backend.ftrl_dense(b.data, n, z, b.grad.contiguous(), *self.linear)
+        out = parts.detach()
+        return out[0], out[1]
+
+    @torch.no_grad()
+    def predict(self, ids):
+        """-> {'ctr_logits', 'cvr_logits', 'ctcvr_logits'} [B_local, 1] each: the grouped inference lookup (the first-order term and the
+        two biases riding along for ESMM_W_D), the sub-models' own tower routing with the SHARDED tables' magnitude, ops.esmm_head."""
+        from .esmm import ctcvr_logits_of
+        with _eval_mode(self.model):
+            ok = ops.f16_range_ok(self.tables.absmax())
+            if self.linear is not None:
+                bias = torch.cat([b.data.reshape(-1)[:1] for b in self.biases])
+                (emb_ctr, emb_cvr), lin = self.tables.lookup(ids, want_lin=True, lin_bias=bias)
+            else:
+                emb_ctr, emb_cvr = self.tables.lookup(ids)
+            ctr_logits, cvr_logits = self.ctr.tower(emb_ctr, ok), self.cvr.tower(emb_cvr, ok)
+            if self.linear is not None:
+                ctr_logits, cvr_logits = ctr_logits + lin[:, 0:1], cvr_logits + lin[:, 1:2]
+            return {"ctr_logits": ctr_logits, "cvr_logits": cvr_logits, "ctcvr_logits": ctcvr_logits_of(ctr_logits, cvr_logits)}

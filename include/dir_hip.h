@@ -572,6 +572,50 @@ int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F, const int
                                             float l2, const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
                                             const void* sorted_from, dir_stream_t stream);
 
+/* The same term with units = U first-order weights per row (ShardedTables.attach_linear([rows, U]); reference: the two linear models of
+ * the wide & deep ESMM over the same categorical columns, ESMM_wide_deep.py:247-262).  rows[slot] is [local rows, 4 * units] floats,
+ * 16-byte aligned: unit u's packed block [w | n | z | -] at float 4 u of a row.  One payload word serves all units; units floats per
+ * slab slot travel back (1 <= units <= 8).  units = 1 computes what the four entries above compute.
+ * dir_shard_linear_gather_units_f32 (owner): out[i * units + u] = unit u's weight of payload word i, in the slab (cap > 0, P <= 64,
+ *   P * cap * units < 2^31) and flat (cap == 0, n words, n * units < 2^31) forms of dir_shard_linear_gather_f32.  One lane reads a row's
+ *   units weights together.  EVERY output word is written: 0.0f behind a header, for p < 0 and for a row >= local_rows[slot].
+ * dir_shard_linear_finish_units_f32 (requester): out[b * out_ld + u] = sum_f wback[inv[b, f] * units + u] + bias[u] (bias: units floats
+ *   or NULL), per unit in the order and arithmetic of dir_shard_linear_finish_f32: column u is dir_linear_onehot_rows_f32's sum over unit
+ *   u's unsharded weights bit for bit.  out_ld >= units.
+ * dir_shard_linear_grad_units_f32 (requester, the transpose): send [n_send * units] is zero-filled by a kernel, then
+ *   send[inv[b, f] * units + u] = g[b * g_ld + u] for every entry with 0 <= inv < n_send (one writer per position).
+ * dir_sparse_ftrl_rows_units_sorted_payload_f32 (owner): dir_sparse_ftrl_rows_sorted_payload_f32 over the units-wide rows; grad is
+ *   [n, units] in payload order and every (row, unit) takes one FTRL-Proximal step with its summed gradient (the run sums inside a
+ *   sort tile of 256 entries are Kahan-compensated, so a hot row's hundreds of entries cost an ulp per tile whatever their order; the
+ *   partial sums of a run that crosses tiles are then added plainly).  Workspace:
+ *   dir_sparse_adagrad_sorted_workspace_bytes(n, 1, units, total_rows) device bytes, 256-byte aligned.  sorted_from (or NULL): the
+ *   workspace of a sorted update of the SAME payload (n, row_base, total_rows) that ran just before on this stream, of ANY row width --
+ *   the pair arrays' offsets depend on n only, so the Adagrad step over rows of G * K floats serves. */
+int dir_shard_linear_gather_units_f32(const float* const* rows, int units, const int64_t* local_rows, int F, const int64_t* recv, int P,
+                                      int64_t cap, int64_t n, float* out, dir_stream_t stream);
+int dir_shard_linear_finish_units_f32(const float* wback, int64_t n_back, int units, const int64_t* inv, int64_t stride_b, int64_t stride_f,
+                                      int F, const float* bias, int64_t B, float* out, int64_t out_ld, dir_stream_t stream);
+int dir_shard_linear_grad_units_f32(const float* g, int64_t g_ld, int units, const int64_t* inv, int64_t stride_b, int64_t stride_f, int F,
+                                    int64_t B, float* send, int64_t n_send, dir_stream_t stream);
+int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows, int F, int units, const int64_t* payload, int64_t n, const float* grad,
+                                                  float lr, float l1, float l2, const int64_t* row_base, int64_t total_rows, void* workspace,
+                                                  int64_t workspace_bytes, const void* sorted_from, dir_stream_t stream);
+
+/* Row groups (ShardedTables(groups=G)): every (slot, local row) stores G rows of K floats side by side -- the wide & deep ESMM's
+ * ctr_model and cvr_model rows of one id (ESMM_wide_deep.py:213-217) -- so the buffers of the sharded lookup hold rows of G * K floats and
+ * bucket, both exchanges and dir_gather_slabs_f32 / dir_gather_packed_f32 run on them unchanged (with K = G * K).  K % 4 == 0,
+ * 1 <= G <= 16, B * F * G * K / 4 < 2^31; all row buffers 16-byte aligned.
+ * dir_shard_finish_groups_f32 (requester): un-permute and de-interleave in one pass -- outs[g][b * out_ld + f * K + k] =
+ *   back[inv[b * stride_b + f * stride_f] * G * K + g * K + k]; inv < 0 (or >= n_back) gives zeros in every group.  Every received row
+ *   is read once, 16 bytes per lane.  outs: a HOST array of G device pointers to [B, out_ld] buffers, out_ld >= F * K, out_ld % 4 == 0.
+ * dir_shard_grad_groups_f32 (requester, the transpose; the training backward): send [n_send, G * K] is zero-filled by a kernel, then
+ *   send[inv[b, f]][g * K + k] = grads[g][b * g_ld + f * K + k] for every entry with 0 <= inv < n_send; training lookups are never
+ *   de-duplicated, so every position has one writer and pruned entries need no dump row.  grads: a HOST array of G device pointers. */
+int dir_shard_finish_groups_f32(const float* back, int64_t n_back, int G, int K, const int64_t* inv, int64_t stride_b, int64_t stride_f,
+                                int F, int64_t B, float* const* outs, int64_t out_ld, dir_stream_t stream);
+int dir_shard_grad_groups_f32(const float* const* grads, int64_t g_ld, int G, int K, const int64_t* inv, int64_t stride_b, int64_t stride_f,
+                              int F, int64_t B, float* send, int64_t n_send, dir_stream_t stream);
+
 /* The first-order term over MULTI-HOT bags on row-sharded weights (ShardedTables.lookup_bags(want_lin=) / lookup_bags_train(with_linear=);
  * reference: the linear model's categorical columns with linear_sparse_combiner, deepFM.py:59,89-95,255-275).  It rides on the bag
  * lookup (dir_shard_bags_bucket / _pool / _combine): no second bucket pass, no second entry exchange; one float per partial-row position
