@@ -42,6 +42,10 @@ template <> struct BV<4> {
     static __device__ __forceinline__ T upd(T x0, float xw, T b, T xl) {
         return make_float4(((x0.x * xw) + b.x) + xl.x, ((x0.y * xw) + b.y) + xl.y, ((x0.z * xw) + b.z) + xl.z, ((x0.w * xw) + b.w) + xl.w);
     }
+    using D = double4;                                     // T in double: adagrad_fix_k's sum of a long run's tile partials
+    static __device__ __forceinline__ D widen(T a) { return make_double4((double)a.x, (double)a.y, (double)a.z, (double)a.w); }
+    static __device__ __forceinline__ D addw(D a, T b) { return make_double4(a.x + (double)b.x, a.y + (double)b.y, a.z + (double)b.z, a.w + (double)b.w); }
+    static __device__ __forceinline__ T narrow(D a) { return make_float4((float)a.x, (float)a.y, (float)a.z, (float)a.w); }
 };
 template <> struct BV<1> {
     using T = float;
@@ -54,6 +58,10 @@ template <> struct BV<1> {
     static __device__ __forceinline__ T fma(T a, float s, T c) { return fmaf(a, s, c); }
     static __device__ __forceinline__ float dot(T a, T b, float acc) { return fmaf(a, b, acc); }
     static __device__ __forceinline__ T upd(T x0, float xw, T b, T xl) { return ((x0 * xw) + b) + xl; }
+    using D = double;
+    static __device__ __forceinline__ D widen(T a) { return (double)a; }
+    static __device__ __forceinline__ D addw(D a, T b) { return a + (double)b; }
+    static __device__ __forceinline__ T narrow(D a) { return (float)a; }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -388,7 +396,8 @@ __global__ __launch_bounds__(256) void adagrad_apply_k(float* const* __restrict_
 // order, so every sum has a fixed order), a workgroup reduces the runs of equal rows inside its tile of 256 sorted
 // entries and applies the update for runs that lie inside the tile; a run that crosses tile borders leaves one
 // partial per tile (`carry`) and adagrad_fix_k adds them in tile order.  No atomics, bitwise reproducible, and the
-// longest serial walk is 256 entries whatever the skew.
+// longest serial walk is 256 entries whatever the skew.  Every run sum is compensated (run_sum below): good to an ulp of
+// the sum whatever the order of the entries and however many of them a row collects in one step.
 // ------------------------------------------------------------------------------------------------
 constexpr int ADA_TILE = 256;
 
@@ -581,15 +590,34 @@ struct AdamUpd {
         if (col == 0) mark[row_base[f] + id] = 1;
     }
 };
-// FtrlUpd with COMPENSATED run sums (Kahan): the update of the units = U first-order rows.  The tile pass adds a run's gradients one after
-// the other in fp32; for a row hit by hundreds of entries of one step (a 7-row table under a batch of 1500: ~140 hits) that sum is off by
-// 1-2e-5 absolute in an order-dependent way, and z = z_prev + g can cancel to O(0.1) against summands of O(10) -- z then misses 1e-5 of
-// float64.  With the compensation a tile's run sum is good to an ulp whatever the order (adagrad_fix_k still adds the partial sums of a
-// run that crosses tiles plainly: one rounding per further tile).  Only the new units export uses it: the units = 1
-// exports keep FtrlUpd and their results bit for bit.
-struct FtrlUnitsUpd : FtrlUpd { static constexpr bool kCompensated = true; };
-template <class U, class = void> struct IsCompensated { static constexpr bool value = false; };
-template <class U> struct IsCompensated<U, std::void_t<decltype(U::kCompensated)>> { static constexpr bool value = U::kCompensated; };
+// The gradient sum of one run inside a tile, COMPENSATED (Kahan), for every rule.  A plain sequential fp32 sum of a row hit by hundreds
+// or thousands of entries of one step (the head of a Zipf slot, a 7-row table under any batch) is off by 1e-5 ... 3e-4 absolute in an
+// order-dependent way, and FTRL's z = z_prev + g - sigma * w can cancel to O(0.1) against summands of O(10): z, and w through it, then
+// miss 1e-5 of float64.  With the compensation the sum is good to an ulp whatever the order -- which on the sharded paths is the order
+// the slab's atomics left, different from run to run.  get(i): the gradient chunk of sorted entry i.  A run of ONE entry -- nearly every
+// run under uniform ids over large tables -- is its own sum and pays nothing.  Longer runs keep four entries' loads in flight before
+// their (ordered) adds.  Every loop of adagrad_tile_k sums through here, so two paths over the same sorted entries (packed and split
+// rows, FM folded in or not, own sort or borrowed) agree bit for bit.
+template <int VEC, class Get>
+__device__ __forceinline__ typename BV<VEC>::T run_sum(int s, int e, Get get) {
+    using V = BV<VEC>;
+    using T = typename V::T;
+    T sum = get(s);
+    if (e - s == 1) return sum;
+    T comp = V::zero();                                    // the low-order part the adds so far have lost
+    auto kahan = [&](T x) {
+        const T y = V::sub(x, comp), t = V::add(sum, y);
+        comp = V::sub(V::sub(t, sum), y);
+        sum = t;
+    };
+    int i = s + 1;
+    for (; i + 4 <= e; i += 4) {
+        const T d0 = get(i), d1 = get(i + 1), d2 = get(i + 2), d3 = get(i + 3);
+        kahan(d0); kahan(d1); kahan(d2); kahan(d3);
+    }
+    for (; i < e; ++i) kahan(get(i));
+    return sum;
+}
 
 template <class U, class = void> struct IsNorm { static constexpr bool value = false; };
 template <class U> struct IsNorm<U, std::void_t<decltype(U::kNorm)>> { static constexpr bool value = U::kNorm; };
@@ -796,14 +824,7 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
                 cur = nxt;
                 fetch(r + NG, nxt);
                 if (!cur.live) continue;
-                T sum = V::zero();
-                int i = cur.s;
-                for (; i + 4 <= cur.e; i += 4) {                    // four entries' loads in flight before their (ordered) adds
-                    const T d0 = entry_grad(i, cur.wv, true), d1 = entry_grad(i + 1, cur.wv, true), d2 = entry_grad(i + 2, cur.wv, true),
-                            d3 = entry_grad(i + 3, cur.wv, true);
-                    sum = V::add(V::add(V::add(V::add(sum, d0), d1), d2), d3);
-                }
-                for (; i < cur.e; ++i) sum = V::add(sum, entry_grad(i, cur.wv, true));
+                const T sum = run_sum<VEC>(cur.s, cur.e, [&](int i) { return entry_grad(i, cur.wv, true); });
                 const bool open_l = r == 0 && cont_l, open_r = r == nruns - 1 && cont_r;
                 if (!open_l && !open_r) {
                     T acc = cur.av, wv = cur.wv;
@@ -836,37 +857,14 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
         const int s = rstart[r], e = rstart[r + 1];
         const uint32_t rk = skey[s];
         if (rk >= total_rows || (!BAG && c >= kv)) continue;  // pruned ids / idle lanes of a padded group (BAG: they join bag_apply)
-        T sum = V::zero();
-        [[maybe_unused]] T comp = V::zero();               // IsCompensated: the low-order part the adds so far have lost
-        auto kahan = [&](T x) {
-            const T y = V::sub(x, comp), t = V::add(sum, y);
-            comp = V::sub(V::sub(t, sum), y);
-            sum = t;
-        };
         int f = (int)(sval[s] % (uint32_t)F);
+        T sum;
         if (staged) {
-            for (int i = s; i < e; ++i) {
-                const T x = V::ld(sd + i * (LPS * VEC) + c * VEC);
-                if constexpr (IsCompensated<U>::value) kahan(x);
-                else sum = V::add(sum, x);
-            }
+            sum = run_sum<VEC>(s, e, [&](int i) { return V::ld(sd + i * (LPS * VEC) + c * VEC); });
         } else {
             T wv = V::zero();
             if constexpr (FM) wv = V::ld(upd.tables[f] + ((int64_t)rk - row_base[f]) * upd.ld + c * VEC);
-            int i = s;
-            for (; i + 4 <= e; i += 4) {                    // four entries' loads in flight before their (ordered) adds
-                const T d0 = entry_grad(i, wv, true), d1 = entry_grad(i + 1, wv, true), d2 = entry_grad(i + 2, wv, true),
-                        d3 = entry_grad(i + 3, wv, true);
-                if constexpr (IsCompensated<U>::value) {
-                    kahan(d0); kahan(d1); kahan(d2); kahan(d3);
-                } else {
-                    sum = V::add(V::add(V::add(V::add(sum, d0), d1), d2), d3);
-                }
-            }
-            for (; i < e; ++i) {
-                if constexpr (IsCompensated<U>::value) kahan(entry_grad(i, wv, true));
-                else sum = V::add(sum, entry_grad(i, wv, true));
-            }
+            sum = run_sum<VEC>(s, e, [&](int i) { return entry_grad(i, wv, true); });
         }
         if (nt > 0) {                                      // payload mode: entries carry no slot; row_base is ascending
             f = 0;
@@ -894,7 +892,8 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
 }
 
 // one thread group per tile: if a run STARTS in this tile and continues to the right, add the partials of the tiles it
-// runs through (in tile order) and apply
+// runs through (in tile order) and apply.  The partials -- each good to an ulp (run_sum) -- are added in double and the total is
+// rounded once: a plain fp32 add per further tile would put back, at 80 tiles, the error the tiles' compensation took out.
 template <int LPS, int VEC, class U, bool BAG = false>
 __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
                                                      int64_t n, int64_t ntiles, const uint32_t* __restrict__ keys,
@@ -913,12 +912,13 @@ __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
     const uint32_t kl = keys[e1 - 1];
     if (kl >= total_rows || keys[e1] != kl) return;                   // not open to the right
     if (t > 0 && keys[e0] == kl && keys[e0 - 1] == kl) return;        // the run started in an earlier tile
-    T sum = V::ld(carry + (t * 2 + 1) * K + c * VEC);
+    typename V::D wide = V::widen(V::ld(carry + (t * 2 + 1) * K + c * VEC));
     for (int64_t u = t + 1; u < ntiles; ++u) {
-        sum = V::add(sum, V::ld(carry + (u * 2) * K + c * VEC));
+        wide = V::addw(wide, V::ld(carry + (u * 2) * K + c * VEC));
         const int64_t u1 = (u + 1) * ADA_TILE;
         if (!(u1 < n && keys[u1] == kl)) break;                       // the run ends inside tile u
     }
+    const T sum = V::narrow(wide);
     const uint32_t ent = vals[e1 - 1];
     int f = (int)(ent % (uint32_t)F);
     if (nt > 0) {
@@ -1398,7 +1398,7 @@ extern "C" int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F
 
 // dir_sparse_ftrl_rows_sorted_payload_f32 with units = U first-order terms per row (ShardedTables.attach_linear([rows, U])): rows[f] is
 // [local rows, 4 U] = U blocks [w | n | z | -], grad is [n, U] in payload order.  Driven through sparse_sorted_update with K = U and
-// grad_ld = U; FtrlUpd's `col` selects the unit's block; the run sums are compensated (FtrlUnitsUpd).  sorted_from works as in the units = 1 form: the pair arrays of a sorted
+// grad_ld = U; FtrlUpd's `col` selects the unit's block; sorted_from works as in the units = 1 form: the pair arrays of a sorted
 // workspace sit at offsets that depend on n only -- not on K -- so the Adagrad step's sort of the same payload at width G * K is
 // reusable here, and the row order (hence every sum) is the one a sort of its own would give.
 extern "C" int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows, int F, int units, const int64_t* payload, int64_t n,
@@ -1410,8 +1410,7 @@ extern "C" int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows,
     DIR_CHECK_ARG(units >= 1 && units <= 8, "%s: units=%d (1 <= units <= 8)", name, units);
     DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
     DIR_CHECK_ARG(rows && (payload || n == 0), "%s: null pointer", name);
-    FtrlUnitsUpd upd;                                      // (compensated run sums: see the struct)
-    static_cast<FtrlUpd&>(upd) = FtrlUpd{rows, rows, rows, lr, l1, l2, (int64_t)4 * units};
+    FtrlUpd upd{rows, rows, rows, lr, l1, l2, (int64_t)4 * units};
     upd.rows = true;
     upd.units = units;
     return sparse_sorted_update(name, upd, F, units, nullptr, 0, 0, grad, (int64_t)units, 0, n, row_base, total_rows, workspace, workspace_bytes,

@@ -585,9 +585,8 @@ int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F, const int
  * dir_shard_linear_grad_units_f32 (requester, the transpose): send [n_send * units] is zero-filled by a kernel, then
  *   send[inv[b, f] * units + u] = g[b * g_ld + u] for every entry with 0 <= inv < n_send (one writer per position).
  * dir_sparse_ftrl_rows_units_sorted_payload_f32 (owner): dir_sparse_ftrl_rows_sorted_payload_f32 over the units-wide rows; grad is
- *   [n, units] in payload order and every (row, unit) takes one FTRL-Proximal step with its summed gradient (the run sums inside a
- *   sort tile of 256 entries are Kahan-compensated, so a hot row's hundreds of entries cost an ulp per tile whatever their order; the
- *   partial sums of a run that crosses tiles are then added plainly).  Workspace:
+ *   [n, units] in payload order and every (row, unit) takes one FTRL-Proximal step with its summed gradient (run sums as in every
+ *   sorted update: see dir_sparse_adagrad_sorted_f32).  Workspace:
  *   dir_sparse_adagrad_sorted_workspace_bytes(n, 1, units, total_rows) device bytes, 256-byte aligned.  sorted_from (or NULL): the
  *   workspace of a sorted update of the SAME payload (n, row_base, total_rows) that ran just before on this stream, of ANY row width --
  *   the pair arrays' offsets depend on n only, so the Adagrad step over rows of G * K floats serves. */
@@ -1114,6 +1113,9 @@ int dir_sparse_adagrad_f32(float* const* tables, float* const* accums, int F, in
 /* The same update with the (row, entry) pairs radix-sorted first (stable: duplicates are summed in batch order; no
  * atomics; bitwise reproducible) and the runs of equal rows reduced per tile of 256 sorted entries -- the longest serial
  * walk is 256 entries whatever the skew of the ids (the chain walk above serialises on hot rows).
+ * Run sums -- here and in every sorted update below (FTRL, Adam, the packed-row, payload and bag forms) -- are Kahan-compensated
+ * inside a tile, and the per-tile partial sums of a run that crosses tiles are added in double and rounded once: a row hit by
+ * thousands of entries of one step gets its summed gradient to about an ulp, whatever the order of the entries.
  * row_base: DEVICE int64 [F], slot f's first row in the concatenation of all tables; total_rows = sum of the vocab sizes
  * (< 2^32 - 1).  An id outside [0, vocab_f) (vocab_f from row_base / total_rows) is skipped like a pruned id: the update
  * never writes outside slot f's table.  workspace: dir_sparse_adagrad_sorted_workspace_bytes(B, F, K, total_rows) device bytes, 256-byte aligned. */

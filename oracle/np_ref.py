@@ -442,3 +442,26 @@ def sparse_ftrl_step(tables, accums, linears, ids, grad, lr, l1=0.0, l2=0.0):
         quad = np.sqrt(n_new) / lr + 2 * l2
         w[t] = np.where(np.abs(z_new) > l1, (np.sign(z_new) * l1 - z_new) / quad, 0.0)
         n[t], z[t] = n_new, z_new
+
+
+def sparse_adam_step(tables, ms, vs, ids, grad, lr, b1, b2, eps, clip, t):
+    """float64 restatement of the reference's train_op on IndexedSlices gradients (DeepCrossNetwork.py:264-290 + [TF-upstream]
+    AdamOptimizer._apply_sparse): clip each table's summed gradient by its own norm, decay m / v of every row, step every row.
+    tables / ms / vs: lists of float64 [V,K] arrays updated in place; ids [B,F] (ids outside a table are skipped); grad [B,F*K]; t: the
+    step count, from 1."""
+    F = len(tables)
+    K = tables[0].shape[1]
+    # the hyper-parameters as the fp32 graph sees them ([TF-upstream] the beta / epsilon / lr tensors are cast to the variable's dtype and
+    # 1 - beta is formed in that dtype: fp32(1) - fp32(0.999) is 1.3e-5 away from 0.001); the arithmetic itself in float64
+    lr_t = float(np.float32(lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)))
+    omb1, omb2 = float(np.float32(1) - np.float32(b1)), float(np.float32(1) - np.float32(b2))
+    b1, b2, eps, clip = float(np.float32(b1)), float(np.float32(b2)), float(np.float32(eps)), float(np.float32(clip))
+    for f in range(F):
+        g = np.zeros_like(tables[f])
+        ok = (ids[:, f] >= 0) & (ids[:, f] < tables[f].shape[0])
+        np.add.at(g, ids[ok, f], grad[ok, f * K:(f + 1) * K].astype(np.float64))
+        if clip > 0:
+            g = g * clip / max(np.sqrt((g * g).sum()), clip)
+        ms[f][:] = ms[f] * b1 + g * omb1
+        vs[f][:] = vs[f] * b2 + g * g * omb2
+        tables[f][:] = tables[f] - lr_t * ms[f] / (np.sqrt(vs[f]) + eps)

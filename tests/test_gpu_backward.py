@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 import torch
 
+from oracle.np_ref import sparse_adam_step
+
 pytestmark = pytest.mark.gpu
 
 
@@ -1625,27 +1627,6 @@ def test_din_saved_activations_backward_matches_recompute(built_lib, normalize, 
 
 
 # ---- tf.train.AdamOptimizer on the embedding tables (dir_sparse_adam_f32) ----------------------------------------------------------
-def _adam_ref64(tables, ms, vs, ids, grad, lr, b1, b2, eps, clip, t):
-    """float64 restatement of the reference's train_op on IndexedSlices gradients (DeepCrossNetwork.py:264-290 + [TF-upstream]
-    AdamOptimizer._apply_sparse): clip each table's summed gradient by its own norm, decay m / v of every row, step every row."""
-    F = len(tables)
-    K = tables[0].shape[1]
-    # the hyper-parameters as the fp32 graph sees them ([TF-upstream] the beta / epsilon / lr tensors are cast to the variable's dtype and
-    # 1 - beta is formed in that dtype: fp32(1) - fp32(0.999) is 1.3e-5 away from 0.001); the arithmetic itself in float64
-    lr_t = float(np.float32(lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)))
-    omb1, omb2 = float(np.float32(1) - np.float32(b1)), float(np.float32(1) - np.float32(b2))
-    b1, b2, eps, clip = float(np.float32(b1)), float(np.float32(b2)), float(np.float32(eps)), float(np.float32(clip))
-    for f in range(F):
-        g = np.zeros_like(tables[f])
-        ok = (ids[:, f] >= 0) & (ids[:, f] < tables[f].shape[0])
-        np.add.at(g, ids[ok, f], grad[ok, f * K:(f + 1) * K].astype(np.float64))
-        if clip > 0:
-            g = g * clip / max(np.sqrt((g * g).sum()), clip)
-        ms[f][:] = ms[f] * b1 + g * omb1
-        vs[f][:] = vs[f] * b2 + g * g * omb2
-        tables[f][:] = tables[f] - lr_t * ms[f] / (np.sqrt(vs[f]) + eps)
-
-
 @pytest.mark.parametrize("K,gscale,clip", [(16, 0.01, 100.0), (16, 40.0, 100.0), (8, 0.01, 0.0), (64, 5.0, 100.0)])
 def test_sparse_adam_matches_tf_semantics_over_steps(built_lib, K, gscale, clip):
     """5 steps of dir_sparse_adam_f32 (duplicate and pruned ids, clipping idle / active) against the float64 restatement at 1e-5; every
@@ -1669,7 +1650,7 @@ def test_sparse_adam_matches_tf_semantics_over_steps(built_lib, K, gscale, clip)
             opt.lr_t = lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t)
             opt.step(torch.from_numpy(ids).cuda(), torch.from_numpy(grad).cuda())
             if rep == 0:
-                _adam_ref64(ref_w, ref_m, ref_v, ids, grad, lr, b1, b2, eps, clip, t)
+                sparse_adam_step(ref_w, ref_m, ref_v, ids, grad, lr, b1, b2, eps, clip, t)
         runs.append(([t.cpu().numpy() for t in tabs], [m.cpu().numpy() for m in opt.ms], [v.cpu().numpy() for v in opt.vs]))
     for f in range(F):
         for what, got, ref in (("var", runs[0][0][f], ref_w[f]), ("m", runs[0][1][f], ref_m[f]), ("v", runs[0][2][f], ref_v[f])):

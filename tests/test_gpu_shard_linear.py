@@ -5,7 +5,7 @@ dir_shard_linear_finish_f32, dir_shard_linear_grad_f32, dir_sparse_ftrl_rows_sor
   (a) world size 1, forward: bitwise equal to ops.linear_logit over the unsharded packed rows (F in {1, 3, 26}, B in {0, 1, 37, 4096},
       pruned ids, with and without bias, de-duplicated, exact path);
   (b) world size 1, training against float64 (oracle.np_ref.sparse_ftrl_step): uniform ids, l1 = l2 = 0 and both non-zero; skewed ids (one
-      row hit > 600 times in a batch of 1500, a Zipf(1.3) slot);
+      row hit > 600 times in a batch of 1500, a Zipf(1.3) slot; one row hit 3000 times in a batch of 4096);
   (c) world size 1 against the single-GPU path (ops.SparseFtrl on TableSet.ftrl_rows);
   (d) one node: the linear term does not perturb the Adagrad side, bit for bit;
   (e) a captured lookup(want_fm, want_lin) replays the eager result bitwise after a training step;
@@ -126,31 +126,50 @@ def _skewed(rng, vocab, B, hot_row, dev):
     return torch.from_numpy(a).to(dev)
 
 
-def test_world1_training_skewed_ids_match_float64(built_lib):
-    """One row hit more than 600 times in a batch of 1500 and a Zipf(1.3) slot: its run crosses sort tiles (the carry / fix path).  w within
-    1e-5; n and z within 5e-5 -- the allowance tests/test_gpu_shard_bags_train.py gives Adagrad accumulators of rows summed over
-    thousands of entries, for the same reason (the float32 sum of a long run of gradients)."""
+def _train_against_float64(make_ids, B, seed, min_hits, hot_row, gscale=1.0):
+    """Three steps on ids from make_ids: the worst error of w, n, z, the embedding tables and the Adagrad accumulators against float64."""
     from dir_amd.shard import ShardedTables
     dev = torch.device("cuda", 0)
-    vocab, K, B = [500, 1000, 7], 16, 1500
+    vocab, K = [500, 1000, 7], 16
     F = len(vocab)
-    full, full_w = _draw(vocab, K, 7, dev)
+    full, full_w = _draw(vocab, K, seed, dev)
     ftrl = dict(lr=0.2, l1=0.01, l2=0.02)
     st = ShardedTables.from_full([t.clone() for t in full]).attach_linear_from_full(full_w, ACC0)
     st.enable_training(LR, ACC0).enable_linear_training(**ftrl)
     ref = Reference([t.cpu().numpy() for t in full], [w.cpu().numpy() for w in full_w])
-    rng = np.random.default_rng(29)
+    rng = np.random.default_rng(seed + 22)
     for step in range(3):
-        ids = _skewed(rng, vocab, B, 321, dev)
-        hits = int((ids[:, 1] == 321).sum())
-        assert hits > 600, hits
+        ids = make_ids(rng, vocab, B, dev)
+        hits = int((ids[:, 1] == hot_row).sum())
+        assert hits >= min_hits, hits
         G = torch.from_numpy(rng.standard_normal((B, F * K)).astype(np.float32)).to(dev)
-        g = torch.from_numpy(rng.standard_normal((B, 1)).astype(np.float32)).to(dev)
+        g = torch.from_numpy((rng.standard_normal((B, 1)) * gscale).astype(np.float32)).to(dev)
         _train(st, ids, G, g)
         ref.step(ids.cpu().numpy(), G.cpu().numpy(), g.cpu().numpy(), ftrl)
         ew, en, ez = _state_err(st, ref)
-        print("skewed step %d (%d hits): w %.2e n %.2e z %.2e" % (step, hits, ew, en, ez))
-        assert ew <= 1e-5 and en <= 5e-5 and ez <= 5e-5, (step, ew, en, ez)
+        et = max(_close(st.local_tables[f], ref.T[f]) for f in range(F))
+        ea = max(_close(st.optimizer.accums[f], ref.acc[f]) for f in range(F))
+        print("step %d (%d hits): w %.2e n %.2e z %.2e tables %.2e accumulators %.2e" % (step, hits, ew, en, ez, et, ea))
+        assert max(ew, en, ez, et, ea) <= 1e-5, (step, ew, en, ez, et, ea)
+
+
+def test_world1_training_skewed_ids_match_float64(built_lib):
+    """One row hit more than 600 times in a batch of 1500 and a Zipf(1.3) slot: its run crosses sort tiles (the carry / fix path).  w, n, z,
+    the tables and the accumulators within 1e-5: the sorted update compensates its run sums (csrc/backward.hip: run_sum)."""
+    _train_against_float64(lambda rng, vocab, B, dev: _skewed(rng, vocab, B, 321, dev), 1500, 7, 601, 321)
+
+
+def _hot(rng, vocab, B, dev):
+    a = np.stack([rng.integers(0, v, size=B) for v in vocab], axis=1).astype(np.int64)
+    a[rng.permutation(B)[:3000], 1] = 321
+    return torch.from_numpy(a).to(dev)
+
+
+def test_world1_training_hot_row_matches_float64(built_lib):
+    """One row hit 3000 times in a batch of 4096: a run over twelve sort tiles whose entries arrive in the order the slab's atomics left --
+    not the same from run to run -- so the bar must hold for any order: every state within 1e-5 over three steps.  (d lin is drawn at
+    0.3: the row's summed gradient, sigma ~ 16, stays below 64, where fp32's own rounding of the sum is under 4e-6.)"""
+    _train_against_float64(_hot, 4096, 31, 3000, 321, gscale=0.3)
 
 
 def test_world1_matches_single_gpu_sparse_ftrl(built_lib):
