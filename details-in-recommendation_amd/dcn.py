@@ -134,30 +134,18 @@ class DeepCrossNetwork(nn.Module):
         return deep_logit + _Units1Fn.apply(cross, wl[:, :d], None)
 
     def _padded_cross_params(self):
-        """cross_w / cross_b zero-padded to a multiple of 4 columns, cached until the parameters change.  Under a default graph capture
-        (ops.capture_bypasses_caches) the pad is computed inline and nothing is remembered: the graph pads the parameters as they are at
-        replay time."""
+        """cross_w / cross_b zero-padded to a multiple of 4 columns, cached until the parameters change (ops.MODULE_PARAMS)."""
         pad = ops.pad4(self.column_num) - self.column_num
-        if ops.capture_bypasses_caches(self.cross_w):
-            return torch.nn.functional.pad(self.cross_w.data, (0, pad)), torch.nn.functional.pad(self.cross_b.data, (0, pad))
-        key = (self.cross_w._version, self.cross_b._version, self.cross_w.data_ptr(), ops._CACHE_GEN[0])
-        if getattr(self, "_cross_pad_key", None) != key:
-            self._cross_pad = (torch.nn.functional.pad(self.cross_w.data, (0, pad)), torch.nn.functional.pad(self.cross_b.data, (0, pad)))
-            self._cross_pad_key = key
-        return ops.held(self._cross_pad)
+        return ops.MODULE_PARAMS.get((id(self), "cross_pad"), (self.cross_w, self.cross_b),
+                                     lambda: (torch.nn.functional.pad(self.cross_w.data, (0, pad)), torch.nn.functional.pad(self.cross_b.data, (0, pad))),
+                                     self.cross_w.data_ptr())
 
     def _logit_split_params(self):
-        """The two halves of the final dense(1)'s weight (cross | deep), aligned copies, once per version (inline under a default capture,
-        as _padded_cross_params)."""
+        """The two halves of the final dense(1)'s weight (cross | deep), aligned copies, once per version (as _padded_cross_params)."""
         d, dp = self.column_num, ops.pad4(self.column_num)
         wl = self.logits_layer.weight                                            # [1, d + h]
-        if ops.capture_bypasses_caches(wl):
-            return torch.nn.functional.pad(wl.data[:, :d], (0, dp - d)), wl.data[:, d:].clone()
-        key = (wl._version, wl.data_ptr(), ops._CACHE_GEN[0])
-        if getattr(self, "_logit_split_key", None) != key:
-            self._logit_split = (torch.nn.functional.pad(wl.data[:, :d], (0, dp - d)), wl.data[:, d:].clone())
-            self._logit_split_key = key
-        return ops.held(self._logit_split)
+        return ops.MODULE_PARAMS.get((id(self), "logit_split"), (wl,),
+                                     lambda: (torch.nn.functional.pad(wl.data[:, :d], (0, dp - d)), wl.data[:, d:].clone()), wl.data_ptr())
 
     def _forward_padded(self, features):
         """Inference with an input width that is not a multiple of 4 (429 = 26 x 16 + 13): the input layer writes x0 with row

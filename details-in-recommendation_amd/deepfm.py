@@ -355,7 +355,8 @@ class DeepFM(nn.Module):
     AUTO_PACK_MAX_BYTES = 32 << 30      # the packed copy of tables beyond this size is built on request only (pack_for_serving)
 
     def _pack_signature(self):
-        return tuple((p._version, p.data_ptr()) for p in self.embedding_weights) + tuple((p._version, p.data_ptr()) for p in self.linear_weights)
+        return (tuple((p._version, p.data_ptr()) for p in self.embedding_weights) + tuple((p._version, p.data_ptr()) for p in self.linear_weights)
+                + (ops._CACHE_GEN[0],))                   # ops.invalidate_caches() rebuilds the pack
 
     def _serving_pack(self):
         """The packed serving layout when it applies to this forward (inference, binary head, one-hot columns, the linear columns equal

@@ -24,7 +24,7 @@ _RELUS = (torch.relu, F.relu, torch.nn.functional.relu)
 # (ops.dense_mid_covers): no batch size sends a covered layer to the library any more (DIR_DENSE_MID_ROWS=0 restores round 5's routing).
 import os as _os
 MIN_ROWS = int(_os.environ.get("DIR_DENSE_MIN_ROWS", "6144"))
-_PACK_CACHE = {}
+_PACK_CACHE = ops.VersionCache("packed_weight", 256)
 # How the hidden layers of the models were routed since the last reset: "hip" (dir_dense_* kernels) or "library" (rocBLAS / hipBLASLt
 # through nn.Linear: batches under MIN_ROWS, uncovered activations, < 16 units), keyed by (in, out): bench.py puts it in the line.
 ROUTING = {"hip": {}, "library": {}}
@@ -66,20 +66,11 @@ def _kernel_weight(x, weight):
     return pack_weight(weight)
 
 
-def _packed_cached(weight):
-    """Inference: one padded copy per weight tensor, refreshed when the parameter is modified in place (tensor._version)."""
-    key = id(weight)
-    hit = _PACK_CACHE.get(key)
-    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()      # under capture: pack inside the graph, remember nothing (ops.CapturedStep)
-    if hit is not None and hit[0] is weight and hit[1] == weight._version and hit[2] == weight.data_ptr() and not ops.capture_bypasses_caches(weight):
-        return ops.held(hit[3])
-    packed = pack_weight(weight)
-    if capturing:
-        return packed
-    if len(_PACK_CACHE) > 256:
-        _PACK_CACHE.clear()
-    _PACK_CACHE[key] = (weight, weight._version, weight.data_ptr(), packed)
-    return packed
+def _packed_cached(weight, pad=0):
+    """Inference: one padded copy per weight tensor (with `pad` zero input columns appended first), refreshed when the parameter is
+    modified in place (tensor._version)."""
+    return _PACK_CACHE.get((id(weight), pad), (weight,), lambda: pack_weight(F.pad(weight.detach(), (0, pad)) if pad else weight),
+                           weight.data_ptr())
 
 
 # dense_dw_auto_arith's answers that are HIP kernels (narrow layers -- an 80-wide last tower layer, ESMM.py:130-147 -- went to the library's
@@ -98,22 +89,6 @@ def _tn_matmul(g, x, splits=16, g_bits=None, x_bits=None):
     if M >= 8192 and M % splits == 0 and g.is_contiguous() and x.is_contiguous():
         return torch.bmm(g.view(splits, M // splits, -1).transpose(1, 2), x.view(splits, M // splits, -1)).sum(dim=0)
     return g.t() @ x
-
-
-def _packed_cached_padded(weight, pad):
-    """Inference: the weight with `pad` zero input columns appended, packed; cached like _packed_cached."""
-    key = (id(weight), pad)
-    hit = _PACK_CACHE.get(key)
-    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
-    if hit is not None and hit[0] is weight and hit[1] == weight._version and hit[2] == weight.data_ptr() and not ops.capture_bypasses_caches(weight):
-        return ops.held(hit[3])
-    packed = pack_weight(F.pad(weight.detach(), (0, pad)))
-    if capturing:
-        return packed
-    if len(_PACK_CACHE) > 256:
-        _PACK_CACHE.clear()
-    _PACK_CACHE[key] = (weight, weight._version, weight.data_ptr(), packed)
-    return packed
 
 
 def _wb_grads(g, x, need_w, need_b, g_bits=None, x_bits=None):
@@ -422,28 +397,18 @@ def units1(lin, x):
     return lin(x)
 
 
-_BN_CACHE = {}
+_BN_CACHE = ops.VersionCache("bn_affine", 256)
 
 
 def _bn_affine(bn):
     """Inference batch-norm as one per-column affine (scale, shift), cached until a statistic or parameter changes."""
-    key = id(bn)
-    ver = (bn.moving_mean._version, bn.moving_variance._version, bn.beta._version, bn.gamma._version if bn.gamma is not None else -1,
-           bn.beta.data_ptr())
-    hit = _BN_CACHE.get(key)
-    capturing = bn.moving_mean.is_cuda and torch.cuda.is_current_stream_capturing()
-    if hit is not None and hit[0] is bn and hit[1] == ver and not ops.capture_bypasses_caches(bn.moving_mean):
-        return ops.held(hit[2]), ops.held(hit[3])
-    inv = torch.rsqrt(bn.moving_variance + bn.eps)
-    if bn.gamma is not None:
-        inv = inv * bn.gamma.data
-    shift = bn.beta.data - bn.moving_mean * inv
-    if capturing:
-        return inv.contiguous(), shift.contiguous()
-    if len(_BN_CACHE) > 256:
-        _BN_CACHE.clear()
-    _BN_CACHE[key] = (bn, ver, inv.contiguous(), shift.contiguous())
-    return _BN_CACHE[key][2], _BN_CACHE[key][3]
+    def build():
+        inv = torch.rsqrt(bn.moving_variance + bn.eps)
+        if bn.gamma is not None:
+            inv = inv * bn.gamma.data
+        return inv.contiguous(), (bn.beta.data - bn.moving_mean * inv).contiguous()
+    watched = (bn.moving_mean, bn.moving_variance, bn.beta) + ((bn.gamma,) if bn.gamma is not None else ())
+    return _BN_CACHE.get(id(bn), watched, build, bn.beta.data_ptr())
 
 
 def dense_act(lin, x, activation=None, bn=None, bounded_input=False):
@@ -472,7 +437,7 @@ def _dense_act(lin, x, activation, bn, bounded=False):
         fold = bn is not None and not (bn.training and torch.is_grad_enabled())
         ps, psh = _bn_affine(bn) if fold else (None, None)
         if prepadded and not train and x.dtype == torch.float32:
-            y = ops.dense(x, _packed_cached_padded(lin.weight, x.shape[1] - lin.in_features), lin.bias, relu=relu, post_scale=ps, post_shift=psh)
+            y = ops.dense(x, _packed_cached(lin.weight, x.shape[1] - lin.in_features), lin.bias, relu=relu, post_scale=ps, post_shift=psh)
             return y if fold else _apply_bn(bn, y)
         if prepadded:
             x = x[:, :lin.in_features]
@@ -484,7 +449,7 @@ def _dense_act(lin, x, activation, bn, bounded=False):
             xp = F.pad(x, (0, pad))
             if train:
                 return _dense_bn_train(bn, xp, F.pad(lin.weight, (0, pad)), lin.bias, relu, bounded)     # pad's backward slices the gradients back
-            y = ops.dense(xp, _packed_cached_padded(lin.weight, pad), lin.bias, relu=relu, post_scale=ps, post_shift=psh)
+            y = ops.dense(xp, _packed_cached(lin.weight, pad), lin.bias, relu=relu, post_scale=ps, post_shift=psh)
             return y if fold else _apply_bn(bn, y)
         if ops.dense_supported(x, lin.weight):
             if train:

@@ -37,23 +37,16 @@ class Dice(nn.Module):
         self.register_buffer("moving_mean", torch.zeros(n))
         self.register_buffer("moving_variance", torch.ones(n))
         self.eps, self.momentum = eps, momentum
-        self._folded = None
 
     def scale_shift(self):
         """(scale, shift) with p = sigmoid(scale * s + shift): the inference form the HIP unit takes.  Folded once per version
-        of the moving statistics (four library kernels per call otherwise: 8 % of the cfg-4 model's forward); under a default graph capture
-        (ops.capture_bypasses_caches) folded inline, so that a replay reads the statistics as they are then."""
-        if ops.capture_bypasses_caches(self.moving_mean):
+        of the moving statistics (four library kernels per call otherwise: 8 % of the cfg-4 model's forward)."""
+        def build():
             with torch.no_grad():
                 scale = torch.rsqrt(self.moving_variance + self.eps)
                 return scale, -self.moving_mean * scale
-        key = (self.moving_mean._version, self.moving_variance._version, self.moving_mean.data_ptr(),
-               self.moving_variance.data_ptr(), self.eps, ops._CACHE_GEN[0])
-        if self._folded is None or self._folded[0] != key:
-            with torch.no_grad():
-                scale = torch.rsqrt(self.moving_variance + self.eps)
-                self._folded = (key, scale, -self.moving_mean * scale)
-        return ops.held(self._folded[1]), ops.held(self._folded[2])
+        return ops.MODULE_PARAMS.get((id(self), "dice"), (self.moving_mean, self.moving_variance), build,
+                                     (self.moving_mean.data_ptr(), self.moving_variance.data_ptr(), self.eps))
 
     def forward(self, s, valid=None):
         """valid (optional, broadcastable to s without its last dimension): rows that take part in the batch statistics."""
@@ -115,21 +108,15 @@ class DINAttentionPool(nn.Module):
         self.normalize = normalize
         self.activation = activation
         self.act1, self.act2 = _make_act(activation, H1), _make_act(activation, H2)
-        self._act_cache = None
 
     def act_params(self):
         """[3 H1 + 3 H2] for the HIP unit (alpha, scale, shift per layer), from the activation modules' inference form."""
         if self.activation == "sigmoid":
             return None
-        if ops.capture_bypasses_caches(self.act1.alpha):
-            return self._build_act_params()                                 # a default capture: built inside the graph, from the values at replay
         src = [self.act1.alpha, self.act2.alpha]
         if self.activation == "dice":
             src += [self.act1.moving_mean, self.act1.moving_variance, self.act2.moving_mean, self.act2.moving_variance]
-        key = tuple((t._version, t.data_ptr()) for t in src) + (ops._CACHE_GEN[0],)
-        if self._act_cache is None or self._act_cache[0] != key:           # rebuilt when a parameter / statistic is written
-            self._act_cache = (key, self._build_act_params())
-        return ops.held(self._act_cache[1])
+        return ops.MODULE_PARAMS.get((id(self), "act"), src, self._build_act_params, tuple(t.data_ptr() for t in src))
 
     def _build_act_params(self):
         if self.activation == "prelu":

@@ -15,12 +15,13 @@ Reference closures (relative to /root/reference):
   cin_layer                  (no reference code; README.md:28)
 """
 import ctypes
-import operator
 import os
 
 import torch
 
 from . import _lib
+from ._cache import (VersionCache, version_caches, invalidate_caches, capture_hold, frozen_weights, held, capture_guard,      # noqa: F401
+                     capture_bypasses_caches, also_cleared, _CACHE_GEN, _HOLDS, _FROZEN_WEIGHTS)
 
 SUM, MEAN, SQRTN = 0, 1, 2
 _COMBINERS = {"sum": SUM, "mean": MEAN, "sqrtn": SQRTN, SUM: SUM, MEAN: MEAN, SQRTN: SQRTN}
@@ -199,7 +200,6 @@ def f16_range_ok(absmax):
     return absmax == 0.0 or (F16_SMALL_GUARD <= absmax < F16_RANGE_GUARD)
 
 
-_CACHE_GEN = [0]                 # bumped by invalidate_caches(): every magnitude measurement taken before it is stale
 _HIP_BUMPS = None                # version-counter owner (a view's base) -> how many of its version bumps mark_written made
 
 
@@ -215,9 +215,9 @@ def hip_bumps(t):
 
 def mark_written(*tensors):
     """A raw-pointer kernel has just written these tensors in place: bump their autograd version counters, as an in-place torch op would
-    have.  Everything cached per weight version (DeepFM's packed serving rows, tower_image / dense_bf3_image, dense._packed_cached,
-    dense._bn_affine, DCN's cross image) keys on tensor._version, so an eval -> train -> eval loop in one process (the reference's
-    train_and_evaluate) rebuilds them after a HIP optimiser step.  Views share their base's counter."""
+    have.  Everything cached per weight version (DeepFM's packed serving rows and every VersionCache: ops.version_caches()) keys on
+    tensor._version, so an eval -> train -> eval loop in one process (the reference's train_and_evaluate) rebuilds them after a HIP
+    optimiser step.  Views share their base's counter."""
     global _HIP_BUMPS
     ts = [t for t in tensors if isinstance(t, torch.Tensor)]
     if ts:
@@ -231,89 +231,6 @@ def mark_written(*tensors):
             if id(o) not in seen:
                 seen.add(id(o))
                 _HIP_BUMPS[o] = _HIP_BUMPS.get(o, 0) + 1
-
-_FROZEN_WEIGHTS = [False]
-_HOLDS = []                      # the keep-alive lists of the captures in progress (capture_hold / frozen_weights), innermost last
-_VERSION = operator.attrgetter("_version")
-
-
-class capture_hold:
-    """with ops.capture_hold() as hold: ... capture ...  -- what a graph captured inside reads through a cache.  A graph keeps raw pointers
-    only: a cache entry it read may be dropped afterwards (an eager call at a new weight version replaces it, invalidate_caches() and the
-    caches' size limits clear it) and the allocator may hand its block out again.  So every cache hit served while a stream is capturing
-    appends what it returned to `keep` (tensors; a TableSet / PackedTables object) -- the owner of the graph stores the hold for the
-    graph's lifetime -- and a cache that is NOT bypassed under a default capture (DeepFM's packed serving rows: a copy of the tables)
-    records the tensors its entry was built from in `guards`: moved() is True once one of them was modified in place or invalidate_caches()
-    ran, and the owner captures again (GraphedForward).  serving.GraphedForward and CapturedStep open one around their capture."""
-
-    def __init__(self):
-        self.keep, self._guard_ts, self._guard_ids = [], [], set()
-        self._guard_vs, self._gen = [], _CACHE_GEN[0]
-
-    def __enter__(self):
-        _HOLDS.append(self)
-        return self
-
-    def __exit__(self, *exc):
-        _HOLDS.remove(self)
-        return False
-
-    def guard(self, tensors):
-        for t in tensors:
-            if id(t) not in self._guard_ids:
-                self._guard_ids.add(id(t))
-                self._guard_ts.append(t)
-                self._guard_vs.append(t._version)
-
-    @property
-    def guarded(self):
-        return bool(self._guard_ts)
-
-    def moved(self):
-        """Whether a guarded tensor was modified in place (tensor._version) or invalidate_caches() ran since the capture."""
-        return self._gen != _CACHE_GEN[0] or list(map(_VERSION, self._guard_ts)) != self._guard_vs
-
-
-def held(obj, guards=()):
-    """A cache hands `obj` to its caller: while a stream is capturing inside a capture_hold / frozen_weights, the hold keeps it alive (and
-    records `guards`, see capture_hold).  Returns obj.  Outside a capture: nothing (one list test)."""
-    if _HOLDS and torch.cuda.is_current_stream_capturing():
-        h = _HOLDS[-1]
-        h.keep.append(obj)
-        if guards:
-            h.guard(guards)
-    return obj
-
-
-def capture_guard(tensors):
-    """A decision taken from the values of `tensors` now (a measured magnitude that picks a kernel's split) is baked into the graph being
-    captured: the open hold records them as guards (capture_hold.moved)."""
-    if _HOLDS and torch.cuda.is_current_stream_capturing():
-        _HOLDS[-1].guard(tensors)
-
-
-class frozen_weights(capture_hold):
-    """with ops.frozen_weights() as hold: ... capture ...  -- a capture taken inside takes the VALID per-version cache entries (weight images,
-    packed weights, folded batch norms: built by an earlier eager call on the same versions) instead of re-packing inside the graph.  For
-    SERVING graphs whose weights do not change between replays: a one-launch DeepFM forward at 1 024-4 096 rows carries three pack launches
-    otherwise (15-20 us of ~70).  The price: a replay after an in-place weight update still runs the images of capture time -- capture again
-    after loading new weights.  What the graph reads stays valid: every entry it took is in `hold.keep` (capture_hold), which the owner of the
-    graph stores, so an eager call at new weights, invalidate_caches() or a cache's size limit cannot free it under the graph.
-    serving.GraphedForward(..., frozen_weights=True) uses it."""
-
-    def __enter__(self):
-        self._old = _FROZEN_WEIGHTS[0]
-        _FROZEN_WEIGHTS[0] = True
-        return super().__enter__()
-
-    def __exit__(self, *exc):
-        _FROZEN_WEIGHTS[0] = self._old
-        return super().__exit__(*exc)
-
-
-def capture_bypasses_caches(t=None):
-    """True while the current stream is capturing and the per-version caches must not be read (the default rule; see frozen_weights)."""
-    return (t is None or t.is_cuda) and torch.cuda.is_current_stream_capturing() and not _FROZEN_WEIGHTS[0]
 
 
 class CapturedStep:
@@ -728,33 +645,24 @@ def din_pack_covers(K, T, H1, H2):
     return K == 64 and 1 <= T <= 65535 and 0 < H1 <= 80 and 0 < H2 <= 48 and H1 % 4 == 0 and H2 % 4 == 0
 
 
-_DIN_PACK_IMAGES = {}
+_DIN_PACK_IMAGES = VersionCache("din_pack_image", 64)
 
 
 def din_pack_image(owners, args, activation, ap):
     """The packed DIN kernel's weight image (include/dir_hip.h: dir_din_pack_weights_f32), built once per version of the weights: keyed on
     the LONG-LIVED tensors `owners` (W1, W2, W3 -- a module's nn.Parameters; their .data views are new objects on every call) plus b1, b2
-    and the activation parameters, by identity, version and storage.  While a stream is capturing no cache is consulted or filled: the pack
-    kernel becomes part of the graph and reads the weights as they are at replay time (the rule of every per-version cache here)."""
-    import weakref
+    and the activation parameters, by identity, version and storage (a VersionCache)."""
     W1, b1, W2, b2, W3, b3 = args
-    lib = _lib.load()
-    H1, H2 = W1.shape[1], W2.shape[1]
     watched = list(owners) + ([] if len(owners) >= 5 else [b1, b2]) + ([ap] if ap is not None else [])      # range_of may name b1 / b2's owners too
-    capturing = torch.cuda.is_current_stream_capturing()
     key = tuple(t.data_ptr() for t in (W1, b1, W2, b2, W3)) + (activation, ap.data_ptr() if ap is not None else 0, W1.device.index)
-    sig = tuple((id(t), t._version if not t.is_inference() else -1) for t in watched) + (_CACHE_GEN[0],)
-    hit = _DIN_PACK_IMAGES.get(key)
-    if hit is not None and not capture_bypasses_caches() and hit[0] == sig and all(r() is t for r, t in zip(hit[1], watched)):
-        return held(hit[2])
-    img = torch.empty(int(lib.dir_din_pack_image_bytes()), dtype=torch.uint8, device=W1.device)
-    _lib.check(lib.dir_din_pack_weights_f32(_ptr(W1), _ptr(b1), H1, _ptr(W2), _ptr(b2), H2, _ptr(W3), DIN_ACTIVATIONS[activation], _ptr(ap),
-                                            _ptr(img), _stream()))
-    if not capturing and not any(t.is_inference() for t in watched):
-        if len(_DIN_PACK_IMAGES) > 64:
-            _DIN_PACK_IMAGES.clear()
-        _DIN_PACK_IMAGES[key] = (sig, [weakref.ref(t) for t in watched], img)
-    return img
+
+    def build():
+        lib = _lib.load()
+        img = torch.empty(int(lib.dir_din_pack_image_bytes()), dtype=torch.uint8, device=W1.device)
+        _lib.check(lib.dir_din_pack_weights_f32(_ptr(W1), _ptr(b1), W1.shape[1], _ptr(W2), _ptr(b2), W2.shape[1], _ptr(W3), DIN_ACTIVATIONS[activation],
+                                                _ptr(ap), _ptr(img), _stream()))
+        return img
+    return _DIN_PACK_IMAGES.get(key, watched, build)
 
 
 def _din_pack_ws(device, nbytes):
@@ -1046,19 +954,9 @@ def dense_mid_covers(M, Kd, N):
     """Whether dense() runs dir_dense_mid_f32 for an [M, Kd] x [N, Kd] layer (given fp32 arithmetic and 16-byte aligned rows)."""
     return 0 < M <= DENSE_MID_ROWS and Kd % 4 == 0 and N >= 16 and not dense_small_covers(M, Kd, N)
 DENSE_BF3_MIN_ROWS = 12288     # below this the 256-row tiles leave too much of the chip idle (tools/dense_bf3_probe.py: x1.14 at 16 384 rows, x0.58 at 4 096)
-_DENSE_IMAGES = {}             # data_ptr -> (weakref to the weight tensor, version, shape, strides, image)
-
-
-def invalidate_caches():
-    """Drop every cached weight image (dense / tower bf16x3 images).  The caches follow tensor._version, which in-place torch ops bump;
-    a write through `param.data`, a raw-pointer kernel or a checkpoint loader that copies into storage directly does not -- call this
-    after such a write (checkpoint.load_* do)."""
-    _DENSE_IMAGES.clear()
-    _TOWER_IMAGES.clear()
-    _WEIGHT_ABSMAX.clear()
-    _DIN_PACK_IMAGES.clear()
-    _CIN_POOLED_IMAGES.clear()
-    _CACHE_GEN[0] += 1             # TableSet.absmax / ShardedTables.absmax measurements taken before this call are stale
+_DENSE_IMAGES = VersionCache("dense_image", 256)
+# what the modules fold or pad from their own parameters (din.Dice, din.DINAttentionPool, dcn.DeepCrossNetwork), keyed (id(module), what)
+MODULE_PARAMS = VersionCache("module_params", 256)
 
 
 def dense_bf16x3_covers(x, weight, out=None, gate=None):
@@ -1138,29 +1036,16 @@ def dense_bf3_image(weight, split="bf16x3"):
     """The packed image (bf16 x 3, or fp16 x 2 pieces with split="f16x2") of a [N, Kd] fp32 weight of ANY strides
     (dir_dense_*_pack_strided_f32: a `.t()` view is packed straight from the storage of the tensor it transposes), cached per tensor and
     split until the tensor is modified in place (tensor._version) or goes away."""
-    import weakref
-    key = weight.data_ptr() if split == "bf16x3" else (weight.data_ptr(), split)
-    sig = (weight._version, tuple(weight.shape), tuple(weight.stride()))
-    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
-    hit = _DENSE_IMAGES.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == sig and not capture_bypasses_caches(weight):
-        return held(hit[2])
-    N, Kd = weight.shape
-    lib = _lib.load()
-    nbytes = int(lib.dir_dense_bf16x3_image_bytes(Kd, N))
-    img = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    pack = lib.dir_dense_f16x2_pack_strided_f32 if split == "f16x2" else lib.dir_dense_bf16x3_pack_strided_f32
-    _lib.check(pack(_ptr(weight), weight.stride(0), weight.stride(1), Kd, N, _ptr(img), nbytes, _stream()))
-    if capturing:
-        # Under graph capture the caches are bypassed in BOTH directions (ADVICE r4): a hit would leave the pack kernel out of the graph --
-        # every replay would then run against the image of the weights as they were at capture time, although the replayed optimiser
-        # kernels keep changing them -- and an image stored now would live in the graph's private pool.  The pack is captured, its
-        # image is graph-owned memory, and nothing is remembered.
+    def build():
+        N, Kd = weight.shape
+        lib = _lib.load()
+        nbytes = int(lib.dir_dense_bf16x3_image_bytes(Kd, N))
+        img = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+        pack = lib.dir_dense_f16x2_pack_strided_f32 if split == "f16x2" else lib.dir_dense_bf16x3_pack_strided_f32
+        _lib.check(pack(_ptr(weight), weight.stride(0), weight.stride(1), Kd, N, _ptr(img), nbytes, _stream()))
         return img
-    if len(_DENSE_IMAGES) > 256:
-        _DENSE_IMAGES.clear()
-    _DENSE_IMAGES[key] = (weakref.ref(weight), sig, img)
-    return img
+    key = weight.data_ptr() if split == "bf16x3" else (weight.data_ptr(), split)
+    return _DENSE_IMAGES.get(key, (weight,), build, (weight.shape, weight.stride()))
 
 
 def _dense_arith(arith, x, weight, out, gate):
@@ -1318,7 +1203,7 @@ TOWER_KERNEL = os.environ.get("DIR_TOWER_KERNEL", "cs")
 TOWER_MIN_WIDTH = 128          # dense.tower_infer: a stage always computes 13 column tiles, so a narrower layer (ESMM's 80-wide one) pads more
                                # than the fusion saves (ESMM forward 0.574 ms layer by layer, 0.580 fused)
 TOWER = os.environ.get("DIR_TOWER", "auto")      # "0": never fuse (per-layer kernels)
-_TOWER_IMAGES = {}
+_TOWER_IMAGES = VersionCache("tower_image", 256)
 
 
 def tower_covers(x, weights, head=None):
@@ -1362,30 +1247,22 @@ F16_SMALL_GUARD = 2.0 ** -6
 def tower_image(weight, split=None):
     """The packed image (bf16 x 3 or fp16 x 2 pieces) of one layer's [N, K] weight in the tower kernel's k order, cached per tensor and
     split until the tensor is modified in place (tensor._version) or goes away."""
-    import weakref
     split = split or TOWER_SPLIT
-    key = (weight.data_ptr(), split)
-    sig = (weight._version, tuple(weight.shape), tuple(weight.stride()))
-    capturing = weight.is_cuda and torch.cuda.is_current_stream_capturing()
-    hit = _TOWER_IMAGES.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == sig and not capture_bypasses_caches(weight):
-        return held(hit[2])
-    N, K = weight.shape
-    lib = _lib.load()
-    nbytes = int(lib.dir_tower_cs_image_bytes(K, N) if split == "f16x2cs" else lib.dir_tower_bf16x3_image_bytes(K, N))
-    img = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    w = weight if weight.stride(1) == 1 else weight.contiguous()
-    pack = {"f16x2": lib.dir_tower_f16x2_pack_f32, "f16x2cs": lib.dir_tower_cs_f16x2_pack_f32}.get(split, lib.dir_tower_bf16x3_pack_f32)
-    _lib.check(pack(_ptr(w), w.stride(0), K, N, _ptr(img), nbytes, _stream()))
-    if capturing:
-        return img                                # (as dense_bf3_image: the pack is part of the graph, the image graph-owned, nothing cached)
-    if len(_TOWER_IMAGES) > 256:
-        _TOWER_IMAGES.clear()
-    _TOWER_IMAGES[key] = (weakref.ref(weight), sig, img)
-    return img
+
+    def build():
+        N, K = weight.shape
+        lib = _lib.load()
+        nbytes = int(lib.dir_tower_cs_image_bytes(K, N) if split == "f16x2cs" else lib.dir_tower_bf16x3_image_bytes(K, N))
+        img = torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
+        w = weight if weight.stride(1) == 1 else weight.contiguous()
+        pack = {"f16x2": lib.dir_tower_f16x2_pack_f32, "f16x2cs": lib.dir_tower_cs_f16x2_pack_f32}.get(split, lib.dir_tower_bf16x3_pack_f32)
+        _lib.check(pack(_ptr(w), w.stride(0), K, N, _ptr(img), nbytes, _stream()))
+        return img
+    return _TOWER_IMAGES.get((weight.data_ptr(), split), (weight,), build, (weight.shape, weight.stride()))
 
 
 _WEIGHT_ABSMAX = {}
+also_cleared.append(_WEIGHT_ABSMAX)
 
 
 def weight_absmax(weight, every=1):
@@ -1947,7 +1824,7 @@ CIN_POOLED_LAST = os.environ.get("DIR_CIN_POOLED_LAST", "1") != "0"  # developme
 
 # development switch: 0 = the pooled last layer of an inference stack stays on the two-pass form (cin_pool_z + the dense kernel)
 CIN_POOLED_FUSED = os.environ.get("DIR_CIN_POOLED_FUSED", "1") != "0"
-_CIN_POOLED_IMAGES = {}
+_CIN_POOLED_IMAGES = VersionCache("cin_pooled_image", 64)
 
 
 def cin_pooled_fused_covers(m, Hp, H, D):
@@ -1956,28 +1833,18 @@ def cin_pooled_fused_covers(m, Hp, H, D):
 
 
 def cin_pooled_image(W, m, Hp, D, owner=None):
-    """The fused pooled layer's weight image (dir_cin_pooled_pack_f32), once per version of W (while a stream is capturing: packed inside the
-    graph, nothing remembered, unless under frozen_weights -- the rule of every per-version cache here).  owner: the LONG-LIVED tensor whose identity and version stand for
-    W's (a module passes its nn.Parameter and `.data` as W: a `.data` view is a new object with a fresh version counter on every call)."""
-    import weakref
-    lib = _lib.load()
-    H = W.shape[0]
-    own = W if owner is None else owner
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (W.data_ptr(), tuple(W.shape), tuple(W.stride()), m, Hp)
-    sig = (own._version if not own.is_inference() else -1, _CACHE_GEN[0])
-    hit = _CIN_POOLED_IMAGES.get(key)
-    if hit is not None and not capture_bypasses_caches(W) and hit[0]() is own and hit[1] == sig:
-        return held(hit[2])
-    Wc = W if W.is_contiguous() else W.contiguous()
-    nbytes = int(lib.dir_cin_pooled_image_bytes(m, Hp, H, D))
-    img = torch.empty(nbytes, dtype=torch.uint8, device=W.device)
-    _lib.check(lib.dir_cin_pooled_pack_f32(_ptr(Wc), m, Hp, H, D, _ptr(img), nbytes, _stream()))
-    if not capturing and not own.is_inference():
-        if len(_CIN_POOLED_IMAGES) > 64:
-            _CIN_POOLED_IMAGES.clear()
-        _CIN_POOLED_IMAGES[key] = (weakref.ref(own), sig, img)
-    return img
+    """The fused pooled layer's weight image (dir_cin_pooled_pack_f32), once per version of W (a VersionCache).  owner: the LONG-LIVED tensor
+    whose identity and version stand for W's (a module passes its nn.Parameter and `.data` as W: a `.data` view is a new object with a
+    fresh version counter on every call)."""
+    def build():
+        lib = _lib.load()
+        H = W.shape[0]
+        Wc = W if W.is_contiguous() else W.contiguous()
+        nbytes = int(lib.dir_cin_pooled_image_bytes(m, Hp, H, D))
+        img = torch.empty(nbytes, dtype=torch.uint8, device=W.device)
+        _lib.check(lib.dir_cin_pooled_pack_f32(_ptr(Wc), m, Hp, H, D, _ptr(img), nbytes, _stream()))
+        return img
+    return _CIN_POOLED_IMAGES.get((W.data_ptr(), W.shape, W.stride(), m, Hp), (W if owner is None else owner,), build)
 
 
 def cin_pooled_covers(m, D, Hp):

@@ -304,14 +304,11 @@ def _storage_bytes(obj, out):
 def _cached_image_sizes(model):
     """Byte sizes of every cached weight image / packed weight the caches hold now (float and byte images only: never a pointer or an
     index array -- a poisoned pointer would be dereferenced, not read)."""
-    from dir_amd import ops, dense
+    from dir_amd import ops
     sizes = []
-    for cache in (ops._DENSE_IMAGES, ops._TOWER_IMAGES, ops._DIN_PACK_IMAGES, ops._CIN_POOLED_IMAGES, dense._PACK_CACHE, dense._BN_CACHE):
-        for entry in list(cache.values()):
-            _storage_bytes([e for e in entry if isinstance(e, torch.Tensor)], sizes)
+    for cache in ops.version_caches():
+        _storage_bytes(cache.values(), sizes)
     for mod in model.modules():
-        for attr in ("_cross_pad", "_logit_split", "_folded", "_act_cache"):
-            _storage_bytes(getattr(mod, attr, None), sizes)
         pk = getattr(mod, "_packed", None)
         if pk is not None:
             sizes.append(pk.arena.untyped_storage().nbytes())
@@ -337,7 +334,7 @@ def _overflow_image_caches():
         ops.dense_bf3_image(w)
         ops.tower_image(w)
     torch.cuda.synchronize()
-    assert len(ops._DENSE_IMAGES) < 300 and len(ops._TOWER_IMAGES) < 300
+    assert all(len(c) <= c.limit + 1 for c in ops.version_caches())      # (300 > every limit: both were cleared on the way)
     return dummies
 
 
@@ -430,3 +427,84 @@ def test_e3_hidden_weight_magnitude(built_lib, graphs, name, scale):
     err32 = float((np.abs(ref32 - ref) / (1 + np.abs(ref))).max())
     _close(_np(got), ref, max(case.tol, 4 * err32))
     assert torch.equal(got, case.eager())
+
+
+def _small_deepfm():
+    from dir_amd.deepfm import DeepFM
+    from dir_amd import feature_column as fc
+    V, K, B = (7, 5, 11), 4, 8
+    gen = torch.Generator().manual_seed(11)
+    cats = [fc.categorical_column_with_identity("C%d" % i, v) for i, v in enumerate(V)]
+    model = DeepFM(linear_feature_columns=cats, dnn_feature_columns=[fc.embedding_column(c, K) for c in cats], dnn_hidden_units=[16],
+                   fm_embedding_size=K).cuda().eval()
+    ids = torch.stack([torch.randint(0, v, (B,), generator=gen) for v in V], 1).cuda()
+    return model, ids
+
+
+def _forward(model, ids):
+    with torch.no_grad():
+        out = model.forward_ids(ids, ids).clone()
+    torch.cuda.synchronize()
+    return out
+
+
+def _fresh_copy_forward(model, ids):
+    """The forward of a deep copy: fresh parameters, no cache entry of any kind."""
+    import copy
+    return _forward(copy.deepcopy(model), ids)
+
+
+def test_invalidate_caches_after_a_raw_write_eager(built_lib):
+    """A write through .data bumps no version counter: after ops.invalidate_caches() the next forward computes from the new values."""
+    from dir_amd import ops
+    model, ids = _small_deepfm()
+    before = _forward(model, ids)
+    model.embedding_weights[0].data.mul_(2)
+    ops.invalidate_caches()
+    got = _forward(model, ids)
+    assert not torch.equal(got, before)
+    assert torch.equal(got, _fresh_copy_forward(model, ids))
+
+
+def test_invalidate_caches_after_a_raw_write_graphed(built_lib, graphs):
+    """... and a GraphedForward captures again and replays the new values."""
+    from dir_amd import ops
+    from dir_amd.serving import GraphedForward
+    model, ids = _small_deepfm()
+    g = GraphedForward(lambda x: model.forward_ids(x, x), ids)
+    graphs.append(g)
+    before = g(ids).clone()
+    model.embedding_weights[0].data.mul_(2)
+    ops.invalidate_caches()
+    got = g(ids).clone()
+    torch.cuda.synchronize()
+    assert g.captures == 2 and not torch.equal(got, before)
+    assert torch.equal(got, _fresh_copy_forward(model, ids))
+
+
+@pytest.mark.parametrize("which", ["dense_bf3_image", "tower_image"])
+def test_weight_image_of_an_inference_tensor(built_lib, which):
+    """A tensor created under torch.inference_mode() has no version counter: its image is built per call, never stored, and has the bytes
+    of an ordinary clone's image.  (The pack kernels leave the tile slots behind a layer's last column tile unwritten -- the forward
+    kernels never load them --, so every image here is built over a zero-filled block: the caching allocator hands the block freed
+    last to the next request of its size, as in _poison.)"""
+    from dir_amd import ops
+    fn = getattr(ops, which)
+    with torch.inference_mode():
+        w = torch.randn(16, 16, device="cuda")
+    plain, sizer = w.clone(), w.clone()
+    assert w.is_inference() and not plain.is_inference()
+    nbytes = fn(sizer).numel()
+
+    def image(t):
+        torch.zeros(nbytes, dtype=torch.uint8, device="cuda")                 # freed at once
+        return fn(t)
+
+    ref = image(plain)
+    entries = sum(len(c) for c in ops.version_caches())
+    img = image(w)
+    torch.cuda.synchronize()
+    assert isinstance(img, torch.Tensor) and img.dtype == torch.uint8 and img.data_ptr() != ref.data_ptr()
+    assert sum(len(c) for c in ops.version_caches()) == entries
+    assert torch.equal(img, ref)
+    assert fn(plain) is ref and fn(w) is not img
