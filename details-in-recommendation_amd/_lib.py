@@ -112,6 +112,10 @@ SIGNATURES = {
     "dir_sparse_adam_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i64]),
     "dir_sparse_adam_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp]),
+    "dir_sparse_adam_payload_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i64]),
+    "dir_sparse_adam_payload_norm_f32": (c_i32, [c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "dir_sparse_adam_payload_apply_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                  ctypes.c_float, ctypes.c_float, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     "dir_sparse_adagrad_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_float, c_i64, c_vp,
                                        c_i64, c_vp, c_vp, c_vp]),
     "dir_sparse_adagrad_sorted_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i64]),

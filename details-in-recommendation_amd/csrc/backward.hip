@@ -46,6 +46,9 @@ template <> struct BV<4> {
     static __device__ __forceinline__ D widen(T a) { return make_double4((double)a.x, (double)a.y, (double)a.z, (double)a.w); }
     static __device__ __forceinline__ D addw(D a, T b) { return make_double4(a.x + (double)b.x, a.y + (double)b.y, a.z + (double)b.z, a.w + (double)b.w); }
     static __device__ __forceinline__ T narrow(D a) { return make_float4((float)a.x, (float)a.y, (float)a.z, (float)a.w); }
+    static __device__ __forceinline__ D addd(D a, D b) { return make_double4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+    static __device__ __forceinline__ D ldw(const double* p) { return *reinterpret_cast<const double4*>(p); }       // 32-byte aligned
+    static __device__ __forceinline__ void stw(double* p, D v) { *reinterpret_cast<double4*>(p) = v; }
 };
 template <> struct BV<1> {
     using T = float;
@@ -62,6 +65,9 @@ template <> struct BV<1> {
     static __device__ __forceinline__ D widen(T a) { return (double)a; }
     static __device__ __forceinline__ D addw(D a, T b) { return a + (double)b; }
     static __device__ __forceinline__ T narrow(D a) { return (float)a; }
+    static __device__ __forceinline__ D addd(D a, D b) { return a + b; }
+    static __device__ __forceinline__ D ldw(const double* p) { return *p; }
+    static __device__ __forceinline__ void stw(double* p, D v) { *p = v; }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -563,6 +569,8 @@ struct AdamUpd {
     const int64_t* row_base;
     float lr_t, b1, b2, eps, clip;
     int64_t ld;
+    const double* norm2_sum = nullptr;         // [F] ||gradient of table f||^2 over ALL owners of a row-sharded table (the payload form: the
+                                               // ranks' fixed-point shares added up exactly, which a u64 word cannot hold for 64 of them)
     __device__ __forceinline__ void one(float g, float den, float& m, float& v, float& w) const {
         if (clip > 0.f) g = (g * clip) / den;                     // tf.clip_by_norm: t * clip_norm / max(l2norm, clip_norm)
         m = m * b1 + g * (1.f - b1);
@@ -573,7 +581,8 @@ struct AdamUpd {
     __device__ __forceinline__ void apply(int f, int64_t id, int col, typename BV<VEC>::T g) const {
         using V = BV<VEC>;
         float den = clip;
-        if (clip > 0.f && norm2) den = fmaxf(sqrtf((float)((double)norm2[f] / ADAM_FX)), clip);
+        if (clip > 0.f && norm2_sum) den = fmaxf(sqrtf((float)norm2_sum[f]), clip);
+        else if (clip > 0.f && norm2) den = fmaxf(sqrtf((float)((double)norm2[f] / ADAM_FX)), clip);
         const int64_t off = id * ld + col;
         float* mp = ms[f] + off;
         float* vp = vs[f] + off;
@@ -621,6 +630,31 @@ __device__ __forceinline__ typename BV<VEC>::T run_sum(int s, int e, Get get) {
 
 template <class U, class = void> struct IsNorm { static constexpr bool value = false; };
 template <class U> struct IsNorm<U, std::void_t<decltype(U::kNorm)>> { static constexpr bool value = U::kNorm; };
+
+// The owner side of a SHARDED Adam step (dir_sparse_adam_payload_*): the same two rules with every run sum formed in DOUBLE -- tile
+// partials kept in double too (the carry rows are [tiles][2][K] doubles) -- and rounded to fp32 once.  Where duplicates of a row sit in
+// the payload depends on the order of the bucket pass's reservation atomics, so two runs of the very same step hand the owner the same
+// entries in different orders; a compensated fp32 sum then agrees to an ulp only, and Adam divides by sqrt(v): the ulp shows in every
+// later step.  A double accumulator holds sums of fp32 terms to 2^-53 of their size: the rounded fp32 sum -- and with it ||S_r||^2, m, v
+// and var -- comes out the same bits whatever the order (short of a double sum within 2^-53 of an fp32 rounding boundary: 2^-29 per sum).
+struct AdamNormUpdW : AdamNormUpd { static constexpr bool kWide = true; };
+struct AdamUpdW : AdamUpd { static constexpr bool kWide = true; };
+template <class U, class = void> struct IsWide { static constexpr bool value = false; };
+template <class U> struct IsWide<U, std::void_t<decltype(U::kWide)>> { static constexpr bool value = U::kWide; };
+
+template <int VEC, class Get>
+__device__ __forceinline__ typename BV<VEC>::D run_sum_wide(int s, int e, Get get) {
+    using V = BV<VEC>;
+    using T = typename V::T;
+    typename V::D acc = V::widen(get(s));
+    int i = s + 1;
+    for (; i + 4 <= e; i += 4) {                           // four entries' loads in flight before their (ordered) adds, as run_sum
+        const T d0 = get(i), d1 = get(i + 1), d2 = get(i + 2), d3 = get(i + 3);
+        acc = V::addw(V::addw(V::addw(V::addw(acc, d0), d1), d2), d3);
+    }
+    for (; i < e; ++i) acc = V::addw(acc, get(i));
+    return acc;
+}
 
 // bag mode: the update of one run (slot f, local row id) from its summed gradient chunk.  All LPS lanes of the group call it (lanes
 // c >= kv of a padded group bring zeros): the clip derivative needs ||row||^2 and row . sum over the whole row.  [TF-upstream] clip_by_norm
@@ -859,7 +893,12 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
         if (rk >= total_rows || (!BAG && c >= kv)) continue;  // pruned ids / idle lanes of a padded group (BAG: they join bag_apply)
         int f = (int)(sval[s] % (uint32_t)F);
         T sum;
-        if (staged) {
+        [[maybe_unused]] typename V::D wsum;
+        if constexpr (IsWide<U>::value) {
+            wsum = staged ? run_sum_wide<VEC>(s, e, [&](int i) { return V::ld(sd + i * (LPS * VEC) + c * VEC); })
+                          : run_sum_wide<VEC>(s, e, [&](int i) { return entry_grad(i, V::zero(), true); });
+            sum = V::narrow(wsum);
+        } else if (staged) {
             sum = run_sum<VEC>(s, e, [&](int i) { return V::ld(sd + i * (LPS * VEC) + c * VEC); });
         } else {
             T wv = V::zero();
@@ -882,7 +921,9 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
                 upd.template apply<VEC>(f, id, c * VEC, sum);
             }
         } else if (c < kv) {
-            V::st(carry + (t * 2 + (open_l ? 0 : 1)) * K + c * VEC, sum);   // a run open on both sides goes to slot 0
+            // a run open on both sides goes to slot 0
+            if constexpr (IsWide<U>::value) V::stw(reinterpret_cast<double*>(carry) + (t * 2 + (open_l ? 0 : 1)) * K + c * VEC, wsum);
+            else V::st(carry + (t * 2 + (open_l ? 0 : 1)) * K + c * VEC, sum);
         }
     }
     if constexpr (IsNorm<U>::value) {
@@ -912,9 +953,13 @@ __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
     const uint32_t kl = keys[e1 - 1];
     if (kl >= total_rows || keys[e1] != kl) return;                   // not open to the right
     if (t > 0 && keys[e0] == kl && keys[e0 - 1] == kl) return;        // the run started in an earlier tile
-    typename V::D wide = V::widen(V::ld(carry + (t * 2 + 1) * K + c * VEC));
+    typename V::D wide;
+    [[maybe_unused]] const double* carry_w = reinterpret_cast<const double*>(carry);      // IsWide: the tiles left their partials in double
+    if constexpr (IsWide<U>::value) wide = V::ldw(carry_w + (t * 2 + 1) * K + c * VEC);
+    else wide = V::widen(V::ld(carry + (t * 2 + 1) * K + c * VEC));
     for (int64_t u = t + 1; u < ntiles; ++u) {
-        wide = V::addw(wide, V::ld(carry + (u * 2) * K + c * VEC));
+        if constexpr (IsWide<U>::value) wide = V::addd(wide, V::ldw(carry_w + (u * 2) * K + c * VEC));
+        else wide = V::addw(wide, V::ld(carry + (u * 2) * K + c * VEC));
         const int64_t u1 = (u + 1) * ADA_TILE;
         if (!(u1 < n && keys[u1] == kl)) break;                       // the run ends inside tile u
     }
@@ -1103,7 +1148,8 @@ static int sparse_sorted_update(const char* name, U upd, int F, int K, const int
     if (total_rows <= 0 || total_rows >= 0xffffffffll) return fail(DIR_E_UNSUPPORTED, "%s: total_rows must be in [1, 2^32-1)", name);
     const int64_t n = B * F;
     AdaSortedPlan p;
-    if (!adagrad_sorted_plan(n, K, total_rows, p, payload ? 0 : B, payload ? 0 : F)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
+    // (IsWide: carry rows of K doubles)
+    if (!adagrad_sorted_plan(n, IsWide<U>::value ? 2 * K : K, total_rows, p, payload ? 0 : B, payload ? 0 : F)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
     // ids [B, F]: the slot-major sort (csrc/radix_sort.hip: the slot is known from the entry's position, the sort runs on local rows)
     const bool slot_sort = !payload && !sorted_from && !use_rocprim_sort() && radix_slot_sort_ok(B, F, p.bits);
     SortedBufs bufs;
@@ -1418,6 +1464,20 @@ extern "C" int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows,
 }
 
 // ---- tf.train.AdamOptimizer on the embedding tables ------------------------------------------------------------------------------
+// the streaming pass over every row of every table: unmarked rows decay and step, marked ones (stepped by AdamUpd) are unmarked
+static int adam_decay_all(const char* name, float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* row_base,
+                          int64_t total_rows, unsigned char* mark, float lr_t, float beta1, float beta2, float eps, hipStream_t st) {
+    dim3 grid((unsigned)(kCUs * 8), (unsigned)F);
+    switch (K / 4) {
+#define DIR_DECAY(L) case L: hipLaunchKernelGGL((adam_decay_k<L>), grid, dim3(256), 0, st, tables, ms, vs, row_base, total_rows, F, mark, lr_t, beta1, beta2, eps); break
+        DIR_DECAY(1); DIR_DECAY(2); DIR_DECAY(4); DIR_DECAY(8); DIR_DECAY(16); DIR_DECAY(32); DIR_DECAY(64);
+#undef DIR_DECAY
+        default: return fail(DIR_E_UNSUPPORTED, "%s: K=%d", name, K);
+    }
+    DIR_CHECK_LAUNCH(name);
+    return DIR_OK;
+}
+
 extern "C" int64_t dir_sparse_adam_workspace_bytes(int64_t B, int F, int K, int64_t total_rows) {
     if (B < 0 || F <= 0 || F > 64 || K <= 0 || (K & 3) || 64 % (K / 4) || total_rows <= 0 || total_rows >= 0xffffffffll || B * F >= 0x7fffffffll) return 0;
     AdaSortedPlan p;
@@ -1460,16 +1520,89 @@ extern "C" int dir_sparse_adam_f32(float* const* tables, float* const* ms, float
                                             stream, nullptr, nullptr, nullptr, clip ? sorted_ws : nullptr);
         if (rc != DIR_OK) return rc;
     }
-    const int lps = K / 4;
-    dim3 grid((unsigned)(kCUs * 8), (unsigned)F);
-    switch (lps) {
-#define DIR_DECAY(L) case L: hipLaunchKernelGGL((adam_decay_k<L>), grid, dim3(256), 0, st, tables, ms, vs, row_base, total_rows, F, mark, lr_t, beta1, beta2, eps); break
-        DIR_DECAY(1); DIR_DECAY(2); DIR_DECAY(4); DIR_DECAY(8); DIR_DECAY(16); DIR_DECAY(32); DIR_DECAY(64);
-#undef DIR_DECAY
-        default: return fail(DIR_E_UNSUPPORTED, "%s: K=%d", name, K);
-    }
-    DIR_CHECK_LAUNCH(name);
+    return adam_decay_all(name, tables, ms, vs, F, K, row_base, total_rows, mark, lr_t, beta1, beta2, eps, st);
+}
+
+// ---- ... on row-sharded tables: the owner's step over the payload it received, in two halves --------------------------------------
+// tf.clip_by_norm takes the norm of a table's WHOLE gradient and an owner sees only its rows' share of it, so the step is cut where the
+// ranks must talk: the norm entry sorts the payload and adds up this owner's share of ||g||^2 per table (AdamNormUpd), the caller sums
+// the shares over the ranks, the apply entry steps the touched rows on the same sort (AdamUpd with the global norms) and then every other
+// local row (adam_decay_k) -- also on an owner that received nothing.  The arguments both halves share are checked here, before any HIP
+// call; p: the plan of the sort area (n > 0).
+static int adam_payload_check(const char* name, int F, int K, const int64_t* payload, int64_t n, const float* grad, const int64_t* row_base,
+                              int64_t total_rows, const void* workspace, int64_t workspace_bytes, AdaSortedPlan& p) {
+    DIR_CHECK_ARG(F > 0 && F <= 64, "%s: F=%d (1 <= F <= 64)", name, F);
+    DIR_CHECK_ARG(K > 0 && !(K & 3) && K / 4 <= 64 && 64 % (K / 4) == 0, "%s: K=%d (a multiple of 4 with K / 4 dividing 64)", name, K);
+    DIR_CHECK_ARG(n >= 0, "%s: n=%lld", name, (long long)n);
+    DIR_CHECK_ARG(n < 0x7fffffffll, "%s: n=%lld entries (the sort takes < 2^31)", name, (long long)n);
+    if (total_rows < 0 || total_rows >= 0xffffffffll) return fail(DIR_E_UNSUPPORTED, "%s: total_rows must be in [0, 2^32-1)", name);
+    DIR_CHECK_ARG(row_base, "%s: null pointer (row_base)", name);
+    if (n == 0) return DIR_OK;
+    DIR_CHECK_ARG(payload, "%s: null pointer (payload)", name);
+    DIR_CHECK_ARG(grad, "%s: null pointer (grad)", name);
+    DIR_CHECK_ARG(workspace, "%s: null pointer (workspace)", name);
+    if (!adagrad_sorted_plan(n, 2 * K, total_rows > 0 ? total_rows : 1, p)) return fail(DIR_E_HIP, "%s: sort size query failed", name);   // carry rows of K doubles
+    if ((int64_t)p.total > workspace_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(DIR_E_BADARG, "%s: workspace needs %lld bytes, 256-byte aligned", name, (long long)p.total);
     return DIR_OK;
+}
+
+extern "C" int64_t dir_sparse_adam_payload_workspace_bytes(int64_t n, int F, int K, int64_t total_rows) {
+    if (n < 0 || n >= 0x7fffffffll || F <= 0 || F > 64 || K <= 0 || (K & 3) || K / 4 > 64 || 64 % (K / 4) || total_rows < 0 ||
+        total_rows >= 0xffffffffll)
+        return 0;
+    if (n == 0) return 256;                      // nothing to sort: a token area, so that 0 keeps meaning "unsupported"
+    AdaSortedPlan p;
+    return adagrad_sorted_plan(n, 2 * K, total_rows > 0 ? total_rows : 1, p) ? (int64_t)p.total : 0;      // carry rows of K doubles
+}
+
+extern "C" int dir_sparse_adam_payload_norm_f32(int F, int K, const int64_t* payload, int64_t n, const float* grad, const int64_t* row_base,
+                                                int64_t total_rows, uint64_t* norm2, void* workspace, int64_t workspace_bytes,
+                                                dir_stream_t stream) {
+    const char* name = "dir_sparse_adam_payload_norm_f32";
+    AdaSortedPlan p;
+    if (int rc = adam_payload_check(name, F, K, payload, n, grad, row_base, total_rows, workspace, workspace_bytes, p)) return rc;
+    DIR_CHECK_ARG(norm2, "%s: null pointer (norm2)", name);
+    DIR_CHECK_ARG(!(reinterpret_cast<uintptr_t>(norm2) & 7u), "%s: norm2 must be 8-byte aligned", name);
+    if (zero_async(norm2, 512, as_stream(stream)) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
+    if (n == 0 || total_rows == 0) return DIR_OK;            // nothing received / no rows here: this owner's share is zero
+    AdamNormUpdW upd;
+    upd.norm2 = reinterpret_cast<unsigned long long*>(norm2);
+    return sparse_sorted_update(name, upd, F, K, nullptr, 0, 0, grad, (int64_t)K, 0, n, row_base, total_rows, workspace, workspace_bytes, stream,
+                                payload);
+}
+
+extern "C" int dir_sparse_adam_payload_apply_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* payload,
+                                                 int64_t n, const float* grad, float lr_t, float beta1, float beta2, float eps,
+                                                 float clip_norm, const double* norm2_global, const int64_t* row_base, int64_t total_rows,
+                                                 unsigned char* marks, void* workspace, int64_t workspace_bytes, int sorted, int first_call,
+                                                 dir_stream_t stream) {
+    const char* name = "dir_sparse_adam_payload_apply_f32";
+    AdaSortedPlan p;
+    if (int rc = adam_payload_check(name, F, K, payload, n, grad, row_base, total_rows, workspace, workspace_bytes, p)) return rc;
+    DIR_CHECK_ARG(tables && ms && vs, "%s: null pointer (tables / ms / vs)", name);
+    DIR_CHECK_ARG(marks || total_rows == 0, "%s: null pointer (marks)", name);
+    DIR_CHECK_ARG(lr_t >= 0.f, "%s: lr_t=%g", name, (double)lr_t);
+    DIR_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f, "%s: beta1=%g (0 <= beta1 < 1)", name, (double)beta1);
+    DIR_CHECK_ARG(beta2 >= 0.f && beta2 < 1.f, "%s: beta2=%g (0 <= beta2 < 1)", name, (double)beta2);
+    DIR_CHECK_ARG(eps > 0.f, "%s: eps=%g (> 0)", name, (double)eps);
+    DIR_CHECK_ARG(clip_norm >= 0.f, "%s: clip_norm=%g (>= 0)", name, (double)clip_norm);
+    DIR_CHECK_ARG((clip_norm > 0.f) == (norm2_global != nullptr), "%s: norm2_global is NULL exactly when clip_norm == 0 (clip_norm=%g)", name,
+                  (double)clip_norm);
+    DIR_CHECK_ARG(!(reinterpret_cast<uintptr_t>(norm2_global) & 7u), "%s: norm2_global must be 8-byte aligned", name);
+    if (total_rows == 0) return DIR_OK;                      // this owner holds no rows (every vocab < P): nothing can move
+    hipStream_t st = as_stream(stream);
+    const int64_t mark_bytes = (total_rows + 255) & ~(int64_t)255;
+    if (first_call && zero_async(marks, (size_t)mark_bytes, st) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
+    if (n > 0) {
+        AdamUpdW upd;
+        static_cast<AdamUpd&>(upd) = AdamUpd{tables, ms, vs, nullptr, marks, row_base, lr_t, beta1, beta2, eps, clip_norm, (int64_t)K};
+        upd.norm2_sum = norm2_global;
+        const int rc = sparse_sorted_update(name, upd, F, K, nullptr, 0, 0, grad, (int64_t)K, 0, n, row_base, total_rows, workspace,
+                                            workspace_bytes, stream, payload, nullptr, nullptr, sorted ? workspace : nullptr);
+        if (rc != DIR_OK) return rc;
+    }
+    return adam_decay_all(name, tables, ms, vs, F, K, row_base, total_rows, marks, lr_t, beta1, beta2, eps, st);
 }
 
 extern "C" int dir_ftrl_dense_f32(float* w, float* accum, float* linear, const float* grad, int64_t count, float lr, float l1, float l2,

@@ -3055,7 +3055,9 @@ class SparseAdam:
     dir_sparse_adam_f32; the reference's train_op: DeepCrossNetwork.py:264-290, train.py:119-124).  [TF-upstream] semantics: every row of
     m, v and var moves every step (IndexedSlices gradients are zero outside the looked-up rows), each table's gradient is clipped on its
     own with tf.clip_by_norm(g, clip_norm) first.  Holds m and v (zeros, like the slots TF creates).  Set .lr_t before every step
-    (lr * sqrt(1 - beta2^t) / (1 - beta1^t), t = global_step + 1); attach() makes loss.backward() perform the update."""
+    (lr * sqrt(1 - beta2^t) / (1 - beta1^t), t = global_step + 1); attach() makes loss.backward() perform the update.
+    On the shards of row-sharded tables the same step runs in two halves, norm_payload / step_payload, around the ranks' sum of the norm
+    shares (shard.ShardedTables.enable_training_adam)."""
 
     def __init__(self, tables, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0):
         self.ts = _as_tableset(tables)
@@ -3076,6 +3078,7 @@ class SparseAdam:
         self.row_base = torch.tensor(base, dtype=torch.int64, device=dev)
         self._ws = None
         self._ws_B = -1
+        self._pws, self._norm2, self._marks, self._sorted = None, None, None, None      # the payload form's sort area, norm words and row marks
         self.steps = 0
 
     @staticmethod
@@ -3112,6 +3115,69 @@ class SparseAdam:
         ts.written(*self.ms, *self.vs)
         self.steps += 1
 
+    # ---- the owner side of a sharded backward (shard.ShardedTables.enable_training_adam): the step in two halves -----------------
+    def _payload_args(self, payload, grad):
+        ts = self.ts
+        _dev(payload, torch.int64, "payload")
+        _dev(grad, torch.float32, "grad")
+        n = payload.numel()
+        if grad.shape != (n, ts.K) or not grad.is_contiguous() or not payload.is_contiguous():
+            raise ValueError("grad must be a contiguous [n, K] tensor matching the payload")
+        lib = _lib.load()
+        need = int(lib.dir_sparse_adam_payload_workspace_bytes(n, ts.F, ts.K, self.total_rows))
+        if need <= 0:
+            raise _lib.DirError(-4, "sparse_adam (payload): unsupported size (F <= 64, K / 4 a power of two, n < 2^31, total rows < 2^32-1)")
+        if self._pws is None or self._pws.numel() < need + 256:
+            self._pws = torch.empty(need + 256, dtype=torch.uint8, device=ts.device)      # the sort area: grows with n (the marks live apart)
+        off = (-self._pws.data_ptr()) % 256
+        return lib, n, ctypes.c_void_p(self._pws.data_ptr() + off), self._pws.numel() - off
+
+    def norm_payload(self, payload, grad):
+        """First half (include/dir_hip.h: dir_sparse_adam_payload_norm_f32): payload [n] int64 (local_row * F + slot, < 0 pruned) as
+        received from all ranks, grad [n, K] in the same order; n == 0 is legal.  -> norm2 [F] device int64: THIS owner's share of every
+        table's ||g||^2 in 2^-32 fixed point (the bits of the kernel's u64 sums).  The payload stays sorted in the workspace for
+        step_payload."""
+        lib, n, ws, ws_bytes = self._payload_args(payload, grad)
+        if self._norm2 is None:
+            self._norm2 = torch.zeros(64, dtype=torch.int64, device=self.ts.device)
+        _lib.check(lib.dir_sparse_adam_payload_norm_f32(self.ts.F, self.ts.K, _ptr(payload), n, _ptr(grad), _ptr(self.row_base), self.total_rows,
+                                                        _ptr(self._norm2), ws, ws_bytes, _stream()))
+        # what step_payload may reuse: this tensor, unchanged, in this sort area, on this stream
+        self._sorted = (payload, payload._version, self._pws, _stream().value)
+        return self._norm2[:self.ts.F]
+
+    def step_payload(self, payload, grad, norm2_global=None):
+        """Second half (dir_sparse_adam_payload_apply_f32): one Adam step of ALL local rows -- the touched ones from the payload, clipped
+        with norm2_global [F] device float64 = every table's GLOBAL ||g||^2 (the owners' norm_payload shares summed over the ranks and
+        divided by 2^32; None exactly when clip_norm == 0), the others by the decay pass; n == 0 runs that pass alone.  The sort of a
+        norm_payload call on the same payload just before is reused."""
+        ts = self.ts
+        lib, n, ws, ws_bytes = self._payload_args(payload, grad)
+        if (self.clip_norm > 0) != (norm2_global is not None):
+            raise ValueError("step_payload: norm2_global goes with clip_norm > 0 (clip_norm=%g)" % self.clip_norm)
+        if norm2_global is not None:
+            _dev(norm2_global, torch.float64, "norm2_global")
+            if norm2_global.numel() != ts.F or not norm2_global.is_contiguous():
+                raise ValueError("norm2_global must be a contiguous [F] float64 tensor")
+        first = 0
+        if self._marks is None:
+            self._marks = torch.empty(max(256, (self.total_rows + 255) // 256 * 256), dtype=torch.uint8, device=ts.device)
+            first = 1
+        was = self._sorted
+        stream = _stream()
+        sorted_ = 1 if (n > 0 and was is not None and was[0] is payload and was[1] == payload._version and was[2] is self._pws
+                        and was[3] == stream.value) else 0
+        self._sorted = None
+        try:
+            _lib.check(lib.dir_sparse_adam_payload_apply_f32(_ptr(ts.ptrs), _ptr(self.m_ptrs), _ptr(self.v_ptrs), ts.F, ts.K, _ptr(payload), n,
+                                                             _ptr(grad), self.lr_t, self.beta1, self.beta2, self.eps, self.clip_norm,
+                                                             _ptr(norm2_global), _ptr(self.row_base), self.total_rows, _ptr(self._marks), ws,
+                                                             ws_bytes, sorted_, first, stream))
+        except _lib.DirError:
+            self._marks = None         # a step that failed between its two passes may have left marks set: the next call zeroes them again
+            raise
+        ts.written(*self.ms, *self.vs)
+        self.steps += 1
 
     def step_table_grad(self, f, grad):
         """Table f's step from a gradient that arrived as its .grad instead of through the sink -- multi-hot / weighted columns, whose

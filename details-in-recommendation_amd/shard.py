@@ -34,6 +34,10 @@ serve all of them; the finish pass de-interleaves into G outputs, the backward i
 is the same for the first-order term: U weights behind one payload word.  ShardedESMMTrainer trains ESMM / ESMM_W_D on them (DESIGN.md
 section 5.2).
 
+DCN trains with the reference's own optimiser on the shards (enable_training_adam, ShardedDCNTrainer): TF's sparse Adam with a per-table
+clip norm.  The clip norm is a property of the whole table, so the owner's step is cut in two around one all-reduce of the [F] norm shares
+(an exact integer sum), and every local row moves every step, also on an owner that received nothing.
+
 The collectives are torch.distributed.all_to_all_single (backend "nccl" = RCCL on ROCm; "gloo" in the CPU tests).
 world_size == 1 skips the collectives (unless force_collective) but still runs the three HIP steps.  The HIP steps sit
 behind a small backend object so that the CPU (gloo) tests can stand the oracle in for them; the default backend is the
@@ -161,6 +165,19 @@ class HipBackend:
 
     def apply_adagrad(self, opt, payload, grad_rows):
         opt.step_payload(payload, grad_rows)                     # HIP: sorted (row, entry) pairs, per-tile segmented reduce
+
+    # ---- owner-side sparse Adam (ShardedTables.enable_training_adam): the step in two halves around the ranks' norm exchange ----
+    def make_adam(self, beta1, beta2, eps, clip_norm):
+        return ops.SparseAdam(self.ts, beta1, beta2, eps, clip_norm)
+
+    def adam_norm(self, opt, payload, grad_rows):
+        """-> [F] int64: this owner's share of every table's ||g||^2, 2^-32 fixed point (HIP: the payload's sort + the norm pass)."""
+        return opt.norm_payload(payload, grad_rows)
+
+    def adam_apply(self, opt, payload, grad_rows, norm2_global):
+        """The touched rows on the norm pass's sort, clipped with the GLOBAL norms ([F] float64, None without a clip), then the decay
+        pass over every other local row."""
+        opt.step_payload(payload, grad_rows, norm2_global)
 
     def back_buffer(self, n, K, device):
         if self._back is None or self._back.shape[0] != n:
@@ -547,7 +564,8 @@ class ShardedTables:
         self._inflight = {}
         self._streams = None          # the two side streams of the pipeline and the verdict's stream (_ensure_streams)
         self._chk_stream = None
-        self.optimizer = None         # enable_training: the owner-side sparse Adagrad
+        self.optimizer = None         # enable_training: the owner-side sparse Adagrad; enable_training_adam: the owner-side sparse Adam
+        self._adam = False
         self.stats = {"lookups": 0, "fallbacks": 0, "cap": None}
         self._updates = 0             # owner-side optimiser steps applied so far (the same on every rank: absmax()'s collective decision)
         self._absmax_all = None
@@ -594,7 +612,7 @@ class ShardedTables:
 
     def group_accums(self, g):
         """Group g's Adagrad accumulators (enable_training first): [local rows, K] views, like group_tables."""
-        if self.optimizer is None:
+        if self.optimizer is None or self._adam:
             raise RuntimeError("call enable_training(lr) first")
         if not 0 <= g < self.G:
             raise ValueError("group %d of %d" % (g, self.G))
@@ -756,7 +774,69 @@ class ShardedTables:
         whose backward() updates every rank's shard in place; duplicate rows -- from one rank or several -- are summed
         first, i.e. one synchronous step over the global batch."""
         self.optimizer = self.backend.make_optimizer(lr, initial_accumulator_value)
+        self._adam = False
         return self
+
+    def enable_training_adam(self, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0):
+        """Attach the owner-side sparse Adam instead (the reference DCN's train_op on its embedding variables: tf.train.AdamOptimizer with
+        tf.clip_by_norm(g, 100) per variable, DeepCrossNetwork.py:264-290).  Every rank holds m and v (zeros) of its
+        shards; lookup_train(ids).backward() then takes one synchronous [TF-upstream] sparse Adam step over the global batch:
+          1. the gradient rows travel the forward's row exchange backwards, as for Adagrad;
+          2. every owner sorts what it received and adds up its rows' share of each table's ||g||^2 (fixed point, integer adds);
+          3. the shares are summed over the ranks -- an exact integer sum, the same on every rank, whatever P and the arrival order --
+             because tf.clip_by_norm divides by the norm of the WHOLE table's gradient;
+          4. every owner steps its touched rows with the global norms, then decays and steps every other local row: TF's sparse Adam moves
+             every row every step, so an owner that received nothing still takes part in 3 and still runs 4.
+        clip_norm == 0: no clip, so no norm pass and no collective.  Set `tables.optimizer.lr_t` (lr * sqrt(1 - beta2^t) / (1 - beta1^t), t
+        = the ONE global step + 1, the same on every rank) before every backward -- ShardedDCNTrainer's train_spec.TrainStep does.
+        Not covered (each raises): with_linear=True, lookup_bags_train, row groups, graph capture of a step."""
+        if self.G > 1:
+            raise NotImplementedError("enable_training_adam: row groups (groups=%d) are trained with the owner-side Adagrad only" % self.G)
+        if not all(hasattr(self.backend, n) for n in ("make_adam", "adam_norm", "adam_apply")):
+            raise NotImplementedError("enable_training_adam: this backend has no owner-side Adam (make_adam / adam_norm / adam_apply)")
+        if not (0 <= beta1 < 1 and 0 <= beta2 < 1 and eps > 0 and clip_norm >= 0):
+            raise ValueError("enable_training_adam: 0 <= beta < 1, eps > 0, clip_norm >= 0")
+        self.optimizer = self.backend.make_adam(float(beta1), float(beta2), float(eps), float(clip_norm))
+        self._adam = True
+        self._adam_clip = float(clip_norm)
+        return self
+
+    def adam_state(self):
+        """(m, v): per slot this rank's [local rows, K] first and second moments (enable_training_adam first)."""
+        if not self._adam:
+            raise RuntimeError("call enable_training_adam() first")
+        return self.optimizer.ms, self.optimizer.vs
+
+    def _sum_norm_shares(self, share):
+        """share [F] int64: the bits of this owner's u64 fixed-point ||g||^2 sums -> [F] float64, every table's GLOBAL ||g||^2 in plain
+        units, the same value on every rank.  The high and low 32-bit halves are summed over the ranks as two int64 vectors (64 ranks x
+        2^32 cannot wrap) and recombined in double: an exact integer sum -- independent of P and of the order the shares arrive in --
+        rounded once.  On the host for gloo, through the device otherwise (as _max_over_ranks)."""
+        halves = torch.stack([(share >> 32) & 0xffffffff, share & 0xffffffff])
+        if self._collective():
+            if dist.get_backend(self.group) == "gloo":
+                h = halves.cpu()
+                dist.all_reduce(h, op=dist.ReduceOp.SUM, group=self.group)
+                halves = h.to(share.device)
+            else:
+                dist.all_reduce(halves, op=dist.ReduceOp.SUM, group=self.group)
+        return (halves[0].double() * 4294967296.0 + halves[1].double()) / 4294967296.0
+
+    def _refuse_adam_capture(self, t):
+        if self._adam and t.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("a sharded Adam step cannot be captured in a graph (its norm exchange is a collective between the two "
+                                      "halves of the owner's step)")
+
+    def _owner_step(self, payload, grad_rows):
+        """The owner-side step of the embedding rows over (payload, gradient rows) as received from all ranks."""
+        be = self.backend
+        if not self._adam:
+            return be.apply_adagrad(self.optimizer, payload, grad_rows)
+        self._refuse_adam_capture(payload)
+        norms = None
+        if self._adam_clip > 0:          # every rank, also one that received nothing: the sum is a collective
+            norms = self._sum_norm_shares(be.adam_norm(self.optimizer, payload, grad_rows))
+        be.adam_apply(self.optimizer, payload, grad_rows, norms)
 
     def lookup_train(self, ids, with_linear=False):
         """Differentiable lookup: emb [B_local, F*K] with a grad_fn (the tables themselves get no .grad).  Runs the fixed-capacity
@@ -769,6 +849,10 @@ class ShardedTables:
         order: the FTRL step reuses the Adagrad step's sort of the payload) -- one optimiser step."""
         if self.optimizer is None:
             raise RuntimeError("call enable_training(lr) first")
+        self._refuse_adam_capture(ids)                   # before anything is enqueued, not first inside backward()
+        if with_linear and self._adam:
+            raise NotImplementedError("lookup_train(with_linear=True) under enable_training_adam: the first-order rows' FTRL rides on the Adagrad "
+                                      "step's sort only")
         if with_linear:
             self._need_linear("lookup_train(with_linear=True)")
             if self._lin_hp is None:
@@ -820,7 +904,8 @@ class ShardedTables:
 
     def _backward_apply(self, saved, g_emb, g_lin=None):
         """g_lin (lookup_train(with_linear=True)): d loss / d lin [B_local, 1].  Its values go where the weights came back from and travel
-        the same exchange as the gradient rows; the owner's FTRL runs after its Adagrad, over the same payload, on that step's sort."""
+        the same exchange as the gradient rows; the owner's FTRL runs after its Adagrad, over the same payload, on that step's sort.
+        The exchange is the same under enable_training_adam; the owner's step (_owner_step) is then norm pass, norm sum over the ranks, apply."""
         K, G = self.K, self.G
         be = self.backend
         U = self.U
@@ -865,7 +950,7 @@ class ShardedTables:
             hdr = slabs[:, 0] & 0xffffffff
             pos = torch.arange(cap, device=slabs.device)
             pay = torch.where(pos.unsqueeze(0) < hdr.unsqueeze(1), slabs[:, 1:], torch.full_like(slabs[:, 1:], -1)).reshape(-1)
-            self.backend.apply_adagrad(self.optimizer, pay, grecv_l[0] if C == 1 else torch.cat(grecv_l, dim=0))
+            self._owner_step(pay, grecv_l[0] if C == 1 else torch.cat(grecv_l, dim=0))
             if g_lin is not None:
                 self._lin_ftrl(pay, plan.lback_all.view(-1), self.optimizer)
             return
@@ -882,7 +967,7 @@ class ShardedTables:
         dev = gsend.device
         grecv = torch.empty((recv.numel(), KW), dtype=torch.float32, device=dev)
         self._a2a(grecv.view(-1), gsend.view(-1), [c * KW for c in rc], [c * KW for c in sc])   # the forward exchange, reversed
-        self.backend.apply_adagrad(self.optimizer, recv, grecv)
+        self._owner_step(recv, grecv)
         if g_lin is not None:
             lsend = torch.empty(n * U, dtype=torch.float32, device=dev)
             self._lin_grad(g_lin, inv.view(-1, self.F), lsend)
@@ -1463,6 +1548,8 @@ class ShardedTables:
         self._no_groups("lookup_bags_train")
         if self.optimizer is None:
             raise RuntimeError("call enable_training(lr) first")
+        if self._adam:
+            raise NotImplementedError("lookup_bags_train under enable_training_adam: the bag records are trained with the owner-side Adagrad only")
         lin_comb = None
         if with_linear:
             self._need_linear("lookup_bags_train(with_linear=True)")
@@ -1983,3 +2070,137 @@ class ShardedESMMTrainer:
             if self.linear is not None:
                 ctr_logits, cvr_logits = ctr_logits + lin[:, 0:1], cvr_logits + lin[:, 1:2]
             return {"ctr_logits": ctr_logits, "cvr_logits": cvr_logits, "ctcvr_logits": ctcvr_logits_of(ctr_logits, cvr_logits)}
+
+
+def _dcn_columns(model):
+    """(the embedding columns in the input layer's name-sorted order = the sharded tables' slots, their common width) of a
+    dcn.DeepCrossNetwork the row-sharded trainer covers; ValueError naming the column otherwise."""
+    from .feature_column import EmbeddingColumn, WeightedCategoricalColumn
+    il = model.input_layer
+    cols = [c for c in il.columns if isinstance(c, EmbeddingColumn)]
+    if not cols:
+        raise ValueError("ShardedDCNTrainer: the model has no embedding columns to shard")
+    dim = cols[0].dimension
+    for c in cols:
+        if isinstance(c.categorical_column, WeightedCategoricalColumn):
+            raise ValueError("ShardedDCNTrainer: column %r: one-hot embedding columns only (weighted bags are not covered)" % c.name)
+        if getattr(c, "max_norm", None):
+            raise ValueError("ShardedDCNTrainer: column %r: max_norm is not carried by the sharded one-hot lookup" % c.name)
+        if c.dimension != dim:
+            raise ValueError("ShardedDCNTrainer: column %r: dimension %d, the other columns have %d (one common dimension)" % (c.name, c.dimension, dim))
+    return cols, dim
+
+
+class ShardedDCNTrainer:
+    """One synchronous multi-GPU training step of a dcn.DeepCrossNetwork over row-sharded embedding tables: the reference's train_op
+    (DeepCrossNetwork.py:264-290: tf.train.AdamOptimizer, every variable's gradient clipped on its own with tf.clip_by_norm(g, 100), a
+    decayed learning rate) with the embedding variables partitioned over the ranks.  The tables take the owner-side sparse Adam
+    (ShardedTables.enable_training_adam: the clip norm of a table is summed over its owners, every row of every shard moves every
+    step); the cross and deep parts are replicated, their gradients are summed with bucketed all-reduces and the per-tensor clip runs
+    on the SUMMED gradients, then the dense Adam steps.  Everything the one-GPU step knows -- the schedule, TF's epsilon placement, the
+    one-global-step bias corrections, l2_reg on the deep kernels -- IS train_spec.TrainStep; the tables' optimiser gets its lr_t from
+    the loop that serves TrainStep.sparse_adam.
+    The loss is _create_loss's MEAN over the GLOBAL batch: every rank back-propagates its summed cross entropy / the all-reduced batch
+    size, so the gradients that ADD over the ranks -- at the owners and in the all-reduce -- are the global mean loss's.  The l2_reg
+    term is a function of replicated weights: every rank adds l2_reg / P of it, so its gradient counts once after the sum.
+    Batch-norm statistics stay per rank: each rank normalises its own local batch and keeps its own moving averages, as each of the
+    reference's workers does with the batch it reads.
+    `model`'s one-hot embedding columns must share one width and carry no max_norm; its own embedding_weights are not used
+    (tables_from_model copies them into the shards).  weight_column and dnn_dropout raise NotImplementedError."""
+
+    def __init__(self, model, tables, group=None):
+        from .train_spec import CLIP_NORM, TrainStep
+        self.model, self.tables, self.group = model, tables, group
+        self.emb_cols, self.K = _dcn_columns(model)
+        hp = model.hparams
+        if hp.get("weight_column") is not None:
+            raise NotImplementedError("ShardedDCNTrainer: weight_column (the weight sum would have to be all-reduced with the batch size)")
+        if hp.get("dnn_dropout"):
+            raise NotImplementedError("ShardedDCNTrainer: dnn_dropout")
+        if tables.G != 1 or tables.F != len(self.emb_cols) or tables.K != self.K:
+            raise ValueError("ShardedDCNTrainer: the tables must hold F=%d slots of K=%d floats (tables_from_model), got G=%d F=%d K=%d"
+                             % (len(self.emb_cols), self.K, tables.G, tables.F, tables.K))
+        P = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.dense_params = [p for n, p in model.named_parameters() if "embedding_weights" not in n]
+        self.train = TrainStep(model, optimizer=hp.get("optimizer") or "Adam", optimizer_spec=hp.get("optimizer_spec"),
+                               learning_rate_spec=hp.get("learning_rate_spec"), l2_reg=(hp["l2_reg"] / P if hp.get("l2_reg") else None),
+                               l2_params=[lin.weight for lin in model.hidden], params=self.dense_params,
+                               after_backward=lambda: allreduce_grads(self.dense_params, self.group))
+        if self.train._tf_adam_eps is None:
+            raise ValueError("ShardedDCNTrainer: the owner-side update is the reference's Adam (optimizer='Adam')")
+        tables.enable_training_adam(self.train._beta1, self.train._beta2, self.train._tf_adam_eps, CLIP_NORM)
+        self.train.sparse_adam.append(tables.optimizer)            # lr_t of the shards from the loop that serves the one-GPU tables
+
+    @classmethod
+    def tables_from_model(cls, model, group=None, **kw):
+        """The ShardedTables of `model` (every rank holds the same replicated model): slot f = the f-th embedding column in the input
+        layer's name-sorted order.  kw: ShardedTables' options (partitions=, chunks=, mode=, ...)."""
+        cols, _ = _dcn_columns(model)
+        il = model.input_layer
+        full = ops.plain_list(il.embedding_weights)
+        return ShardedTables.from_full([full[il.emb_cols.index(c)].data for c in cols], group=group, **kw)
+
+    @property
+    def global_step(self):
+        return self.train.global_step
+
+    def _x0(self, features, train):
+        """The input layer's output over the sharded tables: the columns in name-sorted order, embedding columns as slices of the looked-up
+        matrix (runs of adjacent ones as one slice), numeric and indicator columns as the input layer forms them.  (torch plumbing.)"""
+        from ._input import collect_ids
+        from .feature_column import EmbeddingColumn, NumericColumn
+        il, dev, K = self.model.input_layer, self.tables.device, self.K
+        got = collect_ids(self.emb_cols, features, dev)
+        if got[0] != "onehot":
+            raise ValueError("ShardedDCNTrainer: one id per sample and embedding column (multi-hot features are not covered)")
+        ids = got[1]
+        B = ids.shape[0]
+        emb = self.tables.lookup_train(ids) if train else self.tables.lookup(ids)
+        pieces, f, run0 = [], 0, None
+        for c in list(il.columns) + [None]:
+            if isinstance(c, EmbeddingColumn):
+                run0 = f if run0 is None else run0
+                f += 1
+                continue
+            if run0 is not None:
+                pieces.append(emb[:, run0 * K:f * K])
+                run0 = None
+            if isinstance(c, NumericColumn):
+                pieces.append(features[c.key].to(device=dev, dtype=torch.float32).reshape(-1, c.dimension))
+            elif c is not None:
+                pieces.append(il._indicator(c, features, dev, B))
+        return (pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)), B
+
+    def _global_batch(self, B, device):
+        """The batch size over ALL ranks as a device scalar (one all-reduce of one number: on the host for gloo, no host read otherwise)."""
+        t = torch.tensor([float(B)], dtype=torch.float32)
+        if not dist.is_initialized() or dist.get_world_size(self.group) == 1:
+            return t.to(device)
+        if dist.get_backend(self.group) == "gloo":
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+            return t.to(device)
+        t = t.to(device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t
+
+    def step(self, features, labels):
+        """features: the dict the model takes (this rank's local batch); labels [B_local, 1] -> this rank's share of the global-batch
+        mean loss, its l2 share included (detached; the shares ADD over the ranks)."""
+        from ._input import raise_pending
+        x0, B = self._x0(features, True)                   # every owner's rows update inside backward()
+        logits = self.model(x0)
+        raise_pending()
+        y = labels.to(device=logits.device, dtype=torch.float32).reshape(logits.shape)
+        total = torch.nn.functional.binary_cross_entropy_with_logits(logits, y, reduction="sum")
+        loss, _ = self.train(total / self._global_batch(B, logits.device).clamp_min(1.0).squeeze(0))
+        return loss
+
+    @torch.no_grad()
+    def predict(self, features):
+        """The model's predictions dict for this rank's local batch, x0 assembled from the inference lookup in the same way."""
+        from ._input import raise_pending
+        with _eval_mode(self.model):
+            x0, _ = self._x0(features, False)
+            out = self.model.predict(x0)
+            raise_pending()
+            return out

@@ -169,9 +169,15 @@ _SPEC_KEYS = {"epsilon": "eps", "beta1": None, "beta2": None}   # tf.train.AdamO
 class TrainStep:
     """train_op of the reference DCN (_get_train_op_fn): one call = backward + per-tensor clip + optimizer step with the
     decayed learning rate, global_step += 1.  `optimizer` is a torch optimizer class or one of the names above;
-    `optimizer_spec` uses the tf.train names (epsilon, beta1, beta2)."""
+    `optimizer_spec` uses the tf.train names (epsilon, beta1, beta2).
+    Two optional arguments serve a caller that keeps the embedding tables elsewhere (shard.ShardedDCNTrainer: row-sharded tables with
+    an owner-side Adam); with their defaults nothing changes.  params: the parameters this step owns instead of all of `model`'s -- the
+    model's own embedding tables then get no optimiser of any kind here (such a caller appends its tables' optimiser to .sparse_adam:
+    every object in that list has its .lr_t set before backward()).  after_backward: called with no arguments between backward() and
+    the per-tensor clip (where a multi-GPU step sums the dense gradients over the ranks: the reference clips the summed gradient)."""
 
-    def __init__(self, model, optimizer="Adam", optimizer_spec=None, learning_rate_spec=None, l2_reg=None, l2_params=None):
+    def __init__(self, model, optimizer="Adam", optimizer_spec=None, learning_rate_spec=None, l2_reg=None, l2_params=None, params=None,
+                 after_backward=None):
         if not isinstance(optimizer_spec or {}, dict):
             raise ValueError("optimizer_spec must be a dict.")
         spec = dict(optimizer_spec or {})
@@ -197,13 +203,14 @@ class TrainStep:
             # eps_torch = eps_tf / sqrt(1 - b2^t) (31.6x larger at t = 1 for b2 = 0.999); __call__ sets it every step.
             self._tf_adam_eps = float(kw.get("eps", 1e-8))
             self._beta2 = float(betas[1])
-        self.params = [p for p in model.parameters() if p.requires_grad]
+        self.params = [p for p in (model.parameters() if params is None else params) if p.requires_grad]
+        self.after_backward = after_backward
         # The embedding tables under Adam: the HIP update (ops.SparseAdam: sorted touched rows + one streaming pass over every row of w, m,
         # v -- TF's sparse Adam moves all rows every step) instead of a scatter into a dense gradient, torch's multi-tensor Adam over
         # 1.7 GB of tables and ~10 small torch kernels per table (DIR_TRAIN_HIP_ADAM=0 keeps that path).
         self.sparse_adam = []
         il = getattr(model, "input_layer", None)
-        if cls is torch.optim.Adam and il is not None and hasattr(il, "fused_sparse_adam") and os.environ.get("DIR_TRAIN_HIP_ADAM", "1") == "1" \
+        if params is None and cls is torch.optim.Adam and il is not None and hasattr(il, "fused_sparse_adam") and os.environ.get("DIR_TRAIN_HIP_ADAM", "1") == "1" \
                 and not kw.get("amsgrad") and not kw.get("weight_decay"):
             self.sparse_adam, owned = il.fused_sparse_adam(betas[0], betas[1], self._tf_adam_eps, CLIP_NORM)
             owned = {id(p) for p in owned}
@@ -259,6 +266,8 @@ class TrainStep:
             opt.lr_t = lr * math.sqrt(1.0 - self._beta2 ** t) / (1.0 - self._beta1 ** t)
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
+        if self.after_backward is not None:
+            self.after_backward()
         # Tables owned by the HIP Adam whose gradient did NOT go through the sink this step (multi-hot / weighted columns: their backward
         # returns sparse .grad): the same step on the same m / v, by torch ops -- never left without an optimiser, never accumulating.
         for opt in self.sparse_adam:

@@ -1165,6 +1165,38 @@ int dir_sparse_adagrad_sorted_payload_f32(float* const* tables, float* const* ac
                                           int64_t n, const float* grad, float lr, const int64_t* row_base,
                                           int64_t total_rows, void* workspace, int64_t workspace_bytes, dir_stream_t stream);
 
+/* dir_sparse_adam_f32 on ROW-SHARDED tables: the owner's step over the payload it received (shard.ShardedTables.enable_training_adam; the
+ * reference's DCN train_op on partitioned embedding variables).  payload [n] int64 (p = local_row * F + slot, p < 0 pruned or padding; a
+ * row outside the slot's local rows sorts behind every row) as received from all ranks, grad [n, K] in payload order, tables / ms / vs /
+ * row_base / total_rows describe this rank's shards -- dir_sparse_adagrad_sorted_payload_f32's contract.  Sparse Adam differs from the
+ * other owner-side updates in three ways, and the step is cut in two for the first:
+ *   - tf.clip_by_norm(g, clip) divides by the norm of the table's WHOLE gradient; with the rows spread over P owners each owner sees its
+ *     share of ||g||^2 only.  dir_sparse_adam_payload_norm_f32 sorts the payload and writes this owner's share per table into norm2
+ *     (device, 64 x u64, zeroed by the entry; 2^-32 fixed point: sum over its touched rows r of ||S_r||^2, S_r the sum of the row's
+ *     entries; integer adds, so the sum does not depend on arrival order).  The caller adds the shares up over the ranks -- an exact
+ *     integer sum; 64 shares can overflow a u64, so it is handed back as a DOUBLE per table, ||g||^2 in plain units (share / 2^32) --
+ *     and dir_sparse_adam_payload_apply_f32 clips with norm2_global (device double [F]; NULL exactly when clip_norm == 0).
+ *   - every row moves every step: apply steps the touched rows (AdamUpd, on the norm entry's sort when sorted != 0: that entry has just
+ *     sorted THIS payload into THIS workspace on THIS stream) and then streams over every other local row (m *= beta1, v *= beta2, var
+ *     -= lr_t * m / (sqrt(v) + eps)).  n == 0 -- an owner that received nothing -- runs that pass alone.
+ *   - lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) is a function of ONE global step: the caller hands every owner the same value.
+ * Every run sum S_r is formed in DOUBLE (tile partials too) and rounded to fp32 once: where duplicates of a row sit in the payload depends
+ * on the order of the bucket pass's atomics, and the step must not -- two runs of the same step end bitwise equal, short of a double
+ * sum that lands within 2^-53 of an fp32 rounding boundary (2^-29 per sum).
+ * workspace: dir_sparse_adam_payload_workspace_bytes(n, F, K, total_rows) bytes, 256-byte aligned (the sort area of n flat entries with
+ * carry rows of K doubles; n == 0 is legal and needs none).  marks: (total_rows rounded up to 256) bytes, zero between calls, owned by
+ * the caller -- outside the workspace because the sort area is re-allocated when n grows and the marks must survive that; first_call
+ * != 0 zeroes them.
+ * Limits as dir_sparse_adam_f32: F <= 64, K % 4 == 0 with K / 4 dividing 64, total_rows < 2^32-1 (0: this owner holds no rows, nothing
+ * to do), n < 2^31.  Every argument is checked before the first HIP call. */
+int64_t dir_sparse_adam_payload_workspace_bytes(int64_t n, int F, int K, int64_t total_rows);
+int dir_sparse_adam_payload_norm_f32(int F, int K, const int64_t* payload, int64_t n, const float* grad, const int64_t* row_base,
+                                     int64_t total_rows, uint64_t* norm2, void* workspace, int64_t workspace_bytes, dir_stream_t stream);
+int dir_sparse_adam_payload_apply_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* payload, int64_t n,
+                                      const float* grad, float lr_t, float beta1, float beta2, float eps, float clip_norm,
+                                      const double* norm2_global, const int64_t* row_base, int64_t total_rows, unsigned char* marks,
+                                      void* workspace, int64_t workspace_bytes, int sorted, int first_call, dir_stream_t stream);
+
 /* FTRL-Proximal on sparse rows through the same sorted machinery (the reference's linear_optimizer='Ftrl', deepFM.py:58;
  * [TF-upstream] tf.train.FtrlOptimizer with learning_rate_power = -0.5): per touched row, g = sum of its gradient rows,
  *   n' = n + g^2; sigma = (sqrt(n') - sqrt(n)) / lr; z' = z + g - sigma*w;
