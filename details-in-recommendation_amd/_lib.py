@@ -232,6 +232,8 @@ SIGNATURES = {
     "dir_sparse_ftrl_rows_units_sorted_payload_f32": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                               c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "dir_shard_finish_groups_f32": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp]),
+    "dir_rows_scatter_sum_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64]),
+    "dir_rows_scatter_sum_f32": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "dir_shard_grad_groups_f32": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp]),
     "dir_shard_bags_linear_pool_f32": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp]),
     "dir_shard_bags_linear_combine_f32": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i64, c_i32,

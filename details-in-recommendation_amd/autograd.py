@@ -299,7 +299,7 @@ class DinAttentionPool(torch.autograd.Function):
     rows and candidate rows) and no autograd graph is built."""
 
     @staticmethod
-    def forward(ctx, table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, normalize):
+    def forward(ctx, table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, normalize, arith=None):
         ctx.normalize = bool(normalize)
         B, T = hist.shape
         fused = ops.din_backward_supported(table.shape[1], T, W1.shape[1], W2.shape[1]) and not _DIN_COMPOSITE_BACKWARD
@@ -308,11 +308,11 @@ class DinAttentionPool(torch.autograd.Function):
             # the forward leaves z1 / z2 of every history row in a workspace this node owns: the backward recomputes nothing
             out, scores, ctx.saved_state = ops.din_attention_pool_save(table.detach(), hist, hist_len, cand, W1.detach(), b1.detach(),
                                                                        W2.detach(), b2.detach(), W3.detach(), b3.detach(), normalize=normalize,
-                                                                       range_of=(table, W1, W2, W3))
+                                                                       range_of=(table, W1, W2, W3), arith=arith)
         else:
             res = ops.din_attention_pool(table.detach(), hist, hist_len, cand, W1.detach(), b1.detach(), W2.detach(),
                                          b2.detach(), W3.detach(), b3.detach(), normalize=normalize, want_scores=fused,
-                                         range_of=(table, W1, W2, W3))
+                                         range_of=(table, W1, W2, W3), arith=arith)
             out, scores = res if fused else (res, None)   # the attention weights [B, T] feed the backward (no softmax recompute)
         ctx.has_scores = scores is not None
         ctx.save_for_backward(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, *([scores] if scores is not None else []))
@@ -338,7 +338,7 @@ class DinAttentionPool(torch.autograd.Function):
                 r["ga"].mul_(ok.unsqueeze(1))                       # (a view of r["grows"]: no [N + B, K] copy for the concatenation, 428 MB at cfg 4)
                 gtab = torch.sparse_coo_tensor(idx, r["grows"], table.shape)
             return (gtab, None, None, None, r["gW1"], r["gb1"], r["gW2"], r["gb2"], r["gW3"].reshape(W3.shape),
-                    r["gb3"].reshape(b3.shape), None)
+                    r["gb3"].reshape(b3.shape), None, None)
         valid = hist >= 0
         if hist_len is not None:
             valid &= torch.arange(T, device=dev).unsqueeze(0) < hist_len.clamp(0, T).unsqueeze(1)
@@ -389,11 +389,12 @@ class DinAttentionPool(torch.autograd.Function):
             idx = torch.cat([ids_h, cand.clamp(min=0)]).unsqueeze(0)
             gtab = torch.sparse_coo_tensor(idx, torch.cat([gh, ga * cok.unsqueeze(1)]), table.shape)
         return (gtab, None, None, None, gW1, dpre1.sum(dim=0), gW2, dpre2.sum(dim=0), gW3.reshape(W3.shape),
-                ds.sum().reshape(b3.shape), None)
+                ds.sum().reshape(b3.shape), None, None)
 
 
-def din_attention_pool(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, normalize=False):
-    return DinAttentionPool.apply(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, normalize)
+def din_attention_pool(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, normalize=False, arith=None):
+    """arith: the MFMA layers' arithmetic by name (ops.din_arith; None: measured from the table and the weights)."""
+    return DinAttentionPool.apply(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, normalize, arith)
 
 
 # ---- PReLU / Dice layers and the DIN unit's row-list training path (round 5; csrc/din_rows_train.hip) -----------------------------------------

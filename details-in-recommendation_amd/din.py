@@ -125,15 +125,16 @@ class DINAttentionPool(nn.Module):
         s2, t2 = self.act2.scale_shift()
         return ops.din_act_params(self.b1.numel(), self.b2.numel(), self.act1.alpha, self.act2.alpha, s1, t1, s2, t2)
 
-    def _composite(self, hist, hist_len, cand):
+    def _composite(self, hist, hist_len, cand, table=None):
         """The unit as differentiable torch ops (PReLU / Dice in TRAIN mode): same definition as include/dir_hip.h A13."""
         B, T = hist.shape
-        K = self.table.shape[1]
+        table = self.table if table is None else table
+        K = table.shape[1]
         valid = hist >= 0
         if hist_len is not None:
             valid = valid & (torch.arange(T, device=hist.device).unsqueeze(0) < hist_len.clamp(0, T).unsqueeze(1))
-        h = torch.nn.functional.embedding(hist.clamp_min(0), self.table, sparse=True)                      # [B, T, K]
-        a = torch.nn.functional.embedding(cand.clamp_min(0), self.table, sparse=True) * (cand >= 0).unsqueeze(1)
+        h = torch.nn.functional.embedding(hist.clamp_min(0), table, sparse=True)                           # [B, T, K]
+        a = torch.nn.functional.embedding(cand.clamp_min(0), table, sparse=True) * (cand >= 0).unsqueeze(1)
         ae = a.unsqueeze(1).expand(B, T, K)
         u = torch.cat([h, ae, h - ae, h * ae], dim=-1)
         z1 = u @ self.W1 + self.b1
@@ -149,7 +150,7 @@ class DINAttentionPool(nn.Module):
             w = s * valid
         return (w.unsqueeze(-1) * h).sum(dim=1)
 
-    def _rows_train(self, hist, hist_len, cand):
+    def _rows_train(self, hist, hist_len, cand, table=None):
         """PReLU / Dice in training on HIP kernels (round 5; csrc/din_rows_train.hip): the unit over the compact list of valid (sample, position)
         rows -- X' = [h | h * a | a] (dir_din_feat_rows_f32), pre1 = X' [Wh + Wd; Wp; Wa - Wd] + b1 and pre2 = y1 W2 + b2 on the dense
         kernels (forward, dL/dx and dL/dW: dense._DenseFn), the activations with the batch's statistics (autograd.ActRows: Dice =
@@ -158,8 +159,9 @@ class DINAttentionPool(nn.Module):
         formulation, kept for shapes these kernels do not take); the table gets a sparse gradient.  -> [B, K], or None: not covered."""
         from .dense import _DenseFn, _Units1Fn
         B, T = hist.shape
-        K, H1, H2 = self.table.shape[1], self.b1.numel(), self.b2.numel()
-        if (not self.table.is_cuda or self.table.dtype != torch.float32 or K % 4 or K > 256 or H1 % 4 or H2 % 4 or H1 < 16 or H2 < 16
+        table = self.table if table is None else table
+        K, H1, H2 = table.shape[1], self.b1.numel(), self.b2.numel()
+        if (not table.is_cuda or table.dtype != torch.float32 or K % 4 or K > 256 or H1 % 4 or H2 % 4 or H1 < 16 or H2 < 16
                 or H1 > 1024 or H2 > 1024 or B == 0):
             return None
         valid = hist >= 0
@@ -171,7 +173,7 @@ class DINAttentionPool(nn.Module):
         ids_h = hist[b_idx, j_idx]
         cnt = valid.sum(dim=1)
         row_off = (torch.cumsum(cnt, 0) - cnt).contiguous()
-        X, Hc = ag.DinFeatRows.apply(self.table, ids_h, b_idx, row_off, cand)
+        X, Hc = ag.DinFeatRows.apply(table, ids_h, b_idx, row_off, cand)
         Wh, Wa, Wd, Wp = self.W1[:K], self.W1[K:2 * K], self.W1[2 * K:3 * K], self.W1[3 * K:]
         Wc = torch.cat([Wh + Wd, Wp, Wa - Wd], dim=0)               # [3K, H1]: autograd hands dL/dW1 back through this regrouping
         pre1 = _DenseFn.apply(X, Wc.t(), self.b1, False)
@@ -181,18 +183,23 @@ class DINAttentionPool(nn.Module):
         sc = _Units1Fn.apply(y2, self.W3.reshape(1, -1), self.b3)   # [N, 1]
         return ag.DinPoolRows.apply(sc.reshape(-1), Hc, row_off, B, self.normalize)
 
-    def forward(self, hist, hist_len, cand, want_scores=False):
+    def forward(self, hist, hist_len, cand, want_scores=False, table=None, arith=None):
+        """table (optional): the rows the unit reads INSTEAD of self.table -- the received rows of a sharded lookup, with hist / cand the
+        positions in them (shard.ShardedDINTrainer); it gets the sparse gradient in training.  arith: the arithmetic of the MFMA layers by
+        name (ops.din_arith), for a caller that knows the table's magnitude without measuring `table` (ops.din_arith_name).  Both unused:
+        the unit over its own table, as ever."""
+        tab = self.table if table is None else table
         train = torch.is_grad_enabled() and not want_scores and any(p.requires_grad for p in self.parameters())
         if train and self.activation == "sigmoid":
-            return ag.din_attention_pool(self.table, hist, hist_len, cand, self.W1, self.b1, self.W2, self.b2, self.W3,
-                                         self.b3, normalize=self.normalize)       # sparse table gradient
+            return ag.din_attention_pool(tab, hist, hist_len, cand, self.W1, self.b1, self.W2, self.b2, self.W3,
+                                         self.b3, normalize=self.normalize, arith=arith)       # sparse table gradient
         if train:
-            out = self._rows_train(hist, hist_len, cand) if ROWS_TRAIN else None
-            return out if out is not None else self._composite(hist, hist_len, cand)
-        return ops.din_attention_pool(self.table.data, hist, hist_len, cand, self.W1.data, self.b1.data, self.W2.data,
-                                      self.b2.data, self.W3.data, self.b3.data, normalize=self.normalize,
-                                      want_scores=want_scores, activation=self.activation, act_params=self.act_params(),
-                                      range_of=(self.table, self.W1, self.W2, self.W3, self.b1, self.b2))
+            out = self._rows_train(hist, hist_len, cand, table) if ROWS_TRAIN else None
+            return out if out is not None else self._composite(hist, hist_len, cand, table)
+        return ops.din_attention_pool(tab.detach() if table is not None else self.table.data, hist, hist_len, cand, self.W1.data, self.b1.data,
+                                      self.W2.data, self.b2.data, self.W3.data, self.b3.data, normalize=self.normalize,
+                                      want_scores=want_scores, activation=self.activation, act_params=self.act_params(), arith=arith,
+                                      range_of=(tab, self.W1, self.W2, self.W3, self.b1, self.b2))
 
 
 class DIN(nn.Module):
@@ -250,28 +257,31 @@ class DIN(nn.Module):
         nn.init.zeros_(self.logits_layer.bias)
         self._cand_ts = None
 
-    def _candidate_embedding(self, cand):
-        """The candidate ad's own embedding row (a one-slot lookup of the goods table: csrc/embedding_bag.hip)."""
-        table = self.attention.table
+    def _candidate_embedding(self, cand, table=None):
+        """The candidate ad's own embedding row (a one-slot lookup of the goods table: csrc/embedding_bag.hip).  table: see forward."""
+        table = self.attention.table if table is None else table
         if torch.is_grad_enabled() and table.requires_grad:
             return torch.nn.functional.embedding(cand.clamp_min(0), table, sparse=True) * (cand >= 0).unsqueeze(1)
-        if self._cand_ts is None or self._cand_ts.tables[0].data_ptr() != table.data_ptr():
+        if self._cand_ts is None or self._cand_ts.tables[0].data_ptr() != table.data_ptr() or self._cand_ts.tables[0].shape != table.shape:
             self._cand_ts = ops.TableSet([table.data])
         return ops.embedding_bag(self._cand_ts, cand.reshape(-1, 1).contiguous())
 
-    def forward(self, features):
+    def forward(self, features, table=None, ids=None, arith=None):
+        """table, ids = (hist [B, T], cand [B]), arith (optional, together): the goods rows come from `table` -- the received rows of a
+        sharded lookup -- through the positions `ids` instead of from the model's own table through features' ids (DINAttentionPool.forward;
+        shard.ShardedDINTrainer).  features still supplies the lengths and the profile / context columns."""
         hk, lk, ck = self.keys
-        hist, cand = features[hk], features[ck]
+        hist, cand = (features[hk], features[ck]) if ids is None else ids
         hist_len = features.get(lk) if hasattr(features, "get") else None
-        dev = self.attention.table.device
+        dev = self.attention.table.device if table is None else table.device
         hist, cand = hist.to(device=dev, dtype=torch.int64), cand.to(device=dev, dtype=torch.int64).reshape(-1)
         if hist_len is not None:
             hist_len = hist_len.to(device=dev, dtype=torch.int32).reshape(-1)
-        pooled = self.attention(hist, hist_len, cand)
+        pooled = self.attention(hist, hist_len, cand) if table is None else self.attention(hist, hist_len, cand, table=table, arith=arith)
         pieces = []
         if self.input_layer is not None:
             pieces.append(self.input_layer(features)[:, :self.input_layer.column_num])
-        pieces += [pooled, self._candidate_embedding(cand)]
+        pieces += [pooled, self._candidate_embedding(cand, table)]
         net = torch.cat(pieces, dim=1)
         for lin, act in zip(self.hidden, self.acts):
             if self.dnn_activation_fn == "relu":

@@ -635,6 +635,20 @@ def din_arith(table, weights, arith=None):
     return DIN_ARITHS["f16x2"]
 
 
+def din_arith_name(table_absmax, weights):
+    """din_arith's verdict with the table's magnitude GIVEN instead of measured -- the received rows of a sharded lookup change with every
+    call, and what bounds them is the sharded table's magnitude (shard.ShardedTables.absmax()).  -> "f16x2" | "bf16x3", or None when the
+    DIR_DIN_ARITH switch decides (pass it on as arith=: nothing is measured then)."""
+    if os.environ.get("DIR_DIN_ARITH"):
+        return None
+    if not f16_range_ok(float(table_absmax)):
+        return "bf16x3"
+    for w in weights:
+        if not f16_range_ok(weight_absmax(w, DIN_RANGE_RECHECK)):
+            return "bf16x3"
+    return "f16x2"
+
+
 # development switch: 0 = the fp16 x 2 forward stays on din_wave_k (one wave per sample) instead of the packed kernel of round 6
 DIN_PACKED = os.environ.get("DIR_DIN_PACKED", "1") != "0"
 _DIN_PACK_WS = {}
@@ -866,7 +880,7 @@ class DinTrainPlan:
         self.N, self.n_tiles = (int(v) for v in torch.stack([incl[-1], tincl[-1]]).tolist()) if B else (0, 0)     # the one host read
 
 
-def din_attention_pool_save(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, normalize=False, plan=None, range_of=None):
+def din_attention_pool_save(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, normalize=False, plan=None, range_of=None, arith=None):
     """Training forward of the (K 64, H1 <= 80, H2 <= 48, T <= 64) unit (include/dir_hip.h: dir_din_attention_pool_save_f32): as
     din_attention_pool(..., want_scores=True), and every history row's hidden activations stay in a workspace for
     din_attention_pool_backward(..., saved=...), which then recomputes nothing.  -> out, scores, (plan, workspace)."""
@@ -898,7 +912,7 @@ def din_attention_pool_save(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3,
     out = torch.empty((B, K), dtype=torch.float32, device=table.device)
     scores = torch.empty((B, T), dtype=torch.float32, device=table.device)
     rsrc = range_of if range_of is not None else (table, W1, W2, W3)
-    code = din_arith(rsrc[0], rsrc[1:]) if B > 0 else -1
+    code = din_arith(rsrc[0], rsrc[1:], arith) if B > 0 else -1
     _lib.check(lib.dir_din_attention_pool_save_arith_f32(_ptr(table), K, _ptr(hist), _ptr(hist_len), _ptr(cand), T, _ptr(args[0]), _ptr(args[1]), H1,
                                                          _ptr(args[2]), _ptr(args[3]), H2, _ptr(args[4]), _ptr(args[5]), int(bool(normalize)), code, B,
                                                          _ptr(out), _ptr(scores), _ptr(plan.tile_off), plan.n_tiles, _ptr(ws), need, _stream()))
@@ -2420,6 +2434,49 @@ def shard_grad_groups(grads, inv2d, K, send):
     _lib.check(_lib.load().dir_shard_grad_groups_f32(_host_ptrs(grads), ld, G, K, _ptr(inv2d), inv2d.stride(0), inv2d.stride(1), F, B,
                                                      _ptr(send), send.shape[0], _stream()))
     return send
+
+
+_SCATTER_WS = {}
+
+
+def rows_scatter_sum(idx, vals, R, out=None, K=None):
+    """Sparse rows summed into a dense slab (include/dir_hip.h: dir_rows_scatter_sum_f32): idx [n] int64 positions, vals [n, >= K] fp32 with
+    unit inner stride (K: the leading floats of a row that count; default: all) -> out [R, K], out[r] = sum of vals[i, :K] over
+    idx[i] == r, zeros where nobody names r.  Entries with idx < 0 or idx >= R are dropped.  Sorted, compensated, no float atomics: the
+    same bits on every call; a row named once is that entry's row bit for bit.  The workspace is cached per (device, stream) and grows
+    with the largest call: a call can be captured in a HIP graph after one eager call of the same size."""
+    _dev(idx, torch.int64, "idx")
+    _dev(vals, torch.float32, "vals")
+    if idx.dim() != 1 or not idx.is_contiguous():
+        raise ValueError("rows_scatter_sum: idx must be a contiguous [n] tensor")
+    n = idx.shape[0]
+    if vals.dim() != 2 or vals.shape[0] != n or (n and vals.stride(1) != 1):
+        raise ValueError("rows_scatter_sum: vals must be [n, >= K] with unit inner stride")
+    K = int(vals.shape[1] if K is None else K)
+    R = int(R)
+    if not 0 < K <= vals.shape[1]:
+        raise ValueError("rows_scatter_sum: 0 < K <= vals.shape[1]")
+    if out is None:
+        out = torch.empty((R, K), dtype=torch.float32, device=vals.device)
+    _dev(out, torch.float32, "out")
+    if out.shape != (R, K) or not out.is_contiguous():
+        raise ValueError("rows_scatter_sum: out must be a contiguous [R, K] tensor")
+    lib = _lib.load()
+    need = int(lib.dir_rows_scatter_sum_workspace_bytes(n, K, R))
+    if need < 0:
+        raise _lib.DirError(-4, "rows_scatter_sum: unsupported size (n < 2^30, R < 2^32-1)")
+    if torch.cuda.is_current_stream_capturing():
+        # a capture gets a workspace from the graph's own pool (nothing is read across calls): an eager call never shares it with a replay
+        ws = torch.empty(need + 256, dtype=torch.uint8, device=vals.device)
+    else:
+        key = (vals.device, int(_stream().value or 0))
+        ws = _SCATTER_WS.get(key)
+        if ws is None or ws.numel() < need + 256:
+            ws = _SCATTER_WS[key] = torch.empty(need + 256, dtype=torch.uint8, device=vals.device)
+    ld = vals.stride(0) if n > 1 else max(K, vals.shape[1])
+    _lib.check(lib.dir_rows_scatter_sum_f32(_ptr(idx), _ptr(vals), ld, n, K, R, _ptr(out), ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256),
+                                            need, _stream()))
+    return out
 
 
 def shard_linear_gather_units(lin_ts, recv, P, cap, out):

@@ -38,6 +38,11 @@ DCN trains with the reference's own optimiser on the shards (enable_training_ada
 clip norm.  The clip norm is a property of the whole table, so the owner's step is cut in two around one all-reduce of the [F] norm shares
 (an exact integer sum), and every local row moves every step, also on an owner that received nothing.
 
+DIN's goods table lives on the shards too (ShardedDINTrainer): a sample's T history ids and its candidate are T + 1 entries of a one-slot
+lookup without a finish pass, de-duplicated; the unit's kernels read the received rows through the entries' positions.  What training needs
+for that is the transpose of a de-duplicated lookup -- many entry gradients summed into the one slab position they share -- as a kernel
+(backend.rows_scatter_sum: lookup_train(dedup=True), lookup_rows_train / backward_rows).
+
 The collectives are torch.distributed.all_to_all_single (backend "nccl" = RCCL on ROCm; "gloo" in the CPU tests).
 world_size == 1 skips the collectives (unless force_collective) but still runs the three HIP steps.  The HIP steps sit
 behind a small backend object so that the CPU (gloo) tests can stand the oracle in for them; the default backend is the
@@ -221,6 +226,12 @@ class HipBackend:
             return ops.gather_fm(ts, inv2d, out=out, fm=fm)
         return ops.embedding_bag(ts, inv2d, out=out), None
 
+    def rows_scatter_sum(self, idx, vals, R, out):
+        """Requester, backward: out [R, K] = the rows of vals [n, K] summed per position idx [n] (< 0: dropped), zeros where nobody
+        points -- the transpose of reading `out` through idx, also when many entries share a position (a de-duplicated lookup).
+        HIP: sorted, compensated run sums, no float atomics; a position named once gets its entry's row bit for bit."""
+        ops.rows_scatter_sum(idx, vals, R, out=out)
+
     # ---- row groups (ShardedTables(groups=G), G > 1): the finish pass that de-interleaves, and its transpose --------
     def finish_groups(self, back, inv2d, K, outs):
         """Requester: back [n, G*K], inv2d [Bc, F] -> outs[g][b, f*K:(f+1)*K] = group g's piece of row inv2d[b, f] (zeros where < 0);
@@ -370,6 +381,8 @@ class _Plan:
         dev, P, F, K = st.device, st.P, st.F, st.KW     # (KW: the stored row, G * K floats with row groups)
         self.B, self.cap = B, cap
         self.train = train            # the training pipeline's plan: its verdicts move _cap_train, not _cap (_learn)
+        self.slot = None              # which capacity the plan's slabs follow (_plan)
+        self.dedup = False            # a de-duplicated training plan: positions shared by many entries (the backward sums into them)
         self.P, self.device, self.lrows = P, dev, None
         C = self.C = st._C()
         per = -(-B // C) if B else 0
@@ -385,8 +398,14 @@ class _Plan:
         self.counts = torch.zeros((C, P), **i64)
         self.flags = torch.zeros((C, 1), dtype=torch.int32, device=dev)
         self.ws = [st.backend.new_workspace(dev) for _ in range(C)]
-        self.rows = [torch.empty((P * cap, K), dtype=torch.float32, device=dev) for _ in range(C)]
-        self.back = self.rows if alias else [torch.empty((P * cap, K), dtype=torch.float32, device=dev) for _ in range(C)]
+        # one matrix for all micro-batches (chunk c's positions start at c * P * cap): lookup_rows_train hands it out whole, and a consumer
+        # that needs the whole local batch in ONE kernel call (ShardedDINTrainer.predict) reads it through offset positions
+        # (zeros once, here: a consumer that reads position 0 for a pruned id and multiplies by 0 -- the DIN unit's candidate row -- must
+        # never meet the NaNs of uninitialised memory behind a slab's valid rows)
+        self.rows_all = torch.zeros((C * P * cap, K), dtype=torch.float32, device=dev)
+        self.back_all = self.rows_all if alias else torch.zeros_like(self.rows_all)
+        self.rows = [self.rows_all[c * P * cap:(c + 1) * P * cap] for c in range(C)]
+        self.back = [self.back_all[c * P * cap:(c + 1) * P * cap] for c in range(C)]
         self.cstat = torch.zeros((C, 2), **i64)           # per chunk [overflow, max demand] of THIS rank (diagnostic)
         self.stat = torch.zeros(2, **i64)                 # ... over all chunks and ranks, read off the received slab headers
         self.host = torch.empty(2, dtype=torch.int64, pin_memory=dev.type == "cuda")
@@ -489,6 +508,34 @@ class _RowsLookup:
         return list(self.chunks)
 
 
+class _RowsTrainLookup:
+    """Handle of ShardedTables.lookup_rows_train: .rows [R, K] (the received rows of all micro-batches, one matrix), .inv [B, F] int64 (every
+    entry's position in .rows, < 0: pruned) and backward_rows, which runs exactly once."""
+
+    def __init__(self, st, saved, rows, inv):
+        self.st, self.saved, self.rows, self.inv = st, saved, rows, inv
+
+    def backward_rows(self, idx, grad_rows):
+        """idx [m] int64: positions in .rows (< 0: dropped; any order, any number of entries per position); grad_rows [m, K]: d loss / d
+        .rows[idx[i]] of entry i.  The entries of a position are summed in entry order (backend.rows_scatter_sum), the slabs travel the
+        forward's row exchange backwards and every owner takes its optimiser step (Adagrad, or Adam with its norm exchange): one
+        synchronous step over the global batch.  Every rank must call it (SPMD), exactly once per lookup."""
+        if self.saved is None:
+            raise RuntimeError("backward_rows: this lookup's backward has run already")
+        st, saved = self.st, self.saved
+        self.saved = None
+        K = st.K
+        if grad_rows.dim() != 2 or grad_rows.shape[1] != K or idx.dim() != 1 or idx.shape[0] != grad_rows.shape[0]:
+            raise ValueError("backward_rows: idx [m] and grad_rows [m, K=%d]" % K)
+        st._refuse_adam_capture(grad_rows)
+        R = int(self.rows.shape[0])
+        slabs = torch.empty((R, K), dtype=torch.float32, device=self.rows.device)
+        if grad_rows.shape[0] and grad_rows.stride(1) != 1:
+            grad_rows = grad_rows.contiguous()
+        st.backend.rows_scatter_sum(idx.contiguous(), grad_rows, R, slabs)
+        st._backward_apply(saved, None, slabs=slabs)
+
+
 class ShardedTables:
     """This rank's row slices of F tables [vocab_f, K].
 
@@ -556,6 +603,7 @@ class ShardedTables:
         self._plans = {}
         self._cap = None              # the agreed slab capacity (collective mode); _cap0: its first value (the no-skew demand)
         self._cap_train = None        # the training pipeline's own capacity (never shrunk by de-duplicated inference verdicts)
+        self._cap_train_dedup = None  # ... and the de-duplicated training pipeline's (shrinks to what de-duplication leaves of a micro-batch)
         self._cap0 = None
         self._share0 = None           # an owner's share of a micro-batch without skew (_agree_cap)
         self._use_exact = mode == "exact"
@@ -838,7 +886,17 @@ class ShardedTables:
             norms = self._sum_norm_shares(be.adam_norm(self.optimizer, payload, grad_rows))
         be.adam_apply(self.optimizer, payload, grad_rows, norms)
 
-    def lookup_train(self, ids, with_linear=False):
+    def _need_dedup_train(self, what, with_linear=False):
+        """The combinations de-duplicated training does not cover, refused before anything is enqueued."""
+        if with_linear:
+            raise NotImplementedError("%s with with_linear=True: the first-order term's backward writes one slab position per entry; train it "
+                                      "with dedup=False" % what)
+        if self.G > 1:
+            raise NotImplementedError("%s: row groups (groups=%d) are trained one slab position per entry (dedup=False) only" % (what, self.G))
+        if not hasattr(self.backend, "rows_scatter_sum"):
+            raise NotImplementedError("%s: this backend has no scatter-sum of gradient rows (rows_scatter_sum)" % what)
+
+    def lookup_train(self, ids, with_linear=False, dedup=False):
         """Differentiable lookup: emb [B_local, F*K] with a grad_fn (the tables themselves get no .grad).  Runs the fixed-capacity
         pipeline (no split sizes reach the host; the gradient rows go back through the same equal-split slabs); the exact
         variable-size path only when mode == "exact", after an overflow, or when "auto" has given up on slabs.  One training lookup
@@ -846,9 +904,17 @@ class ShardedTables:
         with_linear: -> (emb, lin) from ONE autograd node; lin [B_local, 1] = the sum of the sample's F first-order weights (no bias: the
         bias is a replicated dense variable of the caller's).  Its backward receives both gradients: the row gradients and d lin travel
         the same equal-split exchange, then every owner applies Adagrad to its embedding rows and FTRL to its first-order rows (in that
-        order: the FTRL step reuses the Adagrad step's sort of the payload) -- one optimiser step."""
+        order: the FTRL step reuses the Adagrad step's sort of the payload) -- one optimiser step.
+        dedup: the training exchange sends each distinct (slot, row) of a 2048/4096-sample tile once (the de-duplicating bucket kernel, on
+        a capacity and plans of its own); the backward sums the gradients of the entries that share a slab position on the requester
+        (backend.rows_scatter_sum: sorted, compensated, no float atomics) before the reversed exchange, and the owner -- which sees fewer
+        payload words -- still sums duplicates across tiles, micro-batches and ranks.  The forward is bit for bit dedup=False's.  The
+        exact path (mode="exact", overflow repair) stays one row per entry.  Not covered (each raises NotImplementedError):
+        with_linear=True, row groups, a backend without rows_scatter_sum."""
         if self.optimizer is None:
             raise RuntimeError("call enable_training(lr) first")
+        if dedup:
+            self._need_dedup_train("lookup_train(dedup=True)", with_linear)
         self._refuse_adam_capture(ids)                   # before anything is enqueued, not first inside backward()
         if with_linear and self._adam:
             raise NotImplementedError("lookup_train(with_linear=True) under enable_training_adam: the first-order rows' FTRL rides on the Adagrad "
@@ -858,38 +924,81 @@ class ShardedTables:
             if self._lin_hp is None:
                 raise RuntimeError("call enable_linear_training(lr) first")
         anchor = torch.zeros((), dtype=torch.float32, device=ids.device, requires_grad=True)
-        res = _ShardedLookup.apply(self, ids, bool(with_linear), anchor)
+        res = _ShardedLookup.apply(self, ids, bool(with_linear), anchor, bool(dedup))
         if self.G == 1:
             return res
         # row groups: a tuple of G embedding matrices (one autograd node: their gradients go back interleaved in ONE row exchange and
         # the owner takes ONE Adagrad step at width G*K), or (that tuple, lin [B_local, U])
         return (tuple(res[:self.G]), res[self.G]) if with_linear else tuple(res)
 
-    def _forward_train(self, ids, with_lin):
-        """The forward of a training lookup -> (emb, what the backward needs, lin [B, 1] | None).  On the fixed-capacity pipeline (never
-        de-duplicated: the backward needs one slab position per entry) unless mode == "exact", "auto" has given up on slabs, or a slab
-        overflows.  The overflow verdict is read here (the one host wait of a training lookup; it covers work that is long done when
+    def lookup_rows_train(self, ids, dedup=True):
+        """The training lookup WITHOUT its finish pass (what lookup_rows is to lookup): -> a handle with
+          .rows [R, K]: the received rows of ALL micro-batches as one matrix (chunk c's slab positions offset by c * P * cap), private to
+                 the training plans -- an inference lookup between this call and backward_rows leaves them alone;
+          .inv  [B_local, F] int64: the position of every entry's row in .rows, < 0 where the id was pruned / out of range;
+          .backward_rows(idx, grad_rows): the per-position sum of the gradient rows (any number of entries per position, any order),
+                 the reversed exchange and the owner's step.  Exactly once.
+        A model whose kernels take (table, ids) trains with table = .rows (a leaf that requires grad) and ids = .inv; the sparse gradient
+        it leaves on that leaf is (idx, grad_rows).  dedup (the default): each distinct (slot, row) of a tile is sent once, on the
+        de-duplicated training capacity (lookup_train(dedup=True)'s).  The overflow verdict is read here, once, as lookup_train does; an
+        overflow is repaired on the exact path (.rows then holds one row per entry).  One training lookup may be outstanding per
+        ShardedTables; every rank must call it (SPMD)."""
+        if self.optimizer is None:
+            raise RuntimeError("call enable_training(lr) first")
+        self._need_dedup_train("lookup_rows_train")
+        self._refuse_adam_capture(ids)
+        if ids.dim() != 2 or ids.shape[1] != self.F:
+            raise ValueError("ids must be [B, F=%d]" % self.F)
+        (rows, inv), saved, _ = self._forward_train(ids, False, dedup=bool(dedup), rows_only=True)
+        return _RowsTrainLookup(self, saved, rows, inv)
+
+    def _forward_train(self, ids, with_lin, dedup=False, rows_only=False):
+        """The forward of a training lookup -> (emb, what the backward needs, lin [B, 1] | None).  On the fixed-capacity pipeline (one slab
+        position per entry; dedup: one per distinct row of a tile, on the de-duplicated training capacity and plans) unless mode == "exact",
+        "auto" has given up on slabs, or a slab overflows.  rows_only (lookup_rows_train): no finish pass -- emb is (rows [R, K], inv [B, F]),
+        the received rows of all micro-batches as one matrix and every entry's position in it (< 0: pruned).  The overflow verdict is read here (the one host wait of a training lookup; it covers work that is long done when
         the dense part of the model has been enqueued in between); the exact path keeps a row buffer of its own."""
         B, F = ids.shape
         lin = (torch.empty((B, self.U), dtype=torch.float32, device=ids.device), None) if with_lin else None
         if not (self._use_exact or B == 0 and not self._collective()):
-            out = self._new_out(B, ids.device)
-            plan = self._plan(B, "train")
-            done = self._enqueue(plan, ids, False, out, None, dedup=False, lin=lin)
+            out = None if rows_only else self._new_out(B, ids.device)
+            plan = self._plan(B, "train_dedup" if dedup else "train")
+            done = self._enqueue(plan, ids, False, out, None, dedup=bool(dedup), lin=lin, consumer=(lambda s, e, rows, inv: None) if rows_only else None)
             _Lookup(self, plan, ids, False, out, None, done).join()
             over = False
             if done is not False:
                 over, demand = self._read_flags(plan, done)
                 self._learn(plan, over, demand)
             if not over:
+                if rows_only:
+                    out = (plan.back_all, self._rows_inv(plan, F, ids.device))
                 return out, ("fixed", plan), lin[0] if with_lin else None
             self.stats["fallbacks"] += 1
         back, inv, sc, rc, recv = self._exchange_exact(ids, lin, private=True)
+        if rows_only:
+            # (the exact path gives pruned entries a position too -- a zero row; the handle's contract is inv < 0 there)
+            live = (ids >= 0) & (ids < self.vocab_dev.unsqueeze(0))
+            return (back, torch.where(live, inv.view(B, F), torch.full_like(ids, -1))), ("exact", inv, sc, rc, recv, True), None
+        if dedup:                                        # (one row per entry here: the backward's scatter-sum sees only runs of one)
+            emb, _ = self.backend.finish(back, inv, B, F, False)
+            return emb, ("exact", inv, sc, rc, recv, True), None
         if self.G == 1:
             emb, _ = self.backend.finish(back, inv, B, F, False)
         else:
             emb, _ = self._finish_groups(back, inv.view(B, F), self._new_out(B, ids.device))
         return emb, ("exact", inv, sc, rc, recv), lin[0] if with_lin else None
+
+    def _rows_inv(self, plan, F, device):
+        """[B, F] int64: every entry's position in plan.back_all (chunk c's slab positions offset by c * P * cap), < 0 where pruned."""
+        be, span = self.backend, self.P * plan.cap
+        parts = []
+        for c, (s, e) in enumerate(plan.bounds):
+            if e > s:
+                iv = be.inv2d(plan.inv[c], e - s, F, plan.dedup)
+                parts.append(torch.where(iv < 0, iv, iv + c * span) if c else iv)
+        if not parts:
+            return torch.empty((0, F), dtype=torch.int64, device=device)
+        return (parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)).contiguous()
 
     def _linear_exact(self, recv, inv2d, sc, rc, lin):
         """The linear term on the exact path: one weight per received payload word, sent back with the row exchange's splits (one float
@@ -902,10 +1011,12 @@ class ShardedTables:
         self._a2a(lback, lw, sc if U == 1 else [c * U for c in sc], rc if U == 1 else [c * U for c in rc])
         self._lin_finish(lback, inv2d, lin[1], lin[0])
 
-    def _backward_apply(self, saved, g_emb, g_lin=None):
+    def _backward_apply(self, saved, g_emb, g_lin=None, slabs=None):
         """g_lin (lookup_train(with_linear=True)): d loss / d lin [B_local, 1].  Its values go where the weights came back from and travel
         the same exchange as the gradient rows; the owner's FTRL runs after its Adagrad, over the same payload, on that step's sort.
-        The exchange is the same under enable_training_adam; the owner's step (_owner_step) is then norm pass, norm sum over the ranks, apply."""
+        The exchange is the same under enable_training_adam; the owner's step (_owner_step) is then norm pass, norm sum over the ranks, apply.
+        slabs (lookup_rows_train's backward_rows; g_emb is None): the gradient slabs already built -- [C * P * cap, K] on the fixed path,
+        [n, K] in exchange order on the exact path."""
         K, G = self.K, self.G
         be = self.backend
         U = self.U
@@ -917,12 +1028,20 @@ class ShardedTables:
             plan = saved[1]
             P, cap = self.P, plan.cap
             C = plan.C
-            g2 = g_emb.contiguous() if G == 1 else None
+            g2 = g_emb.contiguous() if G == 1 and slabs is None else None
             works, grecv_l = [], []
             for c, (s, e) in enumerate(plan.bounds):
                 # entry i's gradient row goes to slab position inv[i] (row P*cap = a dump row for pruned entries); owners receive
                 # the slabs through the forward row exchange reversed (equal splits again)
-                if G > 1:
+                if slabs is not None:
+                    gsend = slabs[c * P * cap:(c + 1) * P * cap]
+                elif plan.dedup:
+                    # de-duplicated: many entries share a position -- their rows are summed in entry order (sorted, compensated, no
+                    # atomics); positions nobody names come out as zeros
+                    gsend = torch.empty((P * cap, K), dtype=torch.float32, device=g2.device)
+                    idx = be.inv2d(plan.inv[c], e - s, self.F, True).reshape(-1)
+                    be.rows_scatter_sum(idx, g2[s:e].reshape(-1, K), P * cap, gsend)
+                elif G > 1:
                     # ... by the HIP transpose of the grouped finish: zero-fill + one writer per position, no dump row
                     gsend = torch.empty((P * cap, self.KW), dtype=torch.float32, device=dev)
                     be.grad_groups([g[s:e] for g in gs], be.inv2d(plan.inv[c], e - s, self.F, False), K, gsend)
@@ -954,10 +1073,15 @@ class ShardedTables:
             if g_lin is not None:
                 self._lin_ftrl(pay, plan.lback_all.view(-1), self.optimizer)
             return
-        _, inv, sc, rc, recv = saved
+        _, inv, sc, rc, recv = saved[:5]
         n = inv.numel()
         KW = self.KW
-        if G == 1:
+        if slabs is not None:
+            gsend = slabs
+        elif len(saved) > 5 and saved[5]:                # a de-duplicated lookup repaired on the exact path: the same kernel, runs of one
+            gsend = torch.empty((n, K), dtype=torch.float32, device=g_emb.device)
+            be.rows_scatter_sum(inv, g_emb.contiguous().view(n, K), n, gsend)
+        elif G == 1:
             g = g_emb.contiguous().view(n, K)
             gsend = torch.empty_like(g)
             gsend[inv] = g                               # entry e's row sits at position inv[e] of the exchange order
@@ -1025,17 +1149,20 @@ class ShardedTables:
         n_chunk = max(1, -(-Bm // self._C())) * self.F
         cap = self._default_cap(n_chunk)
         cap, n_chunk = self._max_over_ranks([cap, n_chunk])
-        self._cap = self._cap_train = self._cap0 = cap
+        self._cap = self._cap_train = self._cap_train_dedup = self._cap0 = cap
         self._share0 = float(n_chunk) / self.P            # an owner's share of a micro-batch without skew
 
     def _plan(self, B, slot=0):
         if self._collective():
             if self._cap is None:
                 self._agree_cap(B)
-            # two capacities: the training pipeline is never de-duplicated (one slab position per entry), so what de-duplicated
+            # two capacities: the plain training pipeline keeps one slab position per entry (dedup=False), so what de-duplicated
             # inference lookups learn (a SMALLER capacity) must not shrink its slabs -- sharing one number made every training lookup
             # after an inference lookup overflow and run twice
-            cap = self._cap_train if slot == "train" else self._cap
+            # ... and a third: de-duplicated TRAINING (lookup_train(dedup=True), lookup_rows_train) learns how many distinct rows a
+            # micro-batch leaves per owner and shrinks to that -- the link bytes it exists to save.  That number must neither shrink the
+            # one-position-per-entry training slabs nor move the inference capacity, and neither of those may grow or shrink it.
+            cap = self._cap_of(slot)
         else:
             cap = _round_up(max(B * self.F, 16), 16)      # one rank: a slab holds the whole batch, nothing can overflow
         key = (B, slot, cap)
@@ -1044,13 +1171,18 @@ class ShardedTables:
             def live(k):      # plans of other (batch, slot) pairs whose slabs still have the capacity in use for their kind
                 if (k[0], k[1]) == (B, slot):
                     return False
-                return not self._collective() or k[2] == (self._cap_train if k[1] == "train" else self._cap)
+                return not self._collective() or k[2] == self._cap_of(k[1])
             self._plans = {k: v for k, v in self._plans.items() if live(k)}
             if len(self._plans) > 8:
                 self._plans.clear()
-            plan = self._plans[key] = _Plan(self, B, cap, train=slot == "train")
+            plan = self._plans[key] = _Plan(self, B, cap, train=slot in ("train", "train_dedup"))
+            plan.slot, plan.dedup = slot, slot == "train_dedup"
         self.stats["cap"] = cap
         return plan
+
+    def _cap_of(self, slot):
+        """The agreed slab capacity the plans of `slot` follow: "train", "train_dedup", or anything else = the inference capacity."""
+        return self._cap_train if slot == "train" else self._cap_train_dedup if slot == "train_dedup" else self._cap
 
     def _ensure_streams(self):
         if self._streams is None and self.device.type == "cuda":
@@ -1168,16 +1300,18 @@ class ShardedTables:
         with dedup, shrink to what de-duplication left; give up on fixed slabs (mode auto) when one owner wants more than twice
         the no-skew share -- padding every slab to that size would cost more link bytes than the exact path's host read."""
         train = plan.train
-        if plan.cap != (self._cap_train if train else self._cap):
+        if plan.cap != self._cap_of(plan.slot):
             return                                         # a verdict about slabs that are no longer in use
         cap = plan.cap
         if over:
             cap = max(cap, _round_up(demand * 1.25 + 64, 16))
-        elif self.dedup and not train:                     # only verdicts of de-duplicated lookups say what de-duplication left
+        elif plan.dedup if train else self.dedup:          # only verdicts of de-duplicated lookups say what de-duplication left
             want = _round_up(demand * 1.25 + 64, 16)
             if want < 0.7 * cap:
                 cap = want
-        if train:
+        if plan.dedup:
+            self._cap_train_dedup = cap
+        elif train:
             self._cap_train = cap
         else:
             self._cap = cap
@@ -1649,8 +1783,8 @@ class _ShardedLookup(torch.autograd.Function):
     embedding rows, then FTRL to its first-order rows -- one optimiser step; no gradient tensor is returned for the tables."""
 
     @staticmethod
-    def forward(ctx, st, ids, with_lin, anchor):
-        emb, ctx.saved, lin = st._forward_train(ids, with_lin)
+    def forward(ctx, st, ids, with_lin, anchor, dedup=False):
+        emb, ctx.saved, lin = st._forward_train(ids, with_lin, dedup)
         ctx.st = st
         if st.G > 1:                                     # row groups: G embedding matrices (+ lin) from the one node
             return tuple(emb) + ((lin,) if with_lin else ())
@@ -1662,10 +1796,10 @@ class _ShardedLookup(torch.autograd.Function):
         if st.G > 1:
             gs, g_lin = (g,) + more[:st.G - 1], (more[st.G - 1] if len(more) >= st.G else None)
             st._backward_apply(ctx.saved, gs, None if g_lin is None else g_lin.contiguous())
-            return None, None, None, None
+            return None, None, None, None, None
         g_lin = more[0] if more else None
         st._backward_apply(ctx.saved, g, None if g_lin is None else g_lin.contiguous())
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 class _ShardedBagLookup(torch.autograd.Function):
@@ -2204,3 +2338,129 @@ class ShardedDCNTrainer:
             out = self.model.predict(x0)
             raise_pending()
             return out
+
+
+class ShardedDINTrainer:
+    """One synchronous multi-GPU training step, and inference, of a din.DIN whose goods table (BASELINE config 4: 10 M x 64 plus its
+    accumulator -- the table that outgrows one GPU first) is row-sharded over the ranks.  Every DIN kernel takes (table, history ids,
+    lengths, candidate ids) and reads rows only through the ids, so the unit, its fused backward and the PReLU / Dice row-list path run
+    UNCHANGED with table = the received rows of a sharded lookup and ids = the entries' positions in them: the [B, T + 1] entries (history,
+    then the candidate) are flattened to a one-slot lookup without a finish pass, de-duplicated -- a sample's 51 entries repeat heavily
+    across samples -- and in training the sparse gradient the model leaves on the received rows goes back through
+    ShardedTables.lookup_rows_train's backward_rows (per-position sums on the requester, the reversed exchange, the owner's Adagrad).
+    The dense parameters (the unit's MLP, the 200-80 tower) are replicated; their gradients are summed with bucketed all-reduces.
+    Semantics: the loss is the SUM-reduced binary cross entropy, so gradients ADD over the ranks -- one step equals the single-process step
+    over the concatenated batch.  Dice's batch statistics and moving averages are per rank, like an unsynchronised batch norm.
+    `model`'s feature_columns are replicated dense-side parameters; a column whose parameter would get a sparse gradient (an embedding
+    column) raises NotImplementedError.  `model`'s own attention.table is not used (tables_from_model copies it into the shards).
+    dedup: the training exchange sends each distinct row of a tile once (lookup_rows_train(dedup=))."""
+
+    def __init__(self, model, tables, lr_sparse, dense_optimizer, group=None, initial_accumulator_value=0.1, dedup=True):
+        self.model, self.tables, self.group, self.dedup = model, tables, group, bool(dedup)
+        il = model.input_layer
+        if il is not None and len(il.embedding_weights):
+            raise NotImplementedError("ShardedDINTrainer: feature_columns are replicated dense-side parameters; an embedding column's table "
+                                      "gets a sparse gradient (use numeric / indicator columns, or shard the column's table)")
+        if tables.G != 1 or tables.F != 1 or tables.K != model.K:
+            raise ValueError("ShardedDINTrainer: the tables must hold the one goods table of K=%d floats (tables_from_model), got G=%d F=%d K=%d"
+                             % (model.K, tables.G, tables.F, tables.K))
+        if tables.check != "eager":
+            raise ValueError("ShardedDINTrainer needs check='eager' (lookup_rows: an overflow is repaired before the rows are handed out)")
+        self.dense_params = [p for n, p in model.named_parameters() if n != "attention.table"]
+        self.dense_optimizer = dense_optimizer
+        tables.enable_training(lr_sparse, initial_accumulator_value)
+
+    @classmethod
+    def tables_from_model(cls, model, group=None, **kw):
+        """The one-table ShardedTables of `model`'s goods table (every rank holds the same replicated model).  kw: ShardedTables' options;
+        inference lookups are de-duplicated unless dedup=False is given."""
+        kw.setdefault("dedup", True)
+        return ShardedTables.from_full([model.attention.table.data], group=group, **kw)
+
+    def _entries(self, features):
+        """[B, T + 1] int64 on the tables' device: the history ids -- positions at or beyond the sample's length set to -1, negative ids stay
+        padding -- then the candidate id."""
+        hk, lk, ck = self.model.keys
+        dev = self.tables.device
+        hist = features[hk].to(device=dev, dtype=torch.int64)
+        cand = features[ck].to(device=dev, dtype=torch.int64).reshape(-1, 1)
+        hist_len = features.get(lk) if hasattr(features, "get") else None
+        if hist_len is not None:
+            T = hist.shape[1]
+            n = hist_len.to(device=dev, dtype=torch.int64).reshape(-1, 1).clamp(0, T)
+            hist = torch.where(torch.arange(T, device=dev).unsqueeze(0) < n, hist, torch.full_like(hist, -1))
+        return torch.cat([hist, cand], dim=1).contiguous()
+
+    def _arith(self):
+        """The unit's arithmetic from the SHARDED table's magnitude (a rank-invariant collective decision, ShardedTables.absmax) -- never from
+        the received rows (a pass and a host wait per call) nor from the model's own unused table."""
+        a = self.model.attention
+        return ops.din_arith_name(self.tables.absmax(), (a.W1, a.W2, a.W3))
+
+    def _rows_of(self, entries):
+        """The inference lookup without its finish pass -> (rows [R, K], inv [B, T + 1]): ONE matrix for the whole local batch (the plan's
+        micro-batches sit in one buffer; chunk c's positions are offset by c * P * cap), because Dice's statistics and the packed unit's
+        partition are per call."""
+        st = self.tables
+        B, T1 = entries.shape
+        flat = entries.reshape(-1, 1)
+        h = st.lookup_rows_async(flat)
+        chunks = h.result()
+        plan = h.lk.plan
+        base = None if plan is None else plan.back_all.untyped_storage().data_ptr()
+        if plan is None or any(rows.untyped_storage().data_ptr() != base for _, _, rows, _ in chunks):
+            # the exact path (from the start, or an overflow's repair): one entry for the whole batch, and pruned entries have a position
+            # too -- a zero row; the unit must see them as padding
+            (_, _, rows, inv), = chunks
+            inv = torch.where((flat >= 0) & (flat < st.vocab_dev[0]), inv.reshape(-1, 1), torch.full_like(flat, -1))
+            return rows, inv.reshape(B, T1)
+        span, first = st.P * plan.cap, {s: c for c, (s, e) in enumerate(plan.bounds)}
+        parts = []
+        for s, e, _, inv in chunks:
+            c = first[s]
+            parts.append((torch.where(inv < 0, inv, inv + c * span) if c else inv).reshape(-1))
+        inv = torch.cat(parts) if parts else torch.empty(0, dtype=torch.int64, device=flat.device)
+        return plan.back_all, inv.reshape(B, T1)
+
+    @torch.no_grad()
+    def predict(self, features):
+        """Inference logits [B_local, 1] for the features dict DIN.forward takes: the entries looked up with lookup_rows (de-duplicated, no
+        finish pass), the model run with the received rows as its table -- the whole local batch in ONE call of the unit.  Bit for bit the
+        single-GPU model holding the full table."""
+        m = self.model
+        entries = self._entries(features)
+        T = entries.shape[1] - 1
+        arith = self._arith()
+        with _eval_mode(m):
+            rows, inv = self._rows_of(entries)
+            return m(features, table=rows, ids=(inv[:, :T], inv[:, T]), arith=arith)
+
+    def step(self, features, labels):
+        """features: the dict DIN.forward takes (this rank's local batch); labels [B_local, 1] -> this rank's summed loss (detached).
+        lookup_rows_train, the model's training forward over the received rows (the sigmoid unit's fused node, the row-list path for PReLU /
+        Dice), the SUM loss, backward; the sparse gradient of the received rows -- the unit's history and candidate rows plus the candidate
+        embedding's -- goes to backward_rows as it is (no dense [R, K] coalesce), where every owner's shard takes its step; then the dense
+        gradients are summed over the ranks and the dense optimiser steps."""
+        m = self.model
+        self.dense_optimizer.zero_grad(set_to_none=True)
+        entries = self._entries(features)
+        B, T = entries.shape[0], entries.shape[1] - 1
+        arith = self._arith()
+        h = self.tables.lookup_rows_train(entries.reshape(-1, 1), dedup=self.dedup)
+        rows = h.rows.detach().requires_grad_(True)
+        inv = h.inv.view(B, T + 1)
+        logits = m(features, table=rows, ids=(inv[:, :T], inv[:, T]), arith=arith)
+        y = labels.to(device=logits.device, dtype=torch.float32).reshape(logits.shape)
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, y, reduction="sum")
+        loss.backward()
+        g = rows.grad
+        if g is None:
+            idx, vals = torch.empty(0, dtype=torch.int64, device=rows.device), torch.empty((0, rows.shape[1]), dtype=torch.float32, device=rows.device)
+        elif g.is_sparse:
+            idx, vals = g._indices()[0], g._values()              # uncoalesced: backward_rows sums the entries of a position
+        else:
+            idx, vals = torch.arange(rows.shape[0], device=rows.device), g
+        h.backward_rows(idx, vals)
+        allreduce_grads(self.dense_params, self.group)
+        self.dense_optimizer.step()
+        return loss.detach()

@@ -600,6 +600,21 @@ int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows, int F, int
                                                   float lr, float l1, float l2, const int64_t* row_base, int64_t total_rows, void* workspace,
                                                   int64_t workspace_bytes, const void* sorted_from, dir_stream_t stream);
 
+/* Sparse rows summed into a dense slab, deterministically (csrc/rows_scatter.hip): the requester-side transpose of a sharded lookup
+ * (ShardedTables.lookup_train / lookup_rows_train), also of a DE-DUPLICATED one, where many entries name one slab position.
+ * dir_rows_scatter_sum_f32: idx [n] int64 positions, vals [n, ld] fp32 (the first K floats of a row are read, ld >= K), out [R, K]
+ *   contiguous: out[r] = sum of vals[i] over idx[i] == r.  Rows nobody names are written as zeros (by a kernel: no memset node, so a
+ *   call can be captured in a HIP graph).  Entries with idx[i] < 0 are dropped; so are entries with idx[i] >= R (checking them would cost
+ *   a pass and a host read: an out-of-range position is never an error here).  The (idx, i) pairs are sorted with the in-tree stable radix
+ *   sort, so a row's entries are summed in ascending i: a run of ONE entry is copied bit for bit, longer runs go through the sorted
+ *   optimiser steps' run sum (compensated inside a 256-entry sort tile; a run's tile partials are added in double and rounded once).  No
+ *   float atomics: two calls on the same input give the same bits.  0 <= n < 2^30, 0 <= R < 2^32 - 1, K <= 256 when K % 4 == 0,
+ *   ld % 4 == 0 and vals / out are 16-byte aligned (16-byte accesses), K <= 64 otherwise.  Workspace:
+ *   dir_rows_scatter_sum_workspace_bytes(n, K, R) device bytes (-1: unsupported size), 256-byte aligned, any content; not read across calls. */
+int64_t dir_rows_scatter_sum_workspace_bytes(int64_t n, int K, int64_t R);
+int dir_rows_scatter_sum_f32(const int64_t* idx, const float* vals, int64_t ld, int64_t n, int K, int64_t R, float* out, void* workspace,
+                             int64_t workspace_bytes, dir_stream_t stream);
+
 /* Row groups (ShardedTables(groups=G)): every (slot, local row) stores G rows of K floats side by side -- the wide & deep ESMM's
  * ctr_model and cvr_model rows of one id (ESMM_wide_deep.py:213-217) -- so the buffers of the sharded lookup hold rows of G * K floats and
  * bucket, both exchanges and dir_gather_slabs_f32 / dir_gather_packed_f32 run on them unchanged (with K = G * K).  K % 4 == 0,
