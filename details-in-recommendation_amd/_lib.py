@@ -113,7 +113,7 @@ SIGNATURES = {
     "dir_sparse_adam_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp]),
     "dir_sparse_adam_payload_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i64]),
-    "dir_sparse_adam_payload_norm_f32": (c_i32, [c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "dir_sparse_adam_payload_norm_f32": (c_i32, [c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),   # norm2: ADAM_NORM_WORDS u64
     "dir_sparse_adam_payload_apply_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                   ctypes.c_float, ctypes.c_float, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     "dir_sparse_adagrad_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_float, c_i64, c_vp,
@@ -244,6 +244,8 @@ SIGNATURES = {
 }
 
 DIR_OK, DIR_E_BADARG, DIR_E_RANGE, DIR_E_HIP, DIR_E_UNSUPPORTED = 0, -1, -2, -3, -4
+# dir_sparse_adam_payload_norm_f32's norm2 and the head of dir_sparse_adam_f32's workspace: u64 words, [f] low and [64 + f] high per table
+ADAM_NORM_WORDS = 128
 _ERRNAMES = {-1: "DIR_E_BADARG", -2: "DIR_E_RANGE", -3: "DIR_E_HIP", -4: "DIR_E_UNSUPPORTED"}
 
 _lib = None

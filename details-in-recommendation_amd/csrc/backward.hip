@@ -511,10 +511,32 @@ struct FtrlUpd {      // FTRL-Proximal, learning_rate_power = -0.5 ([TF-upstream
 // sqrt(1 - b2^t) / (1 - b1^t).  Two sorted passes share one sort: AdamNormUpd adds up ||S_r||^2 per table (S_r = a row's summed
 // gradient) for tf.clip_by_norm(g, clip) -- in 2^-32 fixed point with integer atomics, so the sum does not depend on arrival order --
 // and AdamUpd applies the touched rows and marks them; adam_decay_k then streams over all rows and steps the unmarked ones.
+//
+// The norm words: TWO u64 words per table, norm2[f] (low) and norm2[64 + f] (high); the table's ||g||^2 is high + low * 2^-32.  Every
+// contribution -- the dot product of one row's summed gradient chunk with itself, an fp32 value d -- adds floor(d) to the high word and
+// floor((d - floor(d)) * 2^32) to the low one: what floor(d * 2^32) added to the single word of the first version, without that word's
+// wrap at ||g||^2 = 2^32 (||g|| = 65 536: exploding gradients, the case the clip exists for).  The low word may exceed 2^32 (it is a
+// sum of fractions: carry it with adam_norm_value / SparseAdam.norm_payload).  Exact and order-independent while ||g||^2 < 2^62
+// (||g|| < 2.1e9); one contribution is clamped at 2^62.
 constexpr double ADAM_FX = 4294967296.0;       // 2^32
+constexpr double ADAM_NORM_CAP = 4611686018427387904.0;      // 2^62
+constexpr int ADAM_NORM_WORDS = 128;           // 64 low words, 64 high words
+constexpr size_t ADAM_NORM_BYTES = ADAM_NORM_WORDS * 8;
+__device__ __forceinline__ void adam_norm_split(float dot, unsigned long long& hi, unsigned long long& lo) {
+    double d = (double)dot;
+    d = d < ADAM_NORM_CAP ? d : ADAM_NORM_CAP;                // (also what a NaN becomes)
+    const double ip = floor(d);
+    hi = (unsigned long long)ip;
+    lo = (unsigned long long)((d - ip) * ADAM_FX);            // d - ip and the product are exact
+}
+// the double nearest to high + low * 2^-32 (one rounding: the carried high word and the 32-bit fraction are both exact doubles)
+__device__ __forceinline__ double adam_norm_value(const unsigned long long* norm2, int f) {
+    const unsigned long long lo = norm2[f], hi = norm2[64 + f] + (lo >> 32);
+    return (double)hi + (double)(lo & 0xffffffffull) / ADAM_FX;
+}
 struct AdamNormUpd {
     static constexpr bool kNorm = true;
-    unsigned long long* norm2;                 // [F] fixed point
+    unsigned long long* norm2;                 // [128]: the norm words
     template <int VEC>
     __device__ __forceinline__ void apply(int, int64_t, int, typename BV<VEC>::T) const {}
 };
@@ -522,13 +544,13 @@ struct AdamUpd {
     float* const* tables;
     float* const* ms;
     float* const* vs;
-    const unsigned long long* norm2;           // [F] fixed-point ||gradient of table f||^2 (NULL: no clipping)
+    const unsigned long long* norm2;           // [128] the norm words of ||gradient of table f||^2 (NULL: no clipping)
     unsigned char* mark;                       // [total_rows]: 1 = this row was stepped here
     const int64_t* row_base;
     float lr_t, b1, b2, eps, clip;
     int64_t ld;
     const double* norm2_sum = nullptr;         // [F] ||gradient of table f||^2 over ALL owners of a row-sharded table (the payload form: the
-                                               // ranks' fixed-point shares added up exactly, which a u64 word cannot hold for 64 of them)
+                                               // ranks' norm words added up exactly by the caller and rounded once)
     __device__ __forceinline__ void one(float g, float den, float& m, float& v, float& w) const {
         if (clip > 0.f) g = (g * clip) / den;                     // tf.clip_by_norm: t * clip_norm / max(l2norm, clip_norm)
         m = m * b1 + g * (1.f - b1);
@@ -540,7 +562,7 @@ struct AdamUpd {
         using V = BV<VEC>;
         float den = clip;
         if (clip > 0.f && norm2_sum) den = fmaxf(sqrtf((float)norm2_sum[f]), clip);
-        else if (clip > 0.f && norm2) den = fmaxf(sqrtf((float)((double)norm2[f] / ADAM_FX)), clip);
+        else if (clip > 0.f && norm2) den = fmaxf(sqrtf((float)adam_norm_value(norm2, f)), clip);
         const int64_t off = id * ld + col;
         float* mp = ms[f] + off;
         float* vp = vs[f] + off;
@@ -693,9 +715,9 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
     __shared__ uint32_t skey[ADA_TILE], sval[ADA_TILE];
     __shared__ int rstart[ADA_TILE + 1];
     __shared__ int wcnt[4];
-    __shared__ unsigned long long nsq[IsNorm<U>::value ? 64 : 1];     // norm pass: this tile's ||S_r||^2 per table, fixed point
+    __shared__ unsigned long long nsq[IsNorm<U>::value ? ADAM_NORM_WORDS : 1];     // norm pass: this tile's ||S_r||^2 per table, low and high words
     if constexpr (IsNorm<U>::value) {
-        if (threadIdx.x < 64) nsq[threadIdx.x] = 0ull;
+        if (threadIdx.x < ADAM_NORM_WORDS) nsq[threadIdx.x] = 0ull;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t t = blockIdx.x, e0 = t * ADA_TILE;
@@ -845,8 +867,10 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
             if constexpr (BAG) {
                 bag_apply<LPS, VEC>(upd, bag, f, id, c, kv, sum);
             } else if constexpr (IsNorm<U>::value) {
-                const double d = (double)V::dot(sum, sum, 0.f) * ADAM_FX;
-                atomicAdd(&nsq[f & 63], (unsigned long long)(d < 4.0e18 ? d : 4.0e18));
+                unsigned long long hi, lo;
+                adam_norm_split(V::dot(sum, sum, 0.f), hi, lo);
+                if (lo) atomicAdd(&nsq[f & 63], lo);
+                if (hi) atomicAdd(&nsq[64 + (f & 63)], hi);
             } else {
                 upd.template apply<VEC>(f, id, c * VEC, sum);
             }
@@ -858,7 +882,13 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
     }
     if constexpr (IsNorm<U>::value) {
         __syncthreads();
-        if (threadIdx.x < 64 && nsq[threadIdx.x]) atomicAdd(upd.norm2 + threadIdx.x, nsq[threadIdx.x]);
+        if (threadIdx.x < 64) {
+            // the tile's low word (< 256 * 64 fractions of 32 bits) carries into its high word here: the global low word then grows by
+            // less than 2^32 per tile and per fix-up and cannot wrap for any n the sort takes
+            const unsigned long long lo = nsq[threadIdx.x], hi = nsq[64 + threadIdx.x] + (lo >> 32);
+            if (lo & 0xffffffffull) atomicAdd(upd.norm2 + threadIdx.x, lo & 0xffffffffull);
+            if (hi) atomicAdd(upd.norm2 + 64 + threadIdx.x, hi);
+        }
     }
 }
 
@@ -904,8 +934,10 @@ __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
     if constexpr (BAG) {
         bag_apply<LPS, VEC>(upd, bag, f, id, c0, kv, sum);
     } else if constexpr (IsNorm<U>::value) {
-        const double d = (double)V::dot(sum, sum, 0.f) * ADAM_FX;
-        atomicAdd(upd.norm2 + (f & 63), (unsigned long long)(d < 4.0e18 ? d : 4.0e18));
+        unsigned long long hi, lo;
+        adam_norm_split(V::dot(sum, sum, 0.f), hi, lo);
+        if (lo) atomicAdd(upd.norm2 + (f & 63), lo);
+        if (hi) atomicAdd(upd.norm2 + 64 + (f & 63), hi);
     } else {
         upd.template apply<VEC>(f, id, c * VEC, sum);
     }
@@ -1413,7 +1445,7 @@ extern "C" int64_t dir_sparse_adam_workspace_bytes(int64_t B, int F, int K, int6
     AdaSortedPlan p;
     const int64_t sorted = B > 0 ? (adagrad_sorted_plan(B * F, K, total_rows, p, B, F) ? (int64_t)p.total : -1) : 0;
     if (sorted < 0) return 0;
-    return sorted + 512 + ((total_rows + 255) & ~(int64_t)255);      // + norm2 [64] u64 + the row marks (one byte per row)
+    return sorted + (int64_t)ADAM_NORM_BYTES + ((total_rows + 255) & ~(int64_t)255);      // + the norm words + the row marks (one byte per row)
 }
 
 extern "C" int dir_sparse_adam_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* ids,
@@ -1430,17 +1462,17 @@ extern "C" int dir_sparse_adam_f32(float* const* tables, float* const* ms, float
         return fail(DIR_E_BADARG, "%s: workspace needs %lld bytes, 256-byte aligned", name, (long long)need);
     hipStream_t st = as_stream(stream);
     char* ws = static_cast<char*>(workspace);
-    // layout: [norm2: 64 x u64 = 512 B][marks: total_rows bytes, zero between calls][sorted-update workspace]
+    // layout: [the norm words: 128 x u64 = 1024 B][marks: total_rows bytes, zero between calls][sorted-update workspace]
     unsigned long long* norm2 = reinterpret_cast<unsigned long long*>(ws);
-    unsigned char* mark = reinterpret_cast<unsigned char*>(ws + 512);
+    unsigned char* mark = reinterpret_cast<unsigned char*>(ws + ADAM_NORM_BYTES);
     const int64_t mark_bytes = (total_rows + 255) & ~(int64_t)255;
-    char* sorted_ws = ws + 512 + mark_bytes;
-    const int64_t sorted_bytes = workspace_bytes - 512 - mark_bytes;
+    char* sorted_ws = ws + ADAM_NORM_BYTES + mark_bytes;
+    const int64_t sorted_bytes = workspace_bytes - (int64_t)ADAM_NORM_BYTES - mark_bytes;
     if (first_call && zero_async(mark, (size_t)mark_bytes, st) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
     if (B > 0) {
         const bool clip = clip_norm > 0.f;
         if (clip) {
-            if (zero_async(norm2, 512, st) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
+            if (zero_async(norm2, ADAM_NORM_BYTES, st) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
             const int rc = sparse_sorted_update(name, AdamNormUpd{norm2}, F, K, ids, stride_b, stride_f, grad, grad_ld, (int64_t)K, B, row_base,
                                                 total_rows, sorted_ws, sorted_bytes, stream);
             if (rc != DIR_OK) return rc;
@@ -1494,7 +1526,7 @@ extern "C" int dir_sparse_adam_payload_norm_f32(int F, int K, const int64_t* pay
     if (int rc = adam_payload_check(name, F, K, payload, n, grad, row_base, total_rows, workspace, workspace_bytes, p)) return rc;
     DIR_CHECK_ARG(norm2, "%s: null pointer (norm2)", name);
     DIR_CHECK_ARG(!(reinterpret_cast<uintptr_t>(norm2) & 7u), "%s: norm2 must be 8-byte aligned", name);
-    if (zero_async(norm2, 512, as_stream(stream)) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
+    if (zero_async(norm2, ADAM_NORM_BYTES, as_stream(stream)) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
     if (n == 0 || total_rows == 0) return DIR_OK;            // nothing received / no rows here: this owner's share is zero
     AdamNormUpdW upd;
     upd.norm2 = reinterpret_cast<unsigned long long*>(norm2);

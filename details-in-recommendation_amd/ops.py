@@ -3160,7 +3160,7 @@ class SparseAdam:
             raise _lib.DirError(-4, "sparse_adam: unsupported size (F <= 64, K / 4 a power of two, B*F < 2^31, total rows < 2^32-1)")
         first = 0
         if self._ws is None or self._ws_B < B:
-            # the marks (behind a 512-byte header) must survive from step to step: the buffer is allocated once per batch size (grown,
+            # the marks (behind the 1024 bytes of the norm words) must survive from step to step: the buffer is allocated once per batch size (grown,
             # never shrunk), zeroed by the first call
             self._ws = torch.empty(need + 256, dtype=torch.uint8, device=ts.device)
             self._ws_B = B
@@ -3191,22 +3191,24 @@ class SparseAdam:
 
     def norm_payload(self, payload, grad):
         """First half (include/dir_hip.h: dir_sparse_adam_payload_norm_f32): payload [n] int64 (local_row * F + slot, < 0 pruned) as
-        received from all ranks, grad [n, K] in the same order; n == 0 is legal.  -> norm2 [F] device int64: THIS owner's share of every
-        table's ||g||^2 in 2^-32 fixed point (the bits of the kernel's u64 sums).  The payload stays sorted in the workspace for
-        step_payload."""
+        received from all ranks, grad [n, K] in the same order; n == 0 is legal.  -> norm2 [2, F] device int64: THIS owner's share of
+        every table's ||g||^2 as the kernel's two norm words with the carry taken -- row 0 the low word (the fraction in units of 2^-32,
+        < 2^32), row 1 the high word (the integer part): share = high + low * 2^-32, exact for ||g|| < 2^31.  The payload stays sorted in
+        the workspace for step_payload."""
         lib, n, ws, ws_bytes = self._payload_args(payload, grad)
         if self._norm2 is None:
-            self._norm2 = torch.zeros(64, dtype=torch.int64, device=self.ts.device)
+            self._norm2 = torch.zeros(_lib.ADAM_NORM_WORDS, dtype=torch.int64, device=self.ts.device)      # 64 low words, 64 high words
         _lib.check(lib.dir_sparse_adam_payload_norm_f32(self.ts.F, self.ts.K, _ptr(payload), n, _ptr(grad), _ptr(self.row_base), self.total_rows,
                                                         _ptr(self._norm2), ws, ws_bytes, _stream()))
         # what step_payload may reuse: this tensor, unchanged, in this sort area, on this stream
         self._sorted = (payload, payload._version, self._pws, _stream().value)
-        return self._norm2[:self.ts.F]
+        words = self._norm2.view(2, 64)[:, :self.ts.F]
+        return torch.stack([words[0] & 0xffffffff, words[1] + ((words[0] >> 32) & 0xffffffff)])
 
     def step_payload(self, payload, grad, norm2_global=None):
         """Second half (dir_sparse_adam_payload_apply_f32): one Adam step of ALL local rows -- the touched ones from the payload, clipped
-        with norm2_global [F] device float64 = every table's GLOBAL ||g||^2 (the owners' norm_payload shares summed over the ranks and
-        divided by 2^32; None exactly when clip_norm == 0), the others by the decay pass; n == 0 runs that pass alone.  The sort of a
+        with norm2_global [F] device float64 = every table's GLOBAL ||g||^2 (the owners' norm_payload shares summed over the ranks:
+        high + low / 2^32; None exactly when clip_norm == 0), the others by the decay pass; n == 0 runs that pass alone.  The sort of a
         norm_payload call on the same payload just before is reused."""
         ts = self.ts
         lib, n, ws, ws_bytes = self._payload_args(payload, grad)

@@ -856,11 +856,16 @@ class ShardedTables:
         return self.optimizer.ms, self.optimizer.vs
 
     def _sum_norm_shares(self, share):
-        """share [F] int64: the bits of this owner's u64 fixed-point ||g||^2 sums -> [F] float64, every table's GLOBAL ||g||^2 in plain
-        units, the same value on every rank.  The high and low 32-bit halves are summed over the ranks as two int64 vectors (64 ranks x
-        2^32 cannot wrap) and recombined in double: an exact integer sum -- independent of P and of the order the shares arrive in --
-        rounded once.  On the host for gloo, through the device otherwise (as _max_over_ranks)."""
-        halves = torch.stack([(share >> 32) & 0xffffffff, share & 0xffffffff])
+        """share [2, F] int64: this owner's norm words (ops.SparseAdam.norm_payload: row 0 the low word, < 2^32, in units of 2^-32; row 1
+        the high word, the integer part) -> [F] float64, every table's GLOBAL ||g||^2 in plain units, the same value on every rank.  The
+        two rows are summed over the ranks as int64 vectors (64 ranks x 2^32 cannot wrap the low row; the high row holds while the global
+        ||g||^2 stays below 2^62) and recombined in double: an exact integer sum -- independent of P and of the order the shares arrive
+        in -- rounded once.  On the host for gloo, through the device otherwise (as _max_over_ranks).
+        A backend may still hand over ONE word per table (share [F]: the bits of a u64 in 2^-32 fixed point, good below ||g||^2 = 2^32 on
+        that owner): it is read as its 32-bit halves, the same two rows."""
+        if share.dim() == 1:
+            share = torch.stack([share & 0xffffffff, (share >> 32) & 0xffffffff])
+        halves = torch.stack([share[1], share[0]])
         if self._collective():
             if dist.get_backend(self.group) == "gloo":
                 h = halves.cpu()
@@ -868,7 +873,8 @@ class ShardedTables:
                 halves = h.to(share.device)
             else:
                 dist.all_reduce(halves, op=dist.ReduceOp.SUM, group=self.group)
-        return (halves[0].double() * 4294967296.0 + halves[1].double()) / 4294967296.0
+        high = halves[0] + (halves[1] >> 32)               # the carry of the summed low words: both terms below are exact doubles
+        return high.double() + (halves[1] & 0xffffffff).double() / 4294967296.0
 
     def _refuse_adam_capture(self, t):
         if self._adam and t.is_cuda and torch.cuda.is_current_stream_capturing():

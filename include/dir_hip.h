@@ -1165,8 +1165,12 @@ int dir_sparse_adagrad_sorted_rows_f32(float* const* tables, float* const* accum
  * gathered rows; tables / ms / vs: device arrays of F device pointers to contiguous [vocab_f, K] arrays; row_base: device int64 [F].
  * One radix sort of the (row, entry) pairs serves both sorted passes (per-table gradient norm in fixed point -- order-independent --
  * then the touched rows' update); a streaming pass steps all other rows.  Bitwise reproducible.
- * workspace: dir_sparse_adam_workspace_bytes(B, F, K, total_rows) bytes, 256-byte aligned, the SAME buffer every step (it carries
- * the row marks); first_call != 0 on its first use.  Limits: F <= 64, K % 4 == 0 with K / 4 a power of two <= 64. */
+ * workspace: dir_sparse_adam_workspace_bytes(B, F, K, total_rows) bytes, 256-byte aligned, the SAME buffer every step (it starts
+ * with the 1024 bytes of the norm words, described below, and carries the row marks); first_call != 0 on its first use.
+ * Limits: F <= 64, K % 4 == 0 with K / 4 a power of two <= 64.
+ * The clip norm: ||g||^2 of a table is summed exactly, in 2^-32 fixed point over two u64 words, while it stays below 2^62, i.e. for
+ * ||g|| < 2^31 (2.1e9), down to a resolution of 2^-32 per contribution; one contribution (a row's summed gradient, four columns of
+ * it) is clamped at 2^62.  Above that range the sum may wrap; non-finite gradients are outside the contract. */
 int64_t dir_sparse_adam_workspace_bytes(int64_t B, int F, int K, int64_t total_rows);
 int dir_sparse_adam_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* ids, int64_t stride_b,
                         int64_t stride_f, const float* grad, int64_t grad_ld, float lr_t, float beta1, float beta2, float eps,
@@ -1187,10 +1191,14 @@ int dir_sparse_adagrad_sorted_payload_f32(float* const* tables, float* const* ac
  * other owner-side updates in three ways, and the step is cut in two for the first:
  *   - tf.clip_by_norm(g, clip) divides by the norm of the table's WHOLE gradient; with the rows spread over P owners each owner sees its
  *     share of ||g||^2 only.  dir_sparse_adam_payload_norm_f32 sorts the payload and writes this owner's share per table into norm2
- *     (device, 64 x u64, zeroed by the entry; 2^-32 fixed point: sum over its touched rows r of ||S_r||^2, S_r the sum of the row's
- *     entries; integer adds, so the sum does not depend on arrival order).  The caller adds the shares up over the ranks -- an exact
- *     integer sum; 64 shares can overflow a u64, so it is handed back as a DOUBLE per table, ||g||^2 in plain units (share / 2^32) --
- *     and dir_sparse_adam_payload_apply_f32 clips with norm2_global (device double [F]; NULL exactly when clip_norm == 0).
+ *     (device, 128 x u64 = 1024 bytes, zeroed by the entry): TWO words per table, norm2[f] (low) and norm2[64 + f] (high); the share
+ *     is high + low * 2^-32, the sum over the owner's touched rows r of ||S_r||^2, S_r the sum of the row's entries.  Every
+ *     contribution d (fp32) adds floor(d) to the high word and floor((d - floor(d)) * 2^32) to the low word, which may therefore
+ *     exceed 2^32: carry it (high += low >> 32, low &= 2^32 - 1) before use.  Integer adds, so the sum does not depend on arrival
+ *     order.  Range: exact while the share is below 2^62 (||g|| < 2^31 = 2.1e9), resolution 2^-32 per contribution; one contribution
+ *     is clamped at 2^62; above the range the words may wrap.  The caller adds the shares up over the ranks -- an exact integer sum,
+ *     handed back as a DOUBLE per table, ||g||^2 in plain units (high + low / 2^32, rounded once) -- and
+ *     dir_sparse_adam_payload_apply_f32 clips with norm2_global (device double [F]; NULL exactly when clip_norm == 0).
  *   - every row moves every step: apply steps the touched rows (AdamUpd, on the norm entry's sort when sorted != 0: that entry has just
  *     sorted THIS payload into THIS workspace on THIS stream) and then streams over every other local row (m *= beta1, v *= beta2, var
  *     -= lr_t * m / (sqrt(v) + eps)).  n == 0 -- an owner that received nothing -- runs that pass alone.

@@ -1,7 +1,8 @@
 """The NumPy stand-in for the owner-side sparse Adam of dir_amd.shard (ShardedTables.enable_training_adam): tests/shard_standin.py's
 NumpyBackend plus make_adam / adam_norm / adam_apply, reading and writing what the HIP entries do (include/dir_hip.h:
 dir_sparse_adam_payload_norm_f32 / dir_sparse_adam_payload_apply_f32).  m and v are float64; var lives in the shard's fp32 tensors; the
-norm shares are the kernel's words: sum over the touched rows of floor(||S_r||^2 * 2^32), wrapped to 64 bits, handed over as int64."""
+norm shares are the kernel's two words per table with the carry taken: N = sum over the touched rows of floor(||S_r||^2 * 2^32) handed over
+as int64 [2, F], row 0 = N mod 2^32 (the low word), row 1 = N div 2^32 (the high word)."""
 import numpy as np
 import torch
 
@@ -43,9 +44,9 @@ class NumpyAdamBackend(NumpyBackend):
         opt.norm_calls += 1
         words = []
         for gsum, rows in self._row_sums(payload, grad_rows):
-            total = sum(int(np.floor(float((gsum[r] * gsum[r]).sum()) * FX)) for r in rows) & ((1 << 64) - 1)
-            words.append(total - (1 << 64) if total >= (1 << 63) else total)           # the u64 word's bits as int64
-        return torch.tensor(words, dtype=torch.int64)
+            total = sum(int(np.floor(float((gsum[r] * gsum[r]).sum()) * FX)) for r in rows)
+            words.append((total % FX, total // FX))
+        return torch.tensor(words, dtype=torch.int64).t().contiguous()
 
     def adam_apply(self, opt, payload, grad_rows, norm2_global):
         opt.apply_calls += 1

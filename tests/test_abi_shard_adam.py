@@ -54,6 +54,19 @@ def test_workspace_bytes(built_lib):
         assert ws(*bad) == 0, bad
 
 
+def test_norm_words_are_two_per_table(built_lib):
+    """The norm words' size is part of the ABI: 128 u64 (low [f], high [64 + f]) at the head of dir_sparse_adam_f32's workspace and in
+    dir_sparse_adam_payload_norm_f32's norm2, stated in the header, bound in _lib and documented."""
+    from dir_amd import _lib
+    assert _lib.ADAM_NORM_WORDS == 128
+    B, F, K, total = 1000, 3, 16, 457
+    sort_area = built_lib.dir_sparse_adagrad_sorted_workspace_bytes(B, F, K, total)
+    assert built_lib.dir_sparse_adam_workspace_bytes(B, F, K, total) == sort_area + 8 * _lib.ADAM_NORM_WORDS + (total + 255) // 256 * 256
+    src = open(os.path.join(ROOT, "include", "dir_hip.h")).read()
+    assert "128 x u64" in src and "norm2[64 + f]" in src and "2^62" in src
+    assert "128 x u64" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
+
+
 def _shared_checks(lib, name, call, p):
     """What both entries reject alike: the arguments of adam_payload_check."""
     for arg in ("payload", "grad", "rb", "ws"):
