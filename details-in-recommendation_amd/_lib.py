@@ -234,6 +234,8 @@ SIGNATURES = {
     "dir_shard_finish_groups_f32": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp]),
     "dir_rows_scatter_sum_workspace_bytes": (c_i64, [c_i64, c_i32, c_i64]),
     "dir_rows_scatter_sum_f32": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "dir_rows_scatter_sum_side_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i64]),
+    "dir_rows_scatter_sum_side_f32": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "dir_shard_grad_groups_f32": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp]),
     "dir_shard_bags_linear_pool_f32": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp]),
     "dir_shard_bags_linear_combine_f32": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i64, c_i32,

@@ -2439,6 +2439,17 @@ def shard_grad_groups(grads, inv2d, K, send):
 _SCATTER_WS = {}
 
 
+def _scatter_workspace(need, device):
+    """rows_scatter_sum's workspace: cached per (device, stream), grown with the largest call; from the graph's own pool under capture."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(need + 256, dtype=torch.uint8, device=device)
+    key = (device, int(_stream().value or 0))
+    ws = _SCATTER_WS.get(key)
+    if ws is None or ws.numel() < need + 256:
+        ws = _SCATTER_WS[key] = torch.empty(need + 256, dtype=torch.uint8, device=device)
+    return ws
+
+
 def rows_scatter_sum(idx, vals, R, out=None, K=None):
     """Sparse rows summed into a dense slab (include/dir_hip.h: dir_rows_scatter_sum_f32): idx [n] int64 positions, vals [n, >= K] fp32 with
     unit inner stride (K: the leading floats of a row that count; default: all) -> out [R, K], out[r] = sum of vals[i, :K] over
@@ -2465,18 +2476,57 @@ def rows_scatter_sum(idx, vals, R, out=None, K=None):
     need = int(lib.dir_rows_scatter_sum_workspace_bytes(n, K, R))
     if need < 0:
         raise _lib.DirError(-4, "rows_scatter_sum: unsupported size (n < 2^30, R < 2^32-1)")
-    if torch.cuda.is_current_stream_capturing():
-        # a capture gets a workspace from the graph's own pool (nothing is read across calls): an eager call never shares it with a replay
-        ws = torch.empty(need + 256, dtype=torch.uint8, device=vals.device)
-    else:
-        key = (vals.device, int(_stream().value or 0))
-        ws = _SCATTER_WS.get(key)
-        if ws is None or ws.numel() < need + 256:
-            ws = _SCATTER_WS[key] = torch.empty(need + 256, dtype=torch.uint8, device=vals.device)
+    # a capture gets a workspace from the graph's own pool (nothing is read across calls): an eager call never shares it with a replay
+    ws = _scatter_workspace(need, vals.device)
     ld = vals.stride(0) if n > 1 else max(K, vals.shape[1])
     _lib.check(lib.dir_rows_scatter_sum_f32(_ptr(idx), _ptr(vals), ld, n, K, R, _ptr(out), ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256),
                                             need, _stream()))
     return out
+
+
+def rows_scatter_sum_side(idx, vals, side, side_div, R, out=None, out_side=None, K=None):
+    """rows_scatter_sum with a side sum on the same sort (include/dir_hip.h: dir_rows_scatter_sum_side_f32): idx [n], vals [n, >= K] as
+    there; side [>= ceil(n / side_div), U] fp32 with unit inner stride, 1 <= U <= 4, one row per group of side_div consecutive entries
+    -> (out [R, K], out_side [R, U]): out as rows_scatter_sum writes it, out_side[r] = sum of side[i // side_div] over idx[i] == r -- bit
+    for bit rows_scatter_sum(idx, side.repeat_interleave(side_div, 0)[:n], R), without the expansion, the second key pass and the second
+    sort.  The same workspace cache and the same capture rule as rows_scatter_sum."""
+    _dev(idx, torch.int64, "idx")
+    _dev(vals, torch.float32, "vals")
+    _dev(side, torch.float32, "side")
+    if idx.dim() != 1 or not idx.is_contiguous():
+        raise ValueError("rows_scatter_sum_side: idx must be a contiguous [n] tensor")
+    n = idx.shape[0]
+    if vals.dim() != 2 or vals.shape[0] != n or (n and vals.stride(1) != 1):
+        raise ValueError("rows_scatter_sum_side: vals must be [n, >= K] with unit inner stride")
+    K = int(vals.shape[1] if K is None else K)
+    R, side_div = int(R), int(side_div)
+    if not 0 < K <= vals.shape[1]:
+        raise ValueError("rows_scatter_sum_side: 0 < K <= vals.shape[1]")
+    if side_div < 1:
+        raise ValueError("rows_scatter_sum_side: side_div >= 1")
+    if side.dim() != 2 or not 1 <= side.shape[1] <= 4 or (side.shape[0] and side.stride(1) != 1) or side.shape[0] * side_div < n:
+        raise ValueError("rows_scatter_sum_side: side must be [>= ceil(n / side_div), 1 <= U <= 4] with unit inner stride")
+    U = int(side.shape[1])
+    if out is None:
+        out = torch.empty((R, K), dtype=torch.float32, device=vals.device)
+    if out_side is None:
+        out_side = torch.empty((R, U), dtype=torch.float32, device=vals.device)
+    _dev(out, torch.float32, "out")
+    _dev(out_side, torch.float32, "out_side")
+    if out.shape != (R, K) or not out.is_contiguous():
+        raise ValueError("rows_scatter_sum_side: out must be a contiguous [R, K] tensor")
+    if out_side.shape != (R, U) or not out_side.is_contiguous():
+        raise ValueError("rows_scatter_sum_side: out_side must be a contiguous [R, U] tensor")
+    lib = _lib.load()
+    need = int(lib.dir_rows_scatter_sum_side_workspace_bytes(n, K, U, R))
+    if need < 0:
+        raise _lib.DirError(-4, "rows_scatter_sum_side: unsupported size (n < 2^30, R < 2^32-1)")
+    ws = _scatter_workspace(need, vals.device)
+    ld = vals.stride(0) if n > 1 else max(K, vals.shape[1])
+    side_ld = side.stride(0) if side.shape[0] > 1 else U
+    _lib.check(lib.dir_rows_scatter_sum_side_f32(_ptr(idx), _ptr(vals), ld, _ptr(side), side_ld, side_div, n, K, U, R, _ptr(out), _ptr(out_side),
+                                                 ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256), need, _stream()))
+    return out, out_side
 
 
 def shard_linear_gather_units(lin_ts, recv, P, cap, out):

@@ -43,6 +43,10 @@ lookup without a finish pass, de-duplicated; the unit's kernels read the receive
 for that is the transpose of a de-duplicated lookup -- many entry gradients summed into the one slab position they share -- as a kernel
 (backend.rows_scatter_sum: lookup_train(dedup=True), lookup_rows_train / backward_rows).
 
+xDeepFM trains on the shards as well (ShardedXDeepFMTrainer): its first-order term rides on the de-duplicated training exchange, the
+gradient d lin summed per slab position by the same call and on the same sort as the row gradients (backend.rows_scatter_sum_side:
+lookup_train(with_linear=True, dedup=True)).
+
 The collectives are torch.distributed.all_to_all_single (backend "nccl" = RCCL on ROCm; "gloo" in the CPU tests).
 world_size == 1 skips the collectives (unless force_collective) but still runs the three HIP steps.  The HIP steps sit
 behind a small backend object so that the CPU (gloo) tests can stand the oracle in for them; the default backend is the
@@ -231,6 +235,11 @@ class HipBackend:
         points -- the transpose of reading `out` through idx, also when many entries share a position (a de-duplicated lookup).
         HIP: sorted, compensated run sums, no float atomics; a position named once gets its entry's row bit for bit."""
         ops.rows_scatter_sum(idx, vals, R, out=out)
+
+    def rows_scatter_sum_side(self, idx, vals, side, side_div, R, out, out_side):
+        """rows_scatter_sum plus, on the same sort, out_side [R, U] = side [.., U] row i // side_div summed per position idx[i]: the
+        first-order term's gradient of a de-duplicated lookup (side = d lin [Bc, U], side_div = F), read in place."""
+        ops.rows_scatter_sum_side(idx, vals, side, side_div, R, out=out, out_side=out_side)
 
     # ---- row groups (ShardedTables(groups=G), G > 1): the finish pass that de-interleaves, and its transpose --------
     def finish_groups(self, back, inv2d, K, outs):
@@ -894,11 +903,14 @@ class ShardedTables:
 
     def _need_dedup_train(self, what, with_linear=False):
         """The combinations de-duplicated training does not cover, refused before anything is enqueued."""
-        if with_linear:
-            raise NotImplementedError("%s with with_linear=True: the first-order term's backward writes one slab position per entry; train it "
-                                      "with dedup=False" % what)
+        if with_linear and not hasattr(self.backend, "rows_scatter_sum_side"):
+            raise NotImplementedError("%s with with_linear=True: this backend has no scatter-sum with a side sum (rows_scatter_sum_side), and "
+                                      "the first-order term's plain backward writes one slab position per entry; train it with dedup=False"
+                                      % what)
         if self.G > 1:
             raise NotImplementedError("%s: row groups (groups=%d) are trained one slab position per entry (dedup=False) only" % (what, self.G))
+        if with_linear and self.U != 1:
+            raise NotImplementedError("%s with with_linear=True: one first-order unit per row only (units=%d)" % (what, self.U))
         if not hasattr(self.backend, "rows_scatter_sum"):
             raise NotImplementedError("%s: this backend has no scatter-sum of gradient rows (rows_scatter_sum)" % what)
 
@@ -915,8 +927,11 @@ class ShardedTables:
         a capacity and plans of its own); the backward sums the gradients of the entries that share a slab position on the requester
         (backend.rows_scatter_sum: sorted, compensated, no float atomics) before the reversed exchange, and the owner -- which sees fewer
         payload words -- still sums duplicates across tiles, micro-batches and ranks.  The forward is bit for bit dedup=False's.  The
-        exact path (mode="exact", overflow repair) stays one row per entry.  Not covered (each raises NotImplementedError):
-        with_linear=True, row groups, a backend without rows_scatter_sum."""
+        exact path (mode="exact", overflow repair) stays one row per entry.  with_linear=True under dedup: d lin is summed per slab
+        position by the SAME call on the same sort (backend.rows_scatter_sum_side: one call per micro-batch gives the gradient slab and
+        the first-order slab), and the owner's FTRL sums what is left across tiles, micro-batches and ranks before its non-linear rule.
+        Not covered (each raises NotImplementedError): row groups, a backend without rows_scatter_sum (with_linear: without
+        rows_scatter_sum_side)."""
         if self.optimizer is None:
             raise RuntimeError("call enable_training(lr) first")
         if dedup:
@@ -987,7 +1002,7 @@ class ShardedTables:
             return (back, torch.where(live, inv.view(B, F), torch.full_like(ids, -1))), ("exact", inv, sc, rc, recv, True), None
         if dedup:                                        # (one row per entry here: the backward's scatter-sum sees only runs of one)
             emb, _ = self.backend.finish(back, inv, B, F, False)
-            return emb, ("exact", inv, sc, rc, recv, True), None
+            return emb, ("exact", inv, sc, rc, recv, True), lin[0] if with_lin else None
         if self.G == 1:
             emb, _ = self.backend.finish(back, inv, B, F, False)
         else:
@@ -1046,7 +1061,13 @@ class ShardedTables:
                     # atomics); positions nobody names come out as zeros
                     gsend = torch.empty((P * cap, K), dtype=torch.float32, device=g2.device)
                     idx = be.inv2d(plan.inv[c], e - s, self.F, True).reshape(-1)
-                    be.rows_scatter_sum(idx, g2[s:e].reshape(-1, K), P * cap, gsend)
+                    if g_lin is None:
+                        be.rows_scatter_sum(idx, g2[s:e].reshape(-1, K), P * cap, gsend)
+                    else:
+                        # ... and d lin with them, on the same sort: entry i belongs to sample i // F, so g_lin is read in place and the
+                        # first-order slab (this micro-batch's lrows) comes out of the same call
+                        be.rows_scatter_sum_side(idx, g2[s:e].reshape(-1, K), g_lin[s:e], self.F, P * cap, gsend,
+                                                 plan.lin_buffers(U)[0][c].view(P * cap, U))
                 elif G > 1:
                     # ... by the HIP transpose of the grouped finish: zero-fill + one writer per position, no dump row
                     gsend = torch.empty((P * cap, self.KW), dtype=torch.float32, device=dev)
@@ -1066,7 +1087,8 @@ class ShardedTables:
                 if g_lin is not None:
                     # the forward's linear buffers carry the gradient back: lrows = what this rank sends, lback = what it receives
                     lrows, lback = plan.lin_buffers(U)
-                    self._lin_grad(g_lin[s:e], be.inv2d(plan.inv[c], e - s, self.F, False), lrows[c])
+                    if not plan.dedup:                   # (de-duplicated: rows_scatter_sum_side has written lrows[c] above)
+                        self._lin_grad(g_lin[s:e], be.inv2d(plan.inv[c], e - s, self.F, False), lrows[c])
                     if self._collective():
                         self._a2a(lback[c], lrows[c], None, None)
             # ONE update over all micro-batches (duplicates of a row -- from any chunk, any rank -- are summed before the accumulator
@@ -1914,10 +1936,15 @@ class ShardedDeepFMTrainer:
     compute fm + dnn + lin, and so do step_bags() and predict_bags() over multi-hot bags: the owners pool the first-order weights of
     each bag beside its embedding rows and `model`.linear_sparse_combiner is applied on the requester (lookup_bags(want_lin=True),
     lookup_bags_train(with_linear=True)); a backend without the bag forms of the term raises NotImplementedError there.
-    linear = None: the FM + DNN model, as before."""
+    linear = None: the FM + DNN model, as before.
+    dedup = True: step() runs the de-duplicated training exchange (lookup_train(dedup=True): each distinct (slot, row) of a tile travels
+    once, the entries' gradients -- and, with linear=, d lin on the same sort -- are summed per slab position on the requester); the
+    default keeps one slab position per entry and its bits."""
 
-    def __init__(self, model, tables, lr_sparse, dense_optimizer, group=None, initial_accumulator_value=0.1, linear=None):
+    def __init__(self, model, tables, lr_sparse, dense_optimizer, group=None, initial_accumulator_value=0.1, linear=None, dedup=False):
         self.model, self.tables, self.group = model, tables, group
+        self.dedup = bool(dedup)
+        name = type(self).__name__
         self.dense_params = [p for n, p in model.named_parameters()
                              if not (n.startswith("embedding_weights") or n.startswith("linear_weights"))]
         self.dense_optimizer = dense_optimizer
@@ -1925,10 +1952,10 @@ class ShardedDeepFMTrainer:
         self.linear = None
         if linear is not None:
             if tables.lin_rows is None:
-                raise ValueError("ShardedDeepFMTrainer(linear=...): the tables have no first-order weights (ShardedTables.attach_linear)")
+                raise ValueError("%s(linear=...): the tables have no first-order weights (ShardedTables.attach_linear)" % name)
             bias = model.linear_bias
             if any(p is bias for grp in dense_optimizer.param_groups for p in grp["params"]):
-                raise ValueError("ShardedDeepFMTrainer(linear=...): linear_bias takes the FTRL step here; leave it out of dense_optimizer")
+                raise ValueError("%s(linear=...): linear_bias takes the FTRL step here; leave it out of dense_optimizer" % name)
             hp = (float(linear["lr"]), float(linear.get("l1", 0.0)), float(linear.get("l2", 0.0)))
             tables.enable_linear_training(*hp)
             self.linear = hp
@@ -1954,10 +1981,10 @@ class ShardedDeepFMTrainer:
         self.dense_optimizer.zero_grad(set_to_none=True)
         if self.linear is not None:
             m.linear_bias.grad = None
-            emb, lin = self.tables.lookup_train(ids, with_linear=True)        # both shards' rows update inside backward()
+            emb, lin = self.tables.lookup_train(ids, with_linear=True, dedup=self.dedup)       # both shards' rows update inside backward()
             logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb) + (lin + m.linear_bias)      # ... + linear_logits, deepFM.py:339
         else:
-            emb = self.tables.lookup_train(ids)                               # tables update inside backward()
+            emb = self.tables.lookup_train(ids, dedup=self.dedup)             # tables update inside backward()
             logits = ag.fm_logit(emb, m.F, m.K) + m.dnn_logit_fn(emb)         # fm_logit_fn + dnn_logit_fn, deepFM.py:337-338
         loss = self._loss_backward_dense_step(logits, labels)
         if self.linear is not None:
@@ -2052,6 +2079,70 @@ class ShardedDeepFMTrainer:
             emb, fm, lin = self.tables.lookup_bags(values, offsets, weights, want_lin=True, lin_combiner=m.linear_sparse_combiner,
                                                    lin_bias=m.linear_bias.data.reshape(-1)[:1], **kw)
             return m.dnn_logit_fn(emb, adds=(fm,), range_ok=ops.f16_range_ok(self.tables.absmax())) + lin
+
+
+class ShardedXDeepFMTrainer(ShardedDeepFMTrainer):
+    """One synchronous multi-GPU training step of an xdeepfm.XDeepFM over row-sharded tables (BASELINE config 5, "the config that shards":
+    the reference's README.md:28 model under deepFM.py:163-167's partitioner): the embedding rows and, with linear=, the first-order
+    weights over the same categorical columns live on the shards (tables_from_model); the CIN, the tower and linear_bias are replicated.
+    step() is lookup_train -> XDeepFM.forward_embedded (the model's own training kernels, autograd.CinStack and mlp_head, unchanged) -> the
+    SUM-reduced cross entropy -> backward, inside which every owner takes Adagrad on its embedding rows, then FTRL on its first-order
+    rows -> the dense gradients summed over the ranks -> the dense step.  Gradients ADD over the ranks: two ranks equal one step over the
+    concatenated batch.  `model`'s own embedding_weights and linear_weights are unused (tables_from_model slices them into the shards); the
+    tower's fp16-range verdict comes from the sharded tables.
+    dedup (the default: Criteo-like ids repeat): the de-duplicated training exchange, the first-order gradient summed per slab position
+    on the row gradient's sort (lookup_train(with_linear=True, dedup=True)).
+    linear = dict(lr=, l1=, l2=, initial_accumulator_value=) as in ShardedDeepFMTrainer: the replicated linear_bias takes the dense FTRL
+    step on its all-reduced gradient and must not be in dense_optimizer.  linear = None: the CIN + DNN model.
+    One-hot ids only: step_bags / predict_bags raise NotImplementedError (bags under dedup are out of scope)."""
+
+    def __init__(self, model, tables, lr_sparse, dense_optimizer, group=None, initial_accumulator_value=0.1, linear=None, dedup=True):
+        if tables.F != model.m or tables.K != model.D or tables.G != 1:
+            raise ValueError("ShardedXDeepFMTrainer: the tables must hold F=%d slots of K=%d floats (tables_from_model), got F=%d K=%d groups=%d"
+                             % (model.m, model.D, tables.F, tables.K, tables.G))
+        super().__init__(model, tables, lr_sparse, dense_optimizer, group, initial_accumulator_value, linear, dedup)
+
+    @classmethod
+    def tables_from_model(cls, model, group=None, linear=True, **kw):
+        """The ShardedTables of `model` (every rank holds the same replicated model): slot f = the f-th embedding column; linear: + the
+        first-order weights, which must be over the embedding columns' categoricals (they share the id exchange).  kw: ShardedTables'
+        options (partitions=, chunks=, mode=, ...)."""
+        if linear and not model._same_categoricals():
+            raise ValueError("ShardedXDeepFMTrainer.tables_from_model(linear=True): the linear columns are not the embedding columns' "
+                             "categoricals; pass linear=False and compute the first-order term beside the shards")
+        tables = ShardedTables.from_full([p.data for p in ops.plain_list(model.embedding_weights)], group=group, **kw)
+        if linear:
+            tables.attach_linear_from_full([p.data for p in ops.plain_list(model.linear_weights)])
+        return tables
+
+    def step(self, ids, labels):
+        """ids [B_local, F] global row ids, labels [B_local, 1] -> this rank's summed loss (detached)."""
+        m = self.model
+        if not m.training:
+            m.train()
+        self.dense_optimizer.zero_grad(set_to_none=True)
+        range_ok = ops.f16_range_ok(self.tables.absmax())       # the SHARDED tables' magnitude, not the model's own (unused) tables'
+        with torch.enable_grad():
+            if self.linear is not None:
+                m.linear_bias.grad = None
+                emb, lin = self.tables.lookup_train(ids, with_linear=True, dedup=self.dedup)
+                logits = m.forward_embedded(emb, lin + m.linear_bias, range_ok=range_ok)
+            else:
+                logits = m.forward_embedded(self.tables.lookup_train(ids, dedup=self.dedup), None, range_ok=range_ok)
+            loss = self._loss_backward_dense_step(logits, labels)
+        if self.linear is not None:
+            self._bias_ftrl_step()
+        return loss
+
+    def step_bags(self, *a, **kw):
+        raise NotImplementedError("ShardedXDeepFMTrainer: one-hot ids only (step / predict)")
+
+    predict_bags = step_bags
+
+    @torch.no_grad()
+    def predict(self, ids):
+        """Inference logits [B_local, 1] over the row-sharded tables: xdeepfm_predict(model, tables, ids)."""
+        return xdeepfm_predict(self.model, self.tables, ids)
 
 
 def _esmm_parts(model):

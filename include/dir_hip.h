@@ -615,6 +615,23 @@ int64_t dir_rows_scatter_sum_workspace_bytes(int64_t n, int K, int64_t R);
 int dir_rows_scatter_sum_f32(const int64_t* idx, const float* vals, int64_t ld, int64_t n, int K, int64_t R, float* out, void* workspace,
                              int64_t workspace_bytes, dir_stream_t stream);
 
+/* ... with a SIDE sum on the same sort (the first-order term of a de-duplicated training lookup, ShardedTables.lookup_train(ids,
+ * with_linear=True, dedup=True)).
+ * dir_rows_scatter_sum_side_f32: out [R, K] exactly as dir_rows_scatter_sum_f32 writes it (same bits), and out_side [R, U] contiguous:
+ *   out_side[r, :U] = sum of side[i / side_div, :U] over idx[i] == r -- side [ceil(n / side_div), side_ld] fp32 holds one row per GROUP of
+ *   side_div consecutive entries (entry i of a [Bc * F] entry list belongs to sample i / F: with side_div = F the per-sample gradient
+ *   d lin [Bc, U] is read in place, never expanded to one row per entry).  One key pass (it also zero-fills out_side: no memset node), one
+ *   sort of the (idx, i) pairs and one run discovery serve both sums; the side sums take the same compensated run sum with the same
+ *   256-entry tile cuts and the same combine in double, so out_side is bit for bit dir_rows_scatter_sum_f32 at K = U over the expanded
+ *   rows.  No float atomics.  The shared arguments follow dir_rows_scatter_sum_f32's rules; in addition 1 <= U <= 4, side_div >= 1,
+ *   side_ld >= U, side and out_side non-null when R > 0 (side: and n > 0).  R == 0: nothing is written; n == 0: both outputs are
+ *   zero-filled.  Workspace: dir_rows_scatter_sum_side_workspace_bytes(n, K, U, R) device bytes (-1: unsupported size or U), never less
+ *   than dir_rows_scatter_sum_workspace_bytes(n, K, R), 256-byte aligned, any content; not read across calls. */
+int64_t dir_rows_scatter_sum_side_workspace_bytes(int64_t n, int K, int U, int64_t R);
+int dir_rows_scatter_sum_side_f32(const int64_t* idx, const float* vals, int64_t ld, const float* side, int64_t side_ld, int64_t side_div,
+                                  int64_t n, int K, int U, int64_t R, float* out, float* out_side, void* workspace, int64_t workspace_bytes,
+                                  dir_stream_t stream);
+
 /* Row groups (ShardedTables(groups=G)): every (slot, local row) stores G rows of K floats side by side -- the wide & deep ESMM's
  * ctr_model and cvr_model rows of one id (ESMM_wide_deep.py:213-217) -- so the buffers of the sharded lookup hold rows of G * K floats and
  * bucket, both exchanges and dir_gather_slabs_f32 / dir_gather_packed_f32 run on them unchanged (with K = G * K).  K % 4 == 0,
