@@ -116,6 +116,13 @@ SIGNATURES = {
     "dir_sparse_adam_payload_norm_f32": (c_i32, [c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),   # norm2: ADAM_NORM_WORDS u64
     "dir_sparse_adam_payload_apply_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                   ctypes.c_float, ctypes.c_float, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
+    # ... over received bag records (P, cap_e, cap_b, grecv, slot_max_norm, max_norm: dir_sparse_adagrad_sorted_bags_f32's record arguments)
+    "dir_sparse_adam_bags_workspace_bytes": (c_i64, [c_i32, c_i64, c_i32, c_i32, c_i64]),
+    "dir_sparse_adam_bags_norm_f32": (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, ctypes.c_float, c_vp, c_i64, c_vp, c_vp,
+                                              c_i64, c_vp]),
+    "dir_sparse_adam_bags_apply_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, ctypes.c_float, ctypes.c_float,
+                                               ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64,
+                                               c_i32, c_i32, c_vp]),
     "dir_sparse_adagrad_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_float, c_i64, c_vp,
                                        c_i64, c_vp, c_vp, c_vp]),
     "dir_sparse_adagrad_sorted_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i64]),

@@ -656,6 +656,77 @@ __device__ __forceinline__ void bag_apply(const FtrlUpd& upd, const BagSrc&, int
     if (c < kv) upd.template apply<VEC>(f, id, c * VEC, sum);
 }
 
+// ... and for the two halves of the sharded Adam step (dir_sparse_adam_bags_{norm,apply}_f32).  "The row's gradient" of everything after
+// the run sum is the sum through the slot's max_norm clip derivative (bag_apply(AdagradUpd)'s arithmetic) at the row's pre-update value:
+// TF's train_op clips -- and takes the norm of -- the gradient that reaches the variable.  The butterfly runs over the whole group
+// (every lane ends with the same ||r||^2 and r . S) before any lane writes.
+template <int LPS, int VEC>
+__device__ __forceinline__ typename BV<VEC>::T bag_clip_grad(typename BV<VEC>::T wv, typename BV<VEC>::T sum, float mn) {
+    using V = BV<VEC>;
+    float n2 = V::dot(wv, wv, 0.f), rg = V::dot(wv, sum, 0.f);
+#pragma unroll
+    for (int o = LPS / 2; o > 0; o >>= 1) {
+        n2 += __shfl_xor(n2, o, 64);
+        rg += __shfl_xor(rg, o, 64);
+    }
+    const float nrm = sqrtf(n2);
+    if (nrm > mn) sum = V::scale(V::sub(V::scale(sum, 1.f / nrm), V::scale(wv, rg / (nrm * nrm * nrm))), mn);
+    return sum;
+}
+
+// the norm half: reads the row only where its slot has a max_norm (tables may be NULL otherwise), writes no table; the lane's chunk of
+// ||row gradient||^2 goes into `words` (the tile's LDS words in adagrad_tile_k, the global ones in adagrad_fix_k), as the payload form's
+struct AdamBagNormUpdW : AdamNormUpdW {
+    const float* const* tables = nullptr;
+    int64_t ld = 0;
+};
+template <int LPS, int VEC>
+__device__ __forceinline__ void bag_apply(const AdamBagNormUpdW& upd, const BagSrc& bag, int f, int64_t id, int c, int kv, typename BV<VEC>::T sum,
+                                          unsigned long long* words) {
+    using V = BV<VEC>;
+    const bool act = c < kv;
+    if (!act) sum = V::zero();
+    const float mn = bag.slot_mn ? bag.slot_mn[f] : bag.mn;      // (group-uniform)
+    if (mn > 0.f) {
+        typename V::T wv = V::ld(upd.tables[f] + id * upd.ld + (int64_t)(act ? c : 0) * VEC);
+        if (!act) wv = V::zero();
+        sum = bag_clip_grad<LPS, VEC>(wv, sum, mn);
+    }
+    if (!act) return;
+    unsigned long long hi, lo;
+    adam_norm_split(V::dot(sum, sum, 0.f), hi, lo);
+    if (lo) atomicAdd(words + (f & 63), lo);
+    if (hi) atomicAdd(words + 64 + (f & 63), hi);
+}
+
+// the apply half: the derivative from the row it loaded, AdamUpd::one with the global norm, then m, v and var written once and the row marked
+template <int LPS, int VEC>
+__device__ __forceinline__ void bag_apply(const AdamUpdW& upd, const BagSrc& bag, int f, int64_t id, int c, int kv, typename BV<VEC>::T sum) {
+    using V = BV<VEC>;
+    using T = typename V::T;
+    const bool act = c < kv;
+    const int64_t off = id * upd.ld + (int64_t)(act ? c : 0) * VEC;
+    float* mp = upd.ms[f] + off;
+    float* vp = upd.vs[f] + off;
+    float* wp = upd.tables[f] + off;
+    T m = V::ld(mp), v = V::ld(vp), w = V::ld(wp);
+    if (!act) sum = V::zero();
+    const float mn = bag.slot_mn ? bag.slot_mn[f] : bag.mn;      // (group-uniform)
+    if (mn > 0.f) sum = bag_clip_grad<LPS, VEC>(act ? w : V::zero(), sum, mn);
+    if (!act) return;
+    float den = upd.clip;
+    if (upd.clip > 0.f && upd.norm2_sum) den = fmaxf(sqrtf((float)upd.norm2_sum[f]), upd.clip);
+    if constexpr (VEC == 4) {
+        upd.one(sum.x, den, m.x, v.x, w.x); upd.one(sum.y, den, m.y, v.y, w.y); upd.one(sum.z, den, m.z, v.z, w.z); upd.one(sum.w, den, m.w, v.w, w.w);
+    } else {
+        upd.one(sum, den, m, v, w);
+    }
+    V::st(mp, m);
+    V::st(vp, v);
+    V::st(wp, w);
+    if (c == 0) upd.mark[upd.row_base[f] + id] = 1;
+}
+
 // every row of table f NOT stepped by AdamUpd this step (mark == 0): zero gradient -> m *= b1, v *= b2, var -= lr_t * m / (sqrt(v) + eps);
 // marked rows are skipped and their mark cleared.  LPS = K / 4 adjacent lanes own a row (all of them read the mark before lane 0 of
 // the group clears it: one wave instruction apart).
@@ -864,7 +935,9 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
         const bool open_l = r == 0 && cont_l, open_r = r == nruns - 1 && cont_r;
         if (!open_l && !open_r) {
             const int64_t id = (int64_t)rk - row_base[f];
-            if constexpr (BAG) {
+            if constexpr (BAG && IsNorm<U>::value) {
+                bag_apply<LPS, VEC>(upd, bag, f, id, c, kv, sum, nsq);
+            } else if constexpr (BAG) {
                 bag_apply<LPS, VEC>(upd, bag, f, id, c, kv, sum);
             } else if constexpr (IsNorm<U>::value) {
                 unsigned long long hi, lo;
@@ -931,7 +1004,9 @@ __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
         for (int q = 1; q < nt; ++q) f += (int64_t)kl >= row_base[q] ? 1 : 0;
     }
     const int64_t id = (int64_t)kl - row_base[f];
-    if constexpr (BAG) {
+    if constexpr (BAG && IsNorm<U>::value) {
+        bag_apply<LPS, VEC>(upd, bag, f, id, c0, kv, sum, upd.norm2);
+    } else if constexpr (BAG) {
         bag_apply<LPS, VEC>(upd, bag, f, id, c0, kv, sum);
     } else if constexpr (IsNorm<U>::value) {
         unsigned long long hi, lo;
@@ -1607,7 +1682,8 @@ static int sorted_bags_update(const char* name, U upd, int K, int F, const int64
     if (total_rows < 0 || total_rows >= 0xffffffffll) return fail(DIR_E_UNSUPPORTED, "%s: total_rows must be in [0, 2^32-1)", name);
     if (total_rows == 0) return DIR_OK;          // this rank holds no rows: no record can name one
     AdaSortedPlan p;
-    if (!adagrad_sorted_plan(n, K, total_rows, p)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
+    // (IsWide: carry rows of K doubles)
+    if (!adagrad_sorted_plan(n, IsWide<U>::value ? 2 * K : K, total_rows, p)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
     SortedBufs b;
     if (int rc = sorted_carve(name, p, workspace, workspace_bytes, sorted_from, b)) return rc;
     hipStream_t st = as_stream(stream);
@@ -1629,10 +1705,12 @@ static int sorted_bags_update(const char* name, U upd, int K, int F, const int64
     static const int stage_min = dev_env_int("DIR_ADA_STAGE_MIN", 8);       // development A/B switch
     auto launch = [&](auto L, auto V) {
         constexpr int LPS = decltype(L)::value, VEC = decltype(V)::value;
-        hipLaunchKernelGGL((adagrad_tile_k<LPS, VEC, U, false, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, 1, K, n, b.k1, b.v1, nullptr,
-                           (int64_t)0, (int64_t)0, row_base, (uint32_t)total_rows, F, b.carry, nullptr, nullptr, stage_min, bag);
-        hipLaunchKernelGGL((adagrad_fix_k<LPS, VEC, U, true>), dim3((unsigned)((ntiles * LPS + 255) / 256)), dim3(256), 0, st, upd, 1, K, n, ntiles,
-                           b.k1, b.v1, row_base, (uint32_t)total_rows, F, b.carry, bag);
+        if constexpr (!(IsWide<U>::value && VEC == 1)) {                 // the Adam entries take the 16-byte path only (checked there)
+            hipLaunchKernelGGL((adagrad_tile_k<LPS, VEC, U, false, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, 1, K, n, b.k1, b.v1, nullptr,
+                               (int64_t)0, (int64_t)0, row_base, (uint32_t)total_rows, F, b.carry, nullptr, nullptr, stage_min, bag);
+            hipLaunchKernelGGL((adagrad_fix_k<LPS, VEC, U, true>), dim3((unsigned)((ntiles * LPS + 255) / 256)), dim3(256), 0, st, upd, 1, K, n, ntiles,
+                               b.k1, b.v1, row_base, (uint32_t)total_rows, F, b.carry, bag);
+        }
     };
     if constexpr (std::is_same<U, FtrlUpd>::value) launch(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});     // packed rows: K = 1
     else dispatch_lps(vec, lps, launch);
@@ -1672,4 +1750,85 @@ extern "C" int dir_sparse_ftrl_rows_sorted_bags_f32(float* const* rows, int F, c
     upd.rows = true;
     return sorted_bags_update(name, upd, 1, F, recv, P, cap_e, cap_b, grecv, nullptr, 0.f, row_base, total_rows, workspace, workspace_bytes,
                               sorted_from, stream);
+}
+
+// ---- tf.train.AdamOptimizer over the received bag records: ShardedTables.lookup_bags_train under enable_training_adam ---------------
+// The bag counterparts of dir_sparse_adam_payload_{norm,apply}_f32: the same two halves around the ranks' norm sum, over the record
+// arguments of dir_sparse_adagrad_sorted_bags_f32.  A row's sum is formed in double over all its entries (kWide) and rounded once, goes
+// through the slot's max_norm clip derivative at the row's pre-update value, and IS the row's gradient from there on: the norm half
+// adds up its squares, the apply half steps the row with it.  The arguments both halves share are checked here, before any HIP call.
+static int adam_bags_check(const char* name, int F, int K, const int64_t* recv, int P, int64_t cap_e, int64_t cap_b, const float* grecv,
+                           float max_norm, const int64_t* row_base, int64_t total_rows, const void* workspace, int64_t workspace_bytes) {
+    DIR_CHECK_ARG(F > 0 && F <= 64, "%s: F=%d (1 <= F <= 64)", name, F);
+    DIR_CHECK_ARG(K > 0 && !(K & 3) && K / 4 <= 64 && 64 % (K / 4) == 0, "%s: K=%d (a multiple of 4 with K / 4 dividing 64)", name, K);
+    if (int rc = check_slab_geometry(name, P, cap_e, cap_b)) return rc;
+    const int64_t n = (int64_t)P * cap_e;
+    if (n >= ((int64_t)1 << 30)) return fail(DIR_E_UNSUPPORTED, "%s: P*cap_e=%lld entry slots (the sort takes < 2^30)", name, (long long)n);
+    if (total_rows < 0 || total_rows >= 0xffffffffll) return fail(DIR_E_UNSUPPORTED, "%s: total_rows must be in [0, 2^32-1)", name);
+    DIR_CHECK_ARG(!(max_norm < 0.f), "%s: max_norm=%g", name, (double)max_norm);
+    DIR_CHECK_ARG(recv, "%s: null pointer (recv)", name);
+    DIR_CHECK_ARG(grecv, "%s: null pointer (grecv)", name);
+    DIR_CHECK_ARG(row_base, "%s: null pointer (row_base)", name);
+    DIR_CHECK_ARG(workspace, "%s: null pointer (workspace)", name);
+    if (!aligned16(grecv)) return fail(DIR_E_UNSUPPORTED, "%s: grecv must be 16-byte aligned (the rows are read 16 bytes per lane)", name);
+    AdaSortedPlan p;
+    if (!adagrad_sorted_plan(n, 2 * K, total_rows > 0 ? total_rows : 1, p)) return fail(DIR_E_HIP, "%s: sort size query failed", name);   // carry rows of K doubles
+    if ((int64_t)p.total > workspace_bytes || (reinterpret_cast<uintptr_t>(workspace) & 255u))
+        return fail(DIR_E_BADARG, "%s: workspace needs %lld bytes, 256-byte aligned", name, (long long)p.total);
+    return DIR_OK;
+}
+
+extern "C" int64_t dir_sparse_adam_bags_workspace_bytes(int P, int64_t cap_e, int F, int K, int64_t total_rows) {
+    if (P <= 0 || P > 64 || cap_e <= 0 || cap_e >= ((int64_t)1 << 31) || (int64_t)P * cap_e >= ((int64_t)1 << 30)) return 0;
+    return dir_sparse_adam_payload_workspace_bytes((int64_t)P * cap_e, F, K, total_rows);
+}
+
+extern "C" int dir_sparse_adam_bags_norm_f32(const float* const* tables, int F, int K, const int64_t* recv, int P, int64_t cap_e, int64_t cap_b,
+                                             const float* grecv, const float* slot_max_norm, float max_norm, const int64_t* row_base,
+                                             int64_t total_rows, uint64_t* norm2, void* workspace, int64_t workspace_bytes,
+                                             dir_stream_t stream) {
+    const char* name = "dir_sparse_adam_bags_norm_f32";
+    if (int rc = adam_bags_check(name, F, K, recv, P, cap_e, cap_b, grecv, max_norm, row_base, total_rows, workspace, workspace_bytes)) return rc;
+    DIR_CHECK_ARG(tables || (!slot_max_norm && max_norm == 0.f), "%s: null pointer (tables: the max_norm clip derivative reads the rows)", name);
+    DIR_CHECK_ARG(norm2, "%s: null pointer (norm2)", name);
+    DIR_CHECK_ARG(!(reinterpret_cast<uintptr_t>(norm2) & 7u), "%s: norm2 must be 8-byte aligned", name);
+    if (zero_async(norm2, ADAM_NORM_BYTES, as_stream(stream)) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
+    if (total_rows == 0) return DIR_OK;                      // no rows here: this owner's share is zero
+    AdamBagNormUpdW upd;
+    upd.norm2 = reinterpret_cast<unsigned long long*>(norm2);
+    upd.tables = tables;
+    upd.ld = (int64_t)K;
+    return sorted_bags_update(name, upd, K, F, recv, P, cap_e, cap_b, grecv, slot_max_norm, max_norm, row_base, total_rows, workspace,
+                              workspace_bytes, nullptr, stream);
+}
+
+extern "C" int dir_sparse_adam_bags_apply_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* recv, int P,
+                                              int64_t cap_e, int64_t cap_b, const float* grecv, const float* slot_max_norm, float max_norm,
+                                              float lr_t, float beta1, float beta2, float eps, float clip_norm, const double* norm2_global,
+                                              const int64_t* row_base, int64_t total_rows, unsigned char* marks, void* workspace,
+                                              int64_t workspace_bytes, int sorted, int first_call, dir_stream_t stream) {
+    const char* name = "dir_sparse_adam_bags_apply_f32";
+    if (int rc = adam_bags_check(name, F, K, recv, P, cap_e, cap_b, grecv, max_norm, row_base, total_rows, workspace, workspace_bytes)) return rc;
+    DIR_CHECK_ARG(tables && ms && vs, "%s: null pointer (tables / ms / vs)", name);
+    DIR_CHECK_ARG(marks || total_rows == 0, "%s: null pointer (marks)", name);
+    DIR_CHECK_ARG(lr_t >= 0.f, "%s: lr_t=%g", name, (double)lr_t);
+    DIR_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f, "%s: beta1=%g (0 <= beta1 < 1)", name, (double)beta1);
+    DIR_CHECK_ARG(beta2 >= 0.f && beta2 < 1.f, "%s: beta2=%g (0 <= beta2 < 1)", name, (double)beta2);
+    DIR_CHECK_ARG(eps > 0.f, "%s: eps=%g (> 0)", name, (double)eps);
+    DIR_CHECK_ARG(clip_norm >= 0.f, "%s: clip_norm=%g (>= 0)", name, (double)clip_norm);
+    DIR_CHECK_ARG((clip_norm > 0.f) == (norm2_global != nullptr), "%s: norm2_global is NULL exactly when clip_norm == 0 (clip_norm=%g)", name,
+                  (double)clip_norm);
+    DIR_CHECK_ARG(!(reinterpret_cast<uintptr_t>(norm2_global) & 7u), "%s: norm2_global must be 8-byte aligned", name);
+    if (total_rows == 0) return DIR_OK;                      // this owner holds no rows (every vocab < P): nothing can move
+    hipStream_t st = as_stream(stream);
+    const int64_t mark_bytes = (total_rows + 255) & ~(int64_t)255;
+    if (first_call && zero_async(marks, (size_t)mark_bytes, st) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
+    AdamUpdW upd;
+    static_cast<AdamUpd&>(upd) = AdamUpd{tables, ms, vs, nullptr, marks, row_base, lr_t, beta1, beta2, eps, clip_norm, (int64_t)K};
+    upd.norm2_sum = norm2_global;
+    // (slabs without a live record sort behind every row: the tile pass touches nothing and the decay pass below steps every row)
+    if (int rc = sorted_bags_update(name, upd, K, F, recv, P, cap_e, cap_b, grecv, slot_max_norm, max_norm, row_base, total_rows, workspace,
+                                    workspace_bytes, sorted ? workspace : nullptr, stream))
+        return rc;
+    return adam_decay_all(name, tables, ms, vs, F, K, row_base, total_rows, marks, lr_t, beta1, beta2, eps, st);
 }

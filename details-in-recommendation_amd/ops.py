@@ -3164,7 +3164,8 @@ class SparseAdam:
     own with tf.clip_by_norm(g, clip_norm) first.  Holds m and v (zeros, like the slots TF creates).  Set .lr_t before every step
     (lr * sqrt(1 - beta2^t) / (1 - beta1^t), t = global_step + 1); attach() makes loss.backward() perform the update.
     On the shards of row-sharded tables the same step runs in two halves, norm_payload / step_payload, around the ranks' sum of the norm
-    shares (shard.ShardedTables.enable_training_adam)."""
+    shares (shard.ShardedTables.enable_training_adam); norm_bags / step_bags are the same halves over the bag records of a multi-hot
+    lookup (lookup_bags_train), on the same marks, norm words and sort area."""
 
     def __init__(self, tables, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0):
         self.ts = _as_tableset(tables)
@@ -3284,6 +3285,77 @@ class SparseAdam:
                                                              ws_bytes, sorted_, first, stream))
         except _lib.DirError:
             self._marks = None         # a step that failed between its two passes may have left marks set: the next call zeroes them again
+            raise
+        ts.written(*self.ms, *self.vs)
+        self.steps += 1
+
+    # ---- ... over received bag records (shard.ShardedTables.lookup_bags_train under enable_training_adam) ------------------------
+    # The marks, the first_call state, the sort area and the norm words are the payload form's: one-hot and bag steps may alternate.
+    def _bags_args(self, recv, P, cap_e, cap_b, grad_rows, slot_mn, what):
+        ts = self.ts
+        _dev(recv, torch.int64, "recv")
+        _dev(grad_rows, torch.float32, "grad_rows")
+        if recv.numel() < P * (cap_e + 1) * 2 or grad_rows.shape != (P * cap_b, ts.K) or not grad_rows.is_contiguous() or not recv.is_contiguous():
+            raise ValueError("%s: recv [P*(cap_e+1)*2] int64, grad_rows a contiguous [P*cap_b, K] tensor" % what)
+        if slot_mn is not None:
+            _dev(slot_mn, torch.float32, "slot_mn")
+            if slot_mn.numel() != ts.F or not slot_mn.is_contiguous():
+                raise ValueError("%s: slot_mn must be a contiguous [F] float32 tensor" % what)
+        lib = _lib.load()
+        need = int(lib.dir_sparse_adam_bags_workspace_bytes(P, cap_e, ts.F, ts.K, self.total_rows))
+        if need <= 0:
+            raise _lib.DirError(-4, "sparse_adam (bags): unsupported size (F <= 64, K / 4 a power of two, P*cap_e < 2^30, total rows < 2^32-1)")
+        if self._pws is None or self._pws.numel() < need + 256:
+            self._pws = torch.empty(need + 256, dtype=torch.uint8, device=ts.device)
+        off = (-self._pws.data_ptr()) % 256
+        return lib, ctypes.c_void_p(self._pws.data_ptr() + off), self._pws.numel() - off
+
+    def norm_bags(self, recv, P, cap_e, cap_b, grad_rows, slot_mn=None, mn=0.0):
+        """First half over bag records (include/dir_hip.h: dir_sparse_adam_bags_norm_f32): recv = the P bag slabs of (cap_e + 1) 16-byte
+        records the forward received, grad_rows [P*cap_b, K] = the gradients of the partial rows as received, slot_mn [F] device fp32 or
+        None + mn as ops.slot_max_norms gives them.  A row's gradient is the sum of w * grad_rows[s*cap_b + ret] over all its entries,
+        through the slot's max_norm clip derivative at the row's current value.  -> norm2 [2, F] device int64, as norm_payload.  The
+        records stay sorted in the workspace for step_bags."""
+        lib, ws, ws_bytes = self._bags_args(recv, P, cap_e, cap_b, grad_rows, slot_mn, "norm_bags")
+        ts = self.ts
+        if self._norm2 is None:
+            self._norm2 = torch.zeros(_lib.ADAM_NORM_WORDS, dtype=torch.int64, device=ts.device)
+        _lib.check(lib.dir_sparse_adam_bags_norm_f32(_ptr(ts.ptrs), ts.F, ts.K, _ptr(recv), P, cap_e, cap_b, _ptr(grad_rows), _ptr(slot_mn),
+                                                     float(mn), _ptr(self.row_base), self.total_rows, _ptr(self._norm2), ws, ws_bytes, _stream()))
+        # what step_bags may reuse: these slabs and gradient rows, unchanged, in this sort area, on this stream
+        self._sorted = (recv, recv._version, self._pws, _stream().value, (P, cap_e, cap_b))
+        words = self._norm2.view(2, 64)[:, :ts.F]
+        return torch.stack([words[0] & 0xffffffff, words[1] + ((words[0] >> 32) & 0xffffffff)])
+
+    def step_bags(self, recv, P, cap_e, cap_b, grad_rows, norm2_global=None, slot_mn=None, mn=0.0):
+        """Second half over bag records (dir_sparse_adam_bags_apply_f32): one Adam step of ALL local rows -- the touched ones from their
+        summed record gradients (through the max_norm clip derivative at the pre-update row), clipped with norm2_global [F] device
+        float64 (None exactly when clip_norm == 0), the others by the decay pass; slabs without a live record run that pass alone.  The
+        sort of a norm_bags call on the same slabs just before is reused."""
+        ts = self.ts
+        lib, ws, ws_bytes = self._bags_args(recv, P, cap_e, cap_b, grad_rows, slot_mn, "step_bags")
+        if (self.clip_norm > 0) != (norm2_global is not None):
+            raise ValueError("step_bags: norm2_global goes with clip_norm > 0 (clip_norm=%g)" % self.clip_norm)
+        if norm2_global is not None:
+            _dev(norm2_global, torch.float64, "norm2_global")
+            if norm2_global.numel() != ts.F or not norm2_global.is_contiguous():
+                raise ValueError("norm2_global must be a contiguous [F] float64 tensor")
+        first = 0
+        if self._marks is None:
+            self._marks = torch.empty(max(256, (self.total_rows + 255) // 256 * 256), dtype=torch.uint8, device=ts.device)
+            first = 1
+        was = self._sorted
+        stream = _stream()
+        sorted_ = 1 if (was is not None and len(was) == 5 and was[0] is recv and was[1] == recv._version and was[2] is self._pws
+                        and was[3] == stream.value and was[4] == (P, cap_e, cap_b)) else 0
+        self._sorted = None
+        try:
+            _lib.check(lib.dir_sparse_adam_bags_apply_f32(_ptr(ts.ptrs), _ptr(self.m_ptrs), _ptr(self.v_ptrs), ts.F, ts.K, _ptr(recv), P, cap_e,
+                                                          cap_b, _ptr(grad_rows), _ptr(slot_mn), float(mn), self.lr_t, self.beta1, self.beta2,
+                                                          self.eps, self.clip_norm, _ptr(norm2_global), _ptr(self.row_base), self.total_rows,
+                                                          _ptr(self._marks), ws, ws_bytes, sorted_, first, stream))
+        except _lib.DirError:
+            self._marks = None         # (as step_payload)
             raise
         ts.written(*self.ms, *self.vs)
         self.steps += 1

@@ -36,7 +36,9 @@ section 5.2).
 
 DCN trains with the reference's own optimiser on the shards (enable_training_adam, ShardedDCNTrainer): TF's sparse Adam with a per-table
 clip norm.  The clip norm is a property of the whole table, so the owner's step is cut in two around one all-reduce of the [F] norm shares
-(an exact integer sum), and every local row moves every step, also on an owner that received nothing.
+(an exact integer sum), and every local row moves every step, also on an owner that received nothing.  The
+reference DCN's own input -- multi-hot bags with per-column combiner, weights and max_norm -- trains the same way over the bag records
+the owners kept (lookup_bags_train under enable_training_adam; ShardedDCNTrainer on ragged features; section 5.3.1).
 
 DIN's goods table lives on the shards too (ShardedDINTrainer): a sample's T history ids and its candidate are T + 1 entries of a one-slot
 lookup without a finish pass, de-duplicated; the unit's kernels read the received rows through the entries' positions.  What training needs
@@ -278,6 +280,19 @@ class HipBackend:
         """Owner: the sorted Adagrad over the received bag records, entry gradient w * grad_rows[src*cap_b + ret]."""
         slot_mn, mn = ops.slot_max_norms(self.ts, max_norm)
         opt.step_bags(recv, self.P, cap_e, cap_b, grad_rows, slot_mn, mn)
+
+    # ... under enable_training_adam: the two halves of the owner's Adam step over the same records
+    def bags_adam_norm(self, opt, recv, cap_e, cap_b, grad_rows, max_norm):
+        """-> [2, F] int64: this owner's share of every table's ||g||^2 (the norm words, as adam_norm), g = the rows' summed record
+        gradients through the max_norm clip derivative (HIP: the records' sort + the norm pass)."""
+        slot_mn, mn = ops.slot_max_norms(self.ts, max_norm)
+        return opt.norm_bags(recv, self.P, cap_e, cap_b, grad_rows, slot_mn, mn)
+
+    def bags_adam_apply(self, opt, recv, cap_e, cap_b, grad_rows, max_norm, norm2_global):
+        """The touched rows on the norm pass's sort, clipped with the GLOBAL norms ([F] float64, None without a clip), then the decay
+        pass over every other local row."""
+        slot_mn, mn = ops.slot_max_norms(self.ts, max_norm)
+        opt.step_bags(recv, self.P, cap_e, cap_b, grad_rows, norm2_global, slot_mn, mn)
 
     # ---- the first-order (linear) term, co-located with the embedding rows (ShardedTables.attach_linear) -------------
     def attach_linear(self, rows, arena):
@@ -846,7 +861,10 @@ class ShardedTables:
              every row every step, so an owner that received nothing still takes part in 3 and still runs 4.
         clip_norm == 0: no clip, so no norm pass and no collective.  Set `tables.optimizer.lr_t` (lr * sqrt(1 - beta2^t) / (1 - beta1^t), t
         = the ONE global step + 1, the same on every rank) before every backward -- ShardedDCNTrainer's train_spec.TrainStep does.
-        Not covered (each raises): with_linear=True, lookup_bags_train, row groups, graph capture of a step."""
+        lookup_bags_train(...).backward() takes the same step over the bag records the owners kept (section 5.3: a row's summed record
+        gradient goes through the slot's max_norm clip derivative first, and that is the gradient whose norm is taken) on a backend
+        with bags_adam_norm / bags_adam_apply; one-hot and bag steps may alternate.
+        Not covered (each raises): with_linear=True, row groups, graph capture of a step."""
         if self.G > 1:
             raise NotImplementedError("enable_training_adam: row groups (groups=%d) are trained with the owner-side Adagrad only" % self.G)
         if not all(hasattr(self.backend, n) for n in ("make_adam", "adam_norm", "adam_apply")):
@@ -1706,12 +1724,22 @@ class ShardedTables:
         (d lin[b] times 1 / the linear denominator for mean and sqrtn, to the position of every partial), the rows travel back, then the
         floats, and every owner applies Adagrad to its embedding rows, then FTRL (enable_linear_training) to its first-order rows over
         the same bag records on the Adagrad step's sort: entry e contributes w_e * c_bag * d lin[b], all contributions to a row summed
-        before n, z and w move -- one optimiser step."""
+        before n, z and w move -- one optimiser step.
+        Under enable_training_adam the owners take TF's sparse Adam step over the same records instead: the row's
+        summed record gradient through the max_norm clip derivative is the gradient whose per-table norm is summed over the ranks and
+        clipped, every local row moves, and two identical steps end bitwise equal (the run sums are formed in double).  Needs a backend
+        with bags_adam_norm / bags_adam_apply; with_linear=True and graph capture are refused there, before anything is enqueued."""
         self._no_groups("lookup_bags_train")
         if self.optimizer is None:
             raise RuntimeError("call enable_training(lr) first")
         if self._adam:
-            raise NotImplementedError("lookup_bags_train under enable_training_adam: the bag records are trained with the owner-side Adagrad only")
+            if not all(hasattr(self.backend, n) for n in ("bags_adam_norm", "bags_adam_apply")):
+                raise NotImplementedError("lookup_bags_train under enable_training_adam: this backend has no owner-side Adam over bag records "
+                                          "(bags_adam_norm / bags_adam_apply)")
+            if with_linear:
+                raise NotImplementedError("lookup_bags_train(with_linear=True) under enable_training_adam: the first-order rows' FTRL rides on "
+                                          "the Adagrad step's sort")
+            self._refuse_adam_capture(values)            # before anything is enqueued, not first inside backward()
         lin_comb = None
         if with_linear:
             self._need_linear("lookup_bags_train(with_linear=True)")
@@ -1753,6 +1781,7 @@ class ShardedTables:
         owner's FTRL runs after its Adagrad, over the same bag records, on that step's sort."""
         plan, B, combiner, max_norm, lin_comb = saved
         be = self.backend
+        self._refuse_adam_capture(g)                     # before anything is enqueued (the plan stays held by its forward)
         self._updates += 1
         try:
             g2 = g if g.dim() == 2 and (B == 0 or g.stride(1) == 1) else g.contiguous()
@@ -1764,7 +1793,14 @@ class ShardedTables:
             _wait(self._a2a_equal(plan.back, plan.rows))
             if g_lin is not None:
                 _wait(self._a2a_equal(lback, lrows))
-            be.bags_adagrad(self.optimizer, plan.recv, plan.cap_e, plan.cap_b, plan.back, max_norm)
+            if self._adam:
+                # norm pass, norm sum over the ranks (every rank, also one that received nothing: a collective), apply on the norm pass's sort
+                norms = None
+                if self._adam_clip > 0:
+                    norms = self._sum_norm_shares(be.bags_adam_norm(self.optimizer, plan.recv, plan.cap_e, plan.cap_b, plan.back, max_norm))
+                be.bags_adam_apply(self.optimizer, plan.recv, plan.cap_e, plan.cap_b, plan.back, max_norm, norms)
+            else:
+                be.bags_adagrad(self.optimizer, plan.recv, plan.cap_e, plan.cap_b, plan.back, max_norm)
             if g_lin is not None:
                 be.bags_ftrl(plan.recv, plan.cap_e, plan.cap_b, lback, *self._lin_hp, sorted_by=self.optimizer)
         finally:
@@ -2306,17 +2342,13 @@ class ShardedESMMTrainer:
 def _dcn_columns(model):
     """(the embedding columns in the input layer's name-sorted order = the sharded tables' slots, their common width) of a
     dcn.DeepCrossNetwork the row-sharded trainer covers; ValueError naming the column otherwise."""
-    from .feature_column import EmbeddingColumn, WeightedCategoricalColumn
+    from .feature_column import EmbeddingColumn
     il = model.input_layer
     cols = [c for c in il.columns if isinstance(c, EmbeddingColumn)]
     if not cols:
         raise ValueError("ShardedDCNTrainer: the model has no embedding columns to shard")
     dim = cols[0].dimension
-    for c in cols:
-        if isinstance(c.categorical_column, WeightedCategoricalColumn):
-            raise ValueError("ShardedDCNTrainer: column %r: one-hot embedding columns only (weighted bags are not covered)" % c.name)
-        if getattr(c, "max_norm", None):
-            raise ValueError("ShardedDCNTrainer: column %r: max_norm is not carried by the sharded one-hot lookup" % c.name)
+    for c in cols:                       # weighted categorical columns, per-column combiners and max_norm travel with the bag lookup
         if c.dimension != dim:
             raise ValueError("ShardedDCNTrainer: column %r: dimension %d, the other columns have %d (one common dimension)" % (c.name, c.dimension, dim))
     return cols, dim
@@ -2336,8 +2368,12 @@ class ShardedDCNTrainer:
     term is a function of replicated weights: every rank adds l2_reg / P of it, so its gradient counts once after the sum.
     Batch-norm statistics stay per rank: each rank normalises its own local batch and keeps its own moving averages, as each of the
     reference's workers does with the batch it reads.
-    `model`'s one-hot embedding columns must share one width and carry no max_norm; its own embedding_weights are not used
-    (tables_from_model copies them into the shards).  weight_column and dnn_dropout raise NotImplementedError."""
+    `model`'s embedding columns must share one width; its own embedding_weights are not used (tables_from_model copies them into the
+    shards).  A batch with one id per sample and column takes the one-hot lookup (lookup_train; a column's max_norm is then the
+    caller's to avoid: the one-hot lookup does not carry it and step() raises).  A batch with a multi-hot or weighted feature -- the
+    reference's own input, safe_embedding_lookup_sparse (DeepCrossNetwork.py:126) -- takes lookup_bags_train with every column's
+    combiner and max_norm, and the owners run the sparse Adam over the bag records; a backend without that form raises
+    NotImplementedError at the first such batch.  weight_column and dnn_dropout raise NotImplementedError."""
 
     def __init__(self, model, tables, group=None):
         from .train_spec import CLIP_NORM, TrainStep
@@ -2382,11 +2418,21 @@ class ShardedDCNTrainer:
         from .feature_column import EmbeddingColumn, NumericColumn
         il, dev, K = self.model.input_layer, self.tables.device, self.K
         got = collect_ids(self.emb_cols, features, dev)
-        if got[0] != "onehot":
-            raise ValueError("ShardedDCNTrainer: one id per sample and embedding column (multi-hot features are not covered)")
-        ids = got[1]
-        B = ids.shape[0]
-        emb = self.tables.lookup_train(ids) if train else self.tables.lookup(ids)
+        if got[0] == "onehot":
+            if any(getattr(c, "max_norm", None) for c in self.emb_cols):
+                raise ValueError("ShardedDCNTrainer: max_norm is not carried by the sharded one-hot lookup (feed the columns as bags)")
+            ids = got[1]
+            B = ids.shape[0]
+            emb = self.tables.lookup_train(ids) if train else self.tables.lookup(ids)
+        else:                            # ("ragged", values, offsets, weights, B): field-major bags, every column's own combiner and max_norm
+            _, values, offsets, weights, B = got
+            comb = [c.combiner for c in self.emb_cols]
+            mn = [float(getattr(c, "max_norm", None) or 0.0) for c in self.emb_cols]
+            mn = mn if any(mn) else None
+            if train:
+                emb = self.tables.lookup_bags_train(values, offsets, weights, combiner=comb, max_norm=mn, field_major=True)
+            else:
+                emb = self.tables.lookup_bags(values, offsets, weights, combiner=comb, max_norm=mn, field_major=True)[0]
         pieces, f, run0 = [], 0, None
         for c in list(il.columns) + [None]:
             if isinstance(c, EmbeddingColumn):

@@ -1237,6 +1237,42 @@ int dir_sparse_adam_payload_apply_f32(float* const* tables, float* const* ms, fl
                                       const double* norm2_global, const int64_t* row_base, int64_t total_rows, unsigned char* marks,
                                       void* workspace, int64_t workspace_bytes, int sorted, int first_call, dir_stream_t stream);
 
+/* The same two halves over received BAG RECORDS: shard.ShardedTables.lookup_bags_train under enable_training_adam (the reference DCN's
+ * train_op on its safe_embedding_lookup_sparse inputs, DeepCrossNetwork.py:126,264-290, with the embedding variables partitioned).  The
+ * record arguments are dir_sparse_adagrad_sorted_bags_f32's: recv = the P slabs of (cap_e + 1) 16-byte records the forward received,
+ * grecv [P * cap_b, K] = the gradients of the partial rows as received, slot_max_norm (device [F], or NULL: max_norm for every slot;
+ * 0 = no clip).  Entry e of slab src contributes w_e * grecv[src * cap_b + ret_e] to its (slot, local row); it is formed where it is
+ * summed, no [entries, K] buffer exists.  Records past the slab header's count, or failing the pool kernel's checks, sort behind
+ * every row and contribute nothing.
+ *   - A row's sum S_r runs over ALL its entries -- inside one bag, across bags, across ranks -- in DOUBLE (tile partials too), rounded
+ *     to fp32 once: where a record sits in a slab depends on the bucket pass's atomics, and the step must not (the payload form's
+ *     guarantee, with the same exception: a double sum within 2^-53 of an fp32 rounding boundary).
+ *   - S_r then goes through the slot's max_norm clip derivative at the row's PRE-UPDATE value r (||r|| > max_norm: max_norm * (S / ||r|| -
+ *     r (r . S) / ||r||^3), else S; dir_sparse_adagrad_sorted_bags_f32's arithmetic).  The result is "the row's gradient" for everything
+ *     after it: TF's train_op clips, and takes the norm of, the gradient that reaches the variable.
+ *   - dir_sparse_adam_bags_norm_f32 zeroes the 128 norm words, sorts the records and adds ||row gradient||^2 per table into norm2 (the
+ *     payload form's two-word 2^-32 fixed point).  It reads `tables` only to evaluate the clip derivative and writes no table; tables may
+ *     be NULL when slot_max_norm == NULL and max_norm == 0.
+ *   - dir_sparse_adam_bags_apply_f32 steps the touched rows (den = max(sqrt(norm2_global[f]), clip_norm); norm2_global NULL exactly
+ *     when clip_norm == 0; the derivative is computed from the row it loaded, then m, v and var are written once) and marks them, then
+ *     streams over every other local row.  sorted != 0: the norm entry has just sorted THESE slabs into THIS workspace on THIS stream
+ *     and its sort is reused.  An owner whose slabs hold no live record still runs the decay pass; total_rows == 0 is a no-op.
+ * workspace: dir_sparse_adam_bags_workspace_bytes(P, cap_e, F, K, total_rows) bytes, 256-byte aligned = the payload form's for n = P *
+ * cap_e entries (carry rows of K doubles); 0 = unsupported sizes.  marks / first_call / lr_t: as the payload form, and the SAME marks
+ * may serve both forms (one-hot and bag steps may alternate on one optimiser state).
+ * Limits (both parents'): F <= 64; K % 4 == 0 with K / 4 dividing 64; grecv 16-byte aligned (the 16-byte path always runs, a thread
+ * group has no padded lanes); 1 <= P <= 64, 0 < cap_e < 2^31, cap_b > 0, P * cap_b < 2^31; P * cap_e < 2^30; total_rows < 2^32 - 1.
+ * Every argument is checked before the first HIP call; a violated limit returns DIR_E_UNSUPPORTED or DIR_E_BADARG with a message. */
+int64_t dir_sparse_adam_bags_workspace_bytes(int P, int64_t cap_e, int F, int K, int64_t total_rows);
+int dir_sparse_adam_bags_norm_f32(const float* const* tables, int F, int K, const int64_t* recv, int P, int64_t cap_e, int64_t cap_b,
+                                  const float* grecv, const float* slot_max_norm, float max_norm, const int64_t* row_base,
+                                  int64_t total_rows, uint64_t* norm2, void* workspace, int64_t workspace_bytes, dir_stream_t stream);
+int dir_sparse_adam_bags_apply_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* recv, int P,
+                                   int64_t cap_e, int64_t cap_b, const float* grecv, const float* slot_max_norm, float max_norm,
+                                   float lr_t, float beta1, float beta2, float eps, float clip_norm, const double* norm2_global,
+                                   const int64_t* row_base, int64_t total_rows, unsigned char* marks, void* workspace,
+                                   int64_t workspace_bytes, int sorted, int first_call, dir_stream_t stream);
+
 /* FTRL-Proximal on sparse rows through the same sorted machinery (the reference's linear_optimizer='Ftrl', deepFM.py:58;
  * [TF-upstream] tf.train.FtrlOptimizer with learning_rate_power = -0.5): per touched row, g = sum of its gradient rows,
  *   n' = n + g^2; sigma = (sqrt(n') - sqrt(n)) / lr; z' = z + g - sigma*w;
