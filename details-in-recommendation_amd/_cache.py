@@ -156,3 +156,37 @@ def invalidate_caches():
     for c in list(_CACHES) + also_cleared:
         c.clear()
     _CACHE_GEN[0] += 1
+
+
+# ---- raw writes: what the fused updaters do to the version counters ---------------------------------------------------------------
+_HIP_BUMPS = None                # version-counter owner (a view's base) -> how many of its version bumps mark_written made
+
+
+def _vc_owner(t):
+    return t._base if t._base is not None else t
+
+
+def hip_bumps(t):
+    """How many of tensor t's version bumps came from mark_written (a fused updater's step), not from torch ops: the magnitude caches
+    (TableSet.absmax / weight_absmax with every > 1) tolerate only those."""
+    return 0 if _HIP_BUMPS is None else _HIP_BUMPS.get(_vc_owner(t), 0)
+
+
+def mark_written(*tensors):
+    """A raw-pointer kernel has just written these tensors in place: bump their autograd version counters, as an in-place torch op would
+    have.  Everything cached per weight version (DeepFM's packed serving rows and every VersionCache: ops.version_caches()) keys on
+    tensor._version, so an eval -> train -> eval loop in one process (the reference's train_and_evaluate) rebuilds them after a HIP
+    optimiser step.  Views share their base's counter."""
+    global _HIP_BUMPS
+    ts = [t for t in tensors if isinstance(t, torch.Tensor)]
+    if ts:
+        torch._C._autograd._unsafe_set_version_counter(ts, [t._version + 1 for t in ts])
+        if _HIP_BUMPS is None:
+            from torch.utils.weak import WeakIdKeyDictionary
+            _HIP_BUMPS = WeakIdKeyDictionary()
+        seen = set()
+        for t in ts:
+            o = _vc_owner(t)
+            if id(o) not in seen:
+                seen.add(id(o))
+                _HIP_BUMPS[o] = _HIP_BUMPS.get(o, 0) + 1

@@ -1164,15 +1164,29 @@ extern "C" int64_t dir_sparse_adagrad_sorted_workspace_bytes(int64_t B, int F, i
     return adagrad_sorted_plan(B * F, K, total_rows, p, B, F) ? (int64_t)p.total : 0;
 }
 
+// Where the entries of a sorted update come from: one-hot ids [B, F] with their strides, or a payload of B entries (grad is [B, K] then).
+// fm(): fold the FM backward in (AdagradUpd only).  reuse(): the workspace of an earlier sorted update of the SAME entries (ids, strides,
+// B, F, row_base, total_rows) on this stream: its sorted (row, entry) pairs are used and the sort is skipped; nullptr sorts.
+struct SortedSrc {
+    const int64_t* ids = nullptr;
+    int64_t stride_b = 0, stride_f = 0;
+    const int64_t* payload = nullptr;
+    const float *fm_g = nullptr, *fm_sum = nullptr;
+    const void* sorted_from = nullptr;
+    static SortedSrc of_ids(const int64_t* ids, int64_t stride_b, int64_t stride_f) { return SortedSrc{ids, stride_b, stride_f}; }
+    static SortedSrc of_payload(const int64_t* payload) { return SortedSrc{nullptr, 0, 0, payload}; }
+    SortedSrc fm(const float* g, const float* sum) const { return SortedSrc{ids, stride_b, stride_f, payload, g, sum, sorted_from}; }
+    SortedSrc reuse(const void* from) const { return SortedSrc{ids, stride_b, stride_f, payload, fm_g, fm_sum, from}; }
+};
+
 template <class U>
-static int sparse_sorted_update(const char* name, U upd, int F, int K, const int64_t* ids, int64_t stride_b, int64_t stride_f,
-                                const float* grad, int64_t grad_ld, int64_t grad_fs, int64_t B, const int64_t* row_base,
-                                int64_t total_rows, void* workspace, int64_t workspace_bytes, dir_stream_t stream,
-                                const int64_t* payload = nullptr /* payload mode: B entries, ids unused, grad is [B, K] */,
-                                const float* fm_g = nullptr, const float* fm_sum = nullptr /* fold the FM backward in (AdagradUpd only) */,
-                                const void* sorted_from = nullptr /* the workspace of an earlier sorted update of the SAME entries (ids,
-                                                                     strides, B, F, row_base, total_rows) on this stream: its sorted
-                                                                     (row, entry) pairs are used and the sort is skipped */) {
+static int sparse_sorted_update(const char* name, U upd, int F, int K, const SortedSrc& src, const float* grad, int64_t grad_ld,
+                                int64_t grad_fs, int64_t B, const int64_t* row_base, int64_t total_rows, void* workspace,
+                                int64_t workspace_bytes, dir_stream_t stream) {
+    const int64_t *ids = src.ids, *const payload = src.payload;
+    const int64_t stride_b = src.stride_b, stride_f = src.stride_f;
+    const float *const fm_g = src.fm_g, *const fm_sum = src.fm_sum;
+    const void* const sorted_from = src.sorted_from;
     const int nt = payload ? F : 0;        // tables to search by key
     if (payload) {                         // entries are a flat list: one "slot" per entry
         ids = payload;
@@ -1251,8 +1265,22 @@ extern "C" int dir_sparse_adagrad_sorted_f32(float* const* tables, float* const*
                                              int64_t workspace_bytes, dir_stream_t stream) {
     DIR_CHECK_ARG(tables && accums, "dir_sparse_adagrad_sorted_f32: null pointer");
     DIR_CHECK_ARG(grad_ld >= (int64_t)F * K, "dir_sparse_adagrad_sorted_f32: grad_ld");
-    return sparse_sorted_update("dir_sparse_adagrad_sorted_f32", AdagradUpd{tables, accums, lr, (int64_t)K}, F, K, ids, stride_b, stride_f, grad,
-                                grad_ld, (int64_t)K, B, row_base, total_rows, workspace, workspace_bytes, stream);
+    return sparse_sorted_update("dir_sparse_adagrad_sorted_f32", AdagradUpd{tables, accums, lr, (int64_t)K}, F, K,
+                                SortedSrc::of_ids(ids, stride_b, stride_f), grad, grad_ld, (int64_t)K, B, row_base, total_rows, workspace,
+                                workspace_bytes, stream);
+}
+
+// dir_sparse_adagrad_sorted_rows_f32 and its _from form (sorted_from != nullptr: the linked optimiser's sort is taken)
+static int adagrad_sorted_rows(const char* name, float* const* tables, float* const* accums, int64_t row_ld, int F, int K, const int64_t* ids,
+                               int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, const float* fm_g, const float* fm_sum,
+                               float lr, int64_t B, const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
+                               const void* sorted_from, dir_stream_t stream) {
+    DIR_CHECK_ARG(row_ld >= K && (!grad || grad_ld >= (int64_t)F * K), "%s: row_ld / grad_ld", name);
+    DIR_CHECK_ARG((fm_g == nullptr) == (fm_sum == nullptr), "%s: fm_g and fm_sum go together", name);
+    if (K % 4 == 0 && (row_ld & 3)) return fail(DIR_E_UNSUPPORTED, "%s: row_ld must be a multiple of 4", name);
+    return sparse_sorted_update(name, AdagradUpd{tables, accums, lr, row_ld}, F, K,
+                                SortedSrc::of_ids(ids, stride_b, stride_f).fm(fm_g, fm_sum).reuse(sorted_from), grad,
+                                grad ? grad_ld : (int64_t)F * K, (int64_t)K, B, row_base, total_rows, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dir_sparse_adagrad_sorted_rows_f32(float* const* tables, float* const* accums, int64_t row_ld, int F, int K,
@@ -1260,23 +1288,31 @@ extern "C" int dir_sparse_adagrad_sorted_rows_f32(float* const* tables, float* c
                                                   int64_t grad_ld, const float* fm_g, const float* fm_sum, float lr, int64_t B,
                                                   const int64_t* row_base, int64_t total_rows, void* workspace,
                                                   int64_t workspace_bytes, dir_stream_t stream) {
-    DIR_CHECK_ARG(tables && accums, "dir_sparse_adagrad_sorted_rows_f32: null pointer");
-    DIR_CHECK_ARG(row_ld >= K && (!grad || grad_ld >= (int64_t)F * K), "dir_sparse_adagrad_sorted_rows_f32: row_ld / grad_ld");
-    DIR_CHECK_ARG((fm_g == nullptr) == (fm_sum == nullptr), "dir_sparse_adagrad_sorted_rows_f32: fm_g and fm_sum go together");
-    if (K % 4 == 0 && (row_ld & 3)) return fail(DIR_E_UNSUPPORTED, "dir_sparse_adagrad_sorted_rows_f32: row_ld must be a multiple of 4");
-    return sparse_sorted_update("dir_sparse_adagrad_sorted_rows_f32", AdagradUpd{tables, accums, lr, row_ld}, F, K, ids, stride_b, stride_f,
-                                grad, grad ? grad_ld : (int64_t)F * K, (int64_t)K, B, row_base, total_rows, workspace, workspace_bytes, stream,
-                                nullptr, fm_g, fm_sum);
+    const char* name = "dir_sparse_adagrad_sorted_rows_f32";
+    DIR_CHECK_ARG(tables && accums, "%s: null pointer", name);
+    return adagrad_sorted_rows(name, tables, accums, row_ld, F, K, ids, stride_b, stride_f, grad, grad_ld, fm_g, fm_sum, lr, B, row_base,
+                               total_rows, workspace, workspace_bytes, nullptr, stream);
+}
+
+// dir_sparse_ftrl_sorted_f32 and its _from form
+static int ftrl_sorted(const char* name, float* const* tables, float* const* accums, float* const* linears, int F, int K, const int64_t* ids,
+                       int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, int64_t grad_slot_stride, float lr, float l1,
+                       float l2, int64_t B, const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
+                       const void* sorted_from, dir_stream_t stream) {
+    DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
+    return sparse_sorted_update(name, FtrlUpd{tables, accums, linears, lr, l1, l2, (int64_t)K}, F, K,
+                                SortedSrc::of_ids(ids, stride_b, stride_f).reuse(sorted_from), grad, grad_ld, grad_slot_stride, B, row_base,
+                                total_rows, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dir_sparse_ftrl_sorted_f32(float* const* tables, float* const* accums, float* const* linears, int F, int K,
                                           const int64_t* ids, int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld,
                                           int64_t grad_slot_stride, float lr, float l1, float l2, int64_t B, const int64_t* row_base,
                                           int64_t total_rows, void* workspace, int64_t workspace_bytes, dir_stream_t stream) {
-    DIR_CHECK_ARG(tables && accums && linears, "dir_sparse_ftrl_sorted_f32: null pointer");
-    DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "dir_sparse_ftrl_sorted_f32: lr=%g l1=%g l2=%g", lr, l1, l2);
-    return sparse_sorted_update("dir_sparse_ftrl_sorted_f32", FtrlUpd{tables, accums, linears, lr, l1, l2, (int64_t)K}, F, K, ids, stride_b,
-                                stride_f, grad, grad_ld, grad_slot_stride, B, row_base, total_rows, workspace, workspace_bytes, stream);
+    const char* name = "dir_sparse_ftrl_sorted_f32";
+    DIR_CHECK_ARG(tables && accums && linears, "%s: null pointer", name);
+    return ftrl_sorted(name, tables, accums, linears, F, K, ids, stride_b, stride_f, grad, grad_ld, grad_slot_stride, lr, l1, l2, B, row_base,
+                       total_rows, workspace, workspace_bytes, nullptr, stream);
 }
 
 // The two updates of one training step of a DeepFM -- Adagrad on the embedding tables (deepFM.py:61), FTRL on the linear columns (:58) --
@@ -1288,12 +1324,8 @@ extern "C" int dir_sparse_adagrad_sorted_rows_from_f32(float* const* tables, flo
                                                        int64_t workspace_bytes, const void* sorted_from, dir_stream_t stream) {
     const char* name = "dir_sparse_adagrad_sorted_rows_from_f32";
     DIR_CHECK_ARG(tables && accums && sorted_from, "%s: null pointer", name);
-    DIR_CHECK_ARG(row_ld >= K && (!grad || grad_ld >= (int64_t)F * K), "%s: row_ld / grad_ld", name);
-    DIR_CHECK_ARG((fm_g == nullptr) == (fm_sum == nullptr), "%s: fm_g and fm_sum go together", name);
-    if (K % 4 == 0 && (row_ld & 3)) return fail(DIR_E_UNSUPPORTED, "%s: row_ld must be a multiple of 4", name);
-    return sparse_sorted_update(name, AdagradUpd{tables, accums, lr, row_ld}, F, K, ids, stride_b, stride_f, grad,
-                                grad ? grad_ld : (int64_t)F * K, (int64_t)K, B, row_base, total_rows, workspace, workspace_bytes, stream, nullptr,
-                                fm_g, fm_sum, sorted_from);
+    return adagrad_sorted_rows(name, tables, accums, row_ld, F, K, ids, stride_b, stride_f, grad, grad_ld, fm_g, fm_sum, lr, B, row_base,
+                               total_rows, workspace, workspace_bytes, sorted_from, stream);
 }
 
 extern "C" int dir_sparse_ftrl_sorted_from_f32(float* const* tables, float* const* accums, float* const* linears, int F, int K,
@@ -1303,10 +1335,8 @@ extern "C" int dir_sparse_ftrl_sorted_from_f32(float* const* tables, float* cons
                                                dir_stream_t stream) {
     const char* name = "dir_sparse_ftrl_sorted_from_f32";
     DIR_CHECK_ARG(tables && accums && linears && sorted_from, "%s: null pointer", name);
-    DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
-    return sparse_sorted_update(name, FtrlUpd{tables, accums, linears, lr, l1, l2, (int64_t)K}, F, K, ids, stride_b, stride_f, grad, grad_ld,
-                                grad_slot_stride, B, row_base, total_rows, workspace, workspace_bytes, stream, nullptr, nullptr, nullptr,
-                                sorted_from);
+    return ftrl_sorted(name, tables, accums, linears, F, K, ids, stride_b, stride_f, grad, grad_ld, grad_slot_stride, lr, l1, l2, B, row_base,
+                       total_rows, workspace, workspace_bytes, sorted_from, stream);
 }
 
 // FTRL on packed linear training rows: rows[f] is [vocab_f, 4] = [w | n | z | unused], 16-byte aligned (units = 1).  sorted_from (optional):
@@ -1320,8 +1350,8 @@ extern "C" int dir_sparse_ftrl_rows_sorted_f32(float* const* rows, int F, const 
     DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
     FtrlUpd upd{rows, rows, rows, lr, l1, l2, (int64_t)4};
     upd.rows = true;
-    return sparse_sorted_update(name, upd, F, 1, ids, stride_b, stride_f, grad, grad_ld, grad_slot_stride, B, row_base, total_rows, workspace,
-                                workspace_bytes, stream, nullptr, nullptr, nullptr, sorted_from);
+    return sparse_sorted_update(name, upd, F, 1, SortedSrc::of_ids(ids, stride_b, stride_f).reuse(sorted_from), grad, grad_ld, grad_slot_stride,
+                                B, row_base, total_rows, workspace, workspace_bytes, stream);
 }
 
 extern "C" int dir_fm_second_order_backward_f32(const float* emb, int64_t emb_ld, const float* g, const float* add_in,
@@ -1457,8 +1487,8 @@ extern "C" int dir_sparse_adagrad_sorted_payload_f32(float* const* tables, float
                                                      int64_t total_rows, void* workspace, int64_t workspace_bytes,
                                                      dir_stream_t stream) {
     DIR_CHECK_ARG(tables && accums && (payload || n == 0), "dir_sparse_adagrad_sorted_payload_f32: null pointer");
-    return sparse_sorted_update("dir_sparse_adagrad_sorted_payload_f32", AdagradUpd{tables, accums, lr, (int64_t)K}, F, K, nullptr, 0, 0, grad,
-                                (int64_t)K, 0, n, row_base, total_rows, workspace, workspace_bytes, stream, payload);
+    return sparse_sorted_update("dir_sparse_adagrad_sorted_payload_f32", AdagradUpd{tables, accums, lr, (int64_t)K}, F, K,
+                                SortedSrc::of_payload(payload), grad, (int64_t)K, 0, n, row_base, total_rows, workspace, workspace_bytes, stream);
 }
 
 // Owner side of the sharded linear term's backward (shard.ShardedTables.lookup_train(with_linear=True)): dir_sparse_ftrl_rows_sorted_f32's
@@ -1475,8 +1505,8 @@ extern "C" int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F
     DIR_CHECK_ARG(rows && (payload || n == 0), "%s: null pointer", name);
     FtrlUpd upd{rows, rows, rows, lr, l1, l2, (int64_t)4};
     upd.rows = true;
-    return sparse_sorted_update(name, upd, F, 1, nullptr, 0, 0, grad, (int64_t)1, 0, n, row_base, total_rows, workspace, workspace_bytes, stream,
-                                payload, nullptr, nullptr, sorted_from);
+    return sparse_sorted_update(name, upd, F, 1, SortedSrc::of_payload(payload).reuse(sorted_from), grad, (int64_t)1, 0, n, row_base, total_rows,
+                                workspace, workspace_bytes, stream);
 }
 
 // dir_sparse_ftrl_rows_sorted_payload_f32 with units = U first-order terms per row (ShardedTables.attach_linear([rows, U])): rows[f] is
@@ -1496,8 +1526,8 @@ extern "C" int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows,
     FtrlUpd upd{rows, rows, rows, lr, l1, l2, (int64_t)4 * units};
     upd.rows = true;
     upd.units = units;
-    return sparse_sorted_update(name, upd, F, units, nullptr, 0, 0, grad, (int64_t)units, 0, n, row_base, total_rows, workspace, workspace_bytes,
-                                stream, payload, nullptr, nullptr, sorted_from);
+    return sparse_sorted_update(name, upd, F, units, SortedSrc::of_payload(payload).reuse(sorted_from), grad, (int64_t)units, 0, n, row_base,
+                                total_rows, workspace, workspace_bytes, stream);
 }
 
 // ---- tf.train.AdamOptimizer on the embedding tables ------------------------------------------------------------------------------
@@ -1548,13 +1578,13 @@ extern "C" int dir_sparse_adam_f32(float* const* tables, float* const* ms, float
         const bool clip = clip_norm > 0.f;
         if (clip) {
             if (zero_async(norm2, ADAM_NORM_BYTES, st) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
-            const int rc = sparse_sorted_update(name, AdamNormUpd{norm2}, F, K, ids, stride_b, stride_f, grad, grad_ld, (int64_t)K, B, row_base,
-                                                total_rows, sorted_ws, sorted_bytes, stream);
+            const int rc = sparse_sorted_update(name, AdamNormUpd{norm2}, F, K, SortedSrc::of_ids(ids, stride_b, stride_f), grad, grad_ld,
+                                                (int64_t)K, B, row_base, total_rows, sorted_ws, sorted_bytes, stream);
             if (rc != DIR_OK) return rc;
         }
         const int rc = sparse_sorted_update(name, AdamUpd{tables, ms, vs, clip ? norm2 : nullptr, mark, row_base, lr_t, beta1, beta2, eps, clip_norm, (int64_t)K},
-                                            F, K, ids, stride_b, stride_f, grad, grad_ld, (int64_t)K, B, row_base, total_rows, sorted_ws, sorted_bytes,
-                                            stream, nullptr, nullptr, nullptr, clip ? sorted_ws : nullptr);
+                                            F, K, SortedSrc::of_ids(ids, stride_b, stride_f).reuse(clip ? sorted_ws : nullptr), grad, grad_ld,
+                                            (int64_t)K, B, row_base, total_rows, sorted_ws, sorted_bytes, stream);
         if (rc != DIR_OK) return rc;
     }
     return adam_decay_all(name, tables, ms, vs, F, K, row_base, total_rows, mark, lr_t, beta1, beta2, eps, st);
@@ -1605,18 +1635,14 @@ extern "C" int dir_sparse_adam_payload_norm_f32(int F, int K, const int64_t* pay
     if (n == 0 || total_rows == 0) return DIR_OK;            // nothing received / no rows here: this owner's share is zero
     AdamNormUpdW upd;
     upd.norm2 = reinterpret_cast<unsigned long long*>(norm2);
-    return sparse_sorted_update(name, upd, F, K, nullptr, 0, 0, grad, (int64_t)K, 0, n, row_base, total_rows, workspace, workspace_bytes, stream,
-                                payload);
+    return sparse_sorted_update(name, upd, F, K, SortedSrc::of_payload(payload), grad, (int64_t)K, 0, n, row_base, total_rows, workspace,
+                                workspace_bytes, stream);
 }
 
-extern "C" int dir_sparse_adam_payload_apply_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* payload,
-                                                 int64_t n, const float* grad, float lr_t, float beta1, float beta2, float eps,
-                                                 float clip_norm, const double* norm2_global, const int64_t* row_base, int64_t total_rows,
-                                                 unsigned char* marks, void* workspace, int64_t workspace_bytes, int sorted, int first_call,
-                                                 dir_stream_t stream) {
-    const char* name = "dir_sparse_adam_payload_apply_f32";
-    AdaSortedPlan p;
-    if (int rc = adam_payload_check(name, F, K, payload, n, grad, row_base, total_rows, workspace, workspace_bytes, p)) return rc;
+// The apply entries (payload, bags) take the same hyper-parameters, slots and marks: checked here for both, after the check their form
+// shares with its norm entry.
+static int adam_apply_check(const char* name, float lr_t, float beta1, float beta2, float eps, float clip_norm, const double* norm2_global,
+                            float* const* tables, float* const* ms, float* const* vs, const unsigned char* marks, int64_t total_rows) {
     DIR_CHECK_ARG(tables && ms && vs, "%s: null pointer (tables / ms / vs)", name);
     DIR_CHECK_ARG(marks || total_rows == 0, "%s: null pointer (marks)", name);
     DIR_CHECK_ARG(lr_t >= 0.f, "%s: lr_t=%g", name, (double)lr_t);
@@ -1627,6 +1653,18 @@ extern "C" int dir_sparse_adam_payload_apply_f32(float* const* tables, float* co
     DIR_CHECK_ARG((clip_norm > 0.f) == (norm2_global != nullptr), "%s: norm2_global is NULL exactly when clip_norm == 0 (clip_norm=%g)", name,
                   (double)clip_norm);
     DIR_CHECK_ARG(!(reinterpret_cast<uintptr_t>(norm2_global) & 7u), "%s: norm2_global must be 8-byte aligned", name);
+    return DIR_OK;
+}
+
+extern "C" int dir_sparse_adam_payload_apply_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* payload,
+                                                 int64_t n, const float* grad, float lr_t, float beta1, float beta2, float eps,
+                                                 float clip_norm, const double* norm2_global, const int64_t* row_base, int64_t total_rows,
+                                                 unsigned char* marks, void* workspace, int64_t workspace_bytes, int sorted, int first_call,
+                                                 dir_stream_t stream) {
+    const char* name = "dir_sparse_adam_payload_apply_f32";
+    AdaSortedPlan p;
+    if (int rc = adam_payload_check(name, F, K, payload, n, grad, row_base, total_rows, workspace, workspace_bytes, p)) return rc;
+    if (int rc = adam_apply_check(name, lr_t, beta1, beta2, eps, clip_norm, norm2_global, tables, ms, vs, marks, total_rows)) return rc;
     if (total_rows == 0) return DIR_OK;                      // this owner holds no rows (every vocab < P): nothing can move
     hipStream_t st = as_stream(stream);
     const int64_t mark_bytes = (total_rows + 255) & ~(int64_t)255;
@@ -1635,8 +1673,8 @@ extern "C" int dir_sparse_adam_payload_apply_f32(float* const* tables, float* co
         AdamUpdW upd;
         static_cast<AdamUpd&>(upd) = AdamUpd{tables, ms, vs, nullptr, marks, row_base, lr_t, beta1, beta2, eps, clip_norm, (int64_t)K};
         upd.norm2_sum = norm2_global;
-        const int rc = sparse_sorted_update(name, upd, F, K, nullptr, 0, 0, grad, (int64_t)K, 0, n, row_base, total_rows, workspace,
-                                            workspace_bytes, stream, payload, nullptr, nullptr, sorted ? workspace : nullptr);
+        const int rc = sparse_sorted_update(name, upd, F, K, SortedSrc::of_payload(payload).reuse(sorted ? workspace : nullptr), grad, (int64_t)K, 0,
+                                            n, row_base, total_rows, workspace, workspace_bytes, stream);
         if (rc != DIR_OK) return rc;
     }
     return adam_decay_all(name, tables, ms, vs, F, K, row_base, total_rows, marks, lr_t, beta1, beta2, eps, st);
@@ -1809,16 +1847,7 @@ extern "C" int dir_sparse_adam_bags_apply_f32(float* const* tables, float* const
                                               int64_t workspace_bytes, int sorted, int first_call, dir_stream_t stream) {
     const char* name = "dir_sparse_adam_bags_apply_f32";
     if (int rc = adam_bags_check(name, F, K, recv, P, cap_e, cap_b, grecv, max_norm, row_base, total_rows, workspace, workspace_bytes)) return rc;
-    DIR_CHECK_ARG(tables && ms && vs, "%s: null pointer (tables / ms / vs)", name);
-    DIR_CHECK_ARG(marks || total_rows == 0, "%s: null pointer (marks)", name);
-    DIR_CHECK_ARG(lr_t >= 0.f, "%s: lr_t=%g", name, (double)lr_t);
-    DIR_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f, "%s: beta1=%g (0 <= beta1 < 1)", name, (double)beta1);
-    DIR_CHECK_ARG(beta2 >= 0.f && beta2 < 1.f, "%s: beta2=%g (0 <= beta2 < 1)", name, (double)beta2);
-    DIR_CHECK_ARG(eps > 0.f, "%s: eps=%g (> 0)", name, (double)eps);
-    DIR_CHECK_ARG(clip_norm >= 0.f, "%s: clip_norm=%g (>= 0)", name, (double)clip_norm);
-    DIR_CHECK_ARG((clip_norm > 0.f) == (norm2_global != nullptr), "%s: norm2_global is NULL exactly when clip_norm == 0 (clip_norm=%g)", name,
-                  (double)clip_norm);
-    DIR_CHECK_ARG(!(reinterpret_cast<uintptr_t>(norm2_global) & 7u), "%s: norm2_global must be 8-byte aligned", name);
+    if (int rc = adam_apply_check(name, lr_t, beta1, beta2, eps, clip_norm, norm2_global, tables, ms, vs, marks, total_rows)) return rc;
     if (total_rows == 0) return DIR_OK;                      // this owner holds no rows (every vocab < P): nothing can move
     hipStream_t st = as_stream(stream);
     const int64_t mark_bytes = (total_rows + 255) & ~(int64_t)255;

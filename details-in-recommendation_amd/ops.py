@@ -3,7 +3,8 @@ the C ABI (include/dir_hip.h) on torch's current HIP stream.
 
 torch is plumbing here: device memory, streams, tensors as buffers.  Every op requires CUDA(ROCm)
 tensors and the in-tree libdir_hip.so; there is no CPU or eager fallback (a missing library or a CPU
-tensor raises).
+tensor raises).  The fused sparse optimisers (SparseAdagrad, SparseAdam, SparseFtrl, share_sorted_entries) live in sparse_opt.py
+and keep their names here; the argument helpers both files use are _abi.py's.
 
 Reference closures (relative to /root/reference):
   embedding_bag / TableSet   myself_input_layer            models/DeepFM/deepFM.py:363-400
@@ -20,32 +21,16 @@ import os
 import torch
 
 from . import _lib
+from ._abi import _stream, _dev, _ptr, _onehot_strides
 from ._cache import (VersionCache, version_caches, invalidate_caches, capture_hold, frozen_weights, held, capture_guard,      # noqa: F401
-                     capture_bypasses_caches, also_cleared, _CACHE_GEN, _HOLDS, _FROZEN_WEIGHTS)
+                     capture_bypasses_caches, also_cleared, hip_bumps, mark_written, _CACHE_GEN, _HOLDS, _FROZEN_WEIGHTS)
+from .sparse_opt import SparseAdagrad, SparseAdam, SparseFtrl, share_sorted_entries      # noqa: F401  (the fused sparse optimisers keep their ops. names)
 
 SUM, MEAN, SQRTN = 0, 1, 2
 _COMBINERS = {"sum": SUM, "mean": MEAN, "sqrtn": SQRTN, SUM: SUM, MEAN: MEAN, SQRTN: SQRTN}
 PRUNE_NONPOSITIVE_WEIGHTS = 1
 STREAM_ROWS = 2  # DIR_GATHER_STREAM_ROWS: non-temporal row loads (uniform ids over tables >> Infinity Cache)
 INFINITY_CACHE_BYTES = 256 << 20
-
-
-def _stream():
-    """The current HIP stream of the current device as the C ABI takes it.  (torch.cuda.current_stream() builds a Stream object per call:
-    5.7 us, 30 times per DeepFM training step; the raw query is 0.3 us.)"""
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch._C._cuda_getDevice()))
-
-
-def _dev(t, dtype, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a CUDA (ROCm) tensor: the HIP path has no CPU fallback" % name)
-    if t.dtype != dtype:
-        raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    return t
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 class TableSet:
@@ -200,39 +185,6 @@ def f16_range_ok(absmax):
     return absmax == 0.0 or (F16_SMALL_GUARD <= absmax < F16_RANGE_GUARD)
 
 
-_HIP_BUMPS = None                # version-counter owner (a view's base) -> how many of its version bumps mark_written made
-
-
-def _vc_owner(t):
-    return t._base if t._base is not None else t
-
-
-def hip_bumps(t):
-    """How many of tensor t's version bumps came from mark_written (a fused updater's step), not from torch ops: the magnitude caches
-    (TableSet.absmax / weight_absmax with every > 1) tolerate only those."""
-    return 0 if _HIP_BUMPS is None else _HIP_BUMPS.get(_vc_owner(t), 0)
-
-
-def mark_written(*tensors):
-    """A raw-pointer kernel has just written these tensors in place: bump their autograd version counters, as an in-place torch op would
-    have.  Everything cached per weight version (DeepFM's packed serving rows and every VersionCache: ops.version_caches()) keys on
-    tensor._version, so an eval -> train -> eval loop in one process (the reference's train_and_evaluate) rebuilds them after a HIP
-    optimiser step.  Views share their base's counter."""
-    global _HIP_BUMPS
-    ts = [t for t in tensors if isinstance(t, torch.Tensor)]
-    if ts:
-        torch._C._autograd._unsafe_set_version_counter(ts, [t._version + 1 for t in ts])
-        if _HIP_BUMPS is None:
-            from torch.utils.weak import WeakIdKeyDictionary
-            _HIP_BUMPS = WeakIdKeyDictionary()
-        seen = set()
-        for t in ts:
-            o = _vc_owner(t)
-            if id(o) not in seen:
-                seen.add(id(o))
-                _HIP_BUMPS[o] = _HIP_BUMPS.get(o, 0) + 1
-
-
 class CapturedStep:
     """A training (or inference) step captured in a HIP graph, replayed with the bookkeeping eager steps do on the host.
 
@@ -301,13 +253,6 @@ def plain_list(plist):
 
 def _as_tableset(tables):
     return tables if isinstance(tables, TableSet) else TableSet(tables)
-
-
-def _onehot_strides(ids, F):
-    """ids [B,F] (any strides) or [F,B] given as transposed view -> (B, stride_b, stride_f)."""
-    if ids.dim() != 2 or ids.shape[1] != F:
-        raise ValueError("one-hot ids must be [B, F=%d], got %s" % (F, tuple(ids.shape)))
-    return ids.shape[0], ids.stride(0), ids.stride(1)
 
 
 def slot_combiners(ts, combiner):
@@ -2946,592 +2891,6 @@ def cin_stack_backward(x0, xks, Ws, g_pooled, need_x0=True, arith=None, z_top=No
     if need_x0:
         dx0 = dx0.add_(G)                                    # layer 1's xk IS x0: its dL/dxk is the last share
     return (dx0 if need_x0 else None), dWs
-
-
-class _SortedShare:
-    """Two sorted sparse updates of one training step that see the same (row, entry) pairs -- DeepFM's Adagrad on the embedding tables
-    and FTRL on the linear columns of the same categorical columns (deepFM.py:58,61) -- sort once: whichever runs first in backward()
-    leaves a token (the id tensor's identity and version, its layout, the stream) and its workspace, the other takes the sorted pairs
-    from it (include/dir_hip.h: dir_sparse_*_sorted_*_from_f32).  A token is used at most once and only by the other optimiser."""
-
-    def __init__(self):
-        self.token = None
-        self.owner = None
-        self.ws = None
-        self.ws_tensor = None
-        self.hits = 0                       # sorts saved so far
-
-    @staticmethod
-    def _token(ids, B, sb, sf):
-        return (ids.data_ptr(), ids._version, B, sb, sf, torch.cuda.current_stream(ids.device).cuda_stream)
-
-    def take(self, who, ids, B, sb, sf):
-        """-> the other optimiser's workspace pointer if it sorted exactly these entries last, else None."""
-        if self.token is not None and self.owner is not who and self.token == self._token(ids, B, sb, sf) \
-                and self.owner._ws is self.ws_tensor:               # (the owner's workspace has not been reallocated since)
-            ws = self.ws
-            self.token = None
-            self.hits += 1
-            return ws
-        return None
-
-    def leave(self, who, ids, B, sb, sf, ws):
-        self.token, self.owner, self.ws, self.ws_tensor = self._token(ids, B, sb, sf), who, ws, who._ws
-
-
-def share_sorted_entries(a, b):
-    """Let two sorted sparse optimisers over table sets with the same vocabularies share one sort per step (see _SortedShare).
-    -> True if they were linked."""
-    if list(a.ts.vocab) != list(b.ts.vocab) or a.ts.F != b.ts.F or getattr(a, "method", "sorted") != "sorted" \
-            or os.environ.get("DIR_SHARE_SORT", "1") == "0":           # (development switch for A/B runs)
-        return False
-    a._share = b._share = _SortedShare()
-    return True
-
-
-class SparseAdagrad:
-    """Fused sparse Adagrad over a TableSet.  Holds the accumulators ([TF-upstream] initial_accumulator_value = 0.1).
-    method "sorted" (default; include/dir_hip.h: dir_sparse_adagrad_sorted_f32): radix sort of (row, entry) pairs +
-    per-tile segmented reduce -- skew-proof and bitwise reproducible.  method "chains" (dir_sparse_adagrad_f32): per-row
-    chains built with integer atomics -- a little faster on near-unique ids, serialises on hot rows.
-    A TableSet.train_rows set brings its accumulators with it (packed [embedding | accumulator] rows: one read and one write
-    per touched row; dir_sparse_adagrad_sorted_rows_f32); step_fm folds the FM backward into the update on either layout."""
-
-    def __init__(self, tables, lr, initial_accumulator_value=0.1, method="sorted"):
-        if method not in ("sorted", "chains"):
-            raise ValueError("method must be 'sorted' or 'chains'")
-        self.ts = _as_tableset(tables)
-        self.lr = float(lr)
-        self.method = method
-        dev = self.ts.device
-        if self.ts.accums is not None:           # packed training rows: the accumulators live beside the embeddings
-            if method != "sorted":
-                raise ValueError("packed training rows are updated by the sorted method")
-            self.accums = self.ts.accums
-        else:
-            self.accums = [torch.full_like(t, initial_accumulator_value) for t in self.ts.tables]
-        self.acc_ptrs = torch.tensor([a.data_ptr() for a in self.accums], dtype=torch.int64, device=dev)
-        base = [0]
-        for v in self.ts.vocab[:-1]:
-            base.append(base[-1] + v)
-        self.total_rows = sum(self.ts.vocab)
-        self.head_base = torch.tensor(base, dtype=torch.int64, device=dev)
-        self.head = torch.full((self.total_rows,), -1, dtype=torch.int32, device=dev) if method == "chains" else None
-        self._next = None
-        self._ws = None
-        self._share = None
-
-    def _rows_update(self, lib, ids, B, sb, sf, grad, fm_g, fm_sum):
-        """dir_sparse_adagrad_sorted_rows_f32, or its _from form when the linked optimiser has just sorted the same entries."""
-        ts = self.ts
-        ws, need = self._sorted_ws(lib, B)
-        src = self._share.take(self, ids, B, sb, sf) if self._share is not None else None
-        args = (_ptr(ts._ptrs), _ptr(self.acc_ptrs), ts.ld, ts.F, ts.K, _ptr(ids), sb, sf, _ptr(grad), grad.stride(0) if grad is not None else 0,
-                _ptr(fm_g), _ptr(fm_sum), self.lr, B, _ptr(self.head_base), self.total_rows, ws, need)
-        self._written()
-        if src is not None:
-            _lib.check(lib.dir_sparse_adagrad_sorted_rows_from_f32(*args, src, _stream()))
-            return
-        _lib.check(lib.dir_sparse_adagrad_sorted_rows_f32(*args, _stream()))
-        if self._share is not None:
-            self._share.leave(self, ids, B, sb, sf, ws)
-
-    def _written(self):
-        """The update kernels write the tables and accumulators through raw pointers: version counters bumped here (ops.mark_written)."""
-        if getattr(self.ts, "arena", None) is not None:
-            self.ts.written()
-        else:
-            self.ts.written(*self.accums)
-
-    def attach(self):
-        """Consume the gather's row gradients directly in backward (autograd.GatherFm): loss.backward() then
-        performs the embedding update itself; the tables get no .grad."""
-        self.ts.grad_sink = self.step
-        if self.method == "sorted":
-            self.ts.fm_sink = self.step_fm
-        return self
-
-    def _sorted_ws(self, lib, B):
-        ts = self.ts
-        need = int(lib.dir_sparse_adagrad_sorted_workspace_bytes(B, ts.F, ts.K, self.total_rows))
-        if need <= 0:
-            raise _lib.DirError(-4, "sparse_adagrad_sorted: unsupported size (B*F < 2^31, total rows < 2^32-1)")
-        if self._ws is None or self._ws.numel() < need + 256:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=ts.device)
-        off = (-self._ws.data_ptr()) % 256
-        return ctypes.c_void_p(self._ws.data_ptr() + off), need
-
-    def step_fm(self, ids, grad, fm_g, fm_sum):
-        """The update with the FM backward folded in (include/dir_hip.h: dir_sparse_adagrad_sorted_rows_f32): entry (b, f)'s
-        gradient is (fm_sum[b] - row) * fm_g[b] + grad[b, f].  grad [B, F*K] or None, fm_g [B] / [B, 1], fm_sum [B, K] from
-        gather_fm(..., fsum=).  Tables bit-identical to fm_logit_backward(add_in=grad) followed by step()."""
-        ts = self.ts
-        _dev(ids, torch.int64, "ids")
-        B, sb, sf = _onehot_strides(ids, ts.F)
-        if grad is not None:
-            _dev(grad, torch.float32, "grad")
-            if grad.shape != (B, ts.F * ts.K) or grad.stride(1) != 1:
-                raise ValueError("grad must be [B, F*K] with unit inner stride")
-        _dev(fm_g, torch.float32, "fm_g")
-        _dev(fm_sum, torch.float32, "fm_sum")
-        if fm_g.numel() != B or not fm_g.is_contiguous() or fm_sum.shape != (B, ts.K) or not fm_sum.is_contiguous():
-            raise ValueError("fm_g must be a contiguous [B] / [B, 1] tensor and fm_sum a contiguous [B, K] one")
-        if B == 0:
-            return
-        self._rows_update(_lib.load(), ids, B, sb, sf, grad, fm_g, fm_sum)
-
-    def step(self, ids, grad):
-        """ids [B, F] int64 (any strides), grad [B, F*K] fp32: d loss / d gathered rows."""
-        ts = self.ts
-        _dev(ids, torch.int64, "ids")
-        _dev(grad, torch.float32, "grad")
-        B, sb, sf = _onehot_strides(ids, ts.F)
-        if grad.shape != (B, ts.F * ts.K) or grad.stride(1) != 1:
-            raise ValueError("grad must be [B, F*K] with unit inner stride")
-        lib = _lib.load()
-        if ts.ld != ts.K or (self._share is not None and self.method == "sorted"):
-            if B == 0:
-                return
-            self._rows_update(lib, ids, B, sb, sf, grad, None, None)
-            return
-        if self.method == "chains":
-            if self._next is None or self._next.numel() < B * ts.F:
-                self._next = torch.empty(B * ts.F, dtype=torch.int32, device=ts.device)
-            _lib.check(lib.dir_sparse_adagrad_f32(_ptr(ts.ptrs), _ptr(self.acc_ptrs), ts.F, ts.K, _ptr(ids), sb, sf,
-                                                  _ptr(grad), grad.stride(0), self.lr, B, _ptr(self.head_base),
-                                                  self.total_rows, _ptr(self.head), _ptr(self._next), _stream()))
-            self._written()
-            return
-        if B == 0:
-            return
-        need = int(lib.dir_sparse_adagrad_sorted_workspace_bytes(B, ts.F, ts.K, self.total_rows))
-        if need <= 0:
-            raise _lib.DirError(-4, "sparse_adagrad_sorted: unsupported size (B*F < 2^31, total rows < 2^32-1)")
-        if self._ws is None or self._ws.numel() < need + 256:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=ts.device)
-        off = (-self._ws.data_ptr()) % 256
-        _lib.check(lib.dir_sparse_adagrad_sorted_f32(_ptr(ts.ptrs), _ptr(self.acc_ptrs), ts.F, ts.K, _ptr(ids), sb, sf,
-                                                     _ptr(grad), grad.stride(0), self.lr, B, _ptr(self.head_base),
-                                                     self.total_rows, ctypes.c_void_p(self._ws.data_ptr() + off), need, _stream()))
-        self._written()
-
-    def step_payload(self, payload, grad):
-        """Owner side of a sharded backward (shard.ShardedTables): payload [n] int64 (local_row * F + slot, < 0 pruned) as
-        received from all ranks, grad [n, K] in the same order (include/dir_hip.h: dir_sparse_adagrad_sorted_payload_f32)."""
-        ts = self.ts
-        _dev(payload, torch.int64, "payload")
-        _dev(grad, torch.float32, "grad")
-        n = payload.numel()
-        if grad.shape != (n, ts.K) or not grad.is_contiguous() or not payload.is_contiguous():
-            raise ValueError("grad must be a contiguous [n, K] tensor matching the payload")
-        if n == 0:
-            return
-        lib = _lib.load()
-        ws, need = _sorted_ws(self, lib, n, 1, ts.K, self.total_rows, ts.device)
-        _lib.check(lib.dir_sparse_adagrad_sorted_payload_f32(_ptr(ts.ptrs), _ptr(self.acc_ptrs), ts.F, ts.K, _ptr(payload), n,
-                                                             _ptr(grad), self.lr, _ptr(self.head_base), self.total_rows, ws, need,
-                                                             _stream()))
-        self._written()
-
-
-    def step_bags(self, recv, P, cap_e, cap_b, grad_rows, slot_mn=None, mn=0.0):
-        """Owner side of a sharded multi-hot backward (shard.ShardedTables.lookup_bags_train; include/dir_hip.h:
-        dir_sparse_adagrad_sorted_bags_f32): recv = the P bag slabs of (cap_e + 1) 16-byte records the forward received, grad_rows
-        [P*cap_b, K] = the gradients of the partial rows as received.  Entry (s, j) adds w * grad_rows[s*cap_b + ret] to its row; every
-        touched row takes one Adagrad step with its summed gradient, through the slot's max_norm clip derivative (slot_mn [F] device
-        fp32 or None + mn, as ops.slot_max_norms gives them) at its pre-update value."""
-        ts = self.ts
-        _dev(recv, torch.int64, "recv")
-        _dev(grad_rows, torch.float32, "grad_rows")
-        if ts.ld != ts.K:
-            raise ValueError("step_bags: plain [vocab, K] tables")
-        if recv.numel() < P * (cap_e + 1) * 2 or grad_rows.shape != (P * cap_b, ts.K) or not grad_rows.is_contiguous():
-            raise ValueError("step_bags: recv [P*(cap_e+1)*2] int64, grad_rows a contiguous [P*cap_b, K] tensor")
-        if self.total_rows == 0:
-            return
-        lib = _lib.load()
-        ws, need = _sorted_ws(self, lib, P * cap_e, 1, ts.K, self.total_rows, ts.device)
-        _lib.check(lib.dir_sparse_adagrad_sorted_bags_f32(_ptr(ts.ptrs), _ptr(self.acc_ptrs), ts.F, ts.K, _ptr(recv), P, cap_e, cap_b,
-                                                          _ptr(grad_rows), _ptr(slot_mn), float(mn), self.lr, _ptr(self.head_base),
-                                                          self.total_rows, ws, need, _stream()))
-        self._written()
-
-
-class SparseAdam:
-    """tf.train.AdamOptimizer on the embedding tables of a TableSet, in place, from the gather's row gradients (include/dir_hip.h:
-    dir_sparse_adam_f32; the reference's train_op: DeepCrossNetwork.py:264-290, train.py:119-124).  [TF-upstream] semantics: every row of
-    m, v and var moves every step (IndexedSlices gradients are zero outside the looked-up rows), each table's gradient is clipped on its
-    own with tf.clip_by_norm(g, clip_norm) first.  Holds m and v (zeros, like the slots TF creates).  Set .lr_t before every step
-    (lr * sqrt(1 - beta2^t) / (1 - beta1^t), t = global_step + 1); attach() makes loss.backward() perform the update.
-    On the shards of row-sharded tables the same step runs in two halves, norm_payload / step_payload, around the ranks' sum of the norm
-    shares (shard.ShardedTables.enable_training_adam); norm_bags / step_bags are the same halves over the bag records of a multi-hot
-    lookup (lookup_bags_train), on the same marks, norm words and sort area."""
-
-    def __init__(self, tables, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0):
-        self.ts = _as_tableset(tables)
-        ts = self.ts
-        if ts.ld != ts.K:
-            raise ValueError("SparseAdam: plain [vocab, K] tables")
-        self.beta1, self.beta2, self.eps, self.clip_norm = float(beta1), float(beta2), float(eps), float(clip_norm)
-        self.lr_t = 0.0
-        self.ms = [torch.zeros_like(t) for t in ts.tables]
-        self.vs = [torch.zeros_like(t) for t in ts.tables]
-        dev = ts.device
-        self.m_ptrs = torch.tensor([t.data_ptr() for t in self.ms], dtype=torch.int64, device=dev)
-        self.v_ptrs = torch.tensor([t.data_ptr() for t in self.vs], dtype=torch.int64, device=dev)
-        base = [0]
-        for v in ts.vocab[:-1]:
-            base.append(base[-1] + v)
-        self.total_rows = sum(ts.vocab)
-        self.row_base = torch.tensor(base, dtype=torch.int64, device=dev)
-        self._ws = None
-        self._ws_B = -1
-        self._pws, self._norm2, self._marks, self._sorted = None, None, None, None      # the payload form's sort area, norm words and row marks
-        self.steps = 0
-
-    @staticmethod
-    def covers(ts):
-        return ts.ld == ts.K and ts.F <= 64 and ts.K % 4 == 0 and 64 % (ts.K // 4) == 0 and sum(ts.vocab) < 0xffffffff
-
-    def attach(self):
-        self.ts.grad_sink = self.step
-        return self
-
-    def step(self, ids, grad):
-        """ids [B, F] int64 (any strides), grad [B, F*K] fp32 = d loss / d gathered rows: one Adam step of ALL rows of every table."""
-        ts = self.ts
-        _dev(ids, torch.int64, "ids")
-        _dev(grad, torch.float32, "grad")
-        B, sb, sf = _onehot_strides(ids, ts.F)
-        if grad.shape != (B, ts.F * ts.K) or grad.stride(1) != 1:
-            raise ValueError("grad must be [B, F*K] with unit inner stride")
-        lib = _lib.load()
-        need = int(lib.dir_sparse_adam_workspace_bytes(B, ts.F, ts.K, self.total_rows))
-        if need <= 0:
-            raise _lib.DirError(-4, "sparse_adam: unsupported size (F <= 64, K / 4 a power of two, B*F < 2^31, total rows < 2^32-1)")
-        first = 0
-        if self._ws is None or self._ws_B < B:
-            # the marks (behind the 1024 bytes of the norm words) must survive from step to step: the buffer is allocated once per batch size (grown,
-            # never shrunk), zeroed by the first call
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=ts.device)
-            self._ws_B = B
-            first = 1
-        off = (-self._ws.data_ptr()) % 256
-        _lib.check(lib.dir_sparse_adam_f32(_ptr(ts.ptrs), _ptr(self.m_ptrs), _ptr(self.v_ptrs), ts.F, ts.K, _ptr(ids), sb, sf, _ptr(grad),
-                                           grad.stride(0), self.lr_t, self.beta1, self.beta2, self.eps, self.clip_norm, B, _ptr(self.row_base),
-                                           self.total_rows, ctypes.c_void_p(self._ws.data_ptr() + off), self._ws.numel() - off, first, _stream()))
-        ts.written(*self.ms, *self.vs)
-        self.steps += 1
-
-    # ---- the owner side of a sharded backward (shard.ShardedTables.enable_training_adam): the step in two halves -----------------
-    def _payload_args(self, payload, grad):
-        ts = self.ts
-        _dev(payload, torch.int64, "payload")
-        _dev(grad, torch.float32, "grad")
-        n = payload.numel()
-        if grad.shape != (n, ts.K) or not grad.is_contiguous() or not payload.is_contiguous():
-            raise ValueError("grad must be a contiguous [n, K] tensor matching the payload")
-        lib = _lib.load()
-        need = int(lib.dir_sparse_adam_payload_workspace_bytes(n, ts.F, ts.K, self.total_rows))
-        if need <= 0:
-            raise _lib.DirError(-4, "sparse_adam (payload): unsupported size (F <= 64, K / 4 a power of two, n < 2^31, total rows < 2^32-1)")
-        if self._pws is None or self._pws.numel() < need + 256:
-            self._pws = torch.empty(need + 256, dtype=torch.uint8, device=ts.device)      # the sort area: grows with n (the marks live apart)
-        off = (-self._pws.data_ptr()) % 256
-        return lib, n, ctypes.c_void_p(self._pws.data_ptr() + off), self._pws.numel() - off
-
-    def norm_payload(self, payload, grad):
-        """First half (include/dir_hip.h: dir_sparse_adam_payload_norm_f32): payload [n] int64 (local_row * F + slot, < 0 pruned) as
-        received from all ranks, grad [n, K] in the same order; n == 0 is legal.  -> norm2 [2, F] device int64: THIS owner's share of
-        every table's ||g||^2 as the kernel's two norm words with the carry taken -- row 0 the low word (the fraction in units of 2^-32,
-        < 2^32), row 1 the high word (the integer part): share = high + low * 2^-32, exact for ||g|| < 2^31.  The payload stays sorted in
-        the workspace for step_payload."""
-        lib, n, ws, ws_bytes = self._payload_args(payload, grad)
-        if self._norm2 is None:
-            self._norm2 = torch.zeros(_lib.ADAM_NORM_WORDS, dtype=torch.int64, device=self.ts.device)      # 64 low words, 64 high words
-        _lib.check(lib.dir_sparse_adam_payload_norm_f32(self.ts.F, self.ts.K, _ptr(payload), n, _ptr(grad), _ptr(self.row_base), self.total_rows,
-                                                        _ptr(self._norm2), ws, ws_bytes, _stream()))
-        # what step_payload may reuse: this tensor, unchanged, in this sort area, on this stream
-        self._sorted = (payload, payload._version, self._pws, _stream().value)
-        words = self._norm2.view(2, 64)[:, :self.ts.F]
-        return torch.stack([words[0] & 0xffffffff, words[1] + ((words[0] >> 32) & 0xffffffff)])
-
-    def step_payload(self, payload, grad, norm2_global=None):
-        """Second half (dir_sparse_adam_payload_apply_f32): one Adam step of ALL local rows -- the touched ones from the payload, clipped
-        with norm2_global [F] device float64 = every table's GLOBAL ||g||^2 (the owners' norm_payload shares summed over the ranks:
-        high + low / 2^32; None exactly when clip_norm == 0), the others by the decay pass; n == 0 runs that pass alone.  The sort of a
-        norm_payload call on the same payload just before is reused."""
-        ts = self.ts
-        lib, n, ws, ws_bytes = self._payload_args(payload, grad)
-        if (self.clip_norm > 0) != (norm2_global is not None):
-            raise ValueError("step_payload: norm2_global goes with clip_norm > 0 (clip_norm=%g)" % self.clip_norm)
-        if norm2_global is not None:
-            _dev(norm2_global, torch.float64, "norm2_global")
-            if norm2_global.numel() != ts.F or not norm2_global.is_contiguous():
-                raise ValueError("norm2_global must be a contiguous [F] float64 tensor")
-        first = 0
-        if self._marks is None:
-            self._marks = torch.empty(max(256, (self.total_rows + 255) // 256 * 256), dtype=torch.uint8, device=ts.device)
-            first = 1
-        was = self._sorted
-        stream = _stream()
-        sorted_ = 1 if (n > 0 and was is not None and was[0] is payload and was[1] == payload._version and was[2] is self._pws
-                        and was[3] == stream.value) else 0
-        self._sorted = None
-        try:
-            _lib.check(lib.dir_sparse_adam_payload_apply_f32(_ptr(ts.ptrs), _ptr(self.m_ptrs), _ptr(self.v_ptrs), ts.F, ts.K, _ptr(payload), n,
-                                                             _ptr(grad), self.lr_t, self.beta1, self.beta2, self.eps, self.clip_norm,
-                                                             _ptr(norm2_global), _ptr(self.row_base), self.total_rows, _ptr(self._marks), ws,
-                                                             ws_bytes, sorted_, first, stream))
-        except _lib.DirError:
-            self._marks = None         # a step that failed between its two passes may have left marks set: the next call zeroes them again
-            raise
-        ts.written(*self.ms, *self.vs)
-        self.steps += 1
-
-    # ---- ... over received bag records (shard.ShardedTables.lookup_bags_train under enable_training_adam) ------------------------
-    # The marks, the first_call state, the sort area and the norm words are the payload form's: one-hot and bag steps may alternate.
-    def _bags_args(self, recv, P, cap_e, cap_b, grad_rows, slot_mn, what):
-        ts = self.ts
-        _dev(recv, torch.int64, "recv")
-        _dev(grad_rows, torch.float32, "grad_rows")
-        if recv.numel() < P * (cap_e + 1) * 2 or grad_rows.shape != (P * cap_b, ts.K) or not grad_rows.is_contiguous() or not recv.is_contiguous():
-            raise ValueError("%s: recv [P*(cap_e+1)*2] int64, grad_rows a contiguous [P*cap_b, K] tensor" % what)
-        if slot_mn is not None:
-            _dev(slot_mn, torch.float32, "slot_mn")
-            if slot_mn.numel() != ts.F or not slot_mn.is_contiguous():
-                raise ValueError("%s: slot_mn must be a contiguous [F] float32 tensor" % what)
-        lib = _lib.load()
-        need = int(lib.dir_sparse_adam_bags_workspace_bytes(P, cap_e, ts.F, ts.K, self.total_rows))
-        if need <= 0:
-            raise _lib.DirError(-4, "sparse_adam (bags): unsupported size (F <= 64, K / 4 a power of two, P*cap_e < 2^30, total rows < 2^32-1)")
-        if self._pws is None or self._pws.numel() < need + 256:
-            self._pws = torch.empty(need + 256, dtype=torch.uint8, device=ts.device)
-        off = (-self._pws.data_ptr()) % 256
-        return lib, ctypes.c_void_p(self._pws.data_ptr() + off), self._pws.numel() - off
-
-    def norm_bags(self, recv, P, cap_e, cap_b, grad_rows, slot_mn=None, mn=0.0):
-        """First half over bag records (include/dir_hip.h: dir_sparse_adam_bags_norm_f32): recv = the P bag slabs of (cap_e + 1) 16-byte
-        records the forward received, grad_rows [P*cap_b, K] = the gradients of the partial rows as received, slot_mn [F] device fp32 or
-        None + mn as ops.slot_max_norms gives them.  A row's gradient is the sum of w * grad_rows[s*cap_b + ret] over all its entries,
-        through the slot's max_norm clip derivative at the row's current value.  -> norm2 [2, F] device int64, as norm_payload.  The
-        records stay sorted in the workspace for step_bags."""
-        lib, ws, ws_bytes = self._bags_args(recv, P, cap_e, cap_b, grad_rows, slot_mn, "norm_bags")
-        ts = self.ts
-        if self._norm2 is None:
-            self._norm2 = torch.zeros(_lib.ADAM_NORM_WORDS, dtype=torch.int64, device=ts.device)
-        _lib.check(lib.dir_sparse_adam_bags_norm_f32(_ptr(ts.ptrs), ts.F, ts.K, _ptr(recv), P, cap_e, cap_b, _ptr(grad_rows), _ptr(slot_mn),
-                                                     float(mn), _ptr(self.row_base), self.total_rows, _ptr(self._norm2), ws, ws_bytes, _stream()))
-        # what step_bags may reuse: these slabs and gradient rows, unchanged, in this sort area, on this stream
-        self._sorted = (recv, recv._version, self._pws, _stream().value, (P, cap_e, cap_b))
-        words = self._norm2.view(2, 64)[:, :ts.F]
-        return torch.stack([words[0] & 0xffffffff, words[1] + ((words[0] >> 32) & 0xffffffff)])
-
-    def step_bags(self, recv, P, cap_e, cap_b, grad_rows, norm2_global=None, slot_mn=None, mn=0.0):
-        """Second half over bag records (dir_sparse_adam_bags_apply_f32): one Adam step of ALL local rows -- the touched ones from their
-        summed record gradients (through the max_norm clip derivative at the pre-update row), clipped with norm2_global [F] device
-        float64 (None exactly when clip_norm == 0), the others by the decay pass; slabs without a live record run that pass alone.  The
-        sort of a norm_bags call on the same slabs just before is reused."""
-        ts = self.ts
-        lib, ws, ws_bytes = self._bags_args(recv, P, cap_e, cap_b, grad_rows, slot_mn, "step_bags")
-        if (self.clip_norm > 0) != (norm2_global is not None):
-            raise ValueError("step_bags: norm2_global goes with clip_norm > 0 (clip_norm=%g)" % self.clip_norm)
-        if norm2_global is not None:
-            _dev(norm2_global, torch.float64, "norm2_global")
-            if norm2_global.numel() != ts.F or not norm2_global.is_contiguous():
-                raise ValueError("norm2_global must be a contiguous [F] float64 tensor")
-        first = 0
-        if self._marks is None:
-            self._marks = torch.empty(max(256, (self.total_rows + 255) // 256 * 256), dtype=torch.uint8, device=ts.device)
-            first = 1
-        was = self._sorted
-        stream = _stream()
-        sorted_ = 1 if (was is not None and len(was) == 5 and was[0] is recv and was[1] == recv._version and was[2] is self._pws
-                        and was[3] == stream.value and was[4] == (P, cap_e, cap_b)) else 0
-        self._sorted = None
-        try:
-            _lib.check(lib.dir_sparse_adam_bags_apply_f32(_ptr(ts.ptrs), _ptr(self.m_ptrs), _ptr(self.v_ptrs), ts.F, ts.K, _ptr(recv), P, cap_e,
-                                                          cap_b, _ptr(grad_rows), _ptr(slot_mn), float(mn), self.lr_t, self.beta1, self.beta2,
-                                                          self.eps, self.clip_norm, _ptr(norm2_global), _ptr(self.row_base), self.total_rows,
-                                                          _ptr(self._marks), ws, ws_bytes, sorted_, first, stream))
-        except _lib.DirError:
-            self._marks = None         # (as step_payload)
-            raise
-        ts.written(*self.ms, *self.vs)
-        self.steps += 1
-
-    def step_table_grad(self, f, grad):
-        """Table f's step from a gradient that arrived as its .grad instead of through the sink -- multi-hot / weighted columns, whose
-        backward (autograd.EmbeddingBag) returns sparse row gradients: the same tf.train.AdamOptimizer step of ALL rows (clip_by_norm on
-        the table's gradient first) on this optimiser's m / v, with torch ops (not a hot path: the one-hot lookups take the HIP update)."""
-        t, m, v = self.ts.tables[f], self.ms[f], self.vs[f]
-        g = (grad.coalesce().to_dense() if grad.is_sparse else grad).to(torch.float32)
-        if self.clip_norm > 0:
-            g = g * (self.clip_norm / torch.clamp(torch.linalg.vector_norm(g), min=self.clip_norm))
-        m.mul_(self.beta1).add_(g, alpha=1.0 - self.beta1)
-        v.mul_(self.beta2).addcmul_(g, g, value=1.0 - self.beta2)
-        t.addcdiv_(m, v.sqrt().add_(self.eps), value=-self.lr_t)
-        mark_written(*self.ts.owners[f:f + 1])
-
-
-def _sorted_ws(holder, lib, n_entries, F, K, total_rows, device):
-    need = int(lib.dir_sparse_adagrad_sorted_workspace_bytes(n_entries, F, K, total_rows))
-    if need <= 0:
-        raise _lib.DirError(-4, "sorted sparse update: unsupported size (entries < 2^31, total rows < 2^32-1)")
-    if holder._ws is None or holder._ws.numel() < need + 256:
-        holder._ws = torch.empty(need + 256, dtype=torch.uint8, device=device)
-    off = (-holder._ws.data_ptr()) % 256
-    return ctypes.c_void_p(holder._ws.data_ptr() + off), need
-
-
-class SparseFtrl:
-    """Fused sparse FTRL-Proximal over a TableSet (include/dir_hip.h: dir_sparse_ftrl_sorted_f32; the reference's
-    linear_optimizer='Ftrl', deepFM.py:58, with [TF-upstream] tf.train.FtrlOptimizer defaults: initial accumulator 0.1,
-    learning_rate_power -0.5, l1 = l2 = 0).  step(ids, grad): grad is [B, F*K] (one gradient row per slot) or [B, K] (the same
-    row for every slot: the linear term, whose d logit is shared by all columns)."""
-
-    def __init__(self, tables, lr=0.2, initial_accumulator_value=0.1, l1=0.0, l2=0.0):
-        self.ts = _as_tableset(tables)
-        self.lr, self.l1, self.l2 = float(lr), float(l1), float(l2)
-        dev = self.ts.device
-        self.packed = getattr(self.ts, "linears", None) is not None      # TableSet.ftrl_rows: n and z live in the weights' rows
-        if self.packed:
-            self.accums, self.linears = self.ts.accums, self.ts.linears
-        else:
-            if self.ts.ld != self.ts.K:
-                raise ValueError("SparseFtrl: tables with a row stride must be TableSet.ftrl_rows")
-            self.accums = [torch.full_like(t, initial_accumulator_value) for t in self.ts.tables]
-            self.linears = [torch.zeros_like(t) for t in self.ts.tables]
-        self.acc_ptrs = torch.tensor([a.data_ptr() for a in self.accums], dtype=torch.int64, device=dev)
-        self.lin_ptrs = torch.tensor([z.data_ptr() for z in self.linears], dtype=torch.int64, device=dev)
-        base = [0]
-        for v in self.ts.vocab[:-1]:
-            base.append(base[-1] + v)
-        self.total_rows = sum(self.ts.vocab)
-        self.row_base = torch.tensor(base, dtype=torch.int64, device=dev)
-        self._ws = None
-        self._share = None
-
-    def attach(self):
-        """Consume the linear term's gradient directly in backward (autograd.LinearLogit)."""
-        self.ts.grad_sink = self.step
-        return self
-
-    def step(self, ids, grad):
-        ts = self.ts
-        _dev(ids, torch.int64, "ids")
-        _dev(grad, torch.float32, "grad")
-        B, sb, sf = _onehot_strides(ids, ts.F)
-        if grad.dim() != 2 or grad.shape[0] != B or grad.stride(1) != 1 or grad.shape[1] not in (ts.K, ts.F * ts.K):
-            raise ValueError("grad must be [B, F*K] or [B, K] with unit inner stride")
-        if B == 0:
-            return
-        slot_stride = ts.K if grad.shape[1] == ts.F * ts.K and ts.F > 1 else 0
-        lib = _lib.load()
-        need = int(lib.dir_sparse_adagrad_sorted_workspace_bytes(B, ts.F, ts.K, self.total_rows))
-        if need <= 0:
-            raise _lib.DirError(-4, "sparse_ftrl_sorted: unsupported size (B*F < 2^31, total rows < 2^32-1)")
-        if self._ws is None or self._ws.numel() < need + 256:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=ts.device)
-        off = (-self._ws.data_ptr()) % 256
-        ws = ctypes.c_void_p(self._ws.data_ptr() + off)
-        src = self._share.take(self, ids, B, sb, sf) if self._share is not None else None
-        ts.written(*self.accums, *self.linears)
-        if self.packed:
-            _lib.check(lib.dir_sparse_ftrl_rows_sorted_f32(_ptr(ts._ptrs), ts.F, _ptr(ids), sb, sf, _ptr(grad), grad.stride(0), slot_stride,
-                                                           self.lr, self.l1, self.l2, B, _ptr(self.row_base), self.total_rows, ws, need, src,
-                                                           _stream()))
-            if src is None and self._share is not None:
-                self._share.leave(self, ids, B, sb, sf, ws)
-            return
-        args = (_ptr(ts.ptrs), _ptr(self.acc_ptrs), _ptr(self.lin_ptrs), ts.F, ts.K, _ptr(ids), sb, sf, _ptr(grad), grad.stride(0), slot_stride,
-                self.lr, self.l1, self.l2, B, _ptr(self.row_base), self.total_rows, ws, need)
-        if src is not None:
-            _lib.check(lib.dir_sparse_ftrl_sorted_from_f32(*args, src, _stream()))
-            return
-        _lib.check(lib.dir_sparse_ftrl_sorted_f32(*args, _stream()))
-        if self._share is not None:
-            self._share.leave(self, ids, B, sb, sf, ws)
-
-
-    def step_payload(self, payload, grad, sorted_by=None):
-        """Owner side of the sharded linear term's backward (shard.ShardedTables; include/dir_hip.h:
-        dir_sparse_ftrl_rows_sorted_payload_f32): payload [n] int64 (local_row * F + slot, < 0 pruned) as received from all ranks, grad [n]
-        fp32 in the same order, over packed rows (TableSet.ftrl_rows).  sorted_by: an optimiser whose step_payload has JUST run over the
-        same payload on this stream with the same local vocabularies (the SparseAdagrad of the co-located embedding rows): its sorted
-        (row, entry) pairs are read from its workspace and this call skips the key pass and the sort."""
-        ts = self.ts
-        if not self.packed:
-            raise ValueError("step_payload: packed linear training rows (TableSet.ftrl_rows)")
-        _dev(payload, torch.int64, "payload")
-        _dev(grad, torch.float32, "grad")
-        n = payload.numel()
-        if grad.numel() != n or not grad.is_contiguous() or not payload.is_contiguous():
-            raise ValueError("grad must be a contiguous [n] tensor matching the payload")
-        if n == 0 or self.total_rows == 0:
-            return
-        lib = _lib.load()
-        ws, need = _sorted_ws(self, lib, n, 1, 1, self.total_rows, ts.device)
-        src = None
-        if sorted_by is not None:
-            if sorted_by.total_rows != self.total_rows or list(sorted_by.ts.vocab) != list(ts.vocab) or sorted_by._ws is None:
-                raise ValueError("step_payload: sorted_by must have just sorted the same payload over the same local vocabularies")
-            src = ctypes.c_void_p(sorted_by._ws.data_ptr() + (-sorted_by._ws.data_ptr()) % 256)
-        _lib.check(lib.dir_sparse_ftrl_rows_sorted_payload_f32(_ptr(ts._ptrs), ts.F, _ptr(payload), n, _ptr(grad), self.lr, self.l1, self.l2,
-                                                               _ptr(self.row_base), self.total_rows, ws, need, src, _stream()))
-        ts.written(*self.accums, *self.linears)
-
-
-    def step_payload_units(self, payload, grad, sorted_by=None):
-        """step_payload over rows of ts.units first-order terms (include/dir_hip.h: dir_sparse_ftrl_rows_units_sorted_payload_f32): grad
-        [n, units] in payload order; sorted_by as in step_payload -- the co-located embedding rows may be of any width."""
-        ts = self.ts
-        U = int(getattr(ts, "units", 1))
-        if not self.packed or ts.ld != 4 * U:
-            raise ValueError("step_payload_units: packed rows of 4 * units floats")
-        _dev(payload, torch.int64, "payload")
-        _dev(grad, torch.float32, "grad")
-        n = payload.numel()
-        if grad.numel() != n * U or not grad.is_contiguous() or not payload.is_contiguous():
-            raise ValueError("grad must be a contiguous [n, units] tensor matching the payload")
-        if n == 0 or self.total_rows == 0:
-            return
-        lib = _lib.load()
-        ws, need = _sorted_ws(self, lib, n, 1, U, self.total_rows, ts.device)
-        src = None
-        if sorted_by is not None:
-            if sorted_by.total_rows != self.total_rows or list(sorted_by.ts.vocab) != list(ts.vocab) or sorted_by._ws is None:
-                raise ValueError("step_payload_units: sorted_by must have just sorted the same payload over the same local vocabularies")
-            src = ctypes.c_void_p(sorted_by._ws.data_ptr() + (-sorted_by._ws.data_ptr()) % 256)
-        _lib.check(lib.dir_sparse_ftrl_rows_units_sorted_payload_f32(_ptr(ts._ptrs), ts.F, U, _ptr(payload), n, _ptr(grad), self.lr, self.l1,
-                                                                     self.l2, _ptr(self.row_base), self.total_rows, ws, need, src, _stream()))
-        ts.written(*self.accums, *self.linears)
-
-    def step_bags(self, recv, P, cap_e, cap_b, grad, sorted_by=None):
-        """Owner side of the first-order term's backward over sharded bags (shard.ShardedTables.lookup_bags_train(with_linear=True);
-        include/dir_hip.h: dir_sparse_ftrl_rows_sorted_bags_f32): recv = the P bag slabs the forward received, grad [P*cap_b] fp32 = d lin
-        of every partial-row position as received.  Entry (s, j) adds w * grad[s*cap_b + ret] to its (slot, row); every touched row takes
-        one FTRL step with its summed gradient.  sorted_by: the SparseAdagrad whose step_bags has JUST run over the same slabs on this
-        stream with the same local vocabularies: its sorted (row, entry) pairs are read and the key pass and the sort are skipped."""
-        ts = self.ts
-        if not self.packed:
-            raise ValueError("step_bags: packed linear training rows (TableSet.ftrl_rows)")
-        _dev(recv, torch.int64, "recv")
-        _dev(grad, torch.float32, "grad")
-        if recv.numel() < P * (cap_e + 1) * 2 or grad.numel() != P * cap_b or not grad.is_contiguous() or not recv.is_contiguous():
-            raise ValueError("step_bags: recv [P*(cap_e+1)*2] int64, grad a contiguous [P*cap_b] tensor")
-        if self.total_rows == 0:
-            return
-        lib = _lib.load()
-        ws, need = _sorted_ws(self, lib, P * cap_e, 1, 1, self.total_rows, ts.device)
-        src = None
-        if sorted_by is not None:
-            if sorted_by.total_rows != self.total_rows or list(sorted_by.ts.vocab) != list(ts.vocab) or sorted_by._ws is None:
-                raise ValueError("step_bags: sorted_by must have just sorted the same slabs over the same local vocabularies")
-            src = ctypes.c_void_p(sorted_by._ws.data_ptr() + (-sorted_by._ws.data_ptr()) % 256)
-        _lib.check(lib.dir_sparse_ftrl_rows_sorted_bags_f32(_ptr(ts._ptrs), ts.F, _ptr(recv), P, cap_e, cap_b, _ptr(grad), self.lr, self.l1,
-                                                            self.l2, _ptr(self.row_base), self.total_rows, ws, need, src, _stream()))
-        ts.written(*self.accums, *self.linears)
 
 
 class PackedTables:

@@ -96,7 +96,7 @@ def halves():
 
 
 def apply_own_sort():
-    opt._sorted = None                                     # forget the norm pass's sort of this payload: key pass + sort run again
+    opt.forget_sort()                                      # forget the norm pass's sort of this payload: key pass + sort run again
     be.adam_apply(opt, pay, rows, norms)
 
 

@@ -107,7 +107,7 @@ for dist in args.dist.split(","):
     rows0 = torch.zeros((0, K), dtype=torch.float32, device=dev)
 
     def apply_own_sort():
-        opt._sorted = None                                     # forget the norm half's sort of these slabs: key pass + sort run again
+        opt.forget_sort()                                      # forget the norm half's sort of these slabs: key pass + sort run again
         be.bags_adam_apply(opt, *rec, norms)
 
     def apply_on_norm_sort():
