@@ -1492,33 +1492,16 @@ extern "C" int dir_sparse_adagrad_sorted_payload_f32(float* const* tables, float
 }
 
 // Owner side of the sharded linear term's backward (shard.ShardedTables.lookup_train(with_linear=True)): dir_sparse_ftrl_rows_sorted_f32's
-// update (FtrlUpd, packed [w | n | z | -] rows, units = 1) driven by the payload the owner received, as dir_sparse_adagrad_sorted_payload_f32
-// is for Adagrad.  sorted_from (optional): the workspace of a sorted update of the SAME payload (same n, row_base, total_rows) that has just
-// run on this stream -- the Adagrad step of the embedding rows the weights are co-located with: its sorted (row, entry) pairs are read
-// and the key pass and the sort are skipped (the pair arrays sit at offsets that depend on n only, not on K).
-extern "C" int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F, const int64_t* payload, int64_t n, const float* grad, float lr,
-                                                       float l1, float l2, const int64_t* row_base, int64_t total_rows, void* workspace,
-                                                       int64_t workspace_bytes, const void* sorted_from, dir_stream_t stream) {
-    const char* name = "dir_sparse_ftrl_rows_sorted_payload_f32";
-    DIR_CHECK_ARG(F > 0 && n >= 0, "%s: F=%d n=%lld", name, F, (long long)n);
-    DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
-    DIR_CHECK_ARG(rows && (payload || n == 0), "%s: null pointer", name);
-    FtrlUpd upd{rows, rows, rows, lr, l1, l2, (int64_t)4};
-    upd.rows = true;
-    return sparse_sorted_update(name, upd, F, 1, SortedSrc::of_payload(payload).reuse(sorted_from), grad, (int64_t)1, 0, n, row_base, total_rows,
-                                workspace, workspace_bytes, stream);
-}
-
-// dir_sparse_ftrl_rows_sorted_payload_f32 with units = U first-order terms per row (ShardedTables.attach_linear([rows, U])): rows[f] is
-// [local rows, 4 U] = U blocks [w | n | z | -], grad is [n, U] in payload order.  Driven through sparse_sorted_update with K = U and
-// grad_ld = U; FtrlUpd's `col` selects the unit's block; sorted_from works as in the units = 1 form: the pair arrays of a sorted
-// workspace sit at offsets that depend on n only -- not on K -- so the Adagrad step's sort of the same payload at width G * K is
+// update (FtrlUpd over packed rows) driven by the payload the owner received, as dir_sparse_adagrad_sorted_payload_f32 is for Adagrad.
+// rows[f] is [local rows, 4 U] = U blocks [w | n | z | -] (ShardedTables.attach_linear([rows, U])), grad is [n, U] in payload order:
+// sparse_sorted_update runs with K = U and grad_ld = U, and FtrlUpd's `col` selects the unit's block.  sorted_from (optional): the
+// workspace of a sorted update of the SAME payload (same n, row_base, total_rows) that has just run on this stream -- the Adagrad step of
+// the embedding rows the weights are co-located with: its sorted (row, entry) pairs are read and the key pass and the sort are skipped.
+// The pair arrays of a sorted workspace sit at offsets that depend on n only -- not on K -- so that step's sort at width G * K is
 // reusable here, and the row order (hence every sum) is the one a sort of its own would give.
-extern "C" int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows, int F, int units, const int64_t* payload, int64_t n,
-                                                             const float* grad, float lr, float l1, float l2, const int64_t* row_base,
-                                                             int64_t total_rows, void* workspace, int64_t workspace_bytes,
-                                                             const void* sorted_from, dir_stream_t stream) {
-    const char* name = "dir_sparse_ftrl_rows_units_sorted_payload_f32";
+static int ftrl_rows_payload(const char* name, float* const* rows, int F, int units, const int64_t* payload, int64_t n, const float* grad, float lr,
+                             float l1, float l2, const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
+                             const void* sorted_from, dir_stream_t stream) {
     DIR_CHECK_ARG(F > 0 && n >= 0, "%s: F=%d n=%lld", name, F, (long long)n);
     DIR_CHECK_ARG(units >= 1 && units <= 8, "%s: units=%d (1 <= units <= 8)", name, units);
     DIR_CHECK_ARG(lr > 0.f && l1 >= 0.f && l2 >= 0.f, "%s: lr=%g l1=%g l2=%g", name, lr, l1, l2);
@@ -1528,6 +1511,22 @@ extern "C" int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows,
     upd.units = units;
     return sparse_sorted_update(name, upd, F, units, SortedSrc::of_payload(payload).reuse(sorted_from), grad, (int64_t)units, 0, n, row_base,
                                 total_rows, workspace, workspace_bytes, stream);
+}
+
+// the units entry at units = 1
+extern "C" int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F, const int64_t* payload, int64_t n, const float* grad, float lr,
+                                                       float l1, float l2, const int64_t* row_base, int64_t total_rows, void* workspace,
+                                                       int64_t workspace_bytes, const void* sorted_from, dir_stream_t stream) {
+    return ftrl_rows_payload("dir_sparse_ftrl_rows_sorted_payload_f32", rows, F, 1, payload, n, grad, lr, l1, l2, row_base, total_rows, workspace,
+                             workspace_bytes, sorted_from, stream);
+}
+
+extern "C" int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows, int F, int units, const int64_t* payload, int64_t n,
+                                                             const float* grad, float lr, float l1, float l2, const int64_t* row_base,
+                                                             int64_t total_rows, void* workspace, int64_t workspace_bytes,
+                                                             const void* sorted_from, dir_stream_t stream) {
+    return ftrl_rows_payload("dir_sparse_ftrl_rows_units_sorted_payload_f32", rows, F, units, payload, n, grad, lr, l1, l2, row_base, total_rows,
+                             workspace, workspace_bytes, sorted_from, stream);
 }
 
 // ---- tf.train.AdamOptimizer on the embedding tables ------------------------------------------------------------------------------

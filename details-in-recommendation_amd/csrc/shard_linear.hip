@@ -2,25 +2,32 @@
 //
 // Replaces (reference): linear_logits under the embedding tables' input_layer_partitioner, models/DeepFM/deepFM.py:199-223, 255-275.
 //
-// The first-order weights of slot f live beside the embedding rows of slot f, on the rank that owns them, as packed 16-byte training rows
-// [w | n | z | -] (TableSet.ftrl_rows' layout).  The linear term rides on the embedding lookup's id exchange: the owner already holds the
-// (slot, local row) payload of every entry it serves, so
-//   linear_gather_k   owner:      one w per received payload word -> one float per slab slot (4 bytes per entry travel back)
-//   linear_finish_k   requester:  lin[b] = bias + sum_f wback[inv[b, f]], in linear_onehot4_k's order and arithmetic (bit for bit)
-//   linear_grad_k     requester:  the transpose of the finish: send[inv[b, f]] = d logit[b]
-// The owner's update is dir_sparse_ftrl_rows_sorted_payload_f32 (backward.hip).
+// The first-order weights of slot f live beside the embedding rows of slot f, on the rank that owns them, as packed training rows: U
+// 16-byte blocks [w | n | z | -], one per unit, side by side (unit u's weight at float 4 u; U = 1: TableSet.ftrl_rows' layout, DeepFM and
+// xDeepFM; U = 2: ESMM_W_D's two linear models over the same ids, ShardedTables.attach_linear([rows, U])).  The linear term rides on the
+// embedding lookup's id exchange: the owner already holds the (slot, local row) payload of every entry it serves, and the U weights of
+// an entry travel behind ONE payload word, so
+//   linear_gather_k   owner:      out[i * U + u] = unit u's weight of payload word i -> U floats per slab slot travel back
+//   linear_finish_k   requester:  lin[b, u] = bias[u] + sum_f wback[inv[b, f] * U + u], per unit in linear_onehot4_k's order and arithmetic
+//                                 (bit for bit)
+//   linear_grad_k     requester:  the transpose of the finish: send[inv[b, f] * U + u] = d logit[b, u]
+// The owner's update is dir_sparse_ftrl_rows_units_sorted_payload_f32 (backward.hip).  U = 1 is a value of U like any other: the plain
+// C entries below are the units entries at units = 1.
 //
-// All three are request-rate-bound (one 4-byte read or write per entry, no reuse): one lane per entry, the payload read coalesced, several
-// independent loads in flight per lane, nothing staged through LDS.
+// All three are request-rate-bound (4-byte reads or writes, no reuse): one lane per entry (the grad: per entry and unit), the payload
+// read coalesced, several independent loads in flight per lane, nothing staged through LDS.
 #include "common.hpp"
 #include "shard_wire.hpp"
 
 namespace dir {
 
-// Owner side.  Slab form (cap > 0): recv = P one-hot slabs (shard_wire.hpp), out[s * cap + j].  Flat form (cap == 0): recv = n payload
-// words, out[i].  p < 0, a slot behind the header, or a row outside the slot's local rows (local_rows, optional) writes 0.0f: every
-// output word is written, nothing uninitialised goes back over the wire.
-template <int EPT>
+constexpr int DIR_MAX_UNITS = 8;
+
+// Owner side.  Slab form (cap > 0): recv = P one-hot slabs (shard_wire.hpp), out[(s * cap + j) * U + u].  Flat form (cap == 0): recv = n
+// payload words, out[i * U + u].  p < 0, a slot behind the header, or a row outside the slot's local rows (local_rows, optional) writes
+// 0.0f: every output word is written, nothing uninitialised goes back over the wire.  ONE lane takes a row and issues its U reads
+// together (they fall into the row's one 16 U-byte piece: for U = 2 one 32-byte segment holds both).
+template <int U, int EPT>
 __global__ __launch_bounds__(256) void linear_gather_k(const float* const* __restrict__ rows, int64_t ld, const int64_t* __restrict__ local_rows,
                                                        int F, const int64_t* __restrict__ recv, int64_t cap, int64_t total,
                                                        float* __restrict__ out) {
@@ -28,150 +35,58 @@ __global__ __launch_bounds__(256) void linear_gather_k(const float* const* __res
     for (int64_t i0 = (int64_t)blockIdx.x * 256 * EPT; i0 < total; i0 += per_grid) {
         int64_t p[EPT];
         const float* src[EPT];
-        float v[EPT];
-#pragma unroll
-        for (int u = 0; u < EPT; ++u) {                        // the payload words: consecutive lanes read consecutive words
-            const int64_t i = i0 + u * 256 + threadIdx.x;
-            p[u] = -1;
-            if (i < total) {
-                if (cap > 0) {
-                    const int64_t sl = (int64_t)((uint32_t)i / (uint32_t)cap);       // total < 2^31
-                    const int64_t j = i - sl * cap;
-                    const int64_t* slab = slab_of(recv, sl, cap);
-                    if (j < slab_count(slab[0])) p[u] = slab[1 + j];
-                } else {
-                    p[u] = recv[i];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < EPT; ++u) {
-            src[u] = nullptr;
-            if (p[u] >= 0) {
-                int slot;
-                int64_t row;
-                unpack_payload(p[u], F, slot, row);
-                if (!local_rows || row < local_rows[slot]) src[u] = rows[slot] + row * ld;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < EPT; ++u) v[u] = src[u] ? *src[u] : 0.f;      // EPT independent 4-byte reads in flight per lane
-#pragma unroll
-        for (int u = 0; u < EPT; ++u) {
-            const int64_t i = i0 + u * 256 + threadIdx.x;
-            if (i < total) out[i] = v[u];
-        }
-    }
-}
-
-// Requester side: FOUR lanes per sample, lane c reads the weights of fields 4 j + c through the inverse positions, and the quad adds them
-// up in FIELD order through quad broadcasts -- linear_onehot4_k's sum (linear_cross.hip), add for add: acc = 0; acc += v_f for f = 0..F-1
-// (a pruned entry adds 0.0f); r = acc + (bias ? bias[0] : 0.0f).
-template <int UFL>
-__global__ __launch_bounds__(256) void linear_finish_k(const float* __restrict__ wback, int64_t n_back, const int64_t* __restrict__ inv,
-                                                       int64_t sb, int64_t sf, int F, const float* __restrict__ bias, int64_t B,
-                                                       float* __restrict__ out, int64_t out_ld) {
-    const int c = threadIdx.x & 3;
-    const int64_t per_grid = ((int64_t)gridDim.x * blockDim.x) >> 2;
-    for (int64_t b0 = ((int64_t)blockIdx.x * blockDim.x) >> 2; b0 < B; b0 += per_grid) {      // (block-uniform trip count: the DPP reads see live lanes)
-        const int64_t b = b0 + (threadIdx.x >> 2);
-        const bool live = b < B;
-        const int64_t* ip = inv + (live ? b : 0) * sb;
-        float acc = 0.f;
-        for (int f0 = 0; f0 < F; f0 += 4 * UFL) {
-            int64_t pos[UFL];
-            float v[UFL];
-#pragma unroll
-            for (int j = 0; j < UFL; ++j) {
-                const int f = f0 + 4 * j + c;
-                pos[j] = (live && f < F) ? ip[(int64_t)f * sf] : (int64_t)-1;
-            }
-#pragma unroll
-            for (int j = 0; j < UFL; ++j) v[j] = (uint64_t)pos[j] < (uint64_t)n_back ? wback[pos[j]] : 0.f;     // inv < 0: pruned
-#pragma unroll
-            for (int j = 0; j < UFL; ++j) acc = quad_add_in_order(v[j], f0 + 4 * j, F, acc);
-        }
-        if (live && c == 0) out[b * out_ld] = acc + (bias ? bias[0] : 0.f);
-    }
-}
-
-// Requester side of the backward: entry (b, f) writes d logit[b] where its weight came back from.  Training lookups are never de-duplicated:
-// every position has exactly one writer (plain stores); `send` was zero-filled by the caller of the kernel (the C entry).
-__global__ __launch_bounds__(256) void linear_grad_k(const float* __restrict__ g, int64_t g_ld, const int64_t* __restrict__ inv, int64_t sb,
-                                                     int64_t sf, int F, int64_t n /* B * F */, float* __restrict__ send, int64_t n_send) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t b = (int64_t)((uint32_t)i / (uint32_t)F);          // n < 2^31
-        const int f = (int)(i - b * F);
-        const int64_t pos = inv[b * sb + (int64_t)f * sf];
-        if ((uint64_t)pos < (uint64_t)n_send) send[pos] = g[b * g_ld];
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// units = U first-order terms over the same ids (ShardedTables.attach_linear([rows, U]): ESMM_W_D's two linear models)
-// ------------------------------------------------------------------------------------------------
-// A row is U packed 16-byte blocks [w | n | z | -], one per unit, side by side (16 U bytes: unit u's weight at float 4 u).  The U weights
-// of an entry travel behind ONE payload word, U floats per slab slot:
-//   linear_gather_units_k   owner:      out[i * U + u] = unit u's weight of payload word i; ONE lane takes a row and issues its U reads
-//                                        together (they fall into the row's one 16 U-byte piece: for U = 2 one 32-byte segment holds both)
-//   linear_finish_units_k   requester:  lin[b, u] = bias[u] + sum_f wback[inv[b, f] * U + u], per unit linear_finish_k's quads and order
-//   linear_grad_units_k     requester:  the transpose, send[inv[b, f] * U + u] = g[b, u]
-// The owner's update is dir_sparse_ftrl_rows_units_sorted_payload_f32 (backward.hip).
-constexpr int DIR_MAX_UNITS = 8;
-
-template <int U, int EPT>
-__global__ __launch_bounds__(256) void linear_gather_units_k(const float* const* __restrict__ rows, const int64_t* __restrict__ local_rows, int F,
-                                                             const int64_t* __restrict__ recv, int64_t cap, int64_t total,
-                                                             float* __restrict__ out) {
-    const int64_t per_grid = (int64_t)gridDim.x * 256 * EPT;
-    for (int64_t i0 = (int64_t)blockIdx.x * 256 * EPT; i0 < total; i0 += per_grid) {
-        const float* src[EPT];
         float v[EPT][U];
 #pragma unroll
-        for (int e = 0; e < EPT; ++e) {                        // linear_gather_k's walk: payload word -> the row's address (or none)
+        for (int e = 0; e < EPT; ++e) {                        // the payload words: consecutive lanes read consecutive words
             const int64_t i = i0 + e * 256 + threadIdx.x;
-            int64_t p = -1;
+            p[e] = -1;
             if (i < total) {
                 if (cap > 0) {
                     const int64_t sl = (int64_t)((uint32_t)i / (uint32_t)cap);       // total < 2^31
                     const int64_t j = i - sl * cap;
                     const int64_t* slab = slab_of(recv, sl, cap);
-                    if (j < slab_count(slab[0])) p = slab[1 + j];
+                    if (j < slab_count(slab[0])) p[e] = slab[1 + j];
                 } else {
-                    p = recv[i];
+                    p[e] = recv[i];
                 }
             }
+        }
+#pragma unroll
+        for (int e = 0; e < EPT; ++e) {
             src[e] = nullptr;
-            if (p >= 0) {
+            if (p[e] >= 0) {
                 int slot;
                 int64_t row;
-                unpack_payload(p, F, slot, row);
-                if (!local_rows || row < local_rows[slot]) src[e] = rows[slot] + row * (4 * U);
+                unpack_payload(p[e], F, slot, row);
+                if (!local_rows || row < local_rows[slot]) src[e] = rows[slot] + row * ld;
             }
         }
 #pragma unroll
         for (int e = 0; e < EPT; ++e)
 #pragma unroll
-            for (int u = 0; u < U; ++u) v[e][u] = src[e] ? src[e][4 * u] : 0.f;     // EPT * U independent reads in flight per lane
+            for (int u = 0; u < U; ++u) v[e][u] = src[e] ? src[e][4 * u] : 0.f;     // EPT * U independent 4-byte reads in flight per lane
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
             const int64_t i = i0 + e * 256 + threadIdx.x;
             if (i < total) {
 #pragma unroll
-                for (int u = 0; u < U; ++u) out[i * U + u] = v[e][u];              // every word is written (0.0 where there is no row)
+                for (int u = 0; u < U; ++u) out[i * U + u] = v[e][u];
             }
         }
     }
 }
 
-// linear_finish_k with blockIdx.y = the unit: the same quads, the same adds in the same order, over wback[pos * U + unit]
-template <int UFL>
-__global__ __launch_bounds__(256) void linear_finish_units_k(const float* __restrict__ wback, int64_t n_back, int U, const int64_t* __restrict__ inv,
-                                                             int64_t sb, int64_t sf, int F, const float* __restrict__ bias, int64_t B,
-                                                             float* __restrict__ out, int64_t out_ld) {
+// Requester side: FOUR lanes per sample and unit (blockIdx.y = the unit), lane c reads the weights of fields 4 j + c through the inverse
+// positions, and the quad adds them up in FIELD order through quad broadcasts -- linear_onehot4_k's sum (linear_cross.hip), add for add:
+// acc = 0; acc += v_f for f = 0..F-1 (a pruned entry adds 0.0f); r = acc + (bias ? bias[unit] : 0.0f).
+// ONE: U == 1 known at compile time (the flagship DeepFM term): no multiply in the address of a weight.
+template <int UFL, bool ONE>
+__global__ __launch_bounds__(256) void linear_finish_k(const float* __restrict__ wback, int64_t n_back, int units, const int64_t* __restrict__ inv,
+                                                       int64_t sb, int64_t sf, int F, const float* __restrict__ bias, int64_t B,
+                                                       float* __restrict__ out, int64_t out_ld) {
     const int c = threadIdx.x & 3;
-    const int unit = blockIdx.y;
+    const int U = ONE ? 1 : units;
+    const int unit = ONE ? 0 : (int)blockIdx.y;
     const int64_t per_grid = ((int64_t)gridDim.x * blockDim.x) >> 2;
     for (int64_t b0 = ((int64_t)blockIdx.x * blockDim.x) >> 2; b0 < B; b0 += per_grid) {      // (block-uniform trip count: the DPP reads see live lanes)
         const int64_t b = b0 + (threadIdx.x >> 2);
@@ -195,13 +110,17 @@ __global__ __launch_bounds__(256) void linear_finish_units_k(const float* __rest
     }
 }
 
-// one lane per (entry, unit): consecutive lanes write the U consecutive floats of a position; `send` was zero-filled by the C entry
-__global__ __launch_bounds__(256) void linear_grad_units_k(const float* __restrict__ g, int64_t g_ld, int U, const int64_t* __restrict__ inv,
-                                                           int64_t sb, int64_t sf, int F, int64_t n /* B * F * U */, float* __restrict__ send,
-                                                           int64_t n_send) {
+// Requester side of the backward, one lane per (entry, unit): entry (b, f) writes d logit[b, u] where its weights came back from --
+// consecutive lanes write the U consecutive floats of a position.  Training lookups are never de-duplicated: every position has exactly
+// one writer (plain stores); `send` was zero-filled by the C entry.  ONE: as in linear_finish_k.
+template <bool ONE>
+__global__ __launch_bounds__(256) void linear_grad_k(const float* __restrict__ g, int64_t g_ld, int units, const int64_t* __restrict__ inv,
+                                                     int64_t sb, int64_t sf, int F, int64_t n /* B * F * U */, float* __restrict__ send,
+                                                     int64_t n_send) {
+    const int U = ONE ? 1 : units;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const uint32_t e = (uint32_t)i / (uint32_t)U;                    // n < 2^31
-        const int u = (int)((uint32_t)i - e * (uint32_t)U);
+        const uint32_t e = ONE ? (uint32_t)i : (uint32_t)i / (uint32_t)U;                    // n < 2^31
+        const int u = ONE ? 0 : (int)((uint32_t)i - e * (uint32_t)U);
         const int64_t b = (int64_t)(e / (uint32_t)F);
         const int f = (int)(e - (uint32_t)b * (uint32_t)F);
         const int64_t pos = inv[b * sb + (int64_t)f * sf];
@@ -386,72 +305,17 @@ __global__ __launch_bounds__(256) void bags_linear_grad_k(const float* __restric
 
 using namespace dir;
 
-extern "C" int dir_shard_linear_gather_f32(const float* const* rows, int64_t row_ld, const int64_t* local_rows, int F, const int64_t* recv,
-                                           int P, int64_t cap, int64_t n, float* out, dir_stream_t stream) {
-    const char* name = "dir_shard_linear_gather_f32";
-    DIR_CHECK_ARG(F > 0 && row_ld >= 1, "%s: F=%d row_ld=%lld", name, F, (long long)row_ld);
-    int64_t total;
-    if (cap > 0) {                                             // the P fixed-capacity slabs
-        if (int rc = check_owners(name, P)) return rc;
-        DIR_CHECK_ARG((int64_t)P * cap < ((int64_t)1 << 31), "%s: cap=%lld (P*cap < 2^31)", name, (long long)cap);
-        total = (int64_t)P * cap;
-    } else {                                                   // a flat payload of n words
-        DIR_CHECK_ARG(cap == 0, "%s: cap=%lld (> 0: slabs, 0: a flat payload of n words)", name, (long long)cap);
-        DIR_CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31), "%s: n=%lld (0 <= n < 2^31)", name, (long long)n);
-        total = n;
-    }
-    if (total == 0) return DIR_OK;
-    DIR_CHECK_ARG(rows && recv && out, "%s: null pointer", name);
-    constexpr int EPT = 4;
-    dim3 grid(grid_for((total + 256 * EPT - 1) / (256 * EPT)));
-    hipLaunchKernelGGL((linear_gather_k<EPT>), grid, dim3(256), 0, as_stream(stream), rows, row_ld, local_rows, F, recv, cap, total, out);
-    DIR_CHECK_LAUNCH(name);
-    return DIR_OK;
-}
-
-extern "C" int dir_shard_linear_finish_f32(const float* wback, int64_t n_back, const int64_t* inv, int64_t stride_b, int64_t stride_f, int F,
-                                           const float* bias, int64_t B, float* out, int64_t out_ld, dir_stream_t stream) {
-    const char* name = "dir_shard_linear_finish_f32";
-    DIR_CHECK_ARG(F > 0 && B >= 0, "%s: F=%d B=%lld", name, F, (long long)B);
-    DIR_CHECK_ARG(n_back >= 0 && n_back < ((int64_t)1 << 31), "%s: n_back=%lld (0 <= n_back < 2^31)", name, (long long)n_back);
-    DIR_CHECK_ARG(out_ld >= 1, "%s: out_ld=%lld", name, (long long)out_ld);
-    if (B == 0) return DIR_OK;
-    DIR_CHECK_ARG(inv && out && (wback || n_back == 0), "%s: null pointer", name);
-    hipLaunchKernelGGL((linear_finish_k<7>), dim3(grid_for((B + 63) / 64)), dim3(256), 0, as_stream(stream), wback, n_back, inv, stride_b,
-                       stride_f, F, bias, B, out, out_ld);
-    DIR_CHECK_LAUNCH(name);
-    return DIR_OK;
-}
-
-extern "C" int dir_shard_linear_grad_f32(const float* g, int64_t g_ld, const int64_t* inv, int64_t stride_b, int64_t stride_f, int F, int64_t B,
-                                         float* send, int64_t n_send, dir_stream_t stream) {
-    const char* name = "dir_shard_linear_grad_f32";
-    DIR_CHECK_ARG(F > 0 && B >= 0 && B * F < ((int64_t)1 << 31), "%s: F=%d B=%lld (B*F < 2^31)", name, F, (long long)B);
-    DIR_CHECK_ARG(n_send >= 0 && n_send < ((int64_t)1 << 31), "%s: n_send=%lld (0 <= n_send < 2^31)", name, (long long)n_send);
-    DIR_CHECK_ARG(g_ld >= 1, "%s: g_ld=%lld", name, (long long)g_ld);
-    DIR_CHECK_ARG(send || n_send == 0, "%s: null pointer", name);
-    DIR_CHECK_ARG(B == 0 || (g && inv), "%s: null pointer", name);
-    hipStream_t st = as_stream(stream);
-    if (n_send > 0 && hipMemsetAsync(send, 0, (size_t)n_send * sizeof(float), st) != hipSuccess)
-        return fail(DIR_E_HIP, "%s: zero-fill of send failed", name);
-    if (B == 0 || n_send == 0) return DIR_OK;
-    const int64_t n = B * F;
-    hipLaunchKernelGGL(linear_grad_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, g, g_ld, inv, stride_b, stride_f, F, n, send, n_send);
-    DIR_CHECK_LAUNCH(name);
-    return DIR_OK;
-}
-
-// ---- units = U (ESMM_W_D's two linear models over one id exchange) ---------------------------------------------------------------------
+// ---- one body per step: the plain entry is the units entry at units = 1 (the gather's plain entry brings its own row stride) --------------
 static int check_units(const char* name, int units) {
     DIR_CHECK_ARG(units >= 1 && units <= DIR_MAX_UNITS, "%s: units=%d (1 <= units <= %d)", name, units, DIR_MAX_UNITS);
     return DIR_OK;
 }
 
-extern "C" int dir_shard_linear_gather_units_f32(const float* const* rows, int units, const int64_t* local_rows, int F, const int64_t* recv,
-                                                 int P, int64_t cap, int64_t n, float* out, dir_stream_t stream) {
-    const char* name = "dir_shard_linear_gather_units_f32";
+static int linear_gather(const char* name, const float* const* rows, int units, int64_t row_ld, const int64_t* local_rows, int F,
+                         const int64_t* recv, int P, int64_t cap, int64_t n, float* out, dir_stream_t stream) {
     DIR_CHECK_ARG(F > 0, "%s: F=%d", name, F);
     if (int rc = check_units(name, units)) return rc;
+    DIR_CHECK_ARG(row_ld >= 1, "%s: row_ld=%lld", name, (long long)row_ld);
     int64_t total;
     if (cap > 0) {                                             // the P fixed-capacity slabs
         if (int rc = check_owners(name, P)) return rc;
@@ -464,36 +328,37 @@ extern "C" int dir_shard_linear_gather_units_f32(const float* const* rows, int u
     }
     if (total == 0) return DIR_OK;
     DIR_CHECK_ARG(rows && recv && out, "%s: null pointer", name);
-    constexpr int EPT = 2;
-    dim3 grid(grid_for((total + 256 * EPT - 1) / (256 * EPT)));
+    const int ept = units == 1 ? 4 : 2;                        // entries per lane: ept * units reads in flight
+    dim3 grid(grid_for((total + 256 * ept - 1) / (256 * ept)));
     hipStream_t st = as_stream(stream);
-#define DIR_LGU(UN) \
-    case UN: hipLaunchKernelGGL((linear_gather_units_k<UN, EPT>), grid, dim3(256), 0, st, rows, local_rows, F, recv, cap, total, out); break;
-    switch (units) { DIR_LGU(1) DIR_LGU(2) DIR_LGU(3) DIR_LGU(4) DIR_LGU(5) DIR_LGU(6) DIR_LGU(7) DIR_LGU(8) }
-#undef DIR_LGU
+#define DIR_LG(UN, EPT) \
+    case UN: hipLaunchKernelGGL((linear_gather_k<UN, EPT>), grid, dim3(256), 0, st, rows, row_ld, local_rows, F, recv, cap, total, out); break;
+    switch (units) { DIR_LG(1, 4) DIR_LG(2, 2) DIR_LG(3, 2) DIR_LG(4, 2) DIR_LG(5, 2) DIR_LG(6, 2) DIR_LG(7, 2) DIR_LG(8, 2) }
+#undef DIR_LG
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
 }
 
-extern "C" int dir_shard_linear_finish_units_f32(const float* wback, int64_t n_back, int units, const int64_t* inv, int64_t stride_b,
-                                                 int64_t stride_f, int F, const float* bias, int64_t B, float* out, int64_t out_ld,
-                                                 dir_stream_t stream) {
-    const char* name = "dir_shard_linear_finish_units_f32";
+static int linear_finish(const char* name, const float* wback, int64_t n_back, int units, const int64_t* inv, int64_t stride_b, int64_t stride_f,
+                         int F, const float* bias, int64_t B, float* out, int64_t out_ld, dir_stream_t stream) {
     DIR_CHECK_ARG(F > 0 && B >= 0, "%s: F=%d B=%lld", name, F, (long long)B);
     if (int rc = check_units(name, units)) return rc;
     DIR_CHECK_ARG(n_back >= 0 && n_back * units < ((int64_t)1 << 31), "%s: n_back=%lld (0 <= n_back, n_back*units < 2^31)", name, (long long)n_back);
     DIR_CHECK_ARG(out_ld >= units, "%s: out_ld=%lld (>= units)", name, (long long)out_ld);
     if (B == 0) return DIR_OK;
     DIR_CHECK_ARG(inv && out && (wback || n_back == 0), "%s: null pointer", name);
-    hipLaunchKernelGGL((linear_finish_units_k<7>), dim3(grid_for((B + 63) / 64), (unsigned)units), dim3(256), 0, as_stream(stream), wback, n_back,
-                       units, inv, stride_b, stride_f, F, bias, B, out, out_ld);
+    const dim3 grid(grid_for((B + 63) / 64), (unsigned)units);
+    hipStream_t st = as_stream(stream);
+    if (units == 1)
+        hipLaunchKernelGGL((linear_finish_k<7, true>), grid, dim3(256), 0, st, wback, n_back, units, inv, stride_b, stride_f, F, bias, B, out, out_ld);
+    else
+        hipLaunchKernelGGL((linear_finish_k<7, false>), grid, dim3(256), 0, st, wback, n_back, units, inv, stride_b, stride_f, F, bias, B, out, out_ld);
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
 }
 
-extern "C" int dir_shard_linear_grad_units_f32(const float* g, int64_t g_ld, int units, const int64_t* inv, int64_t stride_b, int64_t stride_f,
-                                               int F, int64_t B, float* send, int64_t n_send, dir_stream_t stream) {
-    const char* name = "dir_shard_linear_grad_units_f32";
+static int linear_grad(const char* name, const float* g, int64_t g_ld, int units, const int64_t* inv, int64_t stride_b, int64_t stride_f, int F,
+                       int64_t B, float* send, int64_t n_send, dir_stream_t stream) {
     DIR_CHECK_ARG(F > 0 && B >= 0, "%s: F=%d B=%lld", name, F, (long long)B);
     if (int rc = check_units(name, units)) return rc;
     DIR_CHECK_ARG(B * F * units < ((int64_t)1 << 31), "%s: B=%lld (B*F*units < 2^31)", name, (long long)B);
@@ -507,10 +372,44 @@ extern "C" int dir_shard_linear_grad_units_f32(const float* g, int64_t g_ld, int
         return fail(DIR_E_HIP, "%s: zero-fill of send failed", name);
     if (B == 0 || n_send == 0) return DIR_OK;
     const int64_t n = B * F * units;
-    hipLaunchKernelGGL(linear_grad_units_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, g, g_ld, units, inv, stride_b, stride_f, F, n, send,
-                       n_send);
+    const dim3 grid(grid_for((n + 255) / 256));
+    if (units == 1)
+        hipLaunchKernelGGL(linear_grad_k<true>, grid, dim3(256), 0, st, g, g_ld, units, inv, stride_b, stride_f, F, n, send, n_send);
+    else
+        hipLaunchKernelGGL(linear_grad_k<false>, grid, dim3(256), 0, st, g, g_ld, units, inv, stride_b, stride_f, F, n, send, n_send);
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
+}
+
+extern "C" int dir_shard_linear_gather_f32(const float* const* rows, int64_t row_ld, const int64_t* local_rows, int F, const int64_t* recv,
+                                           int P, int64_t cap, int64_t n, float* out, dir_stream_t stream) {
+    return linear_gather("dir_shard_linear_gather_f32", rows, 1, row_ld, local_rows, F, recv, P, cap, n, out, stream);
+}
+
+extern "C" int dir_shard_linear_gather_units_f32(const float* const* rows, int units, const int64_t* local_rows, int F, const int64_t* recv,
+                                                 int P, int64_t cap, int64_t n, float* out, dir_stream_t stream) {
+    return linear_gather("dir_shard_linear_gather_units_f32", rows, units, (int64_t)4 * units, local_rows, F, recv, P, cap, n, out, stream);
+}
+
+extern "C" int dir_shard_linear_finish_f32(const float* wback, int64_t n_back, const int64_t* inv, int64_t stride_b, int64_t stride_f, int F,
+                                           const float* bias, int64_t B, float* out, int64_t out_ld, dir_stream_t stream) {
+    return linear_finish("dir_shard_linear_finish_f32", wback, n_back, 1, inv, stride_b, stride_f, F, bias, B, out, out_ld, stream);
+}
+
+extern "C" int dir_shard_linear_finish_units_f32(const float* wback, int64_t n_back, int units, const int64_t* inv, int64_t stride_b,
+                                                 int64_t stride_f, int F, const float* bias, int64_t B, float* out, int64_t out_ld,
+                                                 dir_stream_t stream) {
+    return linear_finish("dir_shard_linear_finish_units_f32", wback, n_back, units, inv, stride_b, stride_f, F, bias, B, out, out_ld, stream);
+}
+
+extern "C" int dir_shard_linear_grad_f32(const float* g, int64_t g_ld, const int64_t* inv, int64_t stride_b, int64_t stride_f, int F, int64_t B,
+                                         float* send, int64_t n_send, dir_stream_t stream) {
+    return linear_grad("dir_shard_linear_grad_f32", g, g_ld, 1, inv, stride_b, stride_f, F, B, send, n_send, stream);
+}
+
+extern "C" int dir_shard_linear_grad_units_f32(const float* g, int64_t g_ld, int units, const int64_t* inv, int64_t stride_b, int64_t stride_f,
+                                               int F, int64_t B, float* send, int64_t n_send, dir_stream_t stream) {
+    return linear_grad("dir_shard_linear_grad_units_f32", g, g_ld, units, inv, stride_b, stride_f, F, B, send, n_send, stream);
 }
 
 // ---- the term over multi-hot bags ---------------------------------------------------------------------------------------------------

@@ -2289,51 +2289,59 @@ def shard_bags_grad(g, P, pos, mask, denom, B, F, slot_comb, comb, cap_b, send):
 
 
 def shard_linear_gather(lin_ts, recv, P, cap, out):
-    """Owner side of the sharded linear term (include/dir_hip.h: dir_shard_linear_gather_f32): lin_ts = this rank's packed linear rows
-    (TableSet.ftrl_rows' layout), recv = the received payload -- cap > 0: the P fixed-capacity slabs [P*(cap+1)] int64, cap = None: a flat
-    payload [n] -- -> out [P*cap] / [n] fp32, one weight per payload word (0.0 behind a header and for pruned words: every word is
-    written)."""
+    """Owner side of the sharded linear term (include/dir_hip.h: dir_shard_linear_gather_units_f32): lin_ts = this rank's packed linear rows
+    -- U = lin_ts.units first-order terms per row (default 1: TableSet.ftrl_rows' layout), rows of 4 U floats --, recv = the received
+    payload -- cap > 0: the P fixed-capacity slabs [P*(cap+1)] int64, cap = None: a flat payload [n] -- -> out [P*cap*U] / [n*U] fp32, U
+    weights per payload word (0.0 behind a header and for pruned words: every word is written)."""
     _dev(recv, torch.int64, "recv")
     _dev(out, torch.float32, "out")
-    if lin_ts.K != 1 or lin_ts.ld == lin_ts.K:
-        raise ValueError("shard_linear_gather: packed linear training rows (TableSet.ftrl_rows)")
+    U = int(getattr(lin_ts, "units", 1))
+    if lin_ts.K != 1 or lin_ts.ld != 4 * U:
+        raise ValueError("shard_linear_gather: packed linear training rows of 4 * units floats (TableSet.ftrl_rows)")
     n = recv.numel()
-    if not recv.is_contiguous() or not out.is_contiguous() or (cap and n < P * (cap + 1)) or out.numel() < (P * cap if cap else n):
-        raise ValueError("shard_linear_gather: recv [P*(cap+1)] slabs (or a flat payload), out one contiguous float per payload word")
-    _lib.check(_lib.load().dir_shard_linear_gather_f32(_ptr(lin_ts._ptrs), lin_ts.ld, _ptr(lin_ts.vocab_dev), lin_ts.F, _ptr(recv), P,
-                                                       cap or 0, 0 if cap else n, _ptr(out), _stream()))
+    if not recv.is_contiguous() or not out.is_contiguous() or (cap and n < P * (cap + 1)) or out.numel() < (P * cap if cap else n) * U:
+        raise ValueError("shard_linear_gather: recv [P*(cap+1)] slabs (or a flat payload), out `units` contiguous floats per payload word")
+    _lib.check(_lib.load().dir_shard_linear_gather_units_f32(_ptr(lin_ts._ptrs), U, _ptr(lin_ts.vocab_dev), lin_ts.F, _ptr(recv), P,
+                                                             cap or 0, 0 if cap else n, _ptr(out), _stream()))
     return out
 
 
-def shard_linear_finish(wback, inv2d, bias=None, out=None):
-    """Requester side (dir_shard_linear_finish_f32): wback [n] = the weights as the exchange returned them, inv2d [B, F] int64 (any
-    strides; < 0: pruned) -> out [B, 1] = sum_f wback[inv2d[b, f]] + bias, in ops.linear_logit's order and arithmetic (bit for bit)."""
+def shard_linear_finish(wback, inv2d, bias=None, out=None, units=1):
+    """Requester side (dir_shard_linear_finish_units_f32): wback [n*U] = the weights as the exchange returned them (U = units per
+    position), inv2d [B, F] int64 (any strides; < 0: pruned) -> out [B, U], column u = sum_f wback[inv2d[b, f]*U + u] + bias[u], in
+    ops.linear_logit's order and arithmetic (bit for bit)."""
     _dev(wback, torch.float32, "wback")
     _dev(inv2d, torch.int64, "inv")
     B, F = inv2d.shape
+    U = int(units)
     if out is None:
-        out = torch.empty((B, 1), dtype=torch.float32, device=wback.device)
+        out = torch.empty((B, U), dtype=torch.float32, device=wback.device)
     _dev(out, torch.float32, "out")
     if bias is not None:
         _dev(bias, torch.float32, "bias")
-    if not wback.is_contiguous() or out.shape[0] != B:
-        raise ValueError("shard_linear_finish: wback contiguous, out [B, 1]")
-    _lib.check(_lib.load().dir_shard_linear_finish_f32(_ptr(wback), wback.numel(), _ptr(inv2d), inv2d.stride(0), inv2d.stride(1), F, _ptr(bias),
-                                                       B, _ptr(out), out.stride(0) if B > 1 else 1, _stream()))
+        if bias.numel() != U or not bias.is_contiguous():
+            raise ValueError("shard_linear_finish: bias [units], contiguous")
+    if not wback.is_contiguous() or wback.numel() % U or out.shape != (B, U) or (B and U > 1 and out.stride(1) != 1):
+        raise ValueError("shard_linear_finish: wback contiguous [n*units], out [B, units]")
+    _lib.check(_lib.load().dir_shard_linear_finish_units_f32(_ptr(wback), wback.numel() // U, U, _ptr(inv2d), inv2d.stride(0), inv2d.stride(1),
+                                                             F, _ptr(bias), B, _ptr(out), out.stride(0) if B > 1 else U, _stream()))
     return out
 
 
-def shard_linear_grad(g, inv2d, send):
-    """Requester side of the linear term's backward (dir_shard_linear_grad_f32): g [B, 1] (or [B]) = d loss / d lin -> send [n] zero-filled,
-    then send[inv2d[b, f]] = g[b] for every entry with inv2d >= 0."""
+def shard_linear_grad(g, inv2d, send, units=1):
+    """Requester side of the linear term's backward (dir_shard_linear_grad_units_f32): g [B, U] (U = units; [B] at U = 1) = d loss / d lin
+    -> send [n*U] zero-filled, then send[inv2d[b, f]*U + u] = g[b, u] for every entry with inv2d >= 0."""
     _dev(g, torch.float32, "g")
     _dev(inv2d, torch.int64, "inv")
     _dev(send, torch.float32, "send")
     B, F = inv2d.shape
-    if g.numel() != B or not send.is_contiguous():
-        raise ValueError("shard_linear_grad: g [B, 1], send a contiguous buffer")
-    _lib.check(_lib.load().dir_shard_linear_grad_f32(_ptr(g), g.stride(0) if B > 1 else 1, _ptr(inv2d), inv2d.stride(0), inv2d.stride(1), F, B,
-                                                     _ptr(send), send.numel(), _stream()))
+    U = int(units)
+    if U == 1 and g.dim() == 1:
+        g = g.unsqueeze(1)
+    if g.shape != (B, U) or (B and U > 1 and g.stride(1) != 1) or not send.is_contiguous() or send.numel() % U:
+        raise ValueError("shard_linear_grad: g [B, units] with unit inner stride, send a contiguous [n*units] buffer")
+    _lib.check(_lib.load().dir_shard_linear_grad_units_f32(_ptr(g), g.stride(0) if B > 1 else U, U, _ptr(inv2d), inv2d.stride(0),
+                                                           inv2d.stride(1), F, B, _ptr(send), send.numel() // U, _stream()))
     return send
 
 
@@ -2472,56 +2480,6 @@ def rows_scatter_sum_side(idx, vals, side, side_div, R, out=None, out_side=None,
     _lib.check(lib.dir_rows_scatter_sum_side_f32(_ptr(idx), _ptr(vals), ld, _ptr(side), side_ld, side_div, n, K, U, R, _ptr(out), _ptr(out_side),
                                                  ctypes.c_void_p(ws.data_ptr() + (-ws.data_ptr()) % 256), need, _stream()))
     return out, out_side
-
-
-def shard_linear_gather_units(lin_ts, recv, P, cap, out):
-    """shard_linear_gather over rows of lin_ts.units first-order terms (dir_shard_linear_gather_units_f32): -> out [P*cap*U] / [n*U],
-    U floats per payload word; every word is written."""
-    _dev(recv, torch.int64, "recv")
-    _dev(out, torch.float32, "out")
-    U = int(getattr(lin_ts, "units", 1))
-    if lin_ts.K != 1 or lin_ts.ld != 4 * U:
-        raise ValueError("shard_linear_gather_units: packed rows of 4 * units floats")
-    n = recv.numel()
-    if not recv.is_contiguous() or not out.is_contiguous() or (cap and n < P * (cap + 1)) or out.numel() < (P * cap if cap else n) * U:
-        raise ValueError("shard_linear_gather_units: recv [P*(cap+1)] slabs (or a flat payload), out `units` contiguous floats per payload word")
-    _lib.check(_lib.load().dir_shard_linear_gather_units_f32(_ptr(lin_ts._ptrs), U, _ptr(lin_ts.vocab_dev), lin_ts.F, _ptr(recv), P,
-                                                             cap or 0, 0 if cap else n, _ptr(out), _stream()))
-    return out
-
-
-def shard_linear_finish_units(wback, inv2d, U, bias=None, out=None):
-    """Requester side (dir_shard_linear_finish_units_f32): wback [n*U], inv2d [B, F] -> out [B, U], column u = sum_f wback[inv2d[b, f]*U + u]
-    + bias[u] in ops.linear_logit's order and arithmetic."""
-    _dev(wback, torch.float32, "wback")
-    _dev(inv2d, torch.int64, "inv")
-    B, F = inv2d.shape
-    if out is None:
-        out = torch.empty((B, U), dtype=torch.float32, device=wback.device)
-    _dev(out, torch.float32, "out")
-    if bias is not None:
-        _dev(bias, torch.float32, "bias")
-        if bias.numel() != U or not bias.is_contiguous():
-            raise ValueError("shard_linear_finish_units: bias [units], contiguous")
-    if not wback.is_contiguous() or wback.numel() % U or out.shape != (B, U) or (B and out.stride(1) != 1):
-        raise ValueError("shard_linear_finish_units: wback contiguous [n*units], out [B, units]")
-    _lib.check(_lib.load().dir_shard_linear_finish_units_f32(_ptr(wback), wback.numel() // U, U, _ptr(inv2d), inv2d.stride(0), inv2d.stride(1),
-                                                             F, _ptr(bias), B, _ptr(out), out.stride(0) if B > 1 else U, _stream()))
-    return out
-
-
-def shard_linear_grad_units(g, inv2d, U, send):
-    """Requester side of the backward (dir_shard_linear_grad_units_f32): g [B, U] -> send [n*U] zero-filled, then
-    send[inv2d[b, f]*U + u] = g[b, u]."""
-    _dev(g, torch.float32, "g")
-    _dev(inv2d, torch.int64, "inv")
-    _dev(send, torch.float32, "send")
-    B, F = inv2d.shape
-    if g.shape != (B, U) or (B and g.stride(1) != 1) or not send.is_contiguous() or send.numel() % U:
-        raise ValueError("shard_linear_grad_units: g [B, units] with unit inner stride, send a contiguous [n*units] buffer")
-    _lib.check(_lib.load().dir_shard_linear_grad_units_f32(_ptr(g), g.stride(0) if B > 1 else U, U, _ptr(inv2d), inv2d.stride(0),
-                                                           inv2d.stride(1), F, B, _ptr(send), send.numel() // U, _stream()))
-    return send
 
 
 def _lin_combiner(combiner):

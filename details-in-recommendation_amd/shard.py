@@ -67,7 +67,7 @@ _HOST_STAGED = os.environ.get("DIR_SHARD_HOST_STAGED") == "1"
 MIN_SLICE_SIZE = 64 << 20     # deepFM.py:167
 MAX_GROUPS = 16               # include/dir_hip.h: dir_shard_finish_groups_f32
 MAX_ROW_FLOATS = 256          # the widest row the sorted Adagrad covers (64 lanes x 16 bytes)
-MAX_UNITS = 8                 # include/dir_hip.h: dir_shard_linear_gather_units_f32
+MAX_UNITS = 8                 # first-order terms per row (include/dir_hip.h: 1 <= units <= 8)
 
 
 def div_range(vocab, P, rank):
@@ -162,7 +162,7 @@ class HipBackend:
         self.parts_dev, self.first_dev = parts_dev, first_dev
         self._back = None
         self._back_key = None         # rows_as_tables' key of the exact path's last row buffer
-        self.lin_ts, self._ftrl = None, None          # attach_linear
+        self.lin_ts, self._ftrl, self.U = None, None, 1      # attach_linear
 
     # ---- variable-size (exact) path -----------------------------------------------------------------------
     def bucket(self, flat_ids):
@@ -296,8 +296,9 @@ class HipBackend:
 
     # ---- the first-order (linear) term, co-located with the embedding rows (ShardedTables.attach_linear) -------------
     def attach_linear(self, rows, arena):
-        """rows[f]: this rank's packed [local rows, 4] = [w | n | z | -] blocks of one arena (TableSet.ftrl_rows' layout)."""
-        U = rows[0].shape[1] // 4                       # units > 1: U blocks [w | n | z | -] per row; the views below are unit 0's
+        """rows[f]: this rank's packed [local rows, 4 U] rows of one arena: U blocks [w | n | z | -], one per first-order term (unit) of
+        the row (U = 1: TableSet.ftrl_rows' layout).  The four steps below carry U floats per entry; the views here are unit 0's."""
+        U = self.U = rows[0].shape[1] // 4
         ts = ops.TableSet([r[:, 0:1] for r in rows], ld=4 * U)
         ts.accums = [r[:, 1:2] for r in rows]
         ts.linears = [r[:, 2:3] for r in rows]
@@ -305,20 +306,21 @@ class HipBackend:
         self.lin_ts, self._ftrl = ts, None
 
     def linear_gather(self, recv, cap, out):
-        """Owner: one weight per received payload word (cap: the slab capacity, None: recv is a flat payload); every word of out is written."""
+        """Owner: out[i*U + u] = unit u's weight of received payload word i (cap: the slab capacity, None: recv is a flat payload); every
+        word of out is written."""
         ops.shard_linear_gather(self.lin_ts, recv, self.P, cap, out)
 
     def linear_finish(self, wback, inv2d, bias, out):
-        """Requester: out [Bc, 1] = sum_f wback[inv2d[b, f]] + bias, ops.linear_logit's sum bit for bit."""
-        ops.shard_linear_finish(wback, inv2d, bias, out)
+        """Requester: out [Bc, U], column u = sum_f wback[inv2d[b, f]*U + u] + bias[u], ops.linear_logit's sum bit for bit."""
+        ops.shard_linear_finish(wback, inv2d, bias, out, units=self.U)
 
     def linear_grad(self, g, inv2d, send):
-        """Requester, backward: send zero-filled, then send[inv2d[b, f]] = g[b]."""
-        ops.shard_linear_grad(g, inv2d, send)
+        """Requester, backward: send zero-filled, then send[inv2d[b, f]*U + u] = g[b, u]."""
+        ops.shard_linear_grad(g, inv2d, send, units=self.U)
 
     def apply_ftrl(self, payload, grad, lr, l1, l2, sorted_by=None):
-        """Owner, backward: the sorted FTRL over the payload it kept; sorted_by = the Adagrad optimiser that has just sorted the same
-        payload (apply_adagrad): its sorted pairs are reused and the second key pass and sort are skipped."""
+        """Owner, backward: the sorted FTRL over the payload it kept, grad [n, U] in payload order; sorted_by = the Adagrad optimiser that
+        has just sorted the same payload (apply_adagrad): its sorted pairs are reused and the second key pass and sort are skipped."""
         self._ftrl_opt(lr, l1, l2).step_payload(payload, grad, sorted_by=sorted_by)
 
     def _ftrl_opt(self, lr, l1, l2):
@@ -330,23 +332,6 @@ class HipBackend:
     def ftrl_dense(self, w, accum, linear, grad, lr, l1, l2):
         """FTRL step of a replicated dense variable (the linear bias) with its summed gradient."""
         ops.ftrl_dense_(w, accum, linear, grad, lr, l1, l2)
-
-    # ---- ... with units = U > 1 terms per row (attach_linear([rows, U])): U floats per payload word -------------------
-    def linear_gather_units(self, recv, cap, out):
-        """Owner: out[i*U + u] = unit u's weight of payload word i (slab or flat form); every word of out is written."""
-        ops.shard_linear_gather_units(self.lin_ts, recv, self.P, cap, out)
-
-    def linear_finish_units(self, wback, inv2d, U, bias, out):
-        """Requester: out [Bc, U], column u = sum_f wback[inv2d[b, f]*U + u] + bias[u], ops.linear_logit's sum bit for bit."""
-        ops.shard_linear_finish_units(wback, inv2d, U, bias, out)
-
-    def linear_grad_units(self, g, inv2d, U, send):
-        """Requester, backward: send zero-filled, then send[inv2d[b, f]*U + u] = g[b, u]."""
-        ops.shard_linear_grad_units(g, inv2d, U, send)
-
-    def apply_ftrl_units(self, payload, grad, lr, l1, l2, sorted_by=None):
-        """Owner, backward: apply_ftrl over rows of U units; grad [n, U] in payload order."""
-        self._ftrl_opt(lr, l1, l2).step_payload_units(payload, grad, sorted_by=sorted_by)
 
     # ---- ... over multi-hot bags: it rides on the bag lookup (lookup_bags(want_lin=True), lookup_bags_train(with_linear=True)) ------
     def bags_linear_pool(self, recv, cap_e, cap_b, out):
@@ -725,9 +710,6 @@ class ShardedTables:
             rows.append(blk)
             off += v * 4 * U
         self.lin_rows, self._lin_arena, self.U = rows, arena, U
-        if U > 1 and not hasattr(self.backend, "linear_gather_units"):
-            raise NotImplementedError("attach_linear: this backend has no first-order term with units > 1 (linear_gather_units / "
-                                      "_finish_units / _grad_units, apply_ftrl_units)")
         attach = getattr(self.backend, "attach_linear", None)
         if attach is not None:
             attach(rows, arena)
@@ -809,7 +791,7 @@ class ShardedTables:
             t = td.cpu()
         return [int(v) for v in t]
 
-    # ---- the steps that have a grouped / units form: today's backend call at G = 1 / U = 1, the new one otherwise ----------
+    # ---- the steps that have a grouped form: today's backend call at G = 1, the grouped one otherwise ----------------------
     def _new_out(self, B, device):
         """The result buffer(s) of a lookup: [B, F*K], or a tuple of G of them over row groups."""
         if self.G == 1:
@@ -820,24 +802,6 @@ class ShardedTables:
         """Row groups: the finish pass of samples [s, e) (None: all) from `back` through inv2d into the G outputs.  -> (out, None)"""
         self.backend.finish_groups(back, inv2d, self.K, list(out) if s is None else [o[s:e] for o in out])
         return out, None
-
-    def _lin_gather(self, recv, cap, out):
-        be = self.backend
-        return be.linear_gather(recv, cap, out) if self.U == 1 else be.linear_gather_units(recv, cap, out)
-
-    def _lin_finish(self, wback, inv2d, bias, out):
-        be = self.backend
-        return be.linear_finish(wback, inv2d, bias, out) if self.U == 1 else be.linear_finish_units(wback, inv2d, self.U, bias, out)
-
-    def _lin_grad(self, g, inv2d, send):
-        be = self.backend
-        return be.linear_grad(g, inv2d, send) if self.U == 1 else be.linear_grad_units(g, inv2d, self.U, send)
-
-    def _lin_ftrl(self, payload, grad, sorted_by):
-        be, hp = self.backend, self._lin_hp
-        if self.U == 1:
-            return be.apply_ftrl(payload, grad, hp[0], hp[1], hp[2], sorted_by=sorted_by)
-        return be.apply_ftrl_units(payload, grad, hp[0], hp[1], hp[2], sorted_by=sorted_by)
 
     # ---- training: the gradient rows travel the forward's row exchange backwards and the OWNER updates its shard -------
     def enable_training(self, lr, initial_accumulator_value=0.1):
@@ -1045,10 +1009,10 @@ class ShardedTables:
         U = self.U                                       # floats per entry
         n = inv2d.numel()
         lw = torch.empty(recv.numel() * U, dtype=torch.float32, device=recv.device)
-        self._lin_gather(recv, None, lw)
+        self.backend.linear_gather(recv, None, lw)
         lback = torch.empty(n * U, dtype=torch.float32, device=recv.device)
-        self._a2a(lback, lw, sc if U == 1 else [c * U for c in sc], rc if U == 1 else [c * U for c in rc])
-        self._lin_finish(lback, inv2d, lin[1], lin[0])
+        self._a2a(lback, lw, [c * U for c in sc], [c * U for c in rc])
+        self.backend.linear_finish(lback, inv2d, lin[1], lin[0])
 
     def _backward_apply(self, saved, g_emb, g_lin=None, slabs=None):
         """g_lin (lookup_train(with_linear=True)): d loss / d lin [B_local, 1].  Its values go where the weights came back from and travel
@@ -1106,7 +1070,7 @@ class ShardedTables:
                     # the forward's linear buffers carry the gradient back: lrows = what this rank sends, lback = what it receives
                     lrows, lback = plan.lin_buffers(U)
                     if not plan.dedup:                   # (de-duplicated: rows_scatter_sum_side has written lrows[c] above)
-                        self._lin_grad(g_lin[s:e], be.inv2d(plan.inv[c], e - s, self.F, False), lrows[c])
+                        be.linear_grad(g_lin[s:e], be.inv2d(plan.inv[c], e - s, self.F, False), lrows[c])
                     if self._collective():
                         self._a2a(lback[c], lrows[c], None, None)
             # ONE update over all micro-batches (duplicates of a row -- from any chunk, any rank -- are summed before the accumulator
@@ -1117,7 +1081,7 @@ class ShardedTables:
             pay = torch.where(pos.unsqueeze(0) < hdr.unsqueeze(1), slabs[:, 1:], torch.full_like(slabs[:, 1:], -1)).reshape(-1)
             self._owner_step(pay, grecv_l[0] if C == 1 else torch.cat(grecv_l, dim=0))
             if g_lin is not None:
-                self._lin_ftrl(pay, plan.lback_all.view(-1), self.optimizer)
+                be.apply_ftrl(pay, plan.lback_all.view(-1), *self._lin_hp, sorted_by=self.optimizer)
             return
         _, inv, sc, rc, recv = saved[:5]
         n = inv.numel()
@@ -1140,10 +1104,10 @@ class ShardedTables:
         self._owner_step(recv, grecv)
         if g_lin is not None:
             lsend = torch.empty(n * U, dtype=torch.float32, device=dev)
-            self._lin_grad(g_lin, inv.view(-1, self.F), lsend)
+            be.linear_grad(g_lin, inv.view(-1, self.F), lsend)
             lrecv = torch.empty(recv.numel() * U, dtype=torch.float32, device=dev)
-            self._a2a(lrecv, lsend, rc if U == 1 else [c * U for c in rc], sc if U == 1 else [c * U for c in sc])
-            self._lin_ftrl(recv, lrecv, self.optimizer)
+            self._a2a(lrecv, lsend, [c * U for c in rc], [c * U for c in sc])
+            be.apply_ftrl(recv, lrecv, *self._lin_hp, sorted_by=self.optimizer)
 
     # ---- the exact, variable-size lookup (one host read of the split sizes) --------------------------------
     def _exchange_exact(self, ids, lin=None, private=False):
@@ -1255,9 +1219,9 @@ class ShardedTables:
             be.bucket_cap(ids, cap, plan.send[0], plan.inv[0], plan.counts[0], plan.flags[0], plan.ws[0], stat=plan.cstat[0], dedup=dedup)
             be.gather_slabs(plan.recv[0], cap, plan.rows[0])
             if lin is not None:
-                self._lin_gather(plan.recv[0], cap, lrows[0])
+                be.linear_gather(plan.recv[0], cap, lrows[0])
                 if B:
-                    self._lin_finish(lback[0], be.inv2d(plan.inv[0], B, F, dedup), lin[1], lin[0])
+                    be.linear_finish(lback[0], be.inv2d(plan.inv[0], B, F, dedup), lin[1], lin[0])
             if B and consumer is not None:
                 consumer(0, B, plan.back[0], be.inv2d(plan.inv[0], B, F, dedup))
             elif B and self.G > 1:
@@ -1284,7 +1248,7 @@ class ShardedTables:
             if lin is not None:
                 _wait(wl[c])
                 if e > s:
-                    self._lin_finish(lback[c], be.inv2d(plan.inv[c], e - s, F, dedup), lin[1], lin[0][s:e])
+                    be.linear_finish(lback[c], be.inv2d(plan.inv[c], e - s, F, dedup), lin[1], lin[0][s:e])
             if e > s and consumer is not None:
                 consumer(s, e, plan.back[c], be.inv2d(plan.inv[c], e - s, F, dedup))
             elif e > s and self.G > 1:
@@ -1307,7 +1271,7 @@ class ShardedTables:
                 be.gather_slabs(plan.recv[c], cap, plan.rows[c])
                 wr[c] = self._a2a_equal(plan.back[c], plan.rows[c])
                 if lin is not None:
-                    self._lin_gather(plan.recv[c], cap, lrows[c])
+                    be.linear_gather(plan.recv[c], cap, lrows[c])
                     wl[c] = self._a2a_equal(lback[c], lrows[c])
             if c >= 1:
                 with on(c - 1):

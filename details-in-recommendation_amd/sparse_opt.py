@@ -501,40 +501,26 @@ class SparseFtrl(_SortedOpt):
             self._leave_sort(ids, B, sb, sf, ws)
         self._written()
 
-    def _step_payload(self, entry, units, payload, grad, sorted_by):
-        """step_payload (units None: dir_sparse_ftrl_rows_sorted_payload_f32) and step_payload_units (dir_sparse_ftrl_rows_units_...)."""
+    def step_payload(self, payload, grad, sorted_by=None):
+        """Owner side of the sharded linear term's backward (shard.ShardedTables; include/dir_hip.h:
+        dir_sparse_ftrl_rows_units_sorted_payload_f32): payload [n] int64 (local_row * F + slot, < 0 pruned) as received from all ranks,
+        grad [n, U] fp32 in the same order, over packed rows of U = ts.units first-order terms (default 1: TableSet.ftrl_rows, grad [n]).
+        sorted_by: an optimiser whose step_payload has JUST run over the same payload on this stream with the same local vocabularies
+        (the SparseAdagrad of the co-located embedding rows, of any row width): its sorted (row, entry) pairs are read from its
+        workspace and this call skips the key pass and the sort."""
         ts = self.ts
-        U = units or 1
+        U = int(getattr(ts, "units", 1))
+        if not self.packed or ts.ld != 4 * U:
+            raise ValueError("step_payload: packed linear training rows of 4 * units floats (TableSet.ftrl_rows)")
         n = self._check_payload(payload, grad, U, exact=False)
         if n == 0 or self.total_rows == 0:
             return
         lib = _lib.load()
-        ws, need, _ = self._sort_area("SparseFtrl." + entry, lib.dir_sparse_adagrad_sorted_workspace_bytes, n, 1, U)
-        tail = (_ptr(payload), n, _ptr(grad), self.lr, self.l1, self.l2, _ptr(self.row_base), self.total_rows, ws, need,
-                self._sorted_by(entry, sorted_by), _stream())
-        if units is None:
-            _lib.check(lib.dir_sparse_ftrl_rows_sorted_payload_f32(_ptr(ts._ptrs), ts.F, *tail))
-        else:
-            _lib.check(lib.dir_sparse_ftrl_rows_units_sorted_payload_f32(_ptr(ts._ptrs), ts.F, U, *tail))
+        ws, need, _ = self._sort_area("SparseFtrl.step_payload", lib.dir_sparse_adagrad_sorted_workspace_bytes, n, 1, U)
+        _lib.check(lib.dir_sparse_ftrl_rows_units_sorted_payload_f32(_ptr(ts._ptrs), ts.F, U, _ptr(payload), n, _ptr(grad), self.lr, self.l1,
+                                                                     self.l2, _ptr(self.row_base), self.total_rows, ws, need,
+                                                                     self._sorted_by("step_payload", sorted_by), _stream()))
         self._written()
-
-    def step_payload(self, payload, grad, sorted_by=None):
-        """Owner side of the sharded linear term's backward (shard.ShardedTables; include/dir_hip.h:
-        dir_sparse_ftrl_rows_sorted_payload_f32): payload [n] int64 (local_row * F + slot, < 0 pruned) as received from all ranks, grad [n]
-        fp32 in the same order, over packed rows (TableSet.ftrl_rows).  sorted_by: an optimiser whose step_payload has JUST run over the
-        same payload on this stream with the same local vocabularies (the SparseAdagrad of the co-located embedding rows): its sorted
-        (row, entry) pairs are read from its workspace and this call skips the key pass and the sort."""
-        if not self.packed:
-            raise ValueError("step_payload: packed linear training rows (TableSet.ftrl_rows)")
-        self._step_payload("step_payload", None, payload, grad, sorted_by)
-
-    def step_payload_units(self, payload, grad, sorted_by=None):
-        """step_payload over rows of ts.units first-order terms (include/dir_hip.h: dir_sparse_ftrl_rows_units_sorted_payload_f32): grad
-        [n, units] in payload order; sorted_by as in step_payload -- the co-located embedding rows may be of any width."""
-        U = int(getattr(self.ts, "units", 1))
-        if not self.packed or self.ts.ld != 4 * U:
-            raise ValueError("step_payload_units: packed rows of 4 * units floats")
-        self._step_payload("step_payload_units", U, payload, grad, sorted_by)
 
     def step_bags(self, recv, P, cap_e, cap_b, grad, sorted_by=None):
         """Owner side of the first-order term's backward over sharded bags (shard.ShardedTables.lookup_bags_train(with_linear=True);

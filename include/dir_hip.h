@@ -539,7 +539,8 @@ int dir_sparse_adagrad_sorted_bags_f32(float* const* tables, float* const* accum
  * lookup_train(with_linear=); reference: linear_logits under the embedding tables' partitioner, deepFM.py:199-223, 255-275).  Slot f's
  * weights live beside slot f's embedding rows, on the rank that owns them, as packed 16-byte training rows [w | n | z | -]
  * (dir_linear_onehot_rows_f32's layout, row stride row_ld floats, the weight in column 0).  The term rides on the embedding lookup's id
- * exchange: no second bucket pass, no second id all-to-all; one float per entry travels back.
+ * exchange: no second bucket pass, no second id all-to-all; one float per entry travels back.  Each of the four entries IS its _units_
+ * entry below at units = 1 (one implementation, the same kernels; the gather's row_ld, a free row stride here, is 4 * units there).
  * dir_shard_linear_gather_f32 (owner): the received payload -> one weight per payload word.  cap > 0: recv = P slabs of cap + 1 int64
  *   words as dir_gather_slabs_f32 takes them (header word: low 32 bits = valid slots), out[s*cap + j]; n is ignored; P <= 64,
  *   P * cap < 2^31.  cap == 0: recv = a flat payload of n words (0 <= n < 2^31), out[i].  A word p = local_row * F + slot reads
@@ -551,7 +552,7 @@ int dir_sparse_adagrad_sorted_bags_f32(float* const* tables, float* const* accum
  *   acc + bias.  At world size 1, and at any world size (the sum runs per sample in slot order, whoever the owners are), the result is
  *   dir_linear_onehot_rows_f32's over the unsharded rows bit for bit.  The strides take the sample-major inv (F, 1) and the field-major
  *   one of dir_shard_bucket_cap_dedup (1, B).
- * dir_shard_linear_grad_f32 (requester, the transpose of the finish): send [n_send] is zero-filled, then send[inv[b, f]] = g[b * g_ld]
+ * dir_shard_linear_grad_f32 (requester, the transpose of the finish): send [n_send] is zero-filled by a kernel, then send[inv[b, f]] = g[b * g_ld]
  *   for every entry with 0 <= inv < n_send.  Training lookups are never de-duplicated: one writer per position, plain stores.
  *   B * F < 2^31, n_send < 2^31.
  * dir_sparse_ftrl_rows_sorted_payload_f32 (owner): dir_sparse_ftrl_rows_sorted_f32's update driven by a payload, as
@@ -575,7 +576,7 @@ int dir_sparse_ftrl_rows_sorted_payload_f32(float* const* rows, int F, const int
 /* The same term with units = U first-order weights per row (ShardedTables.attach_linear([rows, U]); reference: the two linear models of
  * the wide & deep ESMM over the same categorical columns, ESMM_wide_deep.py:247-262).  rows[slot] is [local rows, 4 * units] floats,
  * 16-byte aligned: unit u's packed block [w | n | z | -] at float 4 u of a row.  One payload word serves all units; units floats per
- * slab slot travel back (1 <= units <= 8).  units = 1 computes what the four entries above compute.
+ * slab slot travel back (1 <= units <= 8).  units = 1 is a value like any other: the four entries above forward here with units = 1.
  * dir_shard_linear_gather_units_f32 (owner): out[i * units + u] = unit u's weight of payload word i, in the slab (cap > 0, P <= 64,
  *   P * cap * units < 2^31) and flat (cap == 0, n words, n * units < 2^31) forms of dir_shard_linear_gather_f32.  One lane reads a row's
  *   units weights together.  EVERY output word is written: 0.0f behind a header, for p < 0 and for a row >= local_rows[slot].

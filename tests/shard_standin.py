@@ -83,8 +83,8 @@ class NumpyBackend:
 
     def __init__(self, local, vocab, parts, first, P, K):
         self.local, self.vocab, self.parts, self.first, self.P, self.K, self.F = local, vocab, parts, first, P, K, len(vocab)
-        self.lin = None
-        self.ftrl_calls = 0
+        self.lin, self.U = None, 1
+        self.ftrl_calls, self.ftrl_widths = 0, []
 
     def owner(self, f, ids):
         """owner rank, local row of ids (all inside [0, vocab_f)) of slot f."""
@@ -220,37 +220,40 @@ class NumpyBackend:
 
     # ---- the linear term ----
     def attach_linear(self, rows, arena):
-        self.lin = rows                                # [local rows, 4] float32 torch tensors = [w | n | z | -]: the kernels' buffers
+        # [local rows, 4 U] float32 torch tensors, U blocks [w | n | z | -] (one per unit) side by side: the kernels' buffers
+        self.lin, self.U = rows, rows[0].shape[1] // 4
 
     def _weights_of(self, p):
-        """One weight per payload word (0.0 for p < 0 and for rows outside the slot's local rows)."""
-        out = np.zeros(p.size, np.float32)
+        """U weights per payload word (0.0 for p < 0 and for rows outside the slot's local rows)."""
+        out = np.zeros((p.size, self.U), np.float32)
         for i, v in enumerate(p):
             if v >= 0 and v // self.F < self.lin[v % self.F].shape[0]:
-                out[i] = self.lin[v % self.F].numpy()[v // self.F, 0]
+                out[i] = self.lin[v % self.F].numpy()[v // self.F, 0::4]
         return out
 
     def linear_gather(self, recv, cap, out):
-        o = out.numpy()
+        U, o = self.U, out.numpy()
         if cap is None:
-            o[:recv.numel()] = self._weights_of(recv.numpy())
+            o[:recv.numel() * U] = self._weights_of(recv.numpy()).reshape(-1)
             return
         r = recv.numpy().reshape(self.P, cap + 1)
-        o[:self.P * cap] = 0.0                         # every word is written: nothing uninitialised crosses the wire
+        o[:self.P * cap * U] = 0.0                     # every word is written: nothing uninitialised crosses the wire
         for s in range(self.P):
             nv = int(r[s, 0] & 0xffffffff)
-            o[s * cap:s * cap + nv] = self._weights_of(r[s, 1:1 + nv])
+            o[s * cap * U:(s * cap + nv) * U] = self._weights_of(r[s, 1:1 + nv]).reshape(-1)
 
     def linear_finish(self, wback, inv2d, bias, out):
-        iv, wb = inv2d.numpy(), wback.numpy()
-        acc = np.zeros(iv.shape[0], np.float32)
-        for f in range(iv.shape[1]):                   # float32, slot order: dir_linear_onehot_rows_f32's sum
-            acc = acc + np.where(iv[:, f] >= 0, wb[np.maximum(iv[:, f], 0)], np.float32(0)).astype(np.float32)
-        acc = acc + (np.float32(bias.numpy().reshape(-1)[0]) if bias is not None else np.float32(0))
-        out.copy_(torch.from_numpy(acc.reshape(-1, 1)))
+        U = self.U
+        iv, wb = inv2d.numpy(), wback.numpy().reshape(-1, U)
+        acc = np.zeros((iv.shape[0], U), np.float32)
+        for f in range(iv.shape[1]):                   # float32, slot order, per unit: dir_linear_onehot_rows_f32's sum
+            acc = acc + np.where((iv[:, f] >= 0)[:, None], wb[np.maximum(iv[:, f], 0)], np.float32(0)).astype(np.float32)
+        acc = acc + (bias.numpy().reshape(1, U).astype(np.float32) if bias is not None else np.float32(0))
+        out.copy_(torch.from_numpy(acc.astype(np.float32)))
 
     def linear_grad(self, g, inv2d, send):
-        iv, gg, sd = inv2d.numpy(), g.detach().numpy().reshape(-1), send.numpy()
+        U = self.U
+        iv, gg, sd = inv2d.numpy(), g.detach().numpy().reshape(-1, U), send.numpy().reshape(-1, U)
         sd[:] = 0.0
         for b in range(iv.shape[0]):
             for f in range(iv.shape[1]):
@@ -266,17 +269,22 @@ class NumpyBackend:
 
     def apply_ftrl(self, payload, grad, lr, l1, l2, sorted_by=None):
         self.ftrl_calls += 1
-        p, g = payload.numpy(), grad.numpy().astype(np.float64)
-        assert g.size == p.size
+        U = self.U
+        p = payload.numpy()
+        self.ftrl_widths.append(grad.numel() // max(1, p.size))      # floats per payload word, as the caller sent them
+        g = grad.numpy().astype(np.float64).reshape(-1, U)
+        assert g.shape[0] == p.size
         for f in range(self.F):
             sel = (p >= 0) & (p % self.F == f)
             rows = p[sel] // self.F
             r = self.lin[f].numpy()
-            gs = np.zeros(r.shape[0])
+            gs = np.zeros((r.shape[0], U))
             np.add.at(gs, rows, g[sel])                # ALL duplicates of a row are summed before n, z and w move
             t = np.zeros(r.shape[0], bool)
             t[rows] = True
-            r[t, 0], r[t, 1], r[t, 2] = self._ftrl(*(r[t, c].astype(np.float64) for c in range(3)), gs[t], lr, l1, l2)
+            for u in range(U):
+                c = 4 * u
+                r[t, c], r[t, c + 1], r[t, c + 2] = self._ftrl(*(r[t, c + k].astype(np.float64) for k in range(3)), gs[t, u], lr, l1, l2)
 
     def ftrl_dense(self, w, accum, linear, grad, lr, l1, l2):
         new = self._ftrl(*(t.numpy().astype(np.float64) for t in (w, accum, linear, grad)), lr, l1, l2)

@@ -696,23 +696,29 @@ def test_ftrl_rows_first_order_readers(built_lib, oracle):
     pay = np.where(ids >= 0, ids * F + np.arange(F)[None, :], -1).reshape(-1).astype(np.int64)
     want = np.stack([_rows(ts.tables[f], ids[:, f])[:, 0] for f in range(2)], 1).reshape(-1)
     n = pay.size
-    out = torch.full((n,), float("nan"), device="cuda")
-    ops.shard_linear_gather(ts, _cuda(pay), 1, None, out)
-    assert np.array_equal(out.cpu().numpy(), want), "shard_linear_gather (flat)"
-    out = torch.full((n,), float("nan"), device="cuda")
-    ops.shard_linear_gather_units(ts, _cuda(pay), 1, None, out)
-    assert np.array_equal(out.cpu().numpy(), want), "shard_linear_gather_units"
+    # ops.shard_linear_gather goes through dir_shard_linear_gather_units_f32 (rows of one unit); the plain entry, which forwards to the
+    # same body with its own row stride, is called through the loaded library: both exported symbols stay exercised past 2^31
+    from dir_amd import _lib
+    from dir_amd._abi import _ptr, _stream
+
+    def plain_entry(ts, recv, P, cap, out):
+        _lib.check(_lib.load().dir_shard_linear_gather_f32(_ptr(ts._ptrs), ts.ld, _ptr(ts.vocab_dev), ts.F, _ptr(recv), P, cap or 0,
+                                                           0 if cap else recv.numel(), _ptr(out), _stream()))
     P, cap = 2, n + 3
     recv = np.full((P, cap + 1), -1, np.int64)
     recv[0, 0], recv[0, 1:1 + n] = n | (n << 32), pay
     recv[1, 0] = 0 | (n << 32)
-    for fn in (ops.shard_linear_gather, ops.shard_linear_gather_units):
+    for fn in (ops.shard_linear_gather, plain_entry):
+        out = torch.full((n,), float("nan"), device="cuda")
+        fn(ts, _cuda(pay), 1, None, out)
+        assert np.array_equal(out.cpu().numpy(), want), fn.__name__ + " (flat)"
         out = torch.full((P * cap,), float("nan"), device="cuda")
         fn(ts, _cuda(recv.reshape(-1)), P, cap, out)
         got = out.cpu().numpy()
         assert np.array_equal(got[:n], want) and not got[n:].any(), fn.__name__ + " (slabs): every word is written, 0.0 behind the count"
 
 
+# the ids name the C entry a case drives: dir_sparse_ftrl_rows_sorted_f32, ..._sorted_payload_f32, ..._units_sorted_payload_f32
 @pytest.mark.parametrize("name", ["step", "step_payload", "step_payload_units"])
 def test_ftrl_rows_steps(built_lib, name):
     from dir_amd import ops
@@ -730,10 +736,15 @@ def test_ftrl_rows_steps(built_lib, name):
         assert opt.packed
         if name == "step":
             opt.step(ids, grad)
-        elif name == "step_payload":
-            opt.step_payload(pay, pgrad)
-        else:
-            opt.step_payload_units(pay, pgrad.view(-1, 1))                  # rows of one unit: the same 16-byte rows
+        elif name == "step_payload_units":                                  # dir_sparse_ftrl_rows_units_sorted_payload_f32 (rows of one unit)
+            opt.step_payload(pay, pgrad.view(-1, 1))
+        else:                                                               # the plain entry, through the loaded library
+            from dir_amd import _lib
+            from dir_amd._abi import _ptr, _stream
+            lib = _lib.load()
+            ws, need, _ = opt._sort_area("step_payload", lib.dir_sparse_adagrad_sorted_workspace_bytes, pay.numel(), 1, 1)
+            _lib.check(lib.dir_sparse_ftrl_rows_sorted_payload_f32(_ptr(ts._ptrs), ts.F, _ptr(pay), pay.numel(), _ptr(pgrad), opt.lr, opt.l1,
+                                                                   opt.l2, _ptr(opt.row_base), opt.total_rows, ws, need, None, _stream()))
         run.arena = ts.arena
         return ts.tables, ts.accums, ts.linears
     _check_writer("ftrl_rows " + name, c, [ts0.tables, ts0.accums, ts0.linears], run, lambda w0, n0, z0: X.ref_ftrl(c, w0, n0, z0),

@@ -210,9 +210,9 @@ def test_owner_ftrl_units_on_its_own_sort_equals_on_the_adagrad_sort(built_lib, 
         be = st.backend
         if reuse:
             be.apply_adagrad(st.optimizer, payload, grows)
-            be.apply_ftrl_units(payload, g, 0.2, 0.01, 0.02, sorted_by=st.optimizer)
+            be.apply_ftrl(payload, g, 0.2, 0.01, 0.02, sorted_by=st.optimizer)
         else:
-            be.apply_ftrl_units(payload, g, 0.2, 0.01, 0.02)
+            be.apply_ftrl(payload, g, 0.2, 0.01, 0.02)
             be.apply_adagrad(st.optimizer, payload, grows)
         sts.append(st)
     torch.cuda.synchronize()

@@ -13,7 +13,7 @@ Tables: F = 3, vocab [5, 1, 70] (a one-row table, a table smaller than a tile), 
   3. Both through a world-1 ShardedTables under enable_training_adam over bag records, local batches 2, 96 and 2 with one-hot steps in
      between: tests.test_gpu_shard_bags_adam's helpers, BagsAdamReference, the same bar.
   4. SparseAdagrad.step_payload then SparseFtrl.step_payload(sorted_by=adagrad) at 5, 700 and 5 words on one pair against a twin pair
-     whose FTRL sorts for itself: weights, n and z bitwise; the same with step_payload_units at units = 2 and with step_bags over the
+     whose FTRL sorts for itself: weights, n and z bitwise; the same over rows of units = 2 and with step_bags over the
      world-1 bag lookup's slabs."""
 import numpy as np
 import pytest
@@ -240,15 +240,14 @@ def test_ftrl_on_a_borrowed_payload_sort_across_growth(built_lib, K, units):
     w0 = _w0(K, 5 * K)
     full_w = [(0.3 * rng.standard_normal((v, units) if units > 1 else v)).astype(np.float32) for v in VOCAB]
     (sa, ada_a, ftrl_a), (sb, ada_b, ftrl_b) = _pair(w0, full_w, dev), _pair(w0, full_w, dev)
-    ftrl_step = (lambda o: o.step_payload_units) if units > 1 else (lambda o: o.step_payload)
     for n in (5, 700, 5):
         _, _, pay, grows = _words(rng, n, K)
         pay, grows = _cuda(pay), _cuda(grows)
         g = _cuda(rng.standard_normal((n, units) if units > 1 else n).astype(np.float32))
         ada_a.step_payload(pay, grows)
-        ftrl_step(ftrl_a)(pay, g, sorted_by=ada_a)      # the Adagrad step's sorted pairs
+        ftrl_a.step_payload(pay, g, sorted_by=ada_a)     # the Adagrad step's sorted pairs
         ada_b.step_payload(pay, grows)
-        ftrl_step(ftrl_b)(pay, g)                       # its own key pass and sort
+        ftrl_b.step_payload(pay, g)                      # its own key pass and sort
         torch.cuda.synchronize()
         _assert_pairs(sa, sb, "units=%d, %d words" % (units, n))
     assert not torch.equal(sa.lin_rows[2][:, 0].cpu(), torch.from_numpy(full_w[2].reshape(VOCAB[2], -1)[:, 0]))

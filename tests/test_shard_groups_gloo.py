@@ -182,7 +182,7 @@ def sc_forward(rank, world):
 def sc_train3(rank, world):
     """Three training steps, Adagrad at width G*K and FTRL over U units with l1 = l2 = 0, against the float64 reference per group and unit."""
     st, be, ref, _ = _train_steps(rank, world, 23, _sizes(world), 3, dict(lr=0.2, l1=0.0, l2=0.0), {})
-    assert be.units_calls == 3 and be.ftrl_calls == 0
+    assert be.ftrl_calls == 3 and be.ftrl_widths == [U] * 3            # one FTRL step per backward, U gradient columns per payload word
     return "3 steps"
 
 

@@ -1,12 +1,12 @@
 """tools/shard_groups_probe.py (GPU box): what storing ESMM's two sub-models' rows side by side buys on the row-sharded tables
-(ShardedTables(groups=2) + attach_linear([rows, 2]); csrc/ids.hip: finish_groups_k / grad_groups_k, csrc/shard_linear.hip: the *_units
-kernels, csrc/backward.hip: dir_sparse_ftrl_rows_units_sorted_payload_f32) at world size 1 on ONE GPU, on the headline shape:
+(ShardedTables(groups=2) + attach_linear([rows, 2]); csrc/ids.hip: finish_groups_k / grad_groups_k, csrc/shard_linear.hip: the linear_*
+kernels at U = 2, csrc/backward.hip: dir_sparse_ftrl_rows_units_sorted_payload_f32) at world size 1 on ONE GPU, on the headline shape:
 B = 65 536 samples x F = 26 slots x 1 M-row tables, K = 16, G = 2, U = 2, uniform ids.
 
   (a) grouped lookup(want_lin=True)                        against  two ShardedTables with attach_linear, back to back (the only way without
   (b) grouped lookup_train forward + backward              against  row groups: the baseline)
-  (c) the new kernels on their own: grouped finish, grouped gradient scatter, the three units kernels, the owner's units FTRL on its own
-      sort and on the Adagrad step's sort
+  (c) the new kernels on their own: grouped finish, grouped gradient scatter, the three linear kernels at U = 2, the owner's FTRL over
+      U units on its own sort and on the Adagrad step's sort
   (d) the owner gather (dir_gather_slabs_f32) at 128-byte rows (G*K = 32 floats) beside the same gather at 64-byte rows
 No exchange runs at world 1 (nothing here measures a link; no N > 1 figure exists on a one-GPU box).  Every measurement: median of --iters
 timed runs, HIP events, after at least 0.25 s of the same work as warm-up (the clocks after idle: profiles/NOTES.md R6.3); (a) and (b)
@@ -126,9 +126,9 @@ if want("kernels"):
     lsend = torch.empty(cap * U, device=dev)
     t_fin = med_us(lambda: be.finish_groups(plan.back[0], inv2d, K, outs))
     t_grad = med_us(lambda: be.grad_groups(Gs, inv2d, K, send))
-    t_lg = med_us(lambda: be.linear_gather_units(plan.recv[0], cap, lrows[0]))
-    t_lf = med_us(lambda: be.linear_finish_units(lback[0], inv2d, U, bias, lin))
-    t_ls = med_us(lambda: be.linear_grad_units(g, inv2d, U, lsend))
+    t_lg = med_us(lambda: be.linear_gather(plan.recv[0], cap, lrows[0]))
+    t_lf = med_us(lambda: be.linear_finish(lback[0], inv2d, bias, lin))
+    t_ls = med_us(lambda: be.linear_grad(g, inv2d, lsend))
     # the finish pass the parent commit would run twice: one gather per sub-model's [n, K] buffer
     b_st = pair[0]
     b_plan = b_st._plan(B, "train")
@@ -143,9 +143,9 @@ if want("kernels"):
 
     def both():
         be.apply_adagrad(grouped.optimizer, pay, grad_rows)
-        be.apply_ftrl_units(pay, lsend, FTRL["lr"], FTRL["l1"], FTRL["l2"], sorted_by=grouped.optimizer)
+        be.apply_ftrl(pay, lsend, FTRL["lr"], FTRL["l1"], FTRL["l2"], sorted_by=grouped.optimizer)
     t_a = med_us(lambda: be.apply_adagrad(grouped.optimizer, pay, grad_rows))
-    t_own = med_us(lambda: be.apply_ftrl_units(pay, lsend, FTRL["lr"], FTRL["l1"], FTRL["l2"]))
+    t_own = med_us(lambda: be.apply_ftrl(pay, lsend, FTRL["lr"], FTRL["l1"], FTRL["l2"]))
     t_both = med_us(both)
     emit(what="groups_kernels", **shape, slab_slots=cap, finish_groups_us=round(t_fin, 1), finish_one_table_us=round(t_fin1, 1),
          grad_groups_us=round(t_grad, 1), linear_gather_units_us=round(t_lg, 1), linear_finish_units_us=round(t_lf, 1),
