@@ -169,9 +169,6 @@ def raise_pending(block=None):
             raise ValueError(describe())
 
 
-_IDS_ALIAS = os.environ.get("DIR_IDS_ALIAS", "1") != "0"      # development switch: 0 = always stack the id columns (round 4's behaviour)
-
-
 def _columns_of_one_matrix(got):
     """The one-hot id columns as ONE strided [B, F] view when they already are the columns (or rows) of one int64 matrix -- what an input
     pipeline that batches the categorical features into one tensor hands over as a dict of views --, else None.  The kernels take ids
@@ -223,7 +220,7 @@ def collect_ids(columns, features, device, memo=None):
         for g in got:
             if g.numel() != B:
                 raise ValueError("features disagree on the batch size")
-        ids_bf = _columns_of_one_matrix(got) if _IDS_ALIAS else None
+        ids_bf = _columns_of_one_matrix(got)
         if ids_bf is None:
             ids_bf = torch.stack(got, dim=0).t()
         if ids_bf.is_cuda:

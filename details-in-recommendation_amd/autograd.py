@@ -286,7 +286,7 @@ def _tn_matmul(A, Bm, splits=128):
     return out
 
 
-_DIN_COMPOSITE_BACKWARD = os.environ.get("DIR_DIN_COMPOSITE_BACKWARD", "0") == "1"   # dev switch: A/B against the fused kernel
+_DIN_COMPOSITE_BACKWARD = False   # True: the composite backward, an A/B against the fused kernel (tests/test_gpu_backward.py sets it)
 _DIN_SAVE_ACTIVATIONS = os.environ.get("DIR_DIN_SAVE", "1") != "0"                   # 0: the backward recomputes the two hidden layers (round 2's form)
 
 
@@ -514,9 +514,6 @@ def cross_network(x0, w, b):
     return CrossNetwork.apply(x0, w, b)
 
 
-_DENSE_OPT_HIP = os.environ.get("DIR_DENSE_OPT_HIP", "1") != "0"      # development switch: 0 keeps the library's dense Adagrad / torch-op FTRL steps
-
-
 class Adagrad(torch.optim.Adagrad):
     """torch.optim.Adagrad ([TF-upstream] tf.train.AdagradOptimizer's rule with eps = 0; the reference's dnn_optimizer='Adagrad',
     deepFM.py:61) whose step on dense float32 CUDA variables is ONE elementwise HIP pass per variable (dir_adagrad_dense_f32) instead of
@@ -537,7 +534,7 @@ class Adagrad(torch.optim.Adagrad):
                 g = p.grad
                 if g is None:
                     continue
-                if not (_DENSE_OPT_HIP and plain and not g.is_sparse and p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and p.is_contiguous()
+                if not (plain and not g.is_sparse and p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and p.is_contiguous()
                         and g.is_contiguous()):
                     rest.append(p)
                     continue
@@ -580,7 +577,7 @@ class Ftrl(torch.optim.Optimizer):
                     st["accum"] = torch.full_like(p, group["init"])
                     st["linear"] = torch.zeros_like(p)
                 g = p.grad
-                if (_DENSE_OPT_HIP and not g.is_sparse and p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and p.is_contiguous()
+                if (not g.is_sparse and p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and p.is_contiguous()
                         and g.is_contiguous()):
                     ops.ftrl_dense_(p, st["accum"], st["linear"], g, lr, l1, l2)          # one elementwise HIP pass (dir_ftrl_dense_f32)
                     continue

@@ -48,8 +48,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
          "-Wall", "-Wno-unused-function"]
 # DIR_DEVELOPMENT=1 python build.py --force: a build whose library honours the development A/B switches read from the environment
-# (DIR_RS_DBG timing masks -- results are WRONG under them --, DIR_SORT, DIR_ADA_STAGE_MIN, DIR_BUCKET_EPT / _NT; csrc/common.hpp: dev_env).
-# The production build ignores them and refuses to sort when DIR_RS_DBG is set.
+# (DIR_RS_DBG timing masks -- results are WRONG under them --, DIR_SORT, DIR_ADA_STAGE_MIN, DIR_BUCKET_EPT / _NT ...; csrc/common.hpp: dev_env;
+# INTEGRATION.md lists them) and holds the kernel instantiations only they select.  The production build ignores them, compiles none of
+# those kernels and refuses to sort when DIR_RS_DBG is set.
 if os.environ.get("DIR_DEVELOPMENT") == "1":
     FLAGS.append("-DDIR_DEVELOPMENT")
 # DIR_ABLATE="cin_bf3.hip:CIN_ABL=1": one timing-ablation macro for one translation unit (development; results are WRONG under most of them)

@@ -1408,8 +1408,7 @@ extern "C" int dir_dcn_cross_backward_f32(const float* x0, int64_t x_ld, const f
     while (nw > 1 && lds(nw) > 150 * 1024) nw >>= 1;
     if (lds(nw) > 150 * 1024) return fail(DIR_E_UNSUPPORTED, "dir_dcn_cross_backward_f32: L=%d d=%d needs %zu B of LDS", L, d, lds(nw));
     float* partial = static_cast<float*>(workspace);
-    static const int reg_env = getenv("DIR_CROSS_BWD_REG") ? atoi(getenv("DIR_CROSS_BWD_REG")) : 1;   // 0: slab kernel (A/B runs)
-    if (reg_env && L >= 1 && L <= 4 && nv <= (vec ? 4 : 8)) {
+    if (L >= 1 && L <= 4 && nv <= (vec ? 4 : 8)) {   // the register kernel; deeper stacks and wider d take the slab kernel below
         const int nblk = (int)((B + 3) / 4 < cross_bwd_blocks() ? (B + 3) / 4 : cross_bwd_blocks());
         const size_t sh = sizeof(float) * (size_t)4 * 2 * L * d;
 #define DIR_REG(NV, V, LT)                                                                                                      \

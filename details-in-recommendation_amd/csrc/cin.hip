@@ -471,22 +471,23 @@ static void launch_cin_ct(dim3 grid, size_t shmem, hipStream_t st, const float* 
                           int64_t pooled_ld) {
     // interleaved fast staging needs: a compatible (m, column-tile) shape, whole 16-byte aligned W rows and at
     // least one whole chunk; everything else takes the generic bulk staging
-    static const int fast_env = getenv("DIR_CIN_FAST") ? atoi(getenv("DIR_CIN_FAST")) : 1;
     const bool wvec = m == MT && ((int64_t)Hp * MT) % 4 == 0 && aligned16(W);
+#ifdef DIR_DEVELOPMENT
     if constexpr (MT == 26 && CT == 4) {
-        static const int stamp_env = getenv("DIR_CIN_STAMP") ? atoi(getenv("DIR_CIN_STAMP")) : 0;
-        if (stamp_env && fast_env && wvec && Hp >= cin_ic(MT)) {   // diagnostic build: cycle stamps, same arithmetic
+        static const int stamp_env = dev_env_int("DIR_CIN_STAMP", 0);
+        if (stamp_env && wvec && Hp >= cin_ic(MT)) {   // diagnostic: cycle stamps, same arithmetic (tools/cin_stamp_probe.py)
             static LdsOnce once;
             (void)lds_limit(once, 160 * 1024, &cin_k<26, 4, true, true>);
             hipLaunchKernelGGL((cin_k<26, 4, true, true>), grid, dim3(256), shmem, st, x0, xk, W, m, Hp, H, D, dshift, hoff, R, xout, pooled, pooled_ld);
             return;
         }
     }
+#endif
     // Hp a multiple of 2 but not of the chunk size (layer 1 of the BASELINE stack: Hp = m = 26): chunks of 2 values of i divide
     // it exactly, instead of a zero-padded tail chunk that also falls off the interleaved staging
     if constexpr (cin_ic(MT) == 4 && cin_fast_shape<MT, CT, 2>()) {
         const bool w8 = m == MT && ((int64_t)Hp * MT) % 2 == 0 && (reinterpret_cast<uintptr_t>(W) & 7u) == 0;
-        if (fast_env && w8 && Hp % 4 != 0 && Hp % 2 == 0) {
+        if (w8 && Hp % 4 != 0 && Hp % 2 == 0) {
             constexpr int mp = (MT + 1) & ~1;
             const size_t sh2 = sizeof(float) * ((size_t)mp * CIN_ROWS + 2 * (size_t)2 * mp * cin_ws(CT) + 2 * (size_t)2 * CIN_ROWS);
             static LdsOnce once;
@@ -496,7 +497,7 @@ static void launch_cin_ct(dim3 grid, size_t shmem, hipStream_t st, const float* 
         }
     }
     if constexpr (cin_fast_shape<MT, CT>()) {
-        if (fast_env && wvec && Hp >= cin_ic(MT)) {
+        if (wvec && Hp >= cin_ic(MT)) {
             launch_cin_one<MT, CT, true>(grid, shmem, st, x0, xk, W, m, Hp, H, D, dshift, hoff, R, xout, pooled, pooled_ld);
             return;
         }
@@ -564,7 +565,7 @@ extern "C" int dir_cin_layer_f32(const float* x0, const float* xk, const float* 
     return DIR_OK;
 }
 
-// Diagnostic only: read (and clear) the cycle stamps accumulated by the DIR_CIN_STAMP=1 build.
+// Diagnostic only: read (and clear) the cycle stamps accumulated under DIR_CIN_STAMP=1 (a -DDIR_DEVELOPMENT build; all zero otherwise).
 extern "C" int dir_debug_cin_stamps(unsigned long long* out8) {
     if (!out8) return dir::fail(DIR_E_BADARG, "dir_debug_cin_stamps: null pointer");
     unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -165,8 +165,9 @@ size_t radix_slot_sort_temp_bytes(int64_t B, int F, unsigned gbits);
 hipError_t radix_slot_sort_entries(void* tmp, const int64_t* ids, int64_t sb, int64_t sf, int F, int64_t B, const int64_t* row_base,
                                    uint32_t total_rows, unsigned gbits, uint32_t* k0, uint32_t* k1, uint32_t* v0, uint32_t* v1, hipStream_t st);
 // Development A/B switches read from the environment (DIR_RS_DBG, DIR_SORT, DIR_ADA_STAGE_MIN, DIR_BUCKET_EPT, DIR_BUCKET_NT ...) exist only in a
-// build with -DDIR_DEVELOPMENT (DIR_DEVELOPMENT=1 python build.py): some of them produce WRONG results by design (timing masks), so the
-// production library does not look at them at all; dev_env_set() lets an entry point fail loudly when one is set anyway.
+// build with -DDIR_DEVELOPMENT (DIR_DEVELOPMENT=1 python build.py), and so do the kernel instantiations that only they select: some of them
+// produce WRONG results by design (timing masks), so the production library does not look at them at all; dev_env_ignored() lets
+// an entry point fail loudly when one is set anyway.
 inline const char* dev_env(const char* name) {
 #ifdef DIR_DEVELOPMENT
     return getenv(name);
@@ -185,6 +186,9 @@ inline bool dev_env_ignored(const char* name) {        // the variable is set, a
     return e && *e && strcmp(e, "0") != 0;
 #endif
 }
+// The runtime switches the production library honours too -- DIR_TOWER_RS, DIR_DIN_ARITH, DIR_DIN_STATIC, DIR_GATHER_UF: these four and no
+// others -- because the committed tests flip them (INTEGRATION.md lists them).  No other getenv in csrc/ (tests/test_abi.py).
+inline const char* runtime_env(const char* name) { return getenv(name); }
 hipError_t zero_async(void* p, size_t bytes, hipStream_t st);                                                // p, bytes: multiples of 4
 hipError_t zero_2d_async(void* p, size_t pitch_bytes, size_t width_bytes, size_t rows, hipStream_t st);      // as hipMemset2DAsync(.., 0, ..)
 

@@ -538,15 +538,9 @@ static int dense_entry(const char* name, const float* X, int64_t x_ld, const flo
     hipStream_t st = as_stream(stream);
     // k chunk 16: 33 KB (NT = 80) / 41 KB (NT = 128) of LDS per workgroup, so four / three workgroups share a CU and hide each other's
     // per-chunk latencies: 0.80 vs 0.72 of the fp32 MFMA peak at 400-wide layers, 0.89 vs 0.81 at 1024 x 1024 (32-wide chunks: two
-    // workgroups per CU).  DIR_DENSE_KC = 32 selects the wide chunks (tools/dense_sweep.py).
-    static const int kc_env = getenv("DIR_DENSE_KC") ? atoi(getenv("DIR_DENSE_KC")) : 16;
-    if (N % 80 == 0 && N % 128 != 0) {
-        if (kc_env == 32) launch_dense<80, 32>(st, X, x_ld, Wt, w_ld, bias, act, M, Kd, N, Y, y_ld, gate, gate_ld, ps, psh);
-        else launch_dense<80, 16>(st, X, x_ld, Wt, w_ld, bias, act, M, Kd, N, Y, y_ld, gate, gate_ld, ps, psh);
-    } else {
-        if (kc_env == 32) launch_dense<128, 32>(st, X, x_ld, Wt, w_ld, bias, act, M, Kd, N, Y, y_ld, gate, gate_ld, ps, psh);
-        else launch_dense<128, 16>(st, X, x_ld, Wt, w_ld, bias, act, M, Kd, N, Y, y_ld, gate, gate_ld, ps, psh);
-    }
+    // workgroups per CU).
+    if (N % 80 == 0 && N % 128 != 0) launch_dense<80, 16>(st, X, x_ld, Wt, w_ld, bias, act, M, Kd, N, Y, y_ld, gate, gate_ld, ps, psh);
+    else launch_dense<128, 16>(st, X, x_ld, Wt, w_ld, bias, act, M, Kd, N, Y, y_ld, gate, gate_ld, ps, psh);
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
 }

@@ -1178,22 +1178,24 @@ extern "C" int dir_din_attention_pool_f32(const float* table, int K, const int64
         return fail(DIR_E_UNSUPPORTED, "dir_din_attention_pool_f32: K, H1, H2 must be multiples of 4 (K=%d H1=%d H2=%d)", K, H1, H2);
     if (!aligned16(table) || !aligned16(W1) || !aligned16(W2) || !aligned16(b1) || !aligned16(b2))
         return fail(DIR_E_BADARG, "dir_din_attention_pool_f32: table / W1 / W2 / b1 / b2 must be 16-byte aligned");
-    static const int mfma_env = getenv("DIR_DIN_MFMA") ? atoi(getenv("DIR_DIN_MFMA")) : 1;
-    static const int wave_env = getenv("DIR_DIN_WAVE") ? atoi(getenv("DIR_DIN_WAVE")) : 1;     // 0: the round-1 workgroup-per-sample kernel (A/B)
-    if (mfma_env && wave_env && din_wave_covers(K, T, H1, H2)) {
+    static const int wave_env = dev_env_int("DIR_DIN_WAVE", 1);     // 0: the round-1 workgroup-per-sample kernel (A/B, tools/din_len_sweep.py)
+    if (wave_env && din_wave_covers(K, T, H1, H2)) {
         const int rc = launch_din_wave(as_stream(stream), table, hist, hist_len, cand, T, W1, b1, H1, W2, b2, H2, W3, b3, normalize, B, out, scores);
         if (rc != DIR_OK) return rc;
         DIR_CHECK_LAUNCH("din_attention_pool(wave)");
         return DIR_OK;
     }
-    if (mfma_env && T <= 64) {
+    if (T <= 64) {
         const int nc1 = (H1 + 15) / 16, nc2 = (H2 + 15) / 16;
         hipStream_t st = as_stream(stream);
         bool done = true;
         // narrower hidden layers run on the same instantiations: columns >= H1 / H2 are zero weights (guards in the loads)
+#ifdef DIR_DEVELOPMENT      // (the wave kernel covers all of this shape class: reachable under DIR_DIN_WAVE=0 alone)
         if (K == 64 && nc1 <= 5 && nc2 <= 3)
             launch_din_mfma<64, 5, 3>(st, table, hist, hist_len, cand, T, W1, b1, H1, W2, b2, H2, W3, b3, normalize, B, out, scores);
-        else if (K == 16 && nc1 <= 2 && nc2 <= 1)
+        else
+#endif
+        if (K == 16 && nc1 <= 2 && nc2 <= 1)
             launch_din_mfma<16, 2, 1>(st, table, hist, hist_len, cand, T, W1, b1, H1, W2, b2, H2, W3, b3, normalize, B, out, scores);
         else if (K == 32 && nc1 <= 3 && nc2 <= 1)
             launch_din_mfma<32, 3, 1>(st, table, hist, hist_len, cand, T, W1, b1, H1, W2, b2, H2, W3, b3, normalize, B, out, scores);

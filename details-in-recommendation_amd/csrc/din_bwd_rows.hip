@@ -858,18 +858,24 @@ static int din_backward_rows(const char* name, bool saved, const float* table, i
     float* partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + scratch_bytes);
     int nwg2 = 0;
     if (B > 0) {
-        // DIR_DIN_BWD_ARITH = bf16x3 (default) | f32: the arithmetic of the saved-activation row pass's two GEMMs (read per call)
-        const char* arith = getenv("DIR_DIN_BWD_ARITH");
+        // DIR_DIN_BWD_ARITH = bf16x3 (default) | f32: the arithmetic of the saved-activation row pass's two GEMMs (-DDIR_DEVELOPMENT builds, read per call)
+        const char* arith = dev_env("DIR_DIN_BWD_ARITH");
         const bool bf3 = saved && !(arith && strcmp(arith, "f32") == 0);
         typedef void (*kern_t)(const float*, const int64_t*, const int32_t*, const int64_t*, int, const float*, const float*, int, const float*,
                                const float*, int, const float*, int, long long, const float*, const float*, const int64_t*, const int64_t*, float*,
                                float*, float*, float*, int);
         const int which = bf3 ? 2 : saved ? 1 : 0;
-        static const kern_t kerns[3] = {&din_rows_k<false, DinRowsSh>, &din_rows_k<true, DinRowsSh>, &din_rows_k<true, DinRowsSh3>};
+        static const kern_t kerns[3] = {&din_rows_k<false, DinRowsSh>,
+#ifdef DIR_DEVELOPMENT
+                                        &din_rows_k<true, DinRowsSh>,
+#else
+                                        nullptr,        // (saved rows in fp32: DIR_DIN_BWD_ARITH=f32 alone selects it)
+#endif
+                                        &din_rows_k<true, DinRowsSh3>};
         static LdsOnce once[3];
         const size_t shmem = bf3 ? sizeof(DinRowsSh3) : sizeof(DinRowsSh);
         if (!lds_limit(once[which], (int)shmem, kerns[which])) return fail(DIR_E_HIP, "%s: cannot reserve %zu B of LDS", name, shmem);
-        const char* stat = getenv("DIR_DIN_STATIC");
+        const char* stat = runtime_env("DIR_DIN_STATIC");
         const bool static_split = stat && atoi(stat) != 0;
         const int slot = static_split ? -1 : (int)(rb_next_slot.fetch_add(1) % RB_SLOTS);
         const int64_t waves_wanted = (B + 1) / 2;

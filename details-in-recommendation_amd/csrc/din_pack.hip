@@ -789,8 +789,8 @@ int launch_din_pack(hipStream_t st, const float* table, const int64_t* hist, con
     int* csum = static_cast<int*>(workspace);
     float* ml = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + round256((int64_t)nchunk * 4));
     // the weight of a sample beyond its rows, in rows: what its candidate row, its share of a block's term and its output cost
-    // (DIR_DIN_PACK_W0: an A/B switch read per call like DIR_DIN_ARITH; any value gives the same results up to the summation order across passes)
-    const char* w0e = getenv("DIR_DIN_PACK_W0");
+    // (DIR_DIN_PACK_W0: an A/B switch of -DDIR_DEVELOPMENT builds, read per call; any value gives the same results up to the summation order across passes)
+    const char* w0e = dev_env("DIR_DIN_PACK_W0");
     const int w0 = w0e ? (atoi(w0e) < 0 ? 0 : atoi(w0e) > 64 ? 64 : atoi(w0e)) : 5;
     typedef void (*kern_t)(const float*, const int64_t*, const int32_t*, const int64_t*, int, const DpImg*, const float*, long long, float*, float*,
                            float*, const int*, int, long long, int);

@@ -812,7 +812,7 @@ int launch_din_wave(hipStream_t st, const float* table, const int64_t* hist, con
     // samples instead of the device-side queue (default: static for bf16x3 -- its per-sample time is short enough that the ticket
     // atomics cost more than the imbalance they remove, 0.45 vs 0.50 ms at config 4 -- and the queue for fp32).  Both are read per call
     // (A/B runs and tests flip them inside one process).  saved != nullptr: the training forward (z1, z2 records for the backward).
-    const char* arith = getenv("DIR_DIN_ARITH");
+    const char* arith = runtime_env("DIR_DIN_ARITH");
     const int ar = dw_arith_override >= 0 ? dw_arith_override
                                           : (arith && strcmp(arith, "f32") == 0) ? 0 : (arith && strcmp(arith, "bf16x3") == 0) ? 1 : 2;      // default: fp16 x 2
     const bool bf3 = ar != 0;
@@ -835,7 +835,7 @@ int launch_din_wave(hipStream_t st, const float* table, const int64_t* hist, con
     const kern_t kern = kerns[ar][which];
     if (!lds_limit(once[ar][which], (int)shmem, kern)) return fail(DIR_E_HIP, "din_wave_k: cannot reserve %zu B of LDS", shmem);
     // Up to DW_SLOTS launches may be in flight at once (distinct streams); a record is reused only after DW_SLOTS further launches.
-    const char* stat = getenv("DIR_DIN_STATIC");
+    const char* stat = runtime_env("DIR_DIN_STATIC");
     const bool static_split = stat ? atoi(stat) != 0 : bf3;
     const int slot = static_split ? -1 : (int)(dw_next_slot.fetch_add(1) % DW_SLOTS);
     const int64_t waves_wanted = (B + 1) / 2;            // a wave should see at least a couple of samples

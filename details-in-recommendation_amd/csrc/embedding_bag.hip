@@ -356,16 +356,11 @@ static int next_pow2(int v) {
     return p;
 }
 
-static int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 template <int LPS, int VEC, int KT, bool DO_FM, bool DO_OUT>
 static void launch_onehot_uf(int uf, bool stream_rows, int64_t work_blocks, hipStream_t st, const float* const* tables,
                              const int64_t* vocab, const int64_t* ids, int64_t sb, int64_t sf, int F, int K, int64_t B, float* out,
                              int64_t out_ld, float* fm) {
-    static const int nt_force = env_int("DIR_GATHER_NT", -1);   // development override: 0 / 1
+    static const int nt_force = dev_env_int("DIR_GATHER_NT", -1);   // development override: 0 / 1
     const bool nt_env = nt_force >= 0 ? nt_force != 0 : stream_rows;
 #define DIR_GO(UF)                                                                                                  \
     do {                                                                                                            \
@@ -390,7 +385,8 @@ template <bool DO_FM, bool DO_OUT>
 static int launch_onehot(const float* const* tables, const int64_t* vocab, int F, int K, const int64_t* ids, int64_t sb, int64_t sf,
                          int flags, int64_t B, float* out, int64_t out_ld, float* fm, hipStream_t st) {
     const bool vec = (K % 4 == 0) && (!DO_OUT || (out_ld % 4 == 0 && aligned16(out)));
-    static const int uf_env = env_int("DIR_GATHER_UF", 0);
+    static const char* uf_str = runtime_env("DIR_GATHER_UF");       // (read once: tests/test_gpu_parity.py runs each value in a process of its own)
+    static const int uf_env = uf_str ? atoi(uf_str) : 0;
     int uf = uf_env > 0 ? uf_env : (F == 26 ? 26 : (F % 13 == 0 ? 13 : (F > 48 ? 26 : 8)));   // measured at F = 100: 26 -> 260 us, 8 -> 298 us
     const bool stream_rows = (flags & DIR_GATHER_STREAM_ROWS) != 0;
     const int lps = next_pow2(vec ? K / 4 : K);

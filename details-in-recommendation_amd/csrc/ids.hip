@@ -462,64 +462,7 @@ __global__ __launch_bounds__(256) void bucket_scatter_k(const int64_t* __restric
 // gather; an overflow is reported through the flag and the caller repeats the lookup on the exact variable-size path.
 // gcount: P int32 counters, zero on entry, zeroed again by fin.
 // ------------------------------------------------------------------------------------------------
-// Elements per workgroup of the one-pass kernel = 256 * EPT.  Two opposing costs: few workgroups leave CUs idle (4096 elements
-// per workgroup on a 16 384 x 26 micro-batch: 104 workgroups, 24 us), many workgroups queue up on the P slab counters (same-address
-// atomics retire at ~90 per us: 1 664 workgroups on the whole 65 536 x 26 batch: 28 us).  The host picks EPT for ~400-800 workgroups.
-template <int BK_EPT>
-__global__ __launch_bounds__(256) void bucket_cap_k(const int64_t* __restrict__ ids, int64_t n,
-                                                    const int64_t* __restrict__ vocab, const int32_t* __restrict__ parts,
-                                                    const int32_t* __restrict__ first, int F, int P, int64_t cap,
-                                                    int32_t* __restrict__ gcount, int64_t* __restrict__ payload,
-                                                    int64_t* __restrict__ inv) {
-    __shared__ int cnt[64];
-    __shared__ int basev[64];
-    __shared__ FieldDiv fd[BK_MAXF];
-    if (threadIdx.x < 64) cnt[threadIdx.x] = 0;
-    for (int f = threadIdx.x; f < F && f < BK_MAXF; f += 256) fd[f] = make_fielddiv(vocab[f], parts ? parts[f] : P, first ? first[f] : 0);
-    __syncthreads();
-    constexpr int BKC_EPB = 256 * BK_EPT;
-    const int64_t base = (int64_t)blockIdx.x * BKC_EPB;
-    const int f0 = (int)(base % F), p0 = (int)(base % P);
-    const int lim = (int)((n - base) < BKC_EPB ? (n - base) : BKC_EPB);
-    int orank[BK_EPT];        // owner << 16 | rank inside the workgroup (rank < 4096); -1: pruned / inactive
-    int64_t pv[BK_EPT];
-#pragma unroll
-    for (int k = 0; k < BK_EPT; ++k) {
-        const int e = k * 256 + threadIdx.x;
-        const bool active = e < lim;
-        int o = 0;
-        bool keep = false;
-        pv[k] = -1;
-        if (active) {
-            BK_ROUTE_ELEMENT()
-            (void)i;
-            o = oo_;
-            keep = l >= 0;
-            pv[k] = pack_payload(l, F, f);
-        }
-        const int rank = wave_agg_rank(cnt, o, keep);
-        orank[k] = keep ? (o << 16) | rank : -1;
-    }
-    __syncthreads();
-    if (threadIdx.x < P) basev[threadIdx.x] = cnt[threadIdx.x] ? atomicAdd(&gcount[threadIdx.x], cnt[threadIdx.x]) : 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < BK_EPT; ++k) {
-        const int e = k * 256 + threadIdx.x;
-        if (e >= lim) continue;
-        int64_t dst = -1;
-        if (orank[k] >= 0) {
-            const int o = orank[k] >> 16;
-            const int64_t pos = (int64_t)basev[o] + (orank[k] & 0xffff);
-            if (pos < cap) {
-                slab_of(payload, o, cap)[1 + pos] = pv[k];
-                dst = (int64_t)o * cap + pos;
-            }
-        }
-        inv[base + e] = dst;
-    }
-}
-
+// (The finalize step as a kernel of its own: what an empty input and the de-duplicating bucket kernel launch.)
 __global__ void bucket_cap_fin_k(int32_t* __restrict__ gcount, int P, int64_t cap, int64_t* __restrict__ payload,
                                  int64_t* __restrict__ counts, int32_t* __restrict__ overflow, int64_t* __restrict__ stat) {
     const int o = threadIdx.x;
@@ -573,9 +516,10 @@ __device__ __forceinline__ void bucket_cap_finalize(int32_t* __restrict__ gcount
     }
 }
 
-// bucket_cap_k, round 4: the same one-pass routing with (a) the finalize step inside (the last workgroup to arrive at a device-scope
-// counter writes headers / demands / verdict: one launch, no 64-thread kernel behind it) and (b) workgroups of NT = 1024 threads.
-// What bounded bucket_cap_k (24 + 4.8 us for 1.7 M ids against ~8 us of traffic) is the returning atomic every workgroup issues on
+// The one-pass routing with (a) the finalize step inside (the last workgroup to arrive at a device-scope counter writes headers /
+// demands / verdict: one launch, no 64-thread kernel behind it) and (b) workgroups of NT = 1024 threads.  What bounded its round-3
+// form (256-thread workgroups + bucket_cap_fin_k: 24 + 4.8 us for 1.7 M ids against ~8 us of traffic; retired, profiles/NOTES.md
+// R4) is the returning atomic every workgroup issues on
 // the P slab counters: one address retires ~90 of them per us, all 832 workgroups were resident and issued theirs together, so the
 // last one waited ~9 us with nothing else to do.  Four times the threads per workgroup = a quarter of the reservations (208 at the
 // BASELINE size: ~2.3 us of queue) at the same number of resident waves.  (Tried first and dropped: persistent 256-thread workgroups
@@ -664,12 +608,12 @@ __global__ void slab_stat_k(const int64_t* __restrict__ recv, int n_slabs, int64
 // Fixed-capacity bucketing WITH duplicate removal ([TF-upstream] embedding_lookup_sparse gathers unique ids): one workgroup takes
 // 256 * EPT samples of ONE slot f, so a tile holds that many draws from one table and a hot row shows up many times in it.  Every
 // entry's row id goes into an LDS hash table (open addressing, 2 slots per entry); the first inserter of a
-// value owns it, reserves a slab position like bucket_cap_k does (one global atomic per owner and workgroup) and publishes it in
+// value owns it, reserves a slab position like bucket_cap2_k does (one global atomic per owner and workgroup) and publishes it in
 // the table; duplicates copy the owner's position into inv.  Duplicates that fall into DIFFERENT tiles are sent once per tile:
 // the lookup's result is the same, only the exchange carries a few more rows than an exact unique() would (on Zipf(1.05) ids over
 // 10^6 rows a 4096-sample tile removes ~49 % of the rows, an exact unique over 65 536 samples ~63 %) for none of a sort's cost.
 // ids are read with strides (sb, sf); inv is written FIELD-MAJOR, inv[f * B + b] (coalesced), and handed to the finish gather as a
-// strided [B, F] view.  gcount / fin as in bucket_cap_k: the demand the headers carry is the de-duplicated one.
+// strided [B, F] view.  gcount as in bucket_cap2_k, the headers by bucket_cap_fin_k: the demand the headers carry is the de-duplicated one.
 template <int EPT>
 __global__ __launch_bounds__(256) void bucket_cap_dedup_k(const int64_t* __restrict__ ids, int64_t sb, int64_t sf, int64_t B,
                                                           const int64_t* __restrict__ vocab, const int32_t* __restrict__ parts,
@@ -1029,15 +973,15 @@ extern "C" int dir_shard_bucket_cap(const int64_t* ids, int64_t n, const int64_t
     if ((int64_t)P * cap >= (int64_t)1 << 40) return fail(DIR_E_UNSUPPORTED, "dir_shard_bucket_cap: P*cap too large");
     hipStream_t st = as_stream(stream);
     int32_t* gcount = static_cast<int32_t*>(workspace);
-    static const int legacy = getenv("DIR_BUCKET_LEGACY") ? atoi(getenv("DIR_BUCKET_LEGACY")) : 0;      // development A/B switch
-    if (n > 0 && !legacy) {
-        static const int ept_env = dev_env_int("DIR_BUCKET_EPT", 0);
-        static const int nt_env = dev_env_int("DIR_BUCKET_NT", 0);
-        const int nt = nt_env ? nt_env : (n <= 256 * 1024 ? 256 : 1024);
-        const int ept = ept_env ? ept_env : 4;            // (1024 x 4: 16.1 us, x 8: 18.5, x 16: 30.3 at 1.7 M ids)
+    if (n > 0) {
 #define DIR_BK2(EPT, NT)                                                                                                              \
     hipLaunchKernelGGL((bucket_cap2_k<EPT, NT>), dim3((unsigned)((n + NT * EPT - 1) / (NT * EPT))), dim3(NT), 0, st, ids, n, vocab, parts, first, F, \
                        P, cap, gcount, payload, inv, counts, overflow, stat)
+#ifdef DIR_DEVELOPMENT      // the other workgroup shapes (1024 x 4: 16.1 us, x 8: 18.5, x 16: 30.3 at 1.7 M ids)
+        static const int ept_env = dev_env_int("DIR_BUCKET_EPT", 0);
+        static const int nt_env = dev_env_int("DIR_BUCKET_NT", 0);
+        const int nt = nt_env ? nt_env : (n <= 256 * 1024 ? 256 : 1024);
+        const int ept = ept_env ? ept_env : 4;
         if (nt != 256 && nt != 512 && nt != 1024) return fail(DIR_E_BADARG, "dir_shard_bucket_cap: DIR_BUCKET_NT must be 256, 512 or 1024");
         if (nt == 512 && ept != 8) return fail(DIR_E_BADARG, "dir_shard_bucket_cap: DIR_BUCKET_NT=512 is instantiated for DIR_BUCKET_EPT=8 only");
         if (nt == 256 && ept <= 4) DIR_BK2(4, 256);
@@ -1046,18 +990,13 @@ extern "C" int dir_shard_bucket_cap(const int64_t* ids, int64_t n, const int64_t
         else if (ept <= 4) DIR_BK2(4, 1024);
         else if (ept <= 8) DIR_BK2(8, 1024);
         else DIR_BK2(16, 1024);
+#else
+        if (n <= 256 * 1024) DIR_BK2(4, 256);
+        else DIR_BK2(4, 1024);
+#endif
 #undef DIR_BK2
         DIR_CHECK_LAUNCH("shard_bucket_cap");
         return DIR_OK;
-    }
-    if (n > 0) {
-#define DIR_BK(EPT)                                                                                                            \
-    hipLaunchKernelGGL((bucket_cap_k<EPT>), dim3((unsigned)((n + 256 * EPT - 1) / (256 * EPT))), dim3(256), 0, st, ids, n, vocab, \
-                       parts, first, F, P, cap, gcount, payload, inv)
-        if (n <= 768 * 1024) DIR_BK(4);
-        else if (n <= 2560 * 1024) DIR_BK(8);
-        else DIR_BK(16);
-#undef DIR_BK
     }
     hipLaunchKernelGGL(bucket_cap_fin_k, dim3(1), dim3(64), 0, st, gcount, P, cap, payload, counts, overflow, stat);
     DIR_CHECK_LAUNCH("shard_bucket_cap");

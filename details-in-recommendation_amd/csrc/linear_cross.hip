@@ -303,9 +303,11 @@ static int launch_cross_nv(int nv, int64_t work_blocks, size_t shmem, hipStream_
     } while (0)
     if (nv <= 2) DIR_GO(2);
     else if (nv <= 4) DIR_GO(4);
-    else if (nv <= 8) DIR_GO(8);
-    else if (nv <= 13) DIR_GO(13);
-    else DIR_GO(16);
+    else if constexpr (G == 64) {        // narrower groups are chosen only where they leave <= 4 chunks per lane
+        if (nv <= 8) DIR_GO(8);
+        else if (nv <= 13) DIR_GO(13);
+        else DIR_GO(16);
+    }
 #undef DIR_GO
     return 0;
 }
@@ -321,14 +323,10 @@ static int cross_dispatch(const float* x0, int64_t x_ld, const float* xinit, con
     const bool vec = (d % 4 == 0) && (x_ld % 4 == 0) && (!out || ((out_ld % 4 == 0) && aligned16(out))) && aligned16(x0) &&
                      (!xinit || aligned16(xinit)) && (L == 0 || (aligned16(w) && aligned16(b)));
     const int nchunk = vec ? d / 4 : d;
-    // smallest group width that keeps <= 16 chunks per lane
-    static const int g_env = getenv("DIR_CROSS_G") ? atoi(getenv("DIR_CROSS_G")) : 0;
     // lanes per sample: the smallest power of two (>= 8) that leaves <= 4 chunks per lane.  Few registers
     // per lane = many waves in flight; measured at d = 416: G = 8 / 16 / 32 -> 45.1 / 42.0 / 40.6 us.
     int G = 8;
     while (G < 64 && (nchunk + G - 1) / G > 4) G <<= 1;
-    if (g_env == 8 || g_env == 16 || g_env == 32 || g_env == 64) G = g_env;
-    while (G < 64 && (nchunk + G - 1) / G > 16) G <<= 1;
     const int nv = (nchunk + G - 1) / G;
     if (nv > 16) return fail(DIR_E_UNSUPPORTED, "dir_dcn_cross_f32: d=%d too wide for the register-resident kernel", d);
     const int spw = 64 / G;

@@ -577,13 +577,15 @@ static int tower_launch_rt(const char* name, const TowerParams& p, dir_stream_t 
 }
 template <bool GATHER, int NP>
 static int tower_launch(const char* name, const TowerParams& p, dir_stream_t stream) {
-    // DIR_TOWER_RT = 1 | 2 (read per call: an A/B switch): row tiles per wave, see TW_ROWS.  Default 1: with RT = 2 the workgroup reads half the
+    // DIR_TOWER_RT = 1 | 2 (-DDIR_DEVELOPMENT builds, read per call: an A/B switch): row tiles per wave, see TW_ROWS.  Default 1: with RT = 2 the workgroup reads half the
     // LDS bytes, but ONE wave per SIMD hides nothing -- mlp_dense 0.240 -> 0.286 ms, deepfm_full 0.278 -> 0.371, pipe busy 0.38 -> 0.29, the
-    // wave issuing a third of its cycles (profiles/NOTES.md R6.4): the stage's LDS reads (812 cycles per k-step and CU at fp16 x 2) were not
+    // wave issuing a third of its cycles (profiles/NOTES.md R6.5): the stage's LDS reads (812 cycles per k-step and CU at fp16 x 2) were not
     // what bounds this kernel.
-    const char* e = getenv("DIR_TOWER_RT");
-    const int rt = e ? atoi(e) : 1;
-    const int rc = rt == 2 ? tower_launch_rt<GATHER, NP, 2>(name, p, stream) : tower_launch_rt<GATHER, NP, 1>(name, p, stream);
+#ifdef DIR_DEVELOPMENT
+    const int rc = dev_env_int("DIR_TOWER_RT", 1) == 2 ? tower_launch_rt<GATHER, NP, 2>(name, p, stream) : tower_launch_rt<GATHER, NP, 1>(name, p, stream);
+#else
+    const int rc = tower_launch_rt<GATHER, NP, 1>(name, p, stream);
+#endif
     if (rc != DIR_OK) return rc;
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;

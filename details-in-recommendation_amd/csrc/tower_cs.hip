@@ -798,7 +798,7 @@ int tower_cs_launch_rs(const char* name, const TowerCsParams& p, dir_stream_t st
 // DIR_TOWER_RS = 1 (default) | 0, read per call (an A/B switch): the rows of every layer's input scaled by powers of two (see tc_row_sft)
 template <bool GATHER>
 int tower_cs_launch(const char* name, const TowerCsParams& p, dir_stream_t stream) {
-    const char* e = getenv("DIR_TOWER_RS");
+    const char* e = runtime_env("DIR_TOWER_RS");
     return (e && e[0] == '0') ? tower_cs_launch_rs<GATHER, false>(name, p, stream) : tower_cs_launch_rs<GATHER, true>(name, p, stream);
 }
 

@@ -14,7 +14,7 @@ import math
 import torch
 from torch import nn
 
-from .dense import dense_act, _RELUS, _MlpHeadFn, _Units1Fn, mlp_stack_supported, MLP_HEAD
+from .dense import dense_act, _RELUS, _MlpHeadFn, _Units1Fn, mlp_stack_supported
 from . import autograd as ag
 from . import ops
 from .deepfm import _BatchNormInfer, _dropout_train, _glorot_uniform_
@@ -110,7 +110,7 @@ class DeepCrossNetwork(nn.Module):
         elementwise backward (dense._Units1Fn).  As library ops the concat, the [B, d + h] x [d + h, 1] product and its backward were
         0.9 ms of the 8.8 ms step at 65 536 x (429 + 1024).  -> [B, 1], or None when the last layer is not covered (then the plain form)."""
         n = len(self.hidden)
-        if (not MLP_HEAD or not n or self.cross_layer_num <= 0 or self.hparams.get("dnn_dropout") or not self.training
+        if (not n or self.cross_layer_num <= 0 or self.hparams.get("dnn_dropout") or not self.training
                 or self.logits_layer.bias is None or self.hidden[-1].out_features > 4096):
             return None
         d = self.column_num

@@ -53,15 +53,12 @@ def pack_weight(weight):
     return buf[:, :Kd]
 
 
-STRIDED_WEIGHTS = _os.environ.get("DIR_DENSE_STRIDED_W", "1") != "0"      # development switch: 0 always makes the padded / transposed copy
-
-
 def _kernel_weight(x, weight):
     """The weight argument for ops.dense / ops.dense_gated in the training paths: the tensor (or `.t()` view) itself when the bf16x3 kernel
     will run -- its image is packed straight from any strides, a [400, 400] transpose copy per layer and step is 12 us -- otherwise the
     64-float-stride copy the fp32 kernel wants."""
     w = weight.detach()
-    if STRIDED_WEIGHTS and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and ops.dense_runs_bf16x3(x, w):
+    if x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and ops.dense_runs_bf16x3(x, w):
         return w
     return pack_weight(weight)
 
@@ -257,9 +254,6 @@ class _MlpStackFn(torch.autograd.Function):
         return (gx,) + tuple(grads)
 
 
-MLP_HEAD = _os.environ.get("DIR_MLP_HEAD", "1") != "0"        # development switch: 0 keeps the two-node formulation (mlp_stack + units1)
-
-
 class _MlpHeadFn(torch.autograd.Function):
     """A stack of dense + ReLU layers AND the units = 1 logit layer on top of it (deepFM.py:284-317, ESMM.py:130-147) as one autograd
     node.  Forward: dir_dense_f32 per layer, the head as a library GEMM with one output column.  Backward: the head's three gradients and the ReLU gate of the
@@ -310,7 +304,7 @@ class _MlpHeadFn(torch.autograd.Function):
 
 def mlp_head_supported(lins, head, x, activation):
     """mlp_stack_supported and a units = 1 head with a bias on top (the fused head backward reads the top layer's output once)."""
-    return (MLP_HEAD and mlp_stack_supported(lins, x, activation) and head.out_features == 1 and head.bias is not None
+    return (mlp_stack_supported(lins, x, activation) and head.out_features == 1 and head.bias is not None
             and head.in_features == lins[-1].out_features and head.in_features <= 4096)
 
 

@@ -950,8 +950,8 @@ def dense_auto_arith(M, Kd, N):
 _ABSMAX_WS = {}
 
 
-# development switch: 0 = the training gather leaves no row maxima on its output (the first dense layer runs its own max pass)
-GATHER_BITS = os.environ.get("DIR_GATHER_BITS", "1") != "0"
+# False: the training gather leaves no row maxima on its output, the first dense layer runs its own max pass (tests/test_gpu_backward.py sets it)
+GATHER_BITS = True
 
 
 def row_absmax_bits(x, want_all=True):
@@ -1161,7 +1161,7 @@ TOWER_GATHER = os.environ.get("DIR_TOWER_GATHER", "1")      # 0: DeepFM inferenc
 TOWER_KERNEL = os.environ.get("DIR_TOWER_KERNEL", "cs")
 TOWER_MIN_WIDTH = 128          # dense.tower_infer: a stage always computes 13 column tiles, so a narrower layer (ESMM's 80-wide one) pads more
                                # than the fusion saves (ESMM forward 0.574 ms layer by layer, 0.580 fused)
-TOWER = os.environ.get("DIR_TOWER", "auto")      # "0": never fuse (per-layer kernels)
+TOWER = "auto"      # "0": never fuse, per-layer kernels (tests/test_gpu_tower.py and tools/small_batch_probe.py assign it)
 _TOWER_IMAGES = VersionCache("tower_image", 256)
 
 
@@ -1687,7 +1687,7 @@ def din_attention_pool_backward(table, hist, hist_len, cand, W1, b1, W2, b2, W3,
         z = torch.zeros((0, K), **f32)
         return {"ids_h": hist.reshape(-1)[:0], "gh": z, "ga": z, "grows": z, "gW1": torch.zeros((4 * K, H1), **f32), "gb1": torch.zeros(H1, **f32),
                 "gW2": torch.zeros((H1, H2), **f32), "gb2": torch.zeros(H2, **f32), "gW3": torch.zeros(H2, **f32), "gb3": torch.zeros(1, **f32)}
-    use_rows = scores is not None and os.environ.get("DIR_DIN_BWD_ROWS", "1") != "0"
+    use_rows = scores is not None
     if saved is not None and not use_rows:
         raise ValueError("DIN backward: saved activations need the forward's scores")
     plan = saved[0] if saved is not None else DinTrainPlan(hist, hist_len)
@@ -1728,8 +1728,8 @@ def din_attention_pool_backward(table, hist, hist_len, cand, W1, b1, W2, b2, W3,
     W1 = args[0]
     C = W1[K:2 * K] - W1[2 * K:3 * K]
     a = table[cand.clamp(min=0)] * (cand >= 0).unsqueeze(1)
-    if _DIN_GA_LIBRARY or not dense_supported(S, C):
-        ga.addmm_(S, C.t())                           # (uncovered widths; DIR_DIN_GA_LIBRARY=1: development A/B switch)
+    if not dense_supported(S, C):
+        ga.addmm_(S, C.t())                           # (uncovered widths)
     else:
         ga.add_(dense(S, C.contiguous(), None, relu=False))
     gCt, gb1 = dense_dw(S, a, want_bias=True)            # S^T a [H1, K] and S's column sums in one pass (dir_dense_dw_small_f32 at 80 x 64)
@@ -1738,8 +1738,6 @@ def din_attention_pool_backward(table, hist, hist_len, cand, W1, b1, W2, b2, W3,
     return {"ids_h": _masked_rows(hist, valid, N), "gh": gh, "ga": ga, "grows": grows, "gW1": torch.cat([gA, gC, gA - gC, gWp], dim=0), "gb1": gb1,
             "gW2": gW2, "gb2": gb2, "gW3": gW3, "gb3": gb3}
 
-
-_DIN_GA_LIBRARY = os.environ.get("DIR_DIN_GA_LIBRARY", "0") == "1"
 
 # default arithmetic of cin_layer: "auto" (the split kernels on the shapes they cover, fp32 MFMA otherwise) | "f32" | "bf16x3" | "f16x2"
 CIN_ARITH = os.environ.get("DIR_CIN_ARITH", "auto")

@@ -4,7 +4,6 @@ current HIP stream; what the entries share -- the row-base prefix, the sort area
 sort -- lives in _SortedOpt."""
 import collections
 import ctypes
-import os
 
 import torch
 
@@ -47,8 +46,7 @@ class _SortedShare:
 def share_sorted_entries(a, b):
     """Let two sorted sparse optimisers over table sets with the same vocabularies share one sort per step (see _SortedShare).
     -> True if they were linked."""
-    if list(a.ts.vocab) != list(b.ts.vocab) or a.ts.F != b.ts.F or getattr(a, "method", "sorted") != "sorted" \
-            or os.environ.get("DIR_SHARE_SORT", "1") == "0":           # (development switch for A/B runs)
+    if list(a.ts.vocab) != list(b.ts.vocab) or a.ts.F != b.ts.F or getattr(a, "method", "sorted") != "sorted":
         return False
     a._share = b._share = _SortedShare()
     return True

@@ -218,8 +218,7 @@ class TrainStep:
         self._beta1 = float(betas[0])
         lr0 = learning_rate_decay(self.learning_rate_spec, 0)
         self.optimizer = None
-        if cls is torch.optim.Adam and self.params and all(p.is_cuda for p in self.params) \
-                and os.environ.get("DIR_TRAIN_FUSED_OPTIMIZER", "1") == "1" and "fused" not in kw:
+        if cls is torch.optim.Adam and self.params and all(p.is_cuda for p in self.params) and "fused" not in kw:
             try:      # one multi-tensor launch family per step instead of ~10 elementwise passes over every variable
                 self.optimizer = cls(self.params, lr=lr0, fused=True, **kw)
             except (RuntimeError, TypeError):

@@ -1331,7 +1331,7 @@ int dir_sparse_ftrl_rows_sorted_f32(float* const* rows, int F, const int64_t* id
                                     int64_t B, const int64_t* row_base, int64_t total_rows, void* workspace,
                                     int64_t workspace_bytes, const void* sorted_from, dir_stream_t stream);
 
-/* Diagnostic only (never on the product path): cycle stamps of the DIR_CIN_STAMP=1 build of the CIN kernel, summed
+/* Diagnostic only (never on the product path): cycle stamps of the CIN kernel under DIR_CIN_STAMP=1 (development build), summed
  * over waves since the last call: [0] chunk start -> end of its MFMA stream, [1] -> past the chunk barrier,
  * [2] chunks, [3] prologue, [4] epilogue, [5] waves.  Synchronises the device. */
 int dir_debug_cin_stamps(unsigned long long* out8);

@@ -105,3 +105,54 @@ def test_no_packed_fp32_beside_wide_mfma_in_the_built_objects(built_lib):
     per = isa_check.scan(text)
     assert per["victim"][0] == 1 and len(per["victim"][1]) == 1
     assert per["fine"][0] == 1 and per["fine"][1] == []
+
+
+PKG = os.path.join(ROOT, "details-in-recommendation_amd")
+
+
+def _csrc_sources():
+    d = os.path.join(PKG, "csrc")
+    return [(f, open(os.path.join(d, f)).read()) for f in sorted(os.listdir(d)) if f.endswith((".hip", ".cpp", ".hpp"))]
+
+
+def test_csrc_reads_the_environment_through_common_hpp_only():
+    """csrc/common.hpp holds the only getenv calls of the library: dev_env* (inert in a production build) and runtime_env (the four
+    switches the committed tests flip).  A bare getenv elsewhere is a switch the shipped library obeys and nobody tests."""
+    srcs = _csrc_sources()
+    assert len(srcs) >= 25
+    assert [f for f, txt in srcs if f != "common.hpp" and "getenv(" in txt] == []
+    assert "getenv(" in dict(srcs)["common.hpp"]
+
+
+def _switches_read():
+    """Every DIR_* name the package reads from the environment: string literals handed to os.environ.get / os.environ[...] in the Python
+    modules and to dev_env / dev_env_int / dev_env_ignored / runtime_env in csrc/."""
+    names = set()
+    for f in sorted(os.listdir(PKG)):
+        if f.endswith(".py"):
+            names |= set(re.findall(r"""environ(?:\.get\(|\[)\s*["'](DIR_[A-Z0-9_]+)["']""", open(os.path.join(PKG, f)).read()))
+    for _, txt in _csrc_sources():
+        names |= set(re.findall(r"""\b(?:dev_env\w*|runtime_env)\(\s*"(DIR_[A-Z0-9_]+)\"""", txt))
+    return names
+
+
+def _switches_documented():
+    """The names in the first column of the tables under INTEGRATION.md's "Environment switches" heading."""
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    section = doc.split("## Environment switches", 1)[1].split("\n## ", 1)[0]
+    names = set()
+    for line in section.split("\n"):
+        if line.startswith("|"):
+            names |= set(re.findall(r"DIR_[A-Z0-9_]+", line.split("|")[1]))
+    return names
+
+
+def test_integration_md_lists_exactly_the_switches_the_package_reads():
+    """Left out of both sides: DIR_BENCH_* (bench.py's own, not the package's) and the build-time DIR_DEVELOPMENT / DIR_NO_PK /
+    DIR_ABLATE (build.py reads them to choose compiler flags; no built library looks at them)."""
+    def kept(names):
+        return {n for n in names if not n.startswith("DIR_BENCH_") and n not in ("DIR_DEVELOPMENT", "DIR_NO_PK", "DIR_ABLATE")}
+    read, documented = kept(_switches_read()), kept(_switches_documented())
+    assert len(read) >= 30
+    assert sorted(read - documented) == [], "read by the package, missing from INTEGRATION.md's switch tables"
+    assert sorted(documented - read) == [], "in INTEGRATION.md's switch tables, read by nothing"
