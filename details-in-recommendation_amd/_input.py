@@ -214,7 +214,19 @@ def collect_ids(columns, features, device, memo=None):
         out = collect_ids(columns, features, device)
         memo[key] = out
         return out
-    got = [c.ids(features, device) for c in cats]
+    crossed = [i for i, c in enumerate(cats) if getattr(c, "is_crossed", False)]
+    if crossed:
+        # the crossed columns of one call are formed together: their one-hot ids are the rows of ONE [NX, B] matrix written by one launch
+        # (feature_column.cross_columns), which _columns_of_one_matrix below recognises -- a linear model over crosses stacks nothing
+        from .feature_column import cross_columns
+        got = [None] * len(cats)
+        for i, g in zip(crossed, cross_columns([cats[i] for i in crossed], features, device)):
+            got[i] = g
+        for i, c in enumerate(cats):
+            if got[i] is None:
+                got[i] = c.ids(features, device)
+    else:
+        got = [c.ids(features, device) for c in cats]
     if all(not isinstance(g, tuple) for g in got):
         B = got[0].numel()
         for g in got:

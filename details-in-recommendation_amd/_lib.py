@@ -209,6 +209,16 @@ SIGNATURES = {
     "dir_hash_bucket_i64_fields_device": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
     "dir_hash_bucket_bytes_device": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
     "dir_bucketize_f32": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp]),
+    "dir_fingerprint_cat64": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "dir_fingerprint64_batch": (c_i32, [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_i64), c_i64, ctypes.POINTER(ctypes.c_uint64)]),
+    "dir_fingerprint64_bytes_device": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    # the tables of the cross entries are HOST arrays (of device pointers / small integers)
+    "dir_cross_onehot_i64": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, ctypes.POINTER(ctypes.c_int32),
+                                     ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_i64), c_i32, c_i64,
+                                     c_vp, c_vp]),
+    "dir_cross_ragged_count_i64": (c_i32, [ctypes.POINTER(c_vp), c_i32, c_i64, c_vp, c_vp]),
+    "dir_cross_ragged_fill_i64": (c_i32, [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, ctypes.c_uint64, c_i64,
+                                          c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "dir_shard_div_owner": (None, [c_i64, c_i64, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i64)]),
     "dir_shard_route": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
     "dir_gather_rows_f32": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -207,6 +207,13 @@ def export_serving(model, export_dir, global_step=0):
             spec[c.key] = {"kind": "FixedLenFeature", "shape": list(c.shape), "dtype": "float32"}
         else:
             cat = categorical_of(c)
+            if getattr(cat, "is_crossed", False):       # [TF-upstream] _CrossedColumn parses its leaf keys: raw names as strings
+                for leaf in cat.keys:
+                    if isinstance(leaf, str):
+                        spec.setdefault(leaf, {"kind": "VarLenFeature", "dtype": "string"})
+                    else:
+                        spec.setdefault(leaf.key, {"kind": "VarLenFeature", "dtype": "int64"})
+                continue
             spec[cat.key] = {"kind": "VarLenFeature", "dtype": "int64"}
             if getattr(cat, "weight_key", None):
                 spec[cat.weight_key] = {"kind": "VarLenFeature", "dtype": "float32"}

@@ -240,6 +240,15 @@ __global__ void hash_bucket_bytes_k(const char* __restrict__ bytes, const int64_
     }
 }
 
+// the raw fingerprints of the same layout (what a crossed column chains: csrc/cross.hip)
+__global__ void fingerprint64_bytes_k(const char* __restrict__ bytes, const int64_t* __restrict__ offsets, int64_t n,
+                                      uint64_t* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = offsets[i], e = offsets[i + 1];
+        out[i] = fh::fingerprint64(bytes + b, (size_t)(e - b));
+    }
+}
+
 __global__ void bucketize_k(const float* __restrict__ x, int64_t n, const float* __restrict__ bd, int nb,
                             int64_t* __restrict__ out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -861,6 +870,24 @@ extern "C" int dir_hash_bucket_fast(const char* const* strs, const int64_t* lens
         DIR_CHECK_ARG(strs[i] || lens[i] == 0, "dir_hash_bucket_fast: null string %lld", (long long)i);
         out[i] = (int64_t)(fh::fingerprint64(strs[i], (size_t)lens[i]) % (uint64_t)num_buckets);
     }
+    return DIR_OK;
+}
+
+extern "C" int dir_fingerprint64_batch(const char* const* strs, const int64_t* lens, int64_t n, uint64_t* out) {
+    DIR_CHECK_ARG(strs && lens && out && n >= 0, "dir_fingerprint64_batch: bad argument");
+    for (int64_t i = 0; i < n; ++i) {
+        DIR_CHECK_ARG(lens[i] >= 0 && (strs[i] || lens[i] == 0), "dir_fingerprint64_batch: bad string %lld", (long long)i);
+        out[i] = fh::fingerprint64(strs[i], (size_t)lens[i]);
+    }
+    return DIR_OK;
+}
+
+extern "C" int dir_fingerprint64_bytes_device(const char* bytes, const int64_t* offsets, int64_t n, uint64_t* out, dir_stream_t stream) {
+    DIR_CHECK_ARG(n >= 0, "dir_fingerprint64_bytes_device: bad argument");
+    if (n == 0) return DIR_OK;
+    DIR_CHECK_ARG(offsets && out, "dir_fingerprint64_bytes_device: null pointer");
+    hipLaunchKernelGGL(fingerprint64_bytes_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, as_stream(stream), bytes, offsets, n, out);
+    DIR_CHECK_LAUNCH("fingerprint64_bytes");
     return DIR_OK;
 }
 

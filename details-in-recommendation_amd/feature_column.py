@@ -6,9 +6,11 @@ vocabulary) and turn a raw feature into int64 ids:
   hash      : FarmHash Fingerprint64(str(x)) mod buckets         models/DeepCrossNetwork/train.py:85-86
   vocabulary: index in the list, OOV -> -1 (dropped by the bag)  models/DeepCrossNetwork/train.py:63-82
   bucketized: number of boundaries <= x                          models/DeepFM/deepFM.py:95 (docstring)
-Column names follow [TF-upstream] naming (`<key>_embedding`, `<key>_indicator`, `<key>_bucketized`) because
+  crossed   : FingerprintCat64 chain over the keys mod buckets   models/ESMM/train.py:94
+Column names follow [TF-upstream] naming (`<key>_embedding`, `<key>_indicator`, `<key>_bucketized`, `<a>_X_<b>`) because
 DCN's input_layer concatenates columns sorted by name (DeepCrossNetwork.py:126).
 """
+import numbers
 from collections import namedtuple
 
 import torch
@@ -147,6 +149,99 @@ class WeightedCategoricalColumn(_Categorical):
         return vals, offs, w.to(device=device, dtype=torch.float32).reshape(-1)
 
 
+class CrossedColumn(_Categorical):
+    """crossed_column (models/ESMM/train.py:94).  [TF-upstream] _CrossedColumn / SparseCross with hashed output, stated and not verified
+    (DESIGN.md section 2): every leaf key gives 64 bits per entry -- an integer feature as it is, a string feature's Fingerprint64, a
+    categorical column's ids as column.ids() returns them --, chained through FingerprintCat64 from hash_key IN THE ORDER GIVEN, modulo
+    hash_bucket_size.  Nothing is dropped (-1 and "" are crossed like any value); the ids are in range by construction; no weights."""
+    is_crossed = True
+    range_checked = False
+
+    def __init__(self, keys, hash_bucket_size, hash_key=None):
+        if hash_bucket_size is None or hash_bucket_size < 1:
+            raise ValueError("hash_bucket_size must be at least 1. hash_bucket_size: {}".format(hash_bucket_size))
+        if not keys or len(keys) < 2:
+            raise ValueError("keys must be a list with length > 1. Given: {}".format(keys))
+        leaves = []
+        for k in keys:
+            if isinstance(k, CrossedColumn):
+                leaves += k.keys                      # a nested cross is its leaf keys, in order
+            elif isinstance(k, HashedCategoricalColumn):
+                raise ValueError("categorical_column_with_hash_bucket is not supported for crossing. Hashing before crossing will increase "
+                                 "probability of collision. Instead, use the feature name as a string. Given: {}".format(k.name))
+            elif isinstance(k, WeightedCategoricalColumn):
+                raise ValueError("a weighted_categorical_column cannot be crossed (a crossed column carries no weights). Given: {}".format(k.name))
+            elif isinstance(k, (str, _Categorical)):
+                leaves.append(k)
+            else:
+                raise ValueError("Unsupported key type. All keys must be either string, or categorical column. Given: {}".format(k))
+        if len(leaves) > ops.CROSS_MAX_KEYS:
+            raise ValueError("a crossed column takes at most %d leaf keys, got %d" % (ops.CROSS_MAX_KEYS, len(leaves)))
+        self.keys = tuple(leaves)
+        self.num_buckets = int(hash_bucket_size)
+        self.hash_key = ops.CROSS_HASH_KEY if hash_key is None else int(hash_key)
+        self.name = "_X_".join(sorted(k if isinstance(k, str) else k.name for k in leaves))
+        self.key = self.name
+
+    def ids(self, features, device):
+        return cross_columns([self], features, device)[0]
+
+
+def _cross_contribution(leaf, features, device):
+    """A leaf key's 64 bits per entry: -> int64 [B], or (values [nnz], offsets [B+1]) for a Ragged feature."""
+    if not isinstance(leaf, str):
+        got = leaf.ids(features, device)
+        return (got[0], got[1]) if isinstance(got, tuple) else got
+
+    def bits(raw):
+        if isinstance(raw, torch.Tensor):
+            if raw.dtype.is_floating_point or raw.dtype == torch.bool:
+                raise TypeError("crossed_column key %r: a %s feature cannot be crossed (integer or string keys only)" % (leaf, raw.dtype))
+            return raw.to(device=device, dtype=torch.int64).reshape(-1)
+        raw = list(raw)
+        if raw and all(isinstance(v, numbers.Integral) for v in raw):
+            return torch.tensor([int(v) for v in raw], dtype=torch.int64, device=device)
+        if any(isinstance(v, numbers.Number) for v in raw):
+            raise TypeError("crossed_column key %r: a float feature cannot be crossed (integer or string keys only)" % leaf)
+        return ops.fingerprint64_strings(raw).to(device)      # one host call for the batch, one upload
+
+    raw = features[leaf]
+    if isinstance(raw, Ragged):
+        return bits(raw.values), raw.offsets.to(device=device, dtype=torch.int64)
+    return bits(raw)
+
+
+def cross_columns(columns, features, device):
+    """The ids of several crossed columns over one features dict: a leaf key they share is turned into its contribution once, and ALL the
+    one-hot crosses are formed by one launch into one field-major [NX, B] matrix whose rows are handed out as views (what
+    _input.collect_ids wants: a linear model over crosses reads that matrix in place).  -> a list as column.ids() would give."""
+    srcs, index = [], {}
+    plans = []
+    for c in columns:
+        ks = []
+        for leaf in c.keys:
+            ident = leaf if isinstance(leaf, str) else id(leaf)
+            if ident not in index:
+                index[ident] = len(srcs)
+                srcs.append(_cross_contribution(leaf, features, device))
+            ks.append(index[ident])
+        plans.append(ks)
+    out = [None] * len(columns)
+    dense = [i for i, ks in enumerate(plans) if not any(isinstance(srcs[k], tuple) for k in ks)]
+    if dense:
+        used = list(dict.fromkeys(k for i in dense for k in plans[i]))
+        local = {k: j for j, k in enumerate(used)}
+        mat = ops.cross_hash([srcs[k] for k in used],
+                             [([local[k] for k in plans[i]], columns[i].num_buckets, columns[i].hash_key) for i in dense])
+        for j, i in enumerate(dense):
+            out[i] = mat[j]
+    for i, ks in enumerate(plans):
+        if out[i] is None:
+            vals, offs = ops.cross_hash_ragged([srcs[k] for k in ks], columns[i].num_buckets, columns[i].hash_key)
+            out[i] = (vals, offs, None)
+    return out
+
+
 class EmbeddingColumn(_Column):
     is_dense = True
 
@@ -194,6 +289,10 @@ def bucketized_column(source_column, boundaries):
 
 def weighted_categorical_column(categorical_column, weight_feature_key):
     return WeightedCategoricalColumn(categorical_column, weight_feature_key)
+
+
+def crossed_column(keys, hash_bucket_size, hash_key=None):
+    return CrossedColumn(keys, hash_bucket_size, hash_key)
 
 
 def embedding_column(categorical_column, dimension, combiner="mean", max_norm=None):

@@ -2121,6 +2121,137 @@ def hash_bucket_bytes(bytes_dev, offsets, num_buckets):
     return out
 
 
+# ---- feature crosses (crossed_column, ESMM/train.py:94) ---------------------------------------------
+CROSS_HASH_KEY = 0xDECAFCAFFE        # [TF-upstream] crossed_column's default hash_key
+CROSS_MAX_KEYS, CROSS_MAX, CROSS_MAX_SOURCES = 8, 16, 32      # per launch (include/dir_hip.h: dir_cross_onehot_i64)
+
+
+def fingerprint_cat64(a, b):
+    """[TF-upstream] FingerprintCat64 of two uint64 (host; the function the cross kernels chain)."""
+    return int(_lib.load().dir_fingerprint_cat64(int(a) & 0xFFFFFFFFFFFFFFFF, int(b) & 0xFFFFFFFFFFFFFFFF))
+
+
+def fingerprint64_strings(strings):
+    """Raw Fingerprint64 of every string in ONE host call -> CPU int64 tensor [n] holding the uint64 bit patterns."""
+    bs = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in strings]
+    n = len(bs)
+    arr = (ctypes.c_char_p * n)(*bs)
+    lens = (ctypes.c_int64 * n)(*[len(b) for b in bs])
+    out = (ctypes.c_uint64 * max(n, 1))()
+    _lib.check(_lib.load().dir_fingerprint64_batch(arr, lens, n, out))
+    return torch.frombuffer(out, dtype=torch.int64, count=n).clone() if n else torch.empty(0, dtype=torch.int64)
+
+
+def fingerprint64_bytes(bytes_dev, offsets):
+    """Byte strings already on the device (uint8 buffer + int64 offsets [n+1]) -> their raw Fingerprint64, int64 bit patterns [n]."""
+    if not isinstance(bytes_dev, torch.Tensor) or bytes_dev.dtype != torch.uint8 or not bytes_dev.is_cuda:
+        raise TypeError("bytes_dev must be a CUDA uint8 tensor")
+    _dev(offsets, torch.int64, "offsets")
+    n = offsets.numel() - 1
+    out = torch.empty(n, dtype=torch.int64, device=offsets.device)
+    _lib.check(_lib.load().dir_fingerprint64_bytes_device(_ptr(bytes_dev.contiguous()), _ptr(offsets.contiguous()), n, _ptr(out), _stream()))
+    return out
+
+
+def _cross_spec(cross, n_sources):
+    keys, buckets = [int(k) for k in cross[0]], int(cross[1])
+    hash_key = CROSS_HASH_KEY if len(cross) < 3 or cross[2] is None else int(cross[2])
+    if not 2 <= len(keys) <= CROSS_MAX_KEYS:
+        raise ValueError("a cross takes 2..%d keys, got %d" % (CROSS_MAX_KEYS, len(keys)))
+    if buckets < 1:
+        raise ValueError("hash_bucket_size must be at least 1")
+    if any(not 0 <= k < n_sources for k in keys):
+        raise ValueError("cross keys %r do not index the %d sources" % (keys, n_sources))
+    return keys, buckets, hash_key & 0xFFFFFFFFFFFFFFFF
+
+
+def cross_hash(sources, crosses, out=None):
+    """One-hot feature crosses.  sources: int64 CUDA vectors [B] (any stride: columns of one [B, F] matrix are read in place);
+    crosses: (key indices into sources in hashing order, hash_bucket_size[, hash_key]) each.  -> ids, field-major [NX, B], every cross that
+    fits one launch (16 crosses over 32 distinct sources) formed by that launch; larger sets are split over launches into the same matrix."""
+    if not sources or not crosses:
+        raise ValueError("cross_hash needs sources and crosses")
+    for i, s in enumerate(sources):
+        _dev(s, torch.int64, "sources[%d]" % i)
+        if s.dim() != 1 or s.numel() != sources[0].numel():
+            raise ValueError("sources must be vectors of one length")
+    specs = [_cross_spec(c, len(sources)) for c in crosses]
+    B, nx = sources[0].numel(), len(specs)
+    if out is None:
+        out = torch.empty((nx, B), dtype=torch.int64, device=sources[0].device)
+    elif out.shape != (nx, B) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous [%d, %d] matrix" % (nx, B))
+    _dev(out, torch.int64, "out")
+    lib, x0 = _lib.load(), 0
+    while x0 < nx:
+        used, x1 = [], x0                     # the longest run of crosses within the launch's limits
+        while x1 < nx and x1 - x0 < CROSS_MAX:
+            more = [k for k in dict.fromkeys(specs[x1][0]) if k not in used]
+            if len(used) + len(more) > CROSS_MAX_SOURCES:
+                break
+            used += more
+            x1 += 1
+        local = {k: i for i, k in enumerate(used)}
+        flat = [local[k] for sp in specs[x0:x1] for k in sp[0]]
+        n = x1 - x0
+        _lib.check(lib.dir_cross_onehot_i64((ctypes.c_void_p * len(used))(*[sources[k].data_ptr() for k in used]),
+                                            (ctypes.c_int64 * len(used))(*[sources[k].stride(0) if B > 1 else 1 for k in used]), len(used),
+                                            (ctypes.c_int32 * len(flat))(*flat), (ctypes.c_int32 * n)(*[len(sp[0]) for sp in specs[x0:x1]]),
+                                            (ctypes.c_uint64 * n)(*[sp[2] for sp in specs[x0:x1]]),
+                                            (ctypes.c_int64 * n)(*[sp[1] for sp in specs[x0:x1]]), n, B, _ptr(out[x0]) if B else None, _stream()))
+        x0 = x1
+    return out
+
+
+def cross_hash_ragged(keys, hash_bucket_size, hash_key=None, B=None, capacity=None, out=None, return_status=False):
+    """One feature cross whose keys may be ragged.  keys: an int64 CUDA vector [B] (one entry per row) or (values [nnz], offsets [B+1]) each,
+    in hashing order.  -> (values, offsets [B+1]): row b holds the cartesian product of the keys' entries of row b, last key fastest; a row
+    with an empty key has none.  One count launch, a cumsum, ONE size read-back, one fill launch parallel over the output entries.
+    capacity / out: the caller knows the size (no read-back); the fill then verifies it on the device -- return_status=True adds the int32
+    status word (0 = filled, 1 = the size did not match and nothing was written)."""
+    vals, offs = [], []
+    for i, k in enumerate(keys):
+        v, o = (k[0], k[1]) if isinstance(k, tuple) else (k, None)
+        _dev(v, torch.int64, "keys[%d]" % i)
+        if o is not None:
+            o = _dev(o, torch.int64, "keys[%d] offsets" % i).contiguous()
+            v = v.contiguous() if v.numel() else o          # (a key without entries: any valid pointer, never read)
+        elif v.dim() != 1:
+            raise ValueError("a one-hot key must be a vector")
+        vals.append(v)
+        offs.append(o)
+    if not 2 <= len(vals) <= CROSS_MAX_KEYS:
+        raise ValueError("a cross takes 2..%d keys, got %d" % (CROSS_MAX_KEYS, len(vals)))
+    if int(hash_bucket_size) < 1:
+        raise ValueError("hash_bucket_size must be at least 1")
+    sizes = {(o.numel() - 1) if o is not None else v.numel() for v, o in zip(vals, offs)} | ({int(B)} if B is not None else set())
+    if len(sizes) != 1:
+        raise ValueError("keys disagree on the batch size")
+    B, dev, nk, lib = sizes.pop(), vals[0].device, len(vals), _lib.load()
+    optr = (ctypes.c_void_p * nk)(*[o.data_ptr() if o is not None else None for o in offs])
+    out_offsets = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    if B:
+        counts = torch.empty(B, dtype=torch.int64, device=dev)
+        _lib.check(lib.dir_cross_ragged_count_i64(optr, nk, B, _ptr(counts), _stream()))
+        torch.cumsum(counts, 0, out=out_offsets[1:])
+    if capacity is None:
+        capacity = int(out.numel()) if out is not None else int(out_offsets[-1])         # the one read-back
+        if capacity >= 1 << 40:
+            raise ValueError("the cross of these keys has more than 2^40 entries")
+    if out is None:
+        out = torch.empty(capacity, dtype=torch.int64, device=dev)
+    _dev(out, torch.int64, "out")
+    if out.numel() < capacity or not out.is_contiguous():
+        raise ValueError("out must be contiguous and hold `capacity` entries")
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    hk = CROSS_HASH_KEY if hash_key is None else int(hash_key)
+    _lib.check(lib.dir_cross_ragged_fill_i64((ctypes.c_void_p * nk)(*[v.data_ptr() for v in vals]), optr,
+                                             (ctypes.c_int64 * nk)(*[v.stride(0) if o is None and B > 1 else 1 for v, o in zip(vals, offs)]), nk,
+                                             hk & 0xFFFFFFFFFFFFFFFF, int(hash_bucket_size), B, _ptr(out_offsets), capacity, _ptr(out),
+                                             _ptr(status), _stream()))
+    return (out[:capacity], out_offsets, status) if return_status else (out[:capacity], out_offsets)
+
+
 def bucketize(x, boundaries):
     """bucketized_column: number of boundaries <= x -> int64 ids."""
     _dev(x, torch.float32, "x")

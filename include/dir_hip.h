@@ -407,6 +407,42 @@ int dir_bucketize_f32(const float* x, int64_t n, const float* boundaries, int nb
                       dir_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * A3  feature crosses.
+ * Replaces: tf.feature_column.crossed_column(["workclass", "education"], 128)   models/ESMM/train.py:94
+ *   [TF-upstream] SparseCross with hashed output: h = hash_key; for every leaf key in order
+ *   h = FingerprintCat64(h, contribution); id = h mod hash_bucket_size (unsigned).  A contribution is 64 bits:
+ *   an integer feature as it is, a string's Fingerprint64, a categorical column's id.
+ * dir_fingerprint_cat64: HOST, compiled from the inline function the kernels call.
+ * dir_fingerprint64_batch: HOST, the raw fingerprints of n strings (dir_hash_bucket_fast without the modulo).
+ * dir_fingerprint64_bytes_device: device kernel, the raw fingerprints of byte strings laid out as for
+ *   dir_hash_bucket_bytes_device.
+ * dir_cross_onehot_i64: ONE launch forms nx crosses of one id per sample into out, field-major [nx, B].
+ *   All table arguments are HOST arrays, copied into the kernel arguments: src_ptrs / src_strides [n_src] are the
+ *   source columns (DEVICE pointers and element strides: a column of a [B, F] matrix is read in place);
+ *   key_count [nx] the number of keys of every cross and key_index their indices into the source table,
+ *   concatenated in hashing order; hash_keys / buckets [nx].  Limits (argument errors): 2..8 keys per cross,
+ *   1..16 crosses and 1..32 source columns per launch.  A source is loaded once per sample.
+ * dir_cross_ragged_count_i64 / dir_cross_ragged_fill_i64: ONE cross whose keys may hold any number of entries per
+ *   row.  values / offsets / strides are HOST arrays [nk] of DEVICE pointers: offsets[k] != NULL -> row b of key k is
+ *   values[k][offsets[k][b] .. offsets[k][b+1]); offsets[k] == NULL -> its one entry values[k][b * strides[k]].
+ *   count writes counts[b] = the product of the keys' lengths in row b, clamped to 2^40 (more than any capacity).
+ *   The caller forms out_offsets [B+1] (exclusive prefix sum, out_offsets[B] = the total) and reads the total back.
+ *   fill writes row b's products to out[out_offsets[b] ..), last key fastest, parallel over output entries;
+ *   capacity = the words behind out: if out_offsets[B] != capacity it sets *status = 1 and writes nothing, else
+ *   *status = 0.
+ * ------------------------------------------------------------------------------------------ */
+uint64_t dir_fingerprint_cat64(uint64_t a, uint64_t b);
+int dir_fingerprint64_batch(const char* const* strs, const int64_t* lens, int64_t n, uint64_t* out);
+int dir_fingerprint64_bytes_device(const char* bytes, const int64_t* offsets, int64_t n, uint64_t* out, dir_stream_t stream);
+int dir_cross_onehot_i64(const int64_t* const* src_ptrs, const int64_t* src_strides, int n_src, const int32_t* key_index,
+                         const int32_t* key_count, const uint64_t* hash_keys, const int64_t* buckets, int nx, int64_t B,
+                         int64_t* out, dir_stream_t stream);
+int dir_cross_ragged_count_i64(const int64_t* const* offsets, int nk, int64_t B, int64_t* counts, dir_stream_t stream);
+int dir_cross_ragged_fill_i64(const int64_t* const* values, const int64_t* const* offsets, const int64_t* strides, int nk,
+                              uint64_t hash_key, int64_t buckets, int64_t B, const int64_t* out_offsets, int64_t capacity,
+                              int64_t* out, int32_t* status, dir_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * A12 row sharding, TF 'div' rule.
  * Replaces: min_max_variable_partitioner + partition_strategy='div'
  *           models/DeepFM/deepFM.py:163-167
