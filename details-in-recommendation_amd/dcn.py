@@ -108,7 +108,8 @@ class DeepCrossNetwork(nn.Module):
         deep share as one autograd node with the last hidden layer (dense._MlpHeadFn: its backward takes dL/dlogit through the logit
         weights and the layer's ReLU in one pass over the activation, dir_units1_relu_backward_f32), the cross share with the
         elementwise backward (dense._Units1Fn).  As library ops the concat, the [B, d + h] x [d + h, 1] product and its backward were
-        0.9 ms of the 8.8 ms step at 65 536 x (429 + 1024).  -> [B, 1], or None when the last layer is not covered (then the plain form)."""
+        0.9 ms of the 8.8 ms step at 65 536 x (429 + 1024).  -> [B, 1]; where the last layer is not covered (a batch under dense.MIN_ROWS) the plain concat + dense(1) on the layers already run; None
+        before anything has run when the model has no such form (no hidden layer, no cross layer, dropout, eval())."""
         n = len(self.hidden)
         if (not n or self.cross_layer_num <= 0 or self.hparams.get("dnn_dropout") or not self.training
                 or self.logits_layer.bias is None or self.hidden[-1].out_features > 4096):
@@ -123,7 +124,10 @@ class DeepCrossNetwork(nn.Module):
             net = dense_act(lin, net, self.activation, bn=bn)
         last = self.hidden[-1]
         if not mlp_stack_supported([last], net, self.activation):
-            return None
+            # the plain form from here: the layers below have run, and their batch norms have advanced the moving statistics -- once per step
+            # (returning None sent forward() through deep_architecture, which ran them a second time at every batch under dense.MIN_ROWS)
+            deep = dense_act(last, net, self.activation)
+            return self.logits_layer(torch.cat([cross, deep], dim=-1))           # :136-137
         wl = self.logits_layer.weight                                            # [1, d + h]
         from . import dense as _dense
         _dense._FWD_BOUNDED[0] = bool(self.batch_norm) and n >= 2              # the last layer reads a batch-normalised activation: fp16 x 2 kernels

@@ -2310,3 +2310,40 @@ def test_captured_step_keeps_caches_honest(built_lib):
         step(md, odd, old_, feats(i), labels[i])
     torch.cuda.synchronize()
     assert all(torch.equal(x, y) for x, y in zip(mc.parameters(), md.parameters())), "a graph captured behind valid caches trained against stale images"
+
+
+@pytest.mark.parametrize("B", [300, 6144])
+def test_dcn_training_step_advances_the_moving_statistics_once(built_lib, monkeypatch, B):
+    """With the PRODUCT's dense.MIN_ROWS (6144; the suite's environment sets 1) a batch below it has no fused last layer, and forward() used
+    to run the hidden layers under it a second time through deep_architecture: two launches of dir_bn_train_stats_f32 per batch norm and
+    step, the moving statistics advanced twice.  One launch per batch norm, and moving = moving * momentum + batch * (1 - momentum) once,
+    on both sides of the threshold."""
+    from dir_amd.dcn import DeepCrossNetwork
+    from dir_amd import feature_column as fc
+    from dir_amd import dense as D, _lib
+    monkeypatch.setattr(D, "MIN_ROWS", 6144)
+    lib = _lib.load()
+    calls = []
+    real = lib.dir_bn_train_stats_f32
+    monkeypatch.setattr(lib, "dir_bn_train_stats_f32", lambda *a: (calls.append(1), real(*a))[1])
+    g = torch.Generator().manual_seed(B)
+    F, K, V = 4, 8, 50
+    cols = [fc.embedding_column(fc.categorical_column_with_identity("C%d" % i, V), K) for i in range(F)] + [fc.numeric_column("x")]
+    dcn = DeepCrossNetwork(columns=cols, cross_layer_num=2, dnn_hidden_units=[32, 32, 16], batch_norm=True).cuda().train()
+    feats = {"C%d" % i: torch.randint(0, V, (B,), generator=g).cuda() for i in range(F)}
+    feats["x"] = torch.rand(B, generator=g).cuda()
+    with torch.no_grad():
+        for bn in dcn.bns:
+            bn.moving_mean.copy_(torch.randn(bn.moving_mean.shape, generator=g) * 0.2)
+    before = [bn.moving_mean.double().clone() for bn in dcn.bns]
+    dcn(feats).sum().backward()
+    assert len(calls) == len(dcn.bns) == 2
+    # the first batch norm's batch mean in float64, from the module's own input layer and first layer weights
+    with torch.no_grad():
+        x0 = dcn.input_layer(feats).double()
+        y = torch.relu(x0 @ dcn.hidden[0].weight.double().t() + dcn.hidden[0].bias.double())
+    m = dcn.bns[0].momentum
+    want = before[0] * m + y.mean(dim=0) * (1 - m)
+    assert float((dcn.bns[0].moving_mean.double() - want).abs().max()) <= 1e-5 * (1 + float(want.abs().max()))
+    twice = want * m + y.mean(dim=0) * (1 - m)
+    assert float((twice - want).abs().max()) > 1e-4                                # (the bar tells one update from two)
