@@ -172,8 +172,12 @@ struct DpDesc {
     int rowbase;            // block-relative index of the pass's first row
     int nrows;              // rows of the block inside the pass (0 .. 32; 0 only for a block of empty samples)
     long long sb;           // the block's first sample
-    int sj[2];              // per lane and tile: (sample in block << 16) | history position (| DP_MASKED once the id has landed); -1: no row
+    int sj[2];              // per lane and tile: (sample in block << PSH) | history position (| DP_MASKED once the id has landed); -1: no row
 };
+// PSH: the width of sj's position field.  16 bits serve T <= 65 535 (din_pack_covers: every shape the product runs); the WIDE instantiations
+// of din_pack_k keep 20 for the histories beyond (din_pack_long_covers: T <= 2^20, the sample in bits 20 .. 23, below DP_MASKED).
+constexpr int DP_T_NARROW = 65535, DP_T_WIDE = 1 << 20;
+template <bool WIDE> struct DpPos { static constexpr int PSH = WIDE ? 20 : 16, MASK = (1 << PSH) - 1; };
 
 // The three layers for the NT row tiles of a pass -> the rows' scores sc (b3 included), identical in the four lane groups of a row.
 template <int NT, int ACT>
@@ -389,7 +393,7 @@ __global__ __launch_bounds__(256) void din_pack_scores_k(float* __restrict__ sco
     }
 }
 
-template <int ACT, bool SCORES, bool NORM>
+template <int ACT, bool SCORES, bool NORM, bool WIDE>
 __global__ __launch_bounds__(64 * DP_WAVES, 2) void din_pack_k(const float* __restrict__ table, const int64_t* __restrict__ hist,
                                                                const int32_t* __restrict__ hist_len, const int64_t* __restrict__ cand, int T,
                                                                const DpImg* __restrict__ img, const float* __restrict__ b3,
@@ -398,6 +402,7 @@ __global__ __launch_bounds__(64 * DP_WAVES, 2) void din_pack_k(const float* __re
                                                                long long chunk, int w0) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dp_smem[];
     DpSh& sh = *reinterpret_cast<DpSh*>(dp_smem);
+    constexpr int PSH = DpPos<WIDE>::PSH, PMASK = DpPos<WIDE>::MASK;
     const float* const actl = sh.w.act;
     const int tid = threadIdx.x, lane = tid & 63, r16 = lane & 15, kk = lane >> 4;
     const int w = dp_uni(tid >> 6);
@@ -542,11 +547,11 @@ __global__ __launch_bounds__(64 * DP_WAVES, 2) void din_pack_k(const float* __re
             }
             a_cur = i;
             if (q0 < a_R) {
-                d.sj[0] = (s0 << 16) | (q0 - p0);
+                d.sj[0] = (s0 << PSH) | (q0 - p0);
                 off0 = (unsigned int)(s0 * T + (q0 - p0));
             }
             if (q1 < a_R) {
-                d.sj[1] = (s1 << 16) | (q1 - p1);
+                d.sj[1] = (s1 << PSH) | (q1 - p1);
                 off1 = (unsigned int)(s1 * T + (q1 - p1));
             }
         }
@@ -665,7 +670,7 @@ __global__ __launch_bounds__(64 * DP_WAVES, 2) void din_pack_k(const float* __re
         fetch(dB, idB, cidB, hvn);          // the next pass's rows (its ids were issued a pass ago)
         advance(dA, idA, cidA);             // the ids of the pass after it
         // ---- this pass: the three layers for its rows ---------------------------------------------------------------------------------------
-        const int srow[2] = {dC.sj[0] < 0 ? -1 : (dC.sj[0] >> 16) & 0xff, dC.sj[1] < 0 ? -1 : (dC.sj[1] >> 16) & 0xff};      // the row's sample, -1: no row
+        const int srow[2] = {dC.sj[0] < 0 ? -1 : (dC.sj[0] >> PSH) & 0xff, dC.sj[1] < 0 ? -1 : (dC.sj[1] >> PSH) & 0xff};      // the row's sample, -1: no row
         const int smem[2] = {(dC.sj[0] & DP_MASKED) ? -1 : srow[0], (dC.sj[1] & DP_MASKED) ? -1 : srow[1]};                  // ... -1 also for a masked position
         const int so[2] = {srow[0] < 0 ? 0 : srow[0], srow[1] < 0 ? 0 : srow[1]};
         float sc[2] = {0.f, 0.f};
@@ -706,16 +711,16 @@ __global__ __launch_bounds__(64 * DP_WAVES, 2) void din_pack_k(const float* __re
                         m_run = mx;
                         if (SCORES && kk == 0) {
                             const long long row = (dC.sb + i) * T;
-                            if (srow[0] == i) scores[row + (dC.sj[0] & 0xffff)] = x0;
-                            if (srow[1] == i) scores[row + (dC.sj[1] & 0xffff)] = x1;
+                            if (srow[0] == i) scores[row + (dC.sj[0] & PMASK)] = x0;
+                            if (srow[1] == i) scores[row + (dC.sj[1] & PMASK)] = x1;
                         }
                     } else {
                         w0_ = mem0 ? sc[0] : 0.f;
                         w1_ = mem1 ? sc[1] : 0.f;
                         if (SCORES && kk == 0) {
                             const long long row = (dC.sb + i) * T;
-                            if (srow[0] == i) scores[row + (dC.sj[0] & 0xffff)] = w0_;
-                            if (srow[1] == i) scores[row + (dC.sj[1] & 0xffff)] = w1_;
+                            if (srow[0] == i) scores[row + (dC.sj[0] & PMASK)] = w0_;
+                            if (srow[1] == i) scores[row + (dC.sj[1] & PMASK)] = w1_;
                         }
                     }
 #pragma unroll
@@ -748,8 +753,10 @@ __global__ __launch_bounds__(64 * DP_WAVES, 2) void din_pack_k(const float* __re
 }  // namespace
 
 bool din_pack_covers(int K, int T, int H1, int H2) {
-    return K == DP_K && T >= 1 && T <= 65535 && H1 > 0 && H2 > 0 && H1 <= DP_H1P && H2 <= DP_H2P && !(H1 & 3) && !(H2 & 3);
+    return K == DP_K && T >= 1 && T <= DP_T_NARROW && H1 > 0 && H2 > 0 && H1 <= DP_H1P && H2 <= DP_H2P && !(H1 & 3) && !(H2 & 3);
 }
+// the same unit with a history beyond the 16-bit position field: the WIDE instantiations (a block of 16 samples is 2^24 rows at most)
+bool din_pack_long_covers(int K, int T, int H1, int H2) { return T > DP_T_NARROW && T <= DP_T_WIDE && din_pack_covers(K, 1, H1, H2); }
 
 static void din_pack_chunks(int64_t B, int64_t& chunk, int& nchunk) {
     chunk = 64;                  // the range search scans one chunk per boundary: small chunks, at most 1024 of them
@@ -794,15 +801,19 @@ int launch_din_pack(hipStream_t st, const float* table, const int64_t* hist, con
     const int w0 = w0e ? (atoi(w0e) < 0 ? 0 : atoi(w0e) > 64 ? 64 : atoi(w0e)) : 5;
     typedef void (*kern_t)(const float*, const int64_t*, const int32_t*, const int64_t*, int, const DpImg*, const float*, long long, float*, float*,
                            float*, const int*, int, long long, int);
-    static const kern_t kerns[3][2][2] = {{{&din_pack_k<0, false, false>, &din_pack_k<0, false, true>}, {&din_pack_k<0, true, false>, &din_pack_k<0, true, true>}},
-                                          {{&din_pack_k<1, false, false>, &din_pack_k<1, false, true>}, {&din_pack_k<1, true, false>, &din_pack_k<1, true, true>}},
-                                          {{&din_pack_k<2, false, false>, &din_pack_k<2, false, true>}, {&din_pack_k<2, true, false>, &din_pack_k<2, true, true>}}};
+#define DP_KERNS(W)                                                                                                                                          \
+    {{{&din_pack_k<0, false, false, W>, &din_pack_k<0, false, true, W>}, {&din_pack_k<0, true, false, W>, &din_pack_k<0, true, true, W>}},                 \
+     {{&din_pack_k<1, false, false, W>, &din_pack_k<1, false, true, W>}, {&din_pack_k<1, true, false, W>, &din_pack_k<1, true, true, W>}},                 \
+     {{&din_pack_k<2, false, false, W>, &din_pack_k<2, false, true, W>}, {&din_pack_k<2, true, false, W>, &din_pack_k<2, true, true, W>}}}
+    static const kern_t kerns[2][3][2][2] = {DP_KERNS(false), DP_KERNS(true)};
+#undef DP_KERNS
     if (activation < 0 || activation > 2) return fail(DIR_E_UNSUPPORTED, "din_pack_k: activation %d (0 sigmoid, 1 PReLU, 2 Dice)", activation);
-    static LdsOnce once[3][2][2];
-    const int sco = scores ? 1 : 0, nrm = normalize ? 1 : 0;
+    if (chunk * ((int64_t)T + 64) > 0x7fffffff) return fail(DIR_E_UNSUPPORTED, "din_pack_k: B=%lld at T=%d: a chunk's weight leaves 31 bits", (long long)B, T);
+    static LdsOnce once[2][3][2][2];
+    const int sco = scores ? 1 : 0, nrm = normalize ? 1 : 0, wide = T > DP_T_NARROW ? 1 : 0;
     const size_t shmem = sizeof(DpSh);
-    const kern_t kern = kerns[activation][sco][nrm];
-    if (!lds_limit(once[activation][sco][nrm], (int)shmem, kern)) return fail(DIR_E_HIP, "din_pack_k: cannot reserve %zu B of LDS", shmem);
+    const kern_t kern = kerns[wide][activation][sco][nrm];
+    if (!lds_limit(once[wide][activation][sco][nrm], (int)shmem, kern)) return fail(DIR_E_HIP, "din_pack_k: cannot reserve %zu B of LDS", shmem);
     hipLaunchKernelGGL(din_pack_sums_k, dim3((unsigned)((nchunk + 3) / 4)), dim3(256), 0, st, hist_len, T, (long long)B, (long long)chunk, nchunk, w0, csum);
     const int64_t waves_wanted = (B + 1) / 2;            // a wave should see at least a couple of samples
     int64_t nwg = (waves_wanted + DP_WAVES - 1) / DP_WAVES;
@@ -845,8 +856,8 @@ extern "C" int dir_din_attention_pool_packed_f32(const float* table, int K, cons
     using namespace dir;
     const char* name = "dir_din_attention_pool_packed_f32";
     DIR_CHECK_ARG(K > 0 && T > 0 && H1 > 0 && H2 > 0 && B >= 0, "%s: K=%d T=%d H1=%d H2=%d", name, K, T, H1, H2);
-    if (!din_pack_covers(K, T, H1, H2))
-        return fail(DIR_E_UNSUPPORTED, "%s: covers K = 64, H1 <= 80, H2 <= 48 (multiples of 4), T <= 65535 (K=%d T=%d H1=%d H2=%d)", name, K, T, H1, H2);
+    if (!din_pack_covers(K, T, H1, H2) && !din_pack_long_covers(K, T, H1, H2))
+        return fail(DIR_E_UNSUPPORTED, "%s: covers K = 64, H1 <= 80, H2 <= 48 (multiples of 4), T <= 1048576 (K=%d T=%d H1=%d H2=%d)", name, K, T, H1, H2);
     if (B == 0) return DIR_OK;
     DIR_CHECK_ARG(table && hist && cand && b3 && out && workspace && (image || (W1 && b1 && W2 && b2 && W3)), "%s: null pointer", name);
     if (!aligned16(table) || !aligned16(workspace) || !aligned16(out) || !aligned16(image))

@@ -604,6 +604,12 @@ def din_pack_covers(K, T, H1, H2):
     return K == 64 and 1 <= T <= 65535 and 0 < H1 <= 80 and 0 < H2 <= 48 and H1 % 4 == 0 and H2 % 4 == 0
 
 
+def din_long_covers(K, T, H1, H2):
+    """Histories beyond din_pack_covers (65 535 < T <= 2^20): no other forward kernel holds them (din_wave_k: T <= 64; din_k: the whole
+    history in LDS), and the same entry runs them on its instantiations with the wider position field."""
+    return 65535 < T <= (1 << 20) and din_pack_covers(K, 1, H1, H2)
+
+
 _DIN_PACK_IMAGES = VersionCache("din_pack_image", 64)
 
 
@@ -672,7 +678,7 @@ def din_attention_pool(table, hist, hist_len, cand, W1, b1, W2, b2, W3, b3, norm
         ap = _dev(act_params.contiguous(), torch.float32, "act_params")
     rsrc = range_of if range_of is not None else (table, W1, W2, W3)
     code = din_arith(rsrc[0], rsrc[1:4], arith) if B > 0 else -1
-    if code == DIN_ARITHS["f16x2"] and DIN_PACKED and din_pack_covers(K, T, H1, H2):
+    if code == DIN_ARITHS["f16x2"] and ((DIN_PACKED and din_pack_covers(K, T, H1, H2)) or din_long_covers(K, T, H1, H2)):
         # round 6: the packed kernel (rows of consecutive samples end to end in the MFMA tiles, a static equal-weight partition of the samples)
         lib = _lib.load()
         ws = _din_pack_ws(table.device, int(lib.dir_din_pack_workspace_bytes(B, 1 if want_scores else 0)))

@@ -1132,7 +1132,8 @@ int dir_din_attention_pool_arith_f32(const float* table, int K, const int64_t* h
                                      const float* W1, const float* b1, int H1, const float* W2, const float* b2, int H2, const float* W3,
                                      const float* b3, int normalize, int activation, const float* act_params, int arith, int64_t B, float* out,
                                      float* scores, dir_stream_t stream);
-/* The PACKED form of the (K = 64, H1 <= 80, H2 <= 48; any T <= 65 535) unit on fp16 x 2 (round 6; csrc/din_pack.hip): a wave lays the valid
+/* The PACKED form of the (K = 64, H1 <= 80, H2 <= 48; any T <= 65 535, and up to 2^20 on instantiations with a wider position field: the only
+ * forward for histories that long; lengths outside [0, T] are held to it) unit on fp16 x 2 (round 6; csrc/din_pack.hip): a wave lays the valid
  * history rows of a run of consecutive samples end to end in 16-row MFMA tiles (no per-sample tile padding: lengths U{1..50} cost 26 rows, not
  * 33), forms the per-sample term of 16 samples as one MFMA operand, and takes its samples from a STATIC equal-weight partition (no queue
  * atomics; bit for bit the same result on every run).  Same definition, arguments and outputs as dir_din_attention_pool_arith_f32 with

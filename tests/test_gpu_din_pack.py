@@ -1,10 +1,15 @@
 """The PACKED DIN unit (round 6: csrc/din_pack.hip, dir_din_attention_pool_packed_f32) against the double-accumulating oracle
 (oracle/dir_oracle.c: paper-derived, README.md:27 -> arXiv:1706.06978; no reference code) at the 1e-5 bar of tests/test_gpu_parity.py, on
 the cases packing makes interesting: rows of several samples in one MFMA tile, samples spanning passes and tiles, empty samples (alone,
-in runs longer than a block, at the ends of the batch), masked positions inside the length, T > 64, one-sample batches, no length vector."""
+in runs longer than a block, at the ends of the batch), masked positions inside the length, T > 64, one-sample batches, no length vector.
+The second half runs the named edge cases of tests/din_pack_inputs.py for sigmoid, PReLU and Dice: padded hidden widths and the one-tile
+pass under the paper's activations, samples without a candidate, a batch past one chunk size of the partition, lengths outside [0, T],
+samples whose positions are all masked, T = 65 535, and the entry without a weight image."""
 import numpy as np
 import pytest
 import torch
+
+from tests import din_pack_inputs as D
 
 pytestmark = pytest.mark.gpu
 
@@ -111,6 +116,131 @@ def test_packed_din_prelu_dice(ops, oracle, activation, normalize):
         O.DIN_PACKED = old
     _close(got_s.cpu().numpy(), ref_s.cpu().numpy().astype(np.float64), 2e-6)
     _close(got_o.cpu().numpy(), ref_o.cpu().numpy().astype(np.float64), 2e-6)
+    # ... and directly against the double-accumulating oracle, at the bar of the sigmoid form
+    orc_o, orc_s = oracle.din_attention_pool(table, hist, hl, cand, *ws, normalize=normalize, acc64=True, activation=activation, act_params=ap)
+    _close(got_s.cpu().numpy(), orc_s)
+    _close(got_o.cpu().numpy(), orc_o)
+
+
+# ---- the edge cases of tests/din_pack_inputs.py (tests/test_din_pack_inputs.py proves on the CPU that each reaches the edge it is named for
+# and that fp32 itself stays within a tenth of the bar on its operands) -------------------------------------------------------------------
+def _err(got, ref):
+    return float((np.abs(got.astype(np.float64) - ref) / (1.0 + np.abs(ref))).max()) if got.size else 0.0
+
+
+def _operands(c, normalize, activation):
+    hist = D.ids(c, normalize)
+    ap = None if activation == "sigmoid" else c.act_params
+    dev = lambda a: torch.tensor(a, device="cuda")      # noqa: E731  (the cases' arrays are read-only: a copy, not from_numpy's view)
+    args = [dev(c.table), dev(hist), None if c.hist_len is None else dev(c.hist_len), dev(c.cand)] + [dev(w) for w in c.unit]
+    return hist, ap, args, (None if ap is None else dev(ap))
+
+
+def _raw_packed(c, args, ap_dev, activation, normalize):
+    """dir_din_attention_pool_packed_f32 with image = NULL (the entry builds the image in the workspace's tail) into out / scores
+    PRE-FILLED with NaN: an element the launch leaves unwritten stays NaN."""
+    import ctypes
+    from dir_amd import _lib
+    lib = _lib.load()
+    B, T = c.hist.shape
+    ws = torch.empty(int(lib.dir_din_pack_workspace_bytes(B, 1)), dtype=torch.uint8, device="cuda")
+    out = torch.full((B, D.K), float("nan"), device="cuda")
+    scores = torch.full((B, T), float("nan"), device="cuda")
+    ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())      # noqa: E731
+    table, hist, hl, cand, W1, b1, W2, b2, W3, b3 = args
+    torch.cuda.synchronize()
+    _lib.check(lib.dir_din_attention_pool_packed_f32(ptr(table), D.K, ptr(hist), ptr(hl), ptr(cand), T, ptr(W1), ptr(b1), c.H1, ptr(W2), ptr(b2), c.H2,
+                                                     ptr(W3), ptr(b3), int(normalize), D.ACTIVATIONS.index(activation), ptr(ap_dev), None, B, ptr(out),
+                                                     ptr(scores), ptr(ws), ws.numel(), None))
+    torch.cuda.synchronize()
+    return out, scores
+
+
+@pytest.mark.parametrize("name,activation,normalize", D.grid(D.PACKED))
+def test_packed_din_edge_cases_match_oracle(ops, oracle, name, activation, normalize):
+    """din_pack_k<ACT, scores, normalize> on the named edge cases against the double-accumulating oracle (and, for B <= 300, the float64
+    NumPy restatement) at 1e-5 (1 + |ref|), pooled rows and weights; without scores and on a rerun the same bits; weights exactly 0 at
+    masked positions and beyond the length, pooled rows exactly 0 where nothing takes part."""
+    from oracle import np_ref as R
+    c = D.case(name)
+    B, T = c.hist.shape
+    assert ops.DIN_PACKED and ops.din_pack_covers(D.K, T, c.H1, c.H2)      # the packed branch is the one ops.din_attention_pool takes
+    hist, ap, args, ap_dev = _operands(c, normalize, activation)
+    ref_o, ref_s = oracle.din_attention_pool(c.table, hist, D.ref_len(c), c.cand, *c.unit, normalize=normalize, acc64=True, activation=activation,
+                                             act_params=ap)
+    kw = dict(normalize=normalize, activation=activation, act_params=ap_dev, arith="f16x2")
+    got_o, got_s = ops.din_attention_pool(*args, want_scores=True, **kw)
+    o, s = got_o.cpu().numpy(), got_s.cpu().numpy()
+    print("%s ACT=%s scores=1 normalize=%d: max scaled err out %.3e scores %.3e" % (name, activation, normalize, _err(o, ref_o), _err(s, ref_s)))
+    _close(s, ref_s)
+    _close(o, ref_o)
+    if B <= 300:
+        r_o, r_s = R.din_attention_pool(c.table, hist, D.ref_len(c), c.cand, *c.unit, normalize=normalize, activation=activation, act_params=ap)
+        _close(s, r_s)
+        _close(o, r_o)
+    only_o = ops.din_attention_pool(*args, **kw)                          # the kernel without the scores output
+    assert torch.equal(only_o, got_o)
+    again = ops.din_attention_pool(*args, **kw)
+    assert torch.equal(again, got_o)
+    valid = D.valid_mask(c, normalize)
+    assert not s[~valid].any()                                             # exactly 0 at masked positions and beyond the length
+    assert not o[~valid.any(1)].any()                                      # exactly 0: empty samples, samples whose positions are all masked
+    if name == "past_one_chunk_size":                                      # every row written (the partition covers the batch): no NaN is left
+        raw_o, raw_s = _raw_packed(c, args, ap_dev, activation, normalize)
+        assert torch.equal(raw_o, got_o) and torch.equal(raw_s, got_s)
+
+
+@pytest.mark.parametrize("activation,normalize", D.PAPER)
+def test_packed_din_null_image_prelu_dice(ops, oracle, activation, normalize):
+    """The raw entry with image = NULL -- the only way a C caller reaches PReLU / Dice without the Python cache: bit for bit what
+    ops.din_attention_pool gives on the same operands (its image comes from dir_din_pack_weights_f32), and the oracle's answer."""
+    c = D.case("null_image")
+    assert ops.din_pack_covers(D.K, c.T, c.H1, c.H2)
+    hist, ap, args, ap_dev = _operands(c, normalize, activation)
+    got_o, got_s = ops.din_attention_pool(*args, want_scores=True, normalize=normalize, activation=activation, act_params=ap_dev, arith="f16x2")
+    raw_o, raw_s = _raw_packed(c, args, ap_dev, activation, normalize)
+    assert torch.equal(raw_o, got_o) and torch.equal(raw_s, got_s)
+    ref_o, ref_s = oracle.din_attention_pool(c.table, hist, c.hist_len, c.cand, *c.unit, normalize=normalize, acc64=True, activation=activation,
+                                             act_params=ap)
+    print("null_image ACT=%s scores=1 normalize=%d: max scaled err out %.3e scores %.3e" % (
+        activation, normalize, _err(raw_o.cpu().numpy(), ref_o), _err(raw_s.cpu().numpy(), ref_s)))
+    _close(raw_s.cpu().numpy(), ref_s)
+    _close(raw_o.cpu().numpy(), ref_o)
+
+
+@pytest.mark.parametrize("activation,normalize", [(a, z) for _, a, z in D.grid(["long_history-beyond"])])
+def test_din_history_one_past_the_packed_limit(ops, oracle, activation, normalize):
+    """T = 65 536: din_pack_covers is False, and the call succeeds and meets the same bar.  (No other forward kernel holds a history this
+    long -- din_wave_k: T <= 64, din_k: the whole history in LDS -- and before the wide instantiations of din_pack_k the call returned
+    DIR_E_UNSUPPORTED: ops.din_long_covers routes it to them.)"""
+    _beyond(ops, oracle, "long_history-beyond", activation, normalize)
+
+
+@pytest.mark.parametrize("activation,normalize", [(a, z) for _, a, z in D.grid(["long_history-widest"])])
+def test_din_history_of_the_widest_position_field(ops, oracle, built_lib, activation, normalize):
+    """T = 2^20, the longest history the 20-bit position field holds: one block of 2^15 passes; one more is DIR_E_UNSUPPORTED."""
+    import ctypes
+    _beyond(ops, oracle, "long_history-widest", activation, normalize)
+    p = ctypes.c_void_p(256)
+    rc = built_lib.dir_din_attention_pool_packed_f32(p, 64, p, p, p, (1 << 20) + 1, p, p, 80, p, p, 40, p, p, 0, 0, None, None, 4, p, None, p, 1 << 20, None)
+    assert rc == -4 and b"T <= 1048576" in built_lib.dir_last_error()
+    assert not ops.din_long_covers(64, (1 << 20) + 1, 80, 40) and not ops.din_long_covers(64, 65535, 80, 40)
+
+
+def _beyond(ops, oracle, name, activation, normalize):
+    c = D.case(name)
+    assert c.T > 65535 and not ops.din_pack_covers(D.K, c.T, c.H1, c.H2) and ops.din_long_covers(D.K, c.T, c.H1, c.H2)
+    hist, ap, args, ap_dev = _operands(c, normalize, activation)
+    kw = dict(normalize=normalize, activation=activation, act_params=ap_dev, arith="f16x2")
+    got_o, got_s = ops.din_attention_pool(*args, want_scores=True, **kw)
+    ref_o, ref_s = oracle.din_attention_pool(c.table, hist, c.hist_len, c.cand, *c.unit, normalize=normalize, acc64=True, activation=activation,
+                                             act_params=ap)
+    o, s = got_o.cpu().numpy(), got_s.cpu().numpy()
+    print("%s ACT=%s scores=1 normalize=%d WIDE: max scaled err out %.3e scores %.3e" % (name, activation, normalize, _err(o, ref_o), _err(s, ref_s)))
+    _close(s, ref_s)
+    _close(o, ref_o)
+    assert torch.equal(ops.din_attention_pool(*args, **kw), got_o)          # without the scores output: the same bits
+    assert not s[~D.valid_mask(c, normalize)].any()
 
 
 def test_packed_din_without_a_length_vector(ops, oracle):
