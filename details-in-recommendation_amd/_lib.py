@@ -29,6 +29,7 @@ SIGNATURES = {
     "dir_sparse_ftrl_rows_sorted_f32": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, ctypes.c_float, ctypes.c_float,
                                                 ctypes.c_float, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
     "dir_gather_fm_fused_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "dir_gather_onehot_route": (c_i32, [c_i32, c_i32, c_i64, c_i64, c_vp, c_i64, c_i32]),
     "dir_gather_fm_linear_packed_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i64, c_i32, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64,
                                                 c_vp, c_vp, c_vp, c_vp]),
     "dir_gather_fm_rows_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_i64, c_i64, c_i32, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),

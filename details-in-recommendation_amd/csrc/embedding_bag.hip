@@ -21,15 +21,104 @@
 namespace dir {
 
 // ------------------------------------------------------------------------------------------------
-// one-hot gather, optional concat write, optional fused FM
+// The issue phase of a unit (one wave, 16 samples, UF slots) for rows of 16-byte chunks owned by QUADS of lanes (K = 16: lane c of a
+// quad owns chunk c), written so that between two row loads there is address arithmetic only -- no scalar-memory round trip and no
+// exec-mask branch (profiles/NOTES.md R7.9):
+//   * the slots' table bases and id bounds come in with TWO vector loads, lane l holding those of slot l, issued beside the id
+//     loads; slot f's pair is then read out of lane f (v_readlane: no memory, no wait);
+//   * a quad loads each id of its sample ONCE (ids [B, F] with unit field stride, F = UF, even): lane c takes the 16-byte pieces
+//     c, c + 4, ... of two ids each, and every id is handed round with a quad broadcast (DPP);
+//   * every address is legal: the caller clamps the sample (tail wave) and a pruned id reads row 0 of its slot -- which exists, the
+//     caller's promise behind DIR_GATHER_TABLES_NONEMPTY -- and the row is replaced by zeros when it is used (bit u of the result);
+//   * the rows are read through global (address space 1) pointers: global_load_dwordx4, counted on vmcnt alone.
+// Lane offsets are unsigned 32-bit BYTE offsets built on c16 = 16 * c (the caller's strides are small enough), so that one register
+// serves the ids, the rows and the caller's output.
+// -> bit u set: slot u's id is looked up (0 <= id < bound); otherwise row[u] is row 0's and the caller uses zeros.
 // ------------------------------------------------------------------------------------------------
-template <int LPS, int VEC, int KT, int UF, bool DO_FM, bool DO_OUT, bool NT>
-__global__ __launch_bounds__(256) void gather_onehot_k(const float* const* __restrict__ tables,
-                                                       const int64_t* __restrict__ vocab,
-                                                       const int64_t* __restrict__ ids, int64_t sb,
-                                                       int64_t sf, int F, int Krt, int64_t B,
-                                                       float* __restrict__ out, int64_t out_ld,
-                                                       float* __restrict__ fm) {
+typedef const char __attribute__((address_space(1))) * gchar_p;
+typedef const f32x4_t __attribute__((address_space(1))) * gf32x4_p;
+typedef int64_t i64x2_a8_t __attribute__((ext_vector_type(2), aligned(8)));
+
+__device__ __forceinline__ int quad_bcast(int v, int q) {      // the value of lane q of the lane's quad (q: constant after unrolling)
+    switch (q & 3) {
+        case 0: return __builtin_amdgcn_mov_dpp(v, 0x00, 0xf, 0xf, true);
+        case 1: return __builtin_amdgcn_mov_dpp(v, 0x55, 0xf, 0xf, true);
+        case 2: return __builtin_amdgcn_mov_dpp(v, 0xaa, 0xf, 0xf, true);
+        default: return __builtin_amdgcn_mov_dpp(v, 0xff, 0xf, 0xf, true);
+    }
+}
+__device__ __forceinline__ int64_t quad_bcast64(int64_t v, int q) {
+    const unsigned lo = (unsigned)quad_bcast((int)(unsigned)(uint64_t)v, q);
+    const unsigned hi = (unsigned)quad_bcast((int)(unsigned)((uint64_t)v >> 32), q);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ uint64_t lane_u64(uint64_t v, int l) {     // v of lane l (uniform l) as a scalar
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+__device__ __forceinline__ float4 keep_if(float4 v, unsigned bit) {    // bit ? v : +0 (a mask, not a branch)
+    const unsigned m = 0u - bit;
+    return make_float4(__uint_as_float(__float_as_uint(v.x) & m), __uint_as_float(__float_as_uint(v.y) & m),
+                       __uint_as_float(__float_as_uint(v.z) & m), __uint_as_float(__float_as_uint(v.w) & m));
+}
+
+template <int UF, bool NT>
+__device__ __forceinline__ unsigned issue_quad_rows(const float* const* __restrict__ tables, const int64_t* __restrict__ vocab,
+                                                    const int64_t* __restrict__ ids_u /* (uniform) the unit's first sample */,
+                                                    unsigned soff /* + this many BYTES: the lane's (clamped) sample, + c16 */,
+                                                    int lane, unsigned c16, float4 (&row)[UF]) {
+    static_assert(UF <= 32 && UF % 2 == 0, "one bit per slot; two ids per piece");
+    const unsigned fl = lane < UF ? lane : UF - 1;
+    const uint64_t tb_l = reinterpret_cast<uint64_t>(tables[fl]);
+    // (id_bound; the load is unconditional -- without a vocabulary it reads the slot's table pointer instead -- so that it is issued
+    // beside the others and not under a branch of its own)
+    const uint64_t bd_v = (uint64_t)(vocab ? vocab : reinterpret_cast<const int64_t*>(tables))[fl];
+    const uint64_t bd_l = vocab ? bd_v : (uint64_t)1 << 63;
+    constexpr int NP = UF / 2, NPL = (NP + 3) / 4;                             // pieces per sample, per lane
+    int64_t pc[NPL][2];
+    const gchar_p q = (gchar_p)ids_u + soff;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {                                            // (a piece past the last one: the last one again)
+        const int o = (4 * j + 3 < NP || c16 + 64 * j < 16 * NP) ? 64 * j : 16 * (NP - 1) - (int)c16;
+        const i64x2_a8_t v = *reinterpret_cast<const i64x2_a8_t __attribute__((address_space(1)))*>(q + o);
+        pc[j][0] = v.x;
+        pc[j][1] = v.y;
+    }
+    __builtin_amdgcn_sched_barrier(0);                                         // (every id load is out before the first id is waited for)
+    unsigned ok = 0u;
+#pragma unroll
+    for (int u = 0; u < UF; ++u) {
+        const int64_t i = quad_bcast64(pc[(u >> 1) >> 2][u & 1], (u >> 1) & 3);    // id u: half u & 1 of piece u / 2 = register (u / 2) / 4 of lane (u / 2) % 4
+        const bool in = (uint64_t)i < lane_u64(bd_l, u);
+        ok |= in ? 1u << u : 0u;
+        const gchar_p t = (gchar_p)lane_u64(tb_l, u) + (((in ? i : (int64_t)0) << 6) + c16);
+        const f32x4_t v = NT ? __builtin_nontemporal_load((gf32x4_p)t) : *(gf32x4_p)t;
+        row[u] = make_float4(v.x, v.y, v.z, v.w);
+    }
+    // The uses stay behind the last load: under register pressure the scheduler otherwise pulls each row's first use up to its load,
+    // and with it a wait for that row -- one round trip per slot.  The identity DPP move keeps `ok` ONE register of bits: seen
+    // through, it becomes a register (or a pair of scalar ones and a branch) per slot.
+    __builtin_amdgcn_sched_barrier(0);
+    return (unsigned)__builtin_amdgcn_mov_dpp((int)ok, 0xe4, 0xf, 0xf, true);      // quad_perm [0,1,2,3]
+}
+
+// ------------------------------------------------------------------------------------------------
+// one-hot gather, optional concat write, optional fused FM
+// QUAD: false = every id and every row under its own predicate (any tables, any strides); true = issue_quad_rows (LPS = 4, K = 16,
+// F = UF even, ids with unit field stride, every table holds a row: DIR_GATHER_TABLES_NONEMPTY).  The values are the same bit for bit.
+// The K = 16 instantiations (KT == 16) are held to 4 waves per SIMD: 128 VGPRs -- UF = 26 rows in flight are 104 of them -- so
+// that the 1 024 workgroups of B = 65 536 are resident at once and the launch is one round.  (The others keep the compiler's own
+// choice: wider rows at UF = 26 need up to 191 registers and would spill under that bound.)
+// ------------------------------------------------------------------------------------------------
+template <int LPS, int VEC, int KT, int UF, bool DO_FM, bool DO_OUT, bool NT, bool QUAD = false>
+__global__ __launch_bounds__(256, (LPS == 4 && VEC == 4 && KT == 16) ? 4 : 1) void gather_onehot_k(const float* const* __restrict__ tables,
+                                                          const int64_t* __restrict__ vocab,
+                                                          const int64_t* __restrict__ ids, int64_t sb,
+                                                          int64_t sf, int F, int Krt, int64_t B,
+                                                          float* __restrict__ out, int64_t out_ld,
+                                                          float* __restrict__ fm) {
     using V = typename VecT<VEC>::T;
     constexpr int SPW = 64 / LPS;
     const int K = KT > 0 ? KT : Krt;
@@ -39,7 +128,43 @@ __global__ __launch_bounds__(256) void gather_onehot_k(const float* const* __res
     const int kv = (K + VEC - 1) / VEC;
     const bool cact = c < kv;
     const int64_t nwave = (int64_t)gridDim.x * (blockDim.x >> 6);
-    for (int64_t g = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); g * SPW < B; g += nwave) {
+    // (the wave's number as a scalar: the unit index g, the loop and the base addresses below are then scalar too)
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if constexpr (QUAD) {
+        static_assert(LPS == 4 && VEC == 4 && KT == 16, "issue_quad_rows: quads of 16-byte chunks");
+        for (int64_t g = (int64_t)blockIdx.x * (blockDim.x >> 6) + wv; g * SPW < B; g += nwave) {
+            const int64_t b0 = g * SPW;                     // samples b0 .. b0 + left - 1
+            const int left = B - b0 < SPW ? (int)(B - b0) : SPW;
+            const bool live = s < left;
+            const unsigned sc = live ? s : left - 1;        // tail wave: the last sample again (never past ids + B * sb), nothing stored
+            const unsigned c16 = 16u * c;
+            float4 sum = make_float4(0.f, 0.f, 0.f, 0.f), sq = sum;
+            float4 row[UF];
+            const unsigned ok = issue_quad_rows<UF, NT>(tables, vocab, ids + b0 * sb, sc * (unsigned)sb * 8u + c16, lane, c16, row);
+            // (the clamped sample through an identity DPP move: seen through, sc is s under the predicate below, the address is the same
+            // for every unit and is kept in a register pair across the loop -- which is what then spills)
+            char* op = DO_OUT ? reinterpret_cast<char*>(out + b0 * out_ld) + ((unsigned)__builtin_amdgcn_mov_dpp((int)sc, 0xe4, 0xf, 0xf, true) * (unsigned)out_ld * 4u + c16) : nullptr;
+            // ONE predicate for the unit: a sample's quad is live as a whole; fm_tail below only moves values inside a quad, and a dead
+            // quad's result is not stored
+            if (live) {
+#pragma unroll
+                for (int u = 0; u < UF; ++u) {
+                    row[u] = keep_if(row[u], (ok >> u) & 1u);
+                    if (DO_OUT) stv(reinterpret_cast<float*>(op + u * KT * 4), row[u]);
+                    if (DO_FM) {
+                        sum = vadd(sum, row[u]);
+                        sq = vadd(sq, vmul(row[u], row[u]));
+                    }
+                }
+            }
+            if (DO_FM) {
+                float r = fm_tail<LPS>(sum, sq, lane, c);
+                if (c == LPS - 1 && live) fm[b0 + s] = r;
+            }
+        }
+        return;
+    }
+    for (int64_t g = (int64_t)blockIdx.x * (blockDim.x >> 6) + wv; g * SPW < B; g += nwave) {
         const int64_t b = g * SPW + s;
         const bool act = cact && (b < B);
         const int64_t* idp = ids + (act ? b * sb : 0);
@@ -357,44 +482,60 @@ static int next_pow2(int v) {
 }
 
 template <int LPS, int VEC, int KT, bool DO_FM, bool DO_OUT>
-static void launch_onehot_uf(int uf, bool stream_rows, int64_t work_blocks, hipStream_t st, const float* const* tables,
+static void launch_onehot_uf(int uf, bool stream_rows, bool quad, int64_t work_blocks, hipStream_t st, const float* const* tables,
                              const int64_t* vocab, const int64_t* ids, int64_t sb, int64_t sf, int F, int K, int64_t B, float* out,
                              int64_t out_ld, float* fm) {
     static const int nt_force = dev_env_int("DIR_GATHER_NT", -1);   // development override: 0 / 1
     const bool nt_env = nt_force >= 0 ? nt_force != 0 : stream_rows;
-#define DIR_GO(UF)                                                                                                  \
-    do {                                                                                                            \
-        if (nt_env) {                                                                                               \
-            dim3 grid(grid_resident(work_blocks, resident_blocks(gather_onehot_k<LPS, VEC, KT, UF, DO_FM, DO_OUT, true>))); \
-            hipLaunchKernelGGL((gather_onehot_k<LPS, VEC, KT, UF, DO_FM, DO_OUT, true>), grid, dim3(256), 0, st, tables, vocab, ids, sb, sf, F, K, B, out, out_ld, fm); \
-        } else {                                                                                                    \
-            dim3 grid(grid_resident(work_blocks, resident_blocks(gather_onehot_k<LPS, VEC, KT, UF, DO_FM, DO_OUT, false>))); \
-            hipLaunchKernelGGL((gather_onehot_k<LPS, VEC, KT, UF, DO_FM, DO_OUT, false>), grid, dim3(256), 0, st, tables, vocab, ids, sb, sf, F, K, B, out, out_ld, fm); \
-        }                                                                                                           \
-    } while (0)
+    auto go = [&](auto kernel) {
+        dim3 grid(grid_resident(work_blocks, resident_blocks(kernel)));
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, tables, vocab, ids, sb, sf, F, K, B, out, out_ld, fm);
+    };
+    auto by_uf = [&](auto ufc) {
+        constexpr int UF = decltype(ufc)::value;
+        if constexpr (LPS == 4 && VEC == 4 && KT == 16 && UF % 2 == 0)          // the quad issue phase (see gather_onehot_k)
+            if (quad) return nt_env ? go(gather_onehot_k<LPS, VEC, KT, UF, DO_FM, DO_OUT, true, true>) : go(gather_onehot_k<LPS, VEC, KT, UF, DO_FM, DO_OUT, false, true>);
+        return nt_env ? go(gather_onehot_k<LPS, VEC, KT, UF, DO_FM, DO_OUT, true>) : go(gather_onehot_k<LPS, VEC, KT, UF, DO_FM, DO_OUT, false>);
+    };
     switch (uf) {
-        case 4: DIR_GO(4); break;
-        case 13: DIR_GO(13); break;
-        case 26: DIR_GO(26); break;
-        default: DIR_GO(8); break;
+        case 4: by_uf(std::integral_constant<int, 4>{}); break;
+        case 13: by_uf(std::integral_constant<int, 13>{}); break;
+        case 26: by_uf(std::integral_constant<int, 26>{}); break;
+        default: by_uf(std::integral_constant<int, 8>{}); break;
     }
-#undef DIR_GO
+}
+
+// slots issued back to back by one unit of the one-hot gather
+static int onehot_uf(int F) {
+    static const char* uf_str = runtime_env("DIR_GATHER_UF");       // (read once: tests/test_gpu_parity.py runs each value in a process of its own)
+    static const int uf_env = uf_str ? atoi(uf_str) : 0;
+    return uf_env > 0 ? uf_env : (F == 26 ? 26 : (F % 13 == 0 ? 13 : (F > 48 ? 26 : 8)));   // measured at F = 100: 26 -> 260 us, 8 -> 298 us
+}
+
+// Whether a one-hot launch takes the quad issue phase (issue_quad_rows): K = 16 on the 16-byte lane mapping, every table holds a row (the
+// caller's promise), ids [B, F] with unit field stride, F even and ONE unit per sample (launch_onehot_uf runs uf = 4, 13, 26, else 8: by
+// default that is F = 26 -- every DeepFM-family model of this library -- and F = 8), and strides that keep a wave's 16 samples inside
+// 32-bit byte offsets from its first one.  out: NULL for an FM-only launch.  The launcher and dir_gather_onehot_route share it.
+static bool onehot_quad_route(int F, int K, int64_t sb, int64_t sf, const float* out, int64_t out_ld, int flags) {
+    const int uf = onehot_uf(F), uf_run = (uf == 4 || uf == 13 || uf == 26) ? uf : 8;
+    const bool vec = !out || (out_ld % 4 == 0 && aligned16(out));
+    return K == 16 && vec && (flags & DIR_GATHER_TABLES_NONEMPTY) && sf == 1 && F == uf_run && F % 2 == 0 && sb >= F && sb < (1 << 24) &&
+           (!out || out_ld < (1 << 24));
 }
 
 template <bool DO_FM, bool DO_OUT>
 static int launch_onehot(const float* const* tables, const int64_t* vocab, int F, int K, const int64_t* ids, int64_t sb, int64_t sf,
                          int flags, int64_t B, float* out, int64_t out_ld, float* fm, hipStream_t st) {
     const bool vec = (K % 4 == 0) && (!DO_OUT || (out_ld % 4 == 0 && aligned16(out)));
-    static const char* uf_str = runtime_env("DIR_GATHER_UF");       // (read once: tests/test_gpu_parity.py runs each value in a process of its own)
-    static const int uf_env = uf_str ? atoi(uf_str) : 0;
-    int uf = uf_env > 0 ? uf_env : (F == 26 ? 26 : (F % 13 == 0 ? 13 : (F > 48 ? 26 : 8)));   // measured at F = 100: 26 -> 260 us, 8 -> 298 us
+    const int uf = onehot_uf(F);
     const bool stream_rows = (flags & DIR_GATHER_STREAM_ROWS) != 0;
     const int lps = next_pow2(vec ? K / 4 : K);
     if (lps > 64) return fail(DIR_E_UNSUPPORTED, "embedding row of K=%d floats is wider than one wave covers (max %d)", K, vec ? 256 : 64);
     const int spw = 64 / lps;
     const int64_t waves = (B + spw - 1) / spw;
     const int64_t grid = (waves + 3) / 4;   // work blocks; the launch picks the resident count
-#define DIR_CASE(L, V, KT) launch_onehot_uf<L, V, KT, DO_FM, DO_OUT>(uf, stream_rows, grid, st, tables, vocab, ids, sb, sf, F, K, B, out, out_ld, fm)
+    const bool quad = onehot_quad_route(F, K, sb, sf, DO_OUT ? out : nullptr, out_ld, flags);
+#define DIR_CASE(L, V, KT) launch_onehot_uf<L, V, KT, DO_FM, DO_OUT>(uf, stream_rows, quad, grid, st, tables, vocab, ids, sb, sf, F, K, B, out, out_ld, fm)
     if (vec) {
         switch (lps) {
             case 1: DIR_CASE(1, 4, 4); break;
@@ -513,6 +654,10 @@ extern "C" int dir_gather_fm_fused_f32(const float* const* tables, const int64_t
     if (out && fm) return launch_onehot<true, true>(tables, vocab, F, K, ids, stride_b, stride_f, flags, B, out, out_ld, fm, st);
     if (fm) return launch_onehot<true, false>(tables, vocab, F, K, ids, stride_b, stride_f, flags, B, nullptr, 0, fm, st);
     return launch_onehot<false, true>(tables, vocab, F, K, ids, stride_b, stride_f, flags, B, out, out_ld, nullptr, st);
+}
+
+extern "C" int dir_gather_onehot_route(int F, int K, int64_t stride_b, int64_t stride_f, const float* out, int64_t out_ld, int flags) {
+    return onehot_quad_route(F, K, stride_b, stride_f, out, out_ld, flags) ? 1 : 0;
 }
 
 extern "C" int dir_fm_second_order_f32(const float* emb, int64_t emb_ld, int64_t B, int F, int K, float* out,

@@ -30,6 +30,7 @@ SUM, MEAN, SQRTN = 0, 1, 2
 _COMBINERS = {"sum": SUM, "mean": MEAN, "sqrtn": SQRTN, SUM: SUM, MEAN: MEAN, SQRTN: SQRTN}
 PRUNE_NONPOSITIVE_WEIGHTS = 1
 STREAM_ROWS = 2  # DIR_GATHER_STREAM_ROWS: non-temporal row loads (uniform ids over tables >> Infinity Cache)
+TABLES_NONEMPTY = 8  # DIR_GATHER_TABLES_NONEMPTY: every table holds a row (the one-hot gather's branch-free issue phase)
 INFINITY_CACHE_BYTES = 256 << 20
 
 
@@ -58,6 +59,7 @@ class TableSet:
         self.F = len(tables)
         self.K = K
         self.vocab = [int(t.shape[0]) for t in tables]
+        self._nonempty = min(self.vocab) > 0     # DIR_GATHER_TABLES_NONEMPTY: no table without a row (data_ptr() of an empty one is 0)
         self.device = tables[0].device
         self.ld = K if ld is None else int(ld)   # floats between rows (> K: packed training rows, see train_rows)
         self.accums = None                       # train_rows: the Adagrad accumulators living in the same rows
@@ -162,9 +164,10 @@ class TableSet:
         return f16_range_ok(self.absmax(every))
 
     def gather_flags(self):
+        flags = TABLES_NONEMPTY if self._nonempty else 0
         if self.row_policy == "stream" or (self.row_policy == "auto" and self.nbytes > 2 * INFINITY_CACHE_BYTES):
-            return STREAM_ROWS
-        return 0
+            flags |= STREAM_ROWS
+        return flags
 
     def written(self, *more):
         """A raw-pointer kernel has just updated the tables (and `more`: optimiser slots) in place: see mark_written."""

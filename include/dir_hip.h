@@ -43,11 +43,15 @@ enum { DIR_COMBINER_SUM = 0, DIR_COMBINER_MEAN = 1, DIR_COMBINER_SQRTN = 2 };
 enum {
     DIR_BAG_PRUNE_NONPOSITIVE_WEIGHTS = 1, /* drop entries with weight <= 0 ([TF-upstream]
                                               safe_embedding_lookup_sparse, later 1.x) */
-    DIR_GATHER_STREAM_ROWS = 2             /* one-hot path: read table rows with non-temporal loads.  Right
+    DIR_GATHER_STREAM_ROWS = 2,            /* one-hot path: read table rows with non-temporal loads.  Right
                                               when ids are spread over tables far larger than the 256 MiB
                                               Infinity Cache (measured 70 -> 62 us at BASELINE config 2,
                                               uniform ids); wrong for skewed ids whose hot rows should stay
                                               cached (Zipf 1.05: 50 -> 60 us).  Values are identical. */
+    DIR_GATHER_TABLES_NONEMPTY = 8         /* one-hot path: the caller guarantees that every tables[f] is non-null and holds
+                                              at least one row.  The K = 16 gather then reads row 0 of the slot for a pruned
+                                              id (and uses zeros) instead of branching round the load.  Values are
+                                              identical.  (4 is DIR_SLAB_SANITIZE, which shares a flags word with these.) */
 };
 
 int dir_version(void);
@@ -123,12 +127,18 @@ int dir_fm_second_order_f32(const float* emb, int64_t emb_ld, int64_t B, int F, 
                             dir_stream_t stream);
 
 /* A1+A4 fused for one-hot slots: one pass over the rows.  out may be NULL (FM only); fm may be NULL
- * (gather only).  flags: DIR_GATHER_STREAM_ROWS.  Replaces deepFM.py:169-177 (inputs) + :321-335
+ * (gather only).  flags: DIR_GATHER_STREAM_ROWS, DIR_GATHER_TABLES_NONEMPTY.  Replaces deepFM.py:169-177 (inputs) + :321-335
  * (fm_logit_fn) in one launch.  vocab: DEVICE int64 [F] or NULL, as in dir_embedding_bag_ex_f32 (an id >= vocab_f
  * contributes a zero row; one scalar compare per slot). */
 int dir_gather_fm_fused_f32(const float* const* tables, const int64_t* vocab, int F, int K, const int64_t* ids,
                             int64_t stride_b, int64_t stride_f, int flags, int64_t B, float* out,
                             int64_t out_ld, float* fm, dir_stream_t stream);
+
+/* HOST: which issue phase a one-hot launch (dir_gather_fm_fused_f32, dir_embedding_bag_f32 without offsets) with these arguments takes:
+ * 1 = the quad issue phase (K = 16, DIR_GATHER_TABLES_NONEMPTY, ids [B, F] with unit field stride, F = 26 or 8), 0 = every id and row
+ * under its own predicate.  out: the launch's output (only its alignment is looked at) or NULL for an FM-only launch.  The values are
+ * the same either way; tests use this to know which kernel they checked. */
+int dir_gather_onehot_route(int F, int K, int64_t stride_b, int64_t stride_f, const float* out, int64_t out_ld, int flags);
 
 /* Packed serving layout (an MI355X-specific option; the reference layout above stays the default): slot f's table is
  * [vocab_f, ld] fp32 with the embedding at columns [0, K) and the first-order weight of the same feature value at
