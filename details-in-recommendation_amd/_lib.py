@@ -131,6 +131,11 @@ SIGNATURES = {
                                               c_vp, c_i64, c_vp, c_i64, c_vp]),
     "dir_sparse_adagrad_sorted_rows_f32": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
                                                    ctypes.c_float, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    # ... over tables shared between slots: + slot_table (device int32 [F]), n_tables after total_rows
+    "dir_sparse_adagrad_sorted_shared_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_float, c_i64,
+                                                     c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp]),
+    "dir_sparse_adagrad_sorted_rows_shared_f32": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                                          ctypes.c_float, c_i64, c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp]),
     "dir_sparse_adagrad_sorted_payload_f32": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, ctypes.c_float, c_vp, c_i64, c_vp,
                                                       c_i64, c_vp]),
     "dir_sparse_ftrl_sorted_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, ctypes.c_float,

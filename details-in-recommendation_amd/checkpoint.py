@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from ._input import categorical_of
+from .feature_column import var_scope_name
 
 
 def _lin(prefix, layer, out):
@@ -35,8 +36,9 @@ def tf_variable_map(model):
     from .esmm import ESMM
     m = {}
     if isinstance(model, DeepFM):
-        for c, p in zip(model.dnn_feature_columns, model.embedding_weights):
-            m["dnn_fm_inputs/myself_input_layer/%s/embedding_weights" % c.name] = (p, None)    # deepFM.py:173-177,386
+        # (one variable per TABLE: a shared_embedding_columns collection is written once, under its collection name -- test02.py:84)
+        for c, p in zip(model._table_columns, model.embedding_weights):
+            m["dnn_fm_inputs/myself_input_layer/%s/embedding_weights" % var_scope_name(c)] = (p, None)    # deepFM.py:173-177,386
         for i, lin in enumerate(model.hidden):
             _lin("dnn_fm/hiddenlayer_%d" % i, lin, m)                                          # deepFM.py:293-300
             if len(model.bns):
@@ -51,8 +53,8 @@ def tf_variable_map(model):
         m["linear/linear_model/bias_weights"] = (model.linear_bias, None)
     elif isinstance(model, DeepCrossNetwork):
         il = model.input_layer
-        for c, p in zip(il.emb_cols, il.embedding_weights):
-            m["dcn_model/input_from_feature_columns/input_layer/%s/embedding_weights" % c.name] = (p, None)   # :109,125-126
+        for c, p in zip(il._table_columns, il.embedding_weights):
+            m["dcn_model/input_from_feature_columns/input_layer/%s/embedding_weights" % var_scope_name(c)] = (p, None)   # :109,125-126
         m["dcn_model/input_from_feature_columns/cross_w"] = (model.cross_w, None)              # :329-330
         m["dcn_model/input_from_feature_columns/cross_b"] = (model.cross_b, None)              # :331-332
         bi = 0
@@ -70,8 +72,8 @@ def tf_variable_map(model):
     elif isinstance(model, ESMM):
         for scope, tower in (("esmm/ctr_model", model.ctr_model), ("esmm/cvr_model", model.cvr_model)):   # ESMM.py:62-66
             il = tower.input_layer
-            for c, p in zip(il.emb_cols, il.embedding_weights):
-                m["%s/input_layer/%s/embedding_weights" % (scope, c.name)] = (p, None)          # ESMM.py:135
+            for c, p in zip(il._table_columns, il.embedding_weights):
+                m["%s/input_layer/%s/embedding_weights" % (scope, var_scope_name(c))] = (p, None)          # ESMM.py:135
             for i, lin in enumerate(tower.hidden):
                 _lin("%s/hiddenlayer_%d" % (scope, i), lin, m)                                  # ESMM.py:137-142
             _lin("%s/dense" % scope, tower.logits, m)                                           # ESMM.py:146

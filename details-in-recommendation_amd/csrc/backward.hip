@@ -365,13 +365,33 @@ __global__ __launch_bounds__(256) void adagrad_apply_k(float* const* __restrict_
 // ------------------------------------------------------------------------------------------------
 constexpr int ADA_TILE = 256;
 
+// Tables shared between slots (shared_embedding_columns): slot_table [F] maps a slot to its table among T distinct ones and row_base
+// [T] runs over the TABLES; nullptr = one table per slot (T = F, the map is the identity).  A map entry outside [0, T) is clamped
+// here and pruned by the key pass, so a bad map can never send a row outside the tables.
+__device__ __forceinline__ int table_of(const int* __restrict__ slot_table, int f, int T) {
+    if (!slot_table) return f;
+    const int t = slot_table[f];
+    return t < 0 ? 0 : (t < T ? t : T - 1);
+}
+
 __global__ __launch_bounds__(256) void adagrad_keys_k(const int64_t* __restrict__ ids, int64_t sb, int64_t sf, int F, int64_t n,
                                                       const int64_t* __restrict__ row_base, uint32_t total_rows,
-                                                      uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+                                                      uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                      const int* __restrict__ slot_table = nullptr, int T = 0 /* slot_table: tables */) {
     for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         const int64_t b = e / F;
         const int f = (int)(e - b * F);
         const int64_t id = ids[b * sb + f * sf];
+        if (slot_table) {
+            // the slot's table t: the key is t's row, pruned against t's rows; every slot of a table gives one row the same key
+            const int t = slot_table[f];
+            const bool ok = t >= 0 && t < T;
+            const int tc = ok ? t : 0;
+            const int64_t vt = (tc + 1 < T ? row_base[tc + 1] : (int64_t)total_rows) - row_base[tc];
+            keys[e] = ok && (uint64_t)id < (uint64_t)vt ? (uint32_t)(row_base[tc] + id) : total_rows;
+            vals[e] = (uint32_t)e;
+            continue;
+        }
         const int64_t vf = (f + 1 < F ? row_base[f + 1] : (int64_t)total_rows) - row_base[f];
         // pruned ids (id < 0, and id >= vocab_f: never written) sort behind every row
         keys[e] = (uint64_t)id < (uint64_t)vf ? (uint32_t)(row_base[f] + id) : total_rows;
@@ -779,7 +799,9 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
                                                       const float* __restrict__ fm_g = nullptr /* FM: d loss / d fm_logit [B] */,
                                                       const float* __restrict__ fm_sum = nullptr /* FM: S[b] = sum_f e[b,f], [B, K] */,
                                                       int stage_min_dups = 8 /* stage the tile's gradients in LDS when it holds at least this many duplicates */,
-                                                      BagSrc bag = BagSrc{} /* BAG: where the entry gradients come from */) {
+                                                      BagSrc bag = BagSrc{} /* BAG: where the entry gradients come from */,
+                                                      const int* __restrict__ slot_table = nullptr /* shared tables: slot -> table, row_base over tables */,
+                                                      int n_tab = 0) {
     using V = BV<VEC>;
     using T = typename V::T;
     constexpr int NG = 256 / LPS;
@@ -831,7 +853,7 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
         if constexpr (FM) {
             // the FM backward folded in (fm_bwd_k's arithmetic, so the row sums are the unfused path's bit for bit): entry (b, f)'s
             // gradient is (S[b] - e) * g[b] + grad[b, f], and e IS the entry's table row
-            if (!have_w) wv = V::ld(upd.tables[f] + ((int64_t)skey[i] - row_base[f]) * upd.ld + c * VEC);
+            if (!have_w) wv = V::ld(upd.tables[f] + ((int64_t)skey[i] - row_base[table_of(slot_table, f, n_tab)]) * upd.ld + c * VEC);
             T d = V::scale(V::sub(V::ld(fm_sum + (int64_t)b * K + c * VEC), wv), fm_g[b]);
             if (grad) d = V::add(d, V::ld(grad + (int64_t)b * g_ld + (int64_t)f * g_fs + c * VEC));
             return d;
@@ -856,7 +878,7 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
             if (tid < F) {
                 stab[tid] = upd.tables[tid];
                 sacc[tid] = upd.accums[tid];
-                sbase[tid] = row_base[tid];
+                sbase[tid] = row_base[table_of(slot_table, tid, n_tab)];
             }
             __syncthreads();
             struct Run { int s, e, f; uint32_t rk; float* wp; float* ap; T wv, av; bool live; };
@@ -925,7 +947,7 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
             sum = run_sum<VEC>(s, e, [&](int i) { return V::ld(sd + i * (LPS * VEC) + c * VEC); });
         } else {
             T wv = V::zero();
-            if constexpr (FM) wv = V::ld(upd.tables[f] + ((int64_t)rk - row_base[f]) * upd.ld + c * VEC);
+            if constexpr (FM) wv = V::ld(upd.tables[f] + ((int64_t)rk - row_base[table_of(slot_table, f, n_tab)]) * upd.ld + c * VEC);
             sum = run_sum<VEC>(s, e, [&](int i) { return entry_grad(i, wv, true); });
         }
         if (nt > 0) {                                      // payload mode: entries carry no slot; row_base is ascending
@@ -934,7 +956,7 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
         }
         const bool open_l = r == 0 && cont_l, open_r = r == nruns - 1 && cont_r;
         if (!open_l && !open_r) {
-            const int64_t id = (int64_t)rk - row_base[f];
+            const int64_t id = (int64_t)rk - row_base[table_of(slot_table, f, n_tab)];
             if constexpr (BAG && IsNorm<U>::value) {
                 bag_apply<LPS, VEC>(upd, bag, f, id, c, kv, sum, nsq);
             } else if constexpr (BAG) {
@@ -972,7 +994,8 @@ template <int LPS, int VEC, class U, bool BAG = false>
 __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
                                                      int64_t n, int64_t ntiles, const uint32_t* __restrict__ keys,
                                                      const uint32_t* __restrict__ vals, const int64_t* __restrict__ row_base,
-                                                     uint32_t total_rows, int nt, const float* __restrict__ carry, BagSrc bag = BagSrc{}) {
+                                                     uint32_t total_rows, int nt, const float* __restrict__ carry, BagSrc bag = BagSrc{},
+                                                     const int* __restrict__ slot_table = nullptr, int n_tab = 0) {
     using V = BV<VEC>;
     using T = typename V::T;
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1003,7 +1026,7 @@ __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
         f = 0;
         for (int q = 1; q < nt; ++q) f += (int64_t)kl >= row_base[q] ? 1 : 0;
     }
-    const int64_t id = (int64_t)kl - row_base[f];
+    const int64_t id = (int64_t)kl - row_base[table_of(slot_table, f, n_tab)];
     if constexpr (BAG && IsNorm<U>::value) {
         bag_apply<LPS, VEC>(upd, bag, f, id, c0, kv, sum, upd.norm2);
     } else if constexpr (BAG) {
@@ -1173,10 +1196,13 @@ struct SortedSrc {
     const int64_t* payload = nullptr;
     const float *fm_g = nullptr, *fm_sum = nullptr;
     const void* sorted_from = nullptr;
+    const int* slot_table = nullptr;    // shared(): slot -> table among `tables` distinct ones; row_base [tables] then runs over the tables
+    int tables = 0;
     static SortedSrc of_ids(const int64_t* ids, int64_t stride_b, int64_t stride_f) { return SortedSrc{ids, stride_b, stride_f}; }
     static SortedSrc of_payload(const int64_t* payload) { return SortedSrc{nullptr, 0, 0, payload}; }
     SortedSrc fm(const float* g, const float* sum) const { return SortedSrc{ids, stride_b, stride_f, payload, g, sum, sorted_from}; }
     SortedSrc reuse(const void* from) const { return SortedSrc{ids, stride_b, stride_f, payload, fm_g, fm_sum, from}; }
+    SortedSrc shared(const int* map, int T) const { return SortedSrc{ids, stride_b, stride_f, payload, fm_g, fm_sum, sorted_from, map, T}; }
 };
 
 template <class U>
@@ -1187,6 +1213,8 @@ static int sparse_sorted_update(const char* name, U upd, int F, int K, const Sor
     const int64_t stride_b = src.stride_b, stride_f = src.stride_f;
     const float *const fm_g = src.fm_g, *const fm_sum = src.fm_sum;
     const void* const sorted_from = src.sorted_from;
+    const int* const slot_table = src.slot_table;
+    const int T = src.tables;
     const int nt = payload ? F : 0;        // tables to search by key
     if (payload) {                         // entries are a flat list: one "slot" per entry
         ids = payload;
@@ -1202,7 +1230,9 @@ static int sparse_sorted_update(const char* name, U upd, int F, int K, const Sor
     // (IsWide: carry rows of K doubles)
     if (!adagrad_sorted_plan(n, IsWide<U>::value ? 2 * K : K, total_rows, p, payload ? 0 : B, payload ? 0 : F)) return fail(DIR_E_HIP, "%s: sort size query failed", name);
     // ids [B, F]: the slot-major sort (csrc/radix_sort.hip: the slot is known from the entry's position, the sort runs on local rows)
-    const bool slot_sort = !payload && !sorted_from && !use_rocprim_sort() && radix_slot_sort_ok(B, F, p.bits);
+    // (not over shared tables: the slots of one table have the same key range, so the slots' sorted segments would not concatenate into
+    // one sorted sequence and a row's entries would form one run per slot -- the global sort puts them into ONE run, in entry order)
+    const bool slot_sort = !payload && !sorted_from && !slot_table && !use_rocprim_sort() && radix_slot_sort_ok(B, F, p.bits);
     SortedBufs bufs;
     if (int rc = sorted_carve(name, p, workspace, workspace_bytes, sorted_from, bufs)) return rc;
     uint32_t *const k0 = bufs.k0, *const k1 = bufs.k1, *const v0 = bufs.v0, *const v1 = bufs.v1;
@@ -1221,7 +1251,7 @@ static int sparse_sorted_update(const char* name, U upd, int F, int K, const Sor
                                (uint32_t)total_rows, kin, vin);
         else
             hipLaunchKernelGGL(adagrad_keys_k, dim3(grid_for((n + 255) / 256)), dim3(256), 0, st, ids, stride_b, stride_f, F, n, row_base,
-                               (uint32_t)total_rows, kin, vin);
+                               (uint32_t)total_rows, kin, vin, slot_table, T);
     }
     DIR_CHECK_LAUNCH(name);
     if (!sorted_from && !slot_sort) {
@@ -1247,13 +1277,13 @@ static int sparse_sorted_update(const char* name, U upd, int F, int K, const Sor
         if constexpr (std::is_same<U, AdagradUpd>::value) {
             if (fm_g)
                 hipLaunchKernelGGL((adagrad_tile_k<LPS, VEC, U, true>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, F, K, n, k1, v1, grad,
-                                   grad_ld, grad_fs, row_base, (uint32_t)total_rows, nt, carry, fm_g, fm_sum, stage_min);
+                                   grad_ld, grad_fs, row_base, (uint32_t)total_rows, nt, carry, fm_g, fm_sum, stage_min, BagSrc{}, slot_table, T);
         }
         if (!fm_g)
             hipLaunchKernelGGL((adagrad_tile_k<LPS, VEC, U>), dim3((unsigned)ntiles), dim3(256), 0, st, upd, F, K, n, k1, v1, grad, grad_ld,
-                               grad_fs, row_base, (uint32_t)total_rows, nt, carry, nullptr, nullptr, stage_min);
+                               grad_fs, row_base, (uint32_t)total_rows, nt, carry, nullptr, nullptr, stage_min, BagSrc{}, slot_table, T);
         hipLaunchKernelGGL((adagrad_fix_k<LPS, VEC, U>), gfix, dim3(256), 0, st, upd, F, K, n, ntiles, k1, v1, row_base,
-                           (uint32_t)total_rows, nt, carry);
+                           (uint32_t)total_rows, nt, carry, BagSrc{}, slot_table, T);
     });
     DIR_CHECK_LAUNCH(name);
     return DIR_OK;
@@ -1274,12 +1304,12 @@ extern "C" int dir_sparse_adagrad_sorted_f32(float* const* tables, float* const*
 static int adagrad_sorted_rows(const char* name, float* const* tables, float* const* accums, int64_t row_ld, int F, int K, const int64_t* ids,
                                int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, const float* fm_g, const float* fm_sum,
                                float lr, int64_t B, const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
-                               const void* sorted_from, dir_stream_t stream) {
+                               const void* sorted_from, dir_stream_t stream, const int* slot_table = nullptr, int T = 0) {
     DIR_CHECK_ARG(row_ld >= K && (!grad || grad_ld >= (int64_t)F * K), "%s: row_ld / grad_ld", name);
     DIR_CHECK_ARG((fm_g == nullptr) == (fm_sum == nullptr), "%s: fm_g and fm_sum go together", name);
     if (K % 4 == 0 && (row_ld & 3)) return fail(DIR_E_UNSUPPORTED, "%s: row_ld must be a multiple of 4", name);
     return sparse_sorted_update(name, AdagradUpd{tables, accums, lr, row_ld}, F, K,
-                                SortedSrc::of_ids(ids, stride_b, stride_f).fm(fm_g, fm_sum).reuse(sorted_from), grad,
+                                SortedSrc::of_ids(ids, stride_b, stride_f).fm(fm_g, fm_sum).reuse(sorted_from).shared(slot_table, T), grad,
                                 grad ? grad_ld : (int64_t)F * K, (int64_t)K, B, row_base, total_rows, workspace, workspace_bytes, stream);
 }
 
@@ -1292,6 +1322,41 @@ extern "C" int dir_sparse_adagrad_sorted_rows_f32(float* const* tables, float* c
     DIR_CHECK_ARG(tables && accums, "%s: null pointer", name);
     return adagrad_sorted_rows(name, tables, accums, row_ld, F, K, ids, stride_b, stride_f, grad, grad_ld, fm_g, fm_sum, lr, B, row_base,
                                total_rows, workspace, workspace_bytes, nullptr, stream);
+}
+
+// The two updates over tables SHARED between slots (shared_embedding_columns): tables / accums stay [F] per-SLOT pointer arrays (the
+// slots of one table hold the same pointer), slot_table [F] maps slot -> table, row_base [n_tables] and total_rows run over the
+// DISTINCT tables.  slot_table == nullptr is the unshared call (n_tables must be F then), bit for bit.
+static int shared_map_check(const char* name, int F, const int32_t* slot_table, int n_tables) {
+    DIR_CHECK_ARG(n_tables >= 1 && n_tables <= F, "%s: n_tables=%d must be in [1, F=%d]", name, n_tables, F);
+    DIR_CHECK_ARG(slot_table || n_tables == F, "%s: without a slot_table every slot is a table (n_tables == F)", name);
+    return DIR_OK;
+}
+
+extern "C" int dir_sparse_adagrad_sorted_shared_f32(float* const* tables, float* const* accums, int F, int K, const int64_t* ids,
+                                                    int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, float lr,
+                                                    int64_t B, const int64_t* row_base, int64_t total_rows, const int32_t* slot_table,
+                                                    int n_tables, void* workspace, int64_t workspace_bytes, dir_stream_t stream) {
+    const char* name = "dir_sparse_adagrad_sorted_shared_f32";
+    DIR_CHECK_ARG(tables && accums, "%s: null pointer", name);
+    DIR_CHECK_ARG(F > 0 && grad_ld >= (int64_t)F * K, "%s: grad_ld", name);
+    if (int rc = shared_map_check(name, F, slot_table, n_tables)) return rc;
+    return sparse_sorted_update(name, AdagradUpd{tables, accums, lr, (int64_t)K}, F, K,
+                                SortedSrc::of_ids(ids, stride_b, stride_f).shared(slot_table, n_tables), grad, grad_ld, (int64_t)K, B, row_base,
+                                total_rows, workspace, workspace_bytes, stream);
+}
+
+extern "C" int dir_sparse_adagrad_sorted_rows_shared_f32(float* const* tables, float* const* accums, int64_t row_ld, int F, int K,
+                                                         const int64_t* ids, int64_t stride_b, int64_t stride_f, const float* grad,
+                                                         int64_t grad_ld, const float* fm_g, const float* fm_sum, float lr, int64_t B,
+                                                         const int64_t* row_base, int64_t total_rows, const int32_t* slot_table,
+                                                         int n_tables, void* workspace, int64_t workspace_bytes, dir_stream_t stream) {
+    const char* name = "dir_sparse_adagrad_sorted_rows_shared_f32";
+    DIR_CHECK_ARG(tables && accums, "%s: null pointer", name);
+    DIR_CHECK_ARG(F > 0, "%s: bad shape", name);
+    if (int rc = shared_map_check(name, F, slot_table, n_tables)) return rc;
+    return adagrad_sorted_rows(name, tables, accums, row_ld, F, K, ids, stride_b, stride_f, grad, grad_ld, fm_g, fm_sum, lr, B, row_base,
+                               total_rows, workspace, workspace_bytes, nullptr, stream, slot_table, n_tables);
 }
 
 // dir_sparse_ftrl_sorted_f32 and its _from form

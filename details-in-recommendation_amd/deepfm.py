@@ -21,6 +21,7 @@ from . import autograd as ag
 from . import ops
 from ._input import checked_forward as _checked_forward
 from ._input import collect_ids, categorical_of, raise_pending
+from .feature_column import table_slots, var_scope_name
 
 
 def _glorot_uniform_(w):  # [TF-upstream] glorot_uniform_initializer, deepFM.py:299
@@ -105,9 +106,11 @@ class DeepFM(nn.Module):
         self.K = fm_embedding_size if fm_embedding_size is not None else (
             dnn_feature_columns[0].dimension if dnn_feature_columns else 0)
         self.F = len(dnn_feature_columns)
-        # embedding_weights per column ([TF-upstream] truncated normal, stddev 1/sqrt(K))
+        # embedding_weights per TABLE ([TF-upstream] truncated normal, stddev 1/sqrt(K)): one per column, except that the columns of
+        # one shared_embedding_columns collection hold one table between them (_slot_table: column -> table)
+        self._slot_table, self._table_columns = table_slots(dnn_feature_columns)
         self.embedding_weights = nn.ParameterList()
-        for c in dnn_feature_columns:
+        for c in self._table_columns:
             w = torch.empty(c.num_buckets, c.dimension)
             nn.init.trunc_normal_(w, std=1.0 / math.sqrt(c.dimension), a=-2.0 / math.sqrt(c.dimension),
                                   b=2.0 / math.sqrt(c.dimension))
@@ -139,14 +142,19 @@ class DeepFM(nn.Module):
         self._lin_ts = None
 
     # ---- TableSets follow the parameters' storage (rebuilt when .to()/.cuda() moved them) ------------
+    def _slot_weights(self):
+        """The embedding parameters indexed by SLOT (dnn column): the columns of one shared collection hold the same parameter."""
+        tabs = ops.plain_list(self.embedding_weights)
+        return tabs if len(tabs) == self.F else [tabs[t] for t in self._slot_table]
+
     def _tablesets(self):
         key = tuple([p.data_ptr() for p in ops.plain_list(self.embedding_weights)] + [p.data_ptr() for p in ops.plain_list(self.linear_weights)])
         if getattr(self, "_ts_key", None) != key:
             ops.refuse_rebuild_under_sink(self._emb_ts, self._lin_ts)
-            self._emb_ts = ops.TableSet([p.data for p in self.embedding_weights]) if len(self.embedding_weights) else None
+            self._emb_ts = ops.TableSet([p.data for p in self._slot_weights()]) if len(self.embedding_weights) else None
             self._lin_ts = ops.TableSet([p.data for p in self.linear_weights]) if len(self.linear_weights) else None
             if self._emb_ts is not None:
-                self._emb_ts.owners = list(self.embedding_weights)      # HIP updates bump the parameters' version counters (ops.mark_written)
+                self._emb_ts.owners = list(self.embedding_weights)      # (each table's parameter once) HIP updates bump the parameters' version counters (ops.mark_written)
             if self._lin_ts is not None:
                 self._lin_ts.owners = list(self.linear_weights)
             self._ts_key = key
@@ -204,20 +212,20 @@ class DeepFM(nn.Module):
         max_norm = self._max_norm()
         if got[0] == "onehot" and max_norm:                                      # clipping needs the bag kernel: one-entry bags
             ids = got[1]
-            emb = (ag.embedding_bag(emb_ts, ids, ops.plain_list(self.embedding_weights), max_norm=max_norm) if train
+            emb = (ag.embedding_bag(emb_ts, ids, self._slot_weights(), max_norm=max_norm) if train
                    else ops.embedding_bag(emb_ts, ids, max_norm=max_norm))
             fm = ag.fm_logit(emb, self.F, self.K) if train else ops.fm_logit(emb, self.F, self.K)
             return self.dnn_logit_fn(emb, adds=(fm,))
         if got[0] == "onehot":
             if train:
-                emb, fm = ag.gather_fm(emb_ts, got[1], ops.plain_list(self.embedding_weights))
+                emb, fm = ag.gather_fm(emb_ts, got[1], self._slot_weights())
             else:
                 emb, fm = ops.gather_fm(emb_ts, got[1])                          # inputs + fm_logit_fn, one pass
         else:
             _, vals, offs, wts, _ = got
             comb = [c.combiner for c in self.dnn_feature_columns]                # every embedding_column carries its own combiner
             if train:
-                emb = ag.embedding_bag(emb_ts, vals, ops.plain_list(self.embedding_weights), offs, wts, combiner=comb, field_major=True,
+                emb = ag.embedding_bag(emb_ts, vals, self._slot_weights(), offs, wts, combiner=comb, field_major=True,
                                        max_norm=max_norm)
                 fm = ag.fm_logit(emb, self.F, self.K)
             else:
@@ -314,8 +322,9 @@ class DeepFM(nn.Module):
         emb_ts, _ = self._tablesets()
         if packed:
             if emb_ts.ld == emb_ts.K:
-                emb_ts = ops.TableSet.train_rows([p.data for p in self.embedding_weights], initial_accumulator_value)
-                for p, view in zip(self.embedding_weights, emb_ts.tables):
+                # (a shared table is laid out once: its slots' views -- and its one parameter -- alias one [embedding | accumulator] block)
+                emb_ts = ops.TableSet.train_rows([p.data for p in self._slot_weights()], initial_accumulator_value)
+                for p, view in zip(self._slot_weights(), emb_ts.tables):
                     p.data = view
                 emb_ts.owners = list(self.embedding_weights)
                 self._emb_ts = emb_ts
@@ -377,7 +386,7 @@ class DeepFM(nn.Module):
         ld = 32
         while ld < self.K + 1:
             ld *= 2
-        if sum(int(p.shape[0]) for p in self.embedding_weights) * ld * 4 > self.AUTO_PACK_MAX_BYTES:
+        if sum(int(p.shape[0]) for p in self._slot_weights()) * ld * 4 > self.AUTO_PACK_MAX_BYTES:      # (the pack copies a table per slot)
             return None
         self.pack_for_serving()
         return self._held_pack()
@@ -397,7 +406,7 @@ class DeepFM(nn.Module):
         lin_names = [categorical_of(c).name for c in self.linear_feature_columns[:n]]
         if len(lin_names) < n or lin_names != [categorical_of(c).name for c in self.dnn_feature_columns]:
             raise ValueError("pack_for_serving: the first %d linear columns must be the dnn columns' categorical columns" % n)
-        self._packed = ops.PackedTables([p.data for p in self.embedding_weights], [p.data for p in self.linear_weights[:n]])
+        self._packed = ops.PackedTables([p.data for p in self._slot_weights()], [p.data for p in self.linear_weights[:n]])
         self._packed_extra = ops.TableSet([p.data for p in self.linear_weights[n:]]) if len(self.linear_weights) > n else None
         self._packed_sig = self._pack_signature()
         return self._packed
@@ -428,7 +437,7 @@ class DeepFM(nn.Module):
         emb_ts, lin_ts = self._tablesets()
         train = torch.is_grad_enabled()
         if train:                                                                # differentiable: the tables get (sparse) gradients
-            emb, fm = ag.gather_fm(emb_ts, dnn_ids, ops.plain_list(self.embedding_weights))
+            emb, fm = ag.gather_fm(emb_ts, dnn_ids, self._slot_weights())
         else:
             emb, fm = ops.gather_fm(emb_ts, dnn_ids)
         logits = self.dnn_logit_fn(emb, adds=(fm,))
@@ -458,8 +467,8 @@ class DeepFM(nn.Module):
     def tf_variable_names(self):
         """Reference checkpoint names of the parameters (deepFM.py:173-196,206-209 scopes)."""
         names = {}
-        for c, _ in zip(self.dnn_feature_columns, self.embedding_weights):
-            names["embedding_weights.%d" % len(names)] = "dnn_fm_inputs/myself_input_layer/%s/embedding_weights" % c.name
+        for c in self._table_columns:          # (a shared table is written once, under its collection's scope: test02.py:84)
+            names["embedding_weights.%d" % len(names)] = "dnn_fm_inputs/myself_input_layer/%s/embedding_weights" % var_scope_name(c)
         for i in range(len(self.hidden)):
             names["hidden.%d.weight" % i] = "dnn_fm/hiddenlayer_%d/kernel" % i
             names["hidden.%d.bias" % i] = "dnn_fm/hiddenlayer_%d/bias" % i

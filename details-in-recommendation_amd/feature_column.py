@@ -7,6 +7,8 @@ vocabulary) and turn a raw feature into int64 ids:
   vocabulary: index in the list, OOV -> -1 (dropped by the bag)  models/DeepCrossNetwork/train.py:63-82
   bucketized: number of boundaries <= x                          models/DeepFM/deepFM.py:95 (docstring)
   crossed   : FingerprintCat64 chain over the keys mod buckets   models/ESMM/train.py:94
+and the dense wrappers: embedding_column, indicator_column, shared_embedding_columns (several id columns on ONE table,
+models/DeepFM/test02.py:30: the models hold one parameter per table, see table_slots).
 Column names follow [TF-upstream] naming (`<key>_embedding`, `<key>_indicator`, `<key>_bucketized`, `<a>_X_<b>`) because
 DCN's input_layer concatenates columns sorted by name (DeepCrossNetwork.py:126).
 """
@@ -258,6 +260,55 @@ class EmbeddingColumn(_Column):
         self.num_buckets = categorical_column.num_buckets
 
 
+class SharedEmbeddingColumn(EmbeddingColumn):
+    """One of the columns shared_embedding_columns returns (models/DeepFM/test02.py:30): an embedding column whose table belongs to a
+    collection.  Columns of one model with the same shared_embedding_collection_name read and train ONE [num_buckets, dimension] table."""
+
+    def __init__(self, categorical_column, dimension, combiner, max_norm, shared_embedding_collection_name):
+        super().__init__(categorical_column, dimension, combiner, max_norm)
+        self.name = categorical_column.name + "_shared_embedding"
+        self.shared_embedding_collection_name = shared_embedding_collection_name
+
+
+def table_key(column):
+    """What names a dense column's embedding table inside one model: the collection of a shared column, the column itself otherwise."""
+    shared = getattr(column, "shared_embedding_collection_name", None)
+    return ("shared", shared) if shared is not None else ("column", id(column))
+
+
+def var_scope_name(column):
+    """The variable scope of a column's embedding table ([TF-upstream] column._var_scope_name, test02.py:84): the collection name of a
+    shared column, the column's own name otherwise."""
+    return getattr(column, "shared_embedding_collection_name", None) or column.name
+
+
+def table_slots(columns):
+    """columns -> (slot_table, firsts): slot_table[i] = the index of column i's table among the distinct tables (in order of first
+    appearance), firsts[t] = the first column of table t.  One collection name must mean one (num_buckets, dimension) here."""
+    index, slot_table, firsts = {}, [], []
+    for c in columns:
+        k = table_key(c)
+        if k not in index:
+            index[k] = len(firsts)
+            firsts.append(c)
+        first = firsts[index[k]]
+        if (first.num_buckets, first.dimension) != (c.num_buckets, c.dimension):
+            raise ValueError("shared_embedding_collection_name %r names tables of different shapes: %s is (%d, %d), %s is (%d, %d)" % (
+                c.shared_embedding_collection_name, first.name, first.num_buckets, first.dimension, c.name, c.num_buckets, c.dimension))
+        slot_table.append(index[k])
+    return slot_table, firsts
+
+
+def first_shared(columns):
+    """-> the first column among `columns` that shares its table with another one of them, or None."""
+    cols = [c for c in columns if isinstance(c, EmbeddingColumn)]
+    slot_table, _ = table_slots(cols)
+    for i, t in enumerate(slot_table):
+        if slot_table.count(t) > 1:
+            return cols[i]
+    return None
+
+
 class IndicatorColumn(_Column):
     is_dense = True
 
@@ -297,6 +348,26 @@ def crossed_column(keys, hash_bucket_size, hash_key=None):
 
 def embedding_column(categorical_column, dimension, combiner="mean", max_norm=None):
     return EmbeddingColumn(categorical_column, dimension, combiner, max_norm)
+
+
+def shared_embedding_columns(categorical_columns, dimension, combiner="mean", shared_embedding_collection_name=None, max_norm=None):
+    """[TF-upstream] shared_embedding_columns (r1.10-r1.13; models/DeepFM/test02.py:30), stated and not verified like the rest of this
+    file: one dense column per categorical column IN THE ORDER GIVEN, named <categorical.name>_shared_embedding, all reading one table.
+    The default collection name is the categorical columns' names, sorted, joined by "_", plus "_shared_embedding"."""
+    categorical_columns = list(categorical_columns or [])
+    if not categorical_columns:
+        raise ValueError("categorical_columns must be a non-empty list.")
+    if dimension is None or dimension < 1:
+        raise ValueError("Invalid dimension {}.".format(dimension))
+    buckets = categorical_columns[0].num_buckets
+    for c in categorical_columns[1:]:
+        if c.num_buckets != buckets:
+            raise ValueError("To use shared_embedding_column, all categorical_columns must have the same number of buckets. "
+                             "Given column: {} with buckets: {} does not match column: {} with buckets: {}".format(
+                                 categorical_columns[0].name, buckets, c.name, c.num_buckets))
+    if not shared_embedding_collection_name:
+        shared_embedding_collection_name = "_".join(sorted(c.name for c in categorical_columns)) + "_shared_embedding"
+    return [SharedEmbeddingColumn(c, dimension, combiner, max_norm, shared_embedding_collection_name) for c in categorical_columns]
 
 
 def indicator_column(categorical_column):

@@ -15,7 +15,7 @@ from torch import nn
 from . import autograd as ag
 from . import ops
 from ._input import collect_ids, categorical_of, raise_pending
-from .feature_column import EmbeddingColumn, IndicatorColumn, NumericColumn
+from .feature_column import EmbeddingColumn, IndicatorColumn, NumericColumn, table_slots
 
 
 class InputLayer(nn.Module):
@@ -38,8 +38,11 @@ class InputLayer(nn.Module):
         # every column an embedding column: the output is a concatenation of (combined) embedding rows -- the bounded magnitudes the
         # fp16 x 2 dense kernels want (dense.mlp_head(embedding_input=...)); numeric columns carry raw values (capital_gain: 99 999)
         self.embedding_only = len(self.emb_cols) == len(self.columns)
+        # one parameter per TABLE: the columns of one shared_embedding_columns collection hold one between them (_col_table: index
+        # into emb_cols -> index into embedding_weights; the identity without shared columns)
+        self._col_table, self._table_columns = table_slots(self.emb_cols)
         self.embedding_weights = nn.ParameterList()
-        for c in self.emb_cols:
+        for c in self._table_columns:
             w = torch.empty(c.num_buckets, c.dimension)
             s = 1.0 / math.sqrt(c.dimension)          # [TF-upstream] embedding_column default initializer
             nn.init.trunc_normal_(w, std=s, a=-2 * s, b=2 * s)
@@ -54,6 +57,17 @@ class InputLayer(nn.Module):
         self._tablesets()
         return all(g[0].range_ok() for g in self._groups)
 
+    def _col_weights(self):
+        """The embedding parameters indexed like emb_cols (the columns of a shared collection hold the same parameter)."""
+        ew = ops.plain_list(self.embedding_weights)
+        return ew if len(ew) == len(self.emb_cols) else [ew[t] for t in self._col_table]
+
+    def _owns_its_tables(self, idxs):
+        """Whether every column of every table that the group of columns `idxs` reads lies inside the group: only then may ONE fused
+        optimiser own those tables (a table with a slot elsewhere would be stepped once per group, with partial gradients)."""
+        inside = [self._col_table[i] for i in idxs]
+        return all(inside.count(t) == self._col_table.count(t) for t in set(inside))
+
     def _col_offset(self, col):
         return self.offsets[self.columns.index(col)]
 
@@ -66,9 +80,11 @@ class InputLayer(nn.Module):
             for i, c in enumerate(self.emb_cols):      # one launch takes one row width and one max_norm; combiners go per slot
                 seen.setdefault((c.dimension, getattr(c, "max_norm", None)), []).append(i)
 
+            cw = self._col_weights()
+
             def close(run, mn):
-                ts = ops.TableSet([self.embedding_weights[j].data for j in run])
-                ts.owners = [self.embedding_weights[j] for j in run]       # HIP updates bump the parameters' version counters
+                ts = ops.TableSet([cw[j].data for j in run])
+                ts.owners = list({id(cw[j]): cw[j] for j in run}.values())       # (each table's parameter once) HIP updates bump the parameters' version counters
                 self._groups.append((ts, run, [self.emb_cols[j].combiner for j in run], mn))
 
             for (dim, mn), idxs in seen.items():
@@ -85,8 +101,11 @@ class InputLayer(nn.Module):
     def fused_sparse_adagrad(self, lr, initial_accumulator_value=0.1):
         """Attach the fused sparse Adagrad (include/dir_hip.h: dir_sparse_adagrad_sorted_f32; the reference's Adagrad on
         `embedding_weights`) to every group of embedding columns: backward() then updates the tables in place for one-hot
-        inputs and they get no .grad.  Returns the optimiser objects (they own the accumulators)."""
-        return [ops.SparseAdagrad(ts, lr, initial_accumulator_value=initial_accumulator_value).attach() for ts, _, _, _ in self._tablesets()]
+        inputs and they get no .grad.  Returns the optimiser objects (they own the accumulators).  A group some of whose tables are
+        shared with a column OUTSIDE it (shared_embedding_columns whose columns are not adjacent in the name-sorted concat) gets none:
+        its tables keep their sparse .grad -- autograd sums the columns' contributions into the one parameter -- like multi-hot columns."""
+        return [ops.SparseAdagrad(ts, lr, initial_accumulator_value=initial_accumulator_value).attach() for ts, idxs, _, _ in self._tablesets()
+                if self._owns_its_tables(idxs)]
 
     def fused_sparse_adam(self, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0):
         """Attach the HIP tf.train.AdamOptimizer update (include/dir_hip.h: dir_sparse_adam_f32; the reference DCN's train_op on
@@ -97,9 +116,12 @@ class InputLayer(nn.Module):
         for ts, idxs, _, mn in self._tablesets():
             if mn or not ts.device.type == "cuda" or not ops.SparseAdam.covers(ts):
                 continue
+            if ts.shared or not self._owns_its_tables(idxs):      # (the HIP Adam's norm words and decay sweep are per slot: shared tables keep .grad)
+                continue
+            cw = self._col_weights()
             opts.append(ops.SparseAdam(ts, beta1, beta2, eps, clip_norm).attach())
-            owned += [self.embedding_weights[i] for i in idxs]
-            opts[-1].owned = [self.embedding_weights[i] for i in idxs]          # parameter of table f of that optimiser's TableSet
+            owned += [cw[i] for i in idxs]
+            opts[-1].owned = [cw[i] for i in idxs]          # parameter of table f of that optimiser's TableSet
         return opts, owned
 
     def _indicator(self, c, features, device, B):
@@ -123,7 +145,7 @@ class InputLayer(nn.Module):
         blocks, inside = {}, set()
         for ts, idxs, comb, mn in self._tablesets():
             cols = [self.emb_cols[i] for i in idxs]
-            ew = ops.plain_list(self.embedding_weights)
+            ew = self._col_weights()
             tabs = [ew[i] for i in idxs]
             got = collect_ids(cols, features, device, memo)
             if got[0] == "onehot":

@@ -37,7 +37,14 @@ INFINITY_CACHE_BYTES = 256 << 20
 class TableSet:
     """F embedding tables [vocab_f, K] plus the device array of their base pointers (built once; the
     kernels read table f's base with a scalar load).  Mirrors the per-column `embedding_weights`
-    variables created under myself_input_layer (deepFM.py:386-390)."""
+    variables created under myself_input_layer (deepFM.py:386-390).
+
+    The same tensor may stand at several slots (feature_column.shared_embedding_columns: several id columns on one table).  Everything
+    indexed by slot (.tables, .vocab, the pointer array) stays per slot -- the forward kernels read slot f through its pointer and do
+    not care --; .slot_table maps a slot to its table among the .distinct ones, .row_base / .total_rows run over the distinct tables
+    (the key space of the sorted sparse updates), and .slot_table_dev is that map as the kernels read it (None without sharing).
+    Sharing is recognised by storage: ANY set in which two slots hold the same rows (same address, shape and strides) is a sharing set,
+    whoever built it (shard.rows_as_tables' [rows] * F among them): its nbytes count those rows once."""
 
     def __init__(self, tables, ld=None):
         tables = list(tables)
@@ -65,15 +72,43 @@ class TableSet:
         self.accums = None                       # train_rows: the Adagrad accumulators living in the same rows
         self._ptrs = torch.tensor([t.data_ptr() for t in tables], dtype=torch.int64, device=self.device)
         self.vocab_dev = torch.tensor(self.vocab, dtype=torch.int64, device=self.device)
+        # slot -> table: two slots share a table when they hold the same rows (same storage address, same shape and row stride)
+        index, self.slot_table, self.distinct = {}, [], []
+        for i, t in enumerate(tables):
+            key = (t.data_ptr(), tuple(t.shape), tuple(t.stride())) if t.numel() else ("empty", i)
+            if key not in index:
+                index[key] = len(self.distinct)
+                self.distinct.append(t)
+            self.slot_table.append(index[key])
+        self.T = len(self.distinct)
+        self.shared = self.T < self.F
+        self.table_vocab = [int(t.shape[0]) for t in self.distinct]
+        self.total_rows = sum(self.table_vocab)
+        self.slot_table_dev = torch.tensor(self.slot_table, dtype=torch.int32, device=self.device) if self.shared else None
+        self._row_base = None
         # row-read policy of the one-hot gather: "stream" = DIR_GATHER_STREAM_ROWS, "reuse" = cacheable,
         # "auto" = stream iff the tables cannot live in the 256 MiB Infinity Cache anyway.  Callers who
         # know their ids are heavily skewed should set "reuse" (see include/dir_hip.h).
         self.row_policy = "auto"
-        self.nbytes = sum(int(t.shape[0]) * self.ld * 4 for t in tables)
+        self.nbytes = sum(v * self.ld * 4 for v in self.table_vocab)         # (a shared table counts once)
         self.owners = []        # tensors sharing these tables' storage under ANOTHER version counter (the nn.Parameters whose .data the
         #                         tables are): written() bumps them too, so caches keyed on parameter._version see HIP updates
         self.grad_sink = None   # callable(ids, d_rows) consuming the gather's row gradients (see SparseAdagrad.attach)
         self.fm_sink = None     # callable(ids, d_rows | None, d_fm, field_sums): the same with the FM backward folded in
+
+    @property
+    def row_base(self):
+        """Device int64 [T]: the first row of every DISTINCT table in the concatenation of them all (built on first use)."""
+        if self._row_base is None:
+            base = [0]
+            for v in self.table_vocab[:-1]:
+                base.append(base[-1] + v)
+            self._row_base = torch.tensor(base, dtype=torch.int64, device=self.device)
+        return self._row_base
+
+    def slots_of(self, t):
+        """The slots that read distinct table t."""
+        return [f for f, u in enumerate(self.slot_table) if u == t]
 
     @property
     def ptrs(self):
@@ -87,24 +122,27 @@ class TableSet:
     def train_rows(cls, tables, initial_accumulator_value=0.1):
         """Packed TRAINING layout (include/dir_hip.h: dir_gather_fm_rows_f32): every slot's table becomes [vocab, 2K] rows
         = [embedding | Adagrad accumulator] in one arena (K = 16: one 128-byte line per row and its optimiser state).
-        .tables are [vocab, K] VIEWS of it (row stride 2K) initialised from `tables`, .accums the accumulator views."""
+        .tables are [vocab, K] VIEWS of it (row stride 2K) initialised from `tables`, .accums the accumulator views.  A table that stands
+        at several slots is laid out ONCE: its slots hold the same view of one row block (two blocks would drift apart)."""
         tables = list(tables)
+        src = cls(tables)                                  # (the slot -> table map of the plain tables)
         K = int(tables[0].shape[1])
         ld = 2 * K
-        vocab = [int(t.shape[0]) for t in tables]
+        vocab = src.table_vocab
         dev = tables[0].device
         arena = torch.empty(sum(vocab) * ld + 32, dtype=torch.float32, device=dev)
         off = (-(arena.data_ptr() // 4)) % 32              # rows 128-byte aligned
-        rows = []
-        for t, v in zip(tables, vocab):
+        blocks = []
+        for t, v in zip(src.distinct, vocab):
             blk = arena[off:off + v * ld].view(v, ld)
             blk[:, :K] = t
             blk[:, K:] = initial_accumulator_value
-            rows.append(blk)
+            blocks.append(blk)
             off += v * ld
-        ts = cls([r[:, :K] for r in rows], ld=ld)
-        ts.accums = [r[:, K:] for r in rows]
-        ts.arena, ts.rows = arena, rows
+        views, accs = [r[:, :K] for r in blocks], [r[:, K:] for r in blocks]
+        ts = cls([views[t] for t in src.slot_table], ld=ld)
+        ts.accums = [accs[t] for t in src.slot_table]
+        ts.arena, ts.rows = arena, [blocks[t] for t in src.slot_table]
         return ts
 
     @classmethod
@@ -152,7 +190,8 @@ class TableSet:
                 if hit is not None:
                     return hit[1]                  # (a sync cannot be captured: the last measurement stands)
                 raise RuntimeError("TableSet.absmax: measure the tables (one eager call) before capturing a graph")
-            m = float(torch.stack([t.abs().max() for t in self.tables if t.numel()] or [torch.zeros((), device=self.device)]).max())
+            once = getattr(self, "distinct", self.tables)       # (a shared table is measured once)
+            m = float(torch.stack([t.abs().max() for t in once if t.numel()] or [torch.zeros((), device=self.device)]).max())
             hit = self._absmax = (sig, m, tuple(hip_bumps(t) for t in watched), _CACHE_GEN[0])
         return hit[1]
 

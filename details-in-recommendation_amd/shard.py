@@ -70,6 +70,16 @@ MAX_ROW_FLOATS = 256          # the widest row the sorted Adagrad covers (64 lan
 MAX_UNITS = 8                 # first-order terms per row (include/dir_hip.h: 1 <= units <= 8)
 
 
+def refuse_shared_columns(who, columns):
+    """The row shards hold one table per slot: a table that several columns share (feature_column.shared_embedding_columns) would be
+    sharded as copies that train apart.  Not covered yet -- refuse by name."""
+    from .feature_column import first_shared
+    c = first_shared(list(columns or []))
+    if c is not None:
+        raise ValueError("%s: column %r shares its embedding table (collection %r) with another column; tables shared between "
+                         "columns are not row-sharded yet" % (who, c.name, c.shared_embedding_collection_name))
+
+
 def div_range(vocab, P, rank):
     """Rows [start, end) that `rank` owns under 'div' (first vocab % P shards hold one extra row)."""
     q, r = divmod(int(vocab), int(P))
@@ -1945,6 +1955,7 @@ class ShardedDeepFMTrainer:
         self.model, self.tables, self.group = model, tables, group
         self.dedup = bool(dedup)
         name = type(self).__name__
+        refuse_shared_columns(name, getattr(model, "dnn_feature_columns", None))
         self.dense_params = [p for n, p in model.named_parameters()
                              if not (n.startswith("embedding_weights") or n.startswith("linear_weights"))]
         self.dense_optimizer = dense_optimizer
@@ -2097,6 +2108,7 @@ class ShardedXDeepFMTrainer(ShardedDeepFMTrainer):
     One-hot ids only: step_bags / predict_bags raise NotImplementedError (bags under dedup are out of scope)."""
 
     def __init__(self, model, tables, lr_sparse, dense_optimizer, group=None, initial_accumulator_value=0.1, linear=None, dedup=True):
+        refuse_shared_columns("ShardedXDeepFMTrainer", getattr(model, "dnn_feature_columns", None))
         if tables.F != model.m or tables.K != model.D or tables.G != 1:
             raise ValueError("ShardedXDeepFMTrainer: the tables must hold F=%d slots of K=%d floats (tables_from_model), got F=%d K=%d groups=%d"
                              % (model.m, model.D, tables.F, tables.K, tables.G))
@@ -2107,6 +2119,7 @@ class ShardedXDeepFMTrainer(ShardedDeepFMTrainer):
         """The ShardedTables of `model` (every rank holds the same replicated model): slot f = the f-th embedding column; linear: + the
         first-order weights, which must be over the embedding columns' categoricals (they share the id exchange).  kw: ShardedTables'
         options (partitions=, chunks=, mode=, ...)."""
+        refuse_shared_columns("ShardedXDeepFMTrainer.tables_from_model", model.dnn_feature_columns)
         if linear and not model._same_categoricals():
             raise ValueError("ShardedXDeepFMTrainer.tables_from_model(linear=True): the linear columns are not the embedding columns' "
                              "categoricals; pass linear=False and compute the first-order term beside the shards")
@@ -2158,6 +2171,8 @@ def _esmm_parts(model):
     if any(t is None for t in towers):
         raise ValueError("ShardedESMMTrainer: both sub-models need a dnn tower (dnn_feature_columns)")
     il = towers[0].input_layer
+    for t in towers:
+        refuse_shared_columns("ShardedESMMTrainer", t.input_layer.columns)
     dim = None
     for c in il.columns:
         cat = categorical_of(c)
@@ -2308,6 +2323,7 @@ def _dcn_columns(model):
     dcn.DeepCrossNetwork the row-sharded trainer covers; ValueError naming the column otherwise."""
     from .feature_column import EmbeddingColumn
     il = model.input_layer
+    refuse_shared_columns("ShardedDCNTrainer", il.columns)
     cols = [c for c in il.columns if isinstance(c, EmbeddingColumn)]
     if not cols:
         raise ValueError("ShardedDCNTrainer: the model has no embedding columns to shard")

@@ -48,6 +48,8 @@ def share_sorted_entries(a, b):
     -> True if they were linked."""
     if list(a.ts.vocab) != list(b.ts.vocab) or a.ts.F != b.ts.F or getattr(a, "method", "sorted") != "sorted":
         return False
+    if a.ts.shared or b.ts.shared:          # a sharing set's keys run over its distinct tables: not the other set's keys
+        return False
     a._share = b._share = _SortedShare()
     return True
 
@@ -67,14 +69,18 @@ class _SortedOpt:
     def __init__(self, tables):
         from .ops import _as_tableset          # (ops imports this module: the name is taken where it is used, once per optimiser)
         self.ts = _as_tableset(tables)
-        base = [0]
-        for v in self.ts.vocab[:-1]:
-            base.append(base[-1] + v)
-        self.total_rows = sum(self.ts.vocab)
-        self.row_base = torch.tensor(base, dtype=torch.int64, device=self.ts.device)
+        # the key space runs over the DISTINCT tables (ts.row_base [T]); without sharing that is one table per slot
+        self.total_rows = self.ts.total_rows
+        self.row_base = self.ts.row_base
         self._slots = []
         self._ws = None
         self._share = None
+
+    def _refuse_shared(self, entry):
+        """Only SparseAdagrad's one-hot steps know the slot -> table map: everything else refuses a set that shares tables."""
+        if self.ts.shared:
+            raise ValueError("%s does not cover tables shared between slots (slots %s read one table)"
+                             % (entry, self.ts.slots_of(next(t for t in range(self.ts.T) if len(self.ts.slots_of(t)) > 1))))
 
     def _ptr_array(self, tensors):
         """The [F] device array of base pointers the kernels read table f's slot through."""
@@ -168,12 +174,17 @@ class SparseAdagrad(_SortedOpt):
         super().__init__(tables)
         self.lr = float(lr)
         self.method = method
+        if self.ts.shared and method != "sorted":
+            # the chains are built per (slot, id): a shared row would get one chain -- and one step -- per slot
+            raise ValueError("method='chains' does not cover tables shared between slots: use the sorted method")
         if self.ts.accums is not None:           # packed training rows: the accumulators live beside the embeddings
             if method != "sorted":
                 raise ValueError("packed training rows are updated by the sorted method")
             self.accums = self.ts.accums
         else:
-            self.accums = [torch.full_like(t, initial_accumulator_value) for t in self.ts.tables]
+            # one accumulator per TABLE; .accums stays indexed by slot (the slots of a shared table hold the same tensor)
+            per_table = [torch.full_like(t, initial_accumulator_value) for t in self.ts.distinct]
+            self.accums = [per_table[t] for t in self.ts.slot_table]
         self._slots = [] if getattr(self.ts, "arena", None) is not None else self.accums      # (one arena: its counter covers the accumulators)
         self.acc_ptrs = self._ptr_array(self.accums)
         self.head = torch.full((self.total_rows,), -1, dtype=torch.int32, device=self.ts.device) if method == "chains" else None
@@ -191,6 +202,12 @@ class SparseAdagrad(_SortedOpt):
         """dir_sparse_adagrad_sorted_rows_f32, or its _from form when the linked optimiser has just sorted the same entries."""
         ts = self.ts
         ws, need, _ = self._sort_area("SparseAdagrad.step", lib.dir_sparse_adagrad_sorted_workspace_bytes, B, ts.F, ts.K)
+        if ts.shared:                            # (never linked to another optimiser's sort: share_sorted_entries refuses a sharing set)
+            _lib.check(lib.dir_sparse_adagrad_sorted_rows_shared_f32(
+                _ptr(ts._ptrs), _ptr(self.acc_ptrs), ts.ld, ts.F, ts.K, _ptr(ids), sb, sf, _ptr(grad), grad.stride(0) if grad is not None else 0,
+                _ptr(fm_g), _ptr(fm_sum), self.lr, B, _ptr(self.row_base), self.total_rows, _ptr(ts.slot_table_dev), ts.T, ws, need, _stream()))
+            self._written()
+            return
         src = self._take_sort(ids, B, sb, sf)
         args = (_ptr(ts._ptrs), _ptr(self.acc_ptrs), ts.ld, ts.F, ts.K, _ptr(ids), sb, sf, _ptr(grad), grad.stride(0) if grad is not None else 0,
                 _ptr(fm_g), _ptr(fm_sum), self.lr, B, _ptr(self.row_base), self.total_rows, ws, need)
@@ -225,6 +242,13 @@ class SparseAdagrad(_SortedOpt):
         if ts.ld != ts.K or (self._share is not None and self.method == "sorted"):
             self._rows_update(lib, ids, B, sb, sf, grad, None, None)
             return
+        if ts.shared:
+            ws, need, _ = self._sort_area("SparseAdagrad.step", lib.dir_sparse_adagrad_sorted_workspace_bytes, B, ts.F, ts.K)
+            _lib.check(lib.dir_sparse_adagrad_sorted_shared_f32(_ptr(ts.ptrs), _ptr(self.acc_ptrs), ts.F, ts.K, _ptr(ids), sb, sf,
+                                                                _ptr(grad), grad.stride(0), self.lr, B, _ptr(self.row_base),
+                                                                self.total_rows, _ptr(ts.slot_table_dev), ts.T, ws, need, _stream()))
+            self._written()
+            return
         if self.method == "chains":
             if self._next is None or self._next.numel() < B * ts.F:
                 self._next = torch.empty(B * ts.F, dtype=torch.int32, device=ts.device)
@@ -242,6 +266,7 @@ class SparseAdagrad(_SortedOpt):
         """Owner side of a sharded backward (shard.ShardedTables): payload [n] int64 (local_row * F + slot, < 0 pruned) as
         received from all ranks, grad [n, K] in the same order (include/dir_hip.h: dir_sparse_adagrad_sorted_payload_f32)."""
         ts = self.ts
+        self._refuse_shared("SparseAdagrad.step_payload")
         n = self._check_payload(payload, grad, ts.K)
         if n == 0:
             return
@@ -259,6 +284,7 @@ class SparseAdagrad(_SortedOpt):
         touched row takes one Adagrad step with its summed gradient, through the slot's max_norm clip derivative (slot_mn [F] device
         fp32 or None + mn, as ops.slot_max_norms gives them) at its pre-update value."""
         ts = self.ts
+        self._refuse_shared("SparseAdagrad.step_bags")
         if ts.ld != ts.K:
             raise ValueError("step_bags: plain [vocab, K] tables")
         self._check_bags("step_bags", recv, P, cap_e, cap_b, grad_rows, ts.K, slot_mn)
@@ -291,6 +317,7 @@ class SparseAdam(_SortedOpt):
     def __init__(self, tables, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0):
         super().__init__(tables)
         ts = self.ts
+        self._refuse_shared("SparseAdam")       # (its norm words and decay sweep are per slot)
         if ts.ld != ts.K:
             raise ValueError("SparseAdam: plain [vocab, K] tables")
         self.beta1, self.beta2, self.eps, self.clip_norm = float(beta1), float(beta2), float(eps), float(clip_norm)
@@ -458,6 +485,7 @@ class SparseFtrl(_SortedOpt):
 
     def __init__(self, tables, lr=0.2, initial_accumulator_value=0.1, l1=0.0, l2=0.0):
         super().__init__(tables)
+        self._refuse_shared("SparseFtrl")
         self.lr, self.l1, self.l2 = float(lr), float(l1), float(l2)
         self.packed = getattr(self.ts, "linears", None) is not None      # TableSet.ftrl_rows: n and z live in the weights' rows
         if self.packed:

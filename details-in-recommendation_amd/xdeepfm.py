@@ -12,6 +12,7 @@ from . import ops
 from ._input import checked_forward as _checked_forward
 from ._input import collect_ids, categorical_of
 from .deepfm import _glorot_uniform_
+from .feature_column import table_slots
 import os as _os
 
 CIN_STACK_NODE = _os.environ.get("DIR_CIN_STACK_NODE", "1") != "0"      # development switch: 0 keeps one autograd node per CIN layer
@@ -31,9 +32,11 @@ class XDeepFM(nn.Module):
             raise ValueError("CIN needs one embedding dimension for every field")
         self.activation = dnn_activation_fn
         s = 1.0 / math.sqrt(self.D)
+        # one parameter per TABLE: the columns of one shared_embedding_columns collection hold one between them (_slot_table)
+        self._slot_table, self._table_columns = table_slots(self.dnn_feature_columns)
         self.embedding_weights = nn.ParameterList(
             [nn.Parameter(nn.init.trunc_normal_(torch.empty(c.num_buckets, self.D), std=s, a=-2 * s, b=2 * s))
-             for c in self.dnn_feature_columns])
+             for c in self._table_columns])
         self.linear_weights = nn.ParameterList(
             [nn.Parameter(torch.zeros(categorical_of(c).num_buckets)) for c in self.linear_feature_columns])
         self.linear_bias = nn.Parameter(torch.zeros(1))
@@ -55,11 +58,16 @@ class XDeepFM(nn.Module):
         self.dnn_out = nn.Linear(d, 1)
         self._ts_key = None
 
+    def _slot_weights(self):
+        """The embedding parameters indexed by field (the columns of a shared collection hold the same parameter)."""
+        tabs = ops.plain_list(self.embedding_weights)
+        return tabs if len(tabs) == self.m else [tabs[t] for t in self._slot_table]
+
     def _tablesets(self):
         key = tuple([p.data_ptr() for p in ops.plain_list(self.embedding_weights)] + [p.data_ptr() for p in ops.plain_list(self.linear_weights)])
         if self._ts_key != key:
             ops.refuse_rebuild_under_sink(getattr(self, "_emb_ts", None), getattr(self, "_lin_ts", None))
-            self._emb_ts = ops.TableSet([p.data for p in self.embedding_weights])
+            self._emb_ts = ops.TableSet([p.data for p in self._slot_weights()])
             self._emb_ts.owners = list(self.embedding_weights)          # HIP updates bump the parameters' version counters (ops.mark_written)
             self._lin_ts = ops.TableSet([p.data for p in self.linear_weights]) if len(self.linear_weights) else None
             if self._lin_ts is not None:
@@ -181,7 +189,7 @@ class XDeepFM(nn.Module):
         got = collect_ids(self.dnn_feature_columns, features, device)
         comb = self.dnn_feature_columns[0].combiner
         if train:      # sparse table gradients (autograd.EmbeddingBag / LinearLogit)
-            tabs = ops.plain_list(self.embedding_weights)
+            tabs = self._slot_weights()
             emb = ag.embedding_bag(emb_ts, got[1], tabs) if got[0] == "onehot" else \
                 ag.embedding_bag(emb_ts, got[1], tabs, got[2], got[3], combiner=comb, field_major=True)
         elif got[0] == "onehot":

@@ -1219,6 +1219,28 @@ int dir_sparse_adagrad_sorted_rows_f32(float* const* tables, float* const* accum
                                        const int64_t* row_base, int64_t total_rows, void* workspace,
                                        int64_t workspace_bytes, dir_stream_t stream);
 
+/* The two sorted Adagrad updates over tables SHARED between slots ([TF-upstream] shared_embedding_columns, models/DeepFM/test02.py:30:
+ * several id columns read and train one table).  tables / accums stay device arrays [F] of per-SLOT pointers (the slots of one table
+ * hold the same pointer); slot_table: DEVICE int32 [F], slot f's table among the n_tables distinct ones; row_base: DEVICE int64
+ * [n_tables] and total_rows run over the DISTINCT tables, ascending.  The key of entry (b, f) is row_base[slot_table[f]] + id, pruned
+ * against that table's rows (an entry whose map value is outside [0, n_tables) is pruned too), and the pairs take the global sort
+ * (the slot-major one relies on disjoint key ranges per slot).  A row's entries from ALL of its slots therefore form ONE run, in
+ * entry order e = b*F + f: it is summed once (compensated, as above) and the row takes ONE Adagrad step with the summed gradient, as
+ * TensorFlow sums duplicate indices of the one variable before the update.  slot_table == NULL (n_tables == F) is the unshared call:
+ * the same results as dir_sparse_adagrad_sorted_f32 / _rows_f32 bit for bit.  An identity map gives the same keys through the global
+ * sort: bit for bit too, except for B >= 4096 with pruned ids, where the unshared call's slot-major sort leaves a slot's pruned entries
+ * at the end of that slot's segment, the tiles cut the later slots' runs elsewhere and the sums agree to about an ulp only.
+ * workspace: dir_sparse_adagrad_sorted_workspace_bytes(B, F, K, total_rows), total_rows over the distinct tables. */
+int dir_sparse_adagrad_sorted_shared_f32(float* const* tables, float* const* accums, int F, int K, const int64_t* ids,
+                                         int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, float lr,
+                                         int64_t B, const int64_t* row_base, int64_t total_rows, const int32_t* slot_table,
+                                         int n_tables, void* workspace, int64_t workspace_bytes, dir_stream_t stream);
+int dir_sparse_adagrad_sorted_rows_shared_f32(float* const* tables, float* const* accums, int64_t row_ld, int F, int K,
+                                              const int64_t* ids, int64_t stride_b, int64_t stride_f, const float* grad,
+                                              int64_t grad_ld, const float* fm_g, const float* fm_sum, float lr, int64_t B,
+                                              const int64_t* row_base, int64_t total_rows, const int32_t* slot_table,
+                                              int n_tables, void* workspace, int64_t workspace_bytes, dir_stream_t stream);
+
 /* tf.train.AdamOptimizer on the embedding tables, as the reference's train_op applies it (models/DeepCrossNetwork/DeepCrossNetwork.py:264-290:
  * every gradient clipped on its own with tf.clip_by_norm(g, 100.0); models/DeepCrossNetwork/train.py:119-124: Adam, epsilon 1e-4).  The
  * tables' gradients are IndexedSlices; [TF-upstream] AdamOptimizer._apply_sparse decays m and v of EVERY row, adds the summed row
