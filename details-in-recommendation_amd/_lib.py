@@ -266,6 +266,12 @@ SIGNATURES = {
     "dir_shard_bags_linear_grad_f32": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
     "dir_sparse_ftrl_rows_sorted_bags_f32": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i64, c_i64, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                      c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    # dropout (csrc/dropout.hip): state = device int64[2] (seed, draw); used / used_in / used_out = device int64 [1] or NULL
+    "dir_philox4x32_10": (None, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "dir_dropout_f32": (c_i32, [c_vp, c_vp, c_i64, c_i64, ctypes.c_float, c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp]),
+    "dir_dropout_mask_u8": (c_i32, [c_i64, c_i64, ctypes.c_float, c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp]),
+    "dir_dropout_advance": (c_i32, [c_vp, c_vp]),
+    "dir_bn_affine_dropout_f32": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, ctypes.c_float, c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp]),
 }
 
 DIR_OK, DIR_E_BADARG, DIR_E_RANGE, DIR_E_HIP, DIR_E_UNSUPPORTED = 0, -1, -2, -3, -4

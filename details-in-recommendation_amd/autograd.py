@@ -514,6 +514,29 @@ def cross_network(x0, w, b):
     return CrossNetwork.apply(x0, w, b)
 
 
+class Dropout(torch.autograd.Function):
+    """core_layers.dropout(net, rate, training=True) (deepFM.py:301-302) on dir_dropout_f32.  What the node keeps for its backward is the
+    16 bytes the forward used -- seed and draw -- never a mask: the backward regenerates it from them alone, whatever the state has become since."""
+
+    @staticmethod
+    def forward(ctx, x, rate, state, stream_id):
+        out, used = ops.dropout(x.contiguous(), rate, state, stream_id, want_used=True)
+        ctx.rate, ctx.state, ctx.stream_id = rate, state, stream_id
+        ctx.save_for_backward(used)
+        return out
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g):
+        used, = ctx.saved_tensors
+        return ops.dropout(g.contiguous(), ctx.rate, ctx.state, ctx.stream_id, used=used), None, None, None
+
+
+def dropout(x, rate, state, stream_id=0):
+    """Dropout of a float32 CUDA tensor with the masks of `state` (ops.DropoutState) at site `stream_id`; differentiable."""
+    return Dropout.apply(x, float(rate), state, int(stream_id))
+
+
 class Adagrad(torch.optim.Adagrad):
     """torch.optim.Adagrad ([TF-upstream] tf.train.AdagradOptimizer's rule with eps = 0; the reference's dnn_optimizer='Adagrad',
     deepFM.py:61) whose step on dense float32 CUDA variables is ONE elementwise HIP pass per variable (dir_adagrad_dense_f32) instead of

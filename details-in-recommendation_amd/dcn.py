@@ -14,10 +14,10 @@ import math
 import torch
 from torch import nn
 
-from .dense import dense_act, _RELUS, _MlpHeadFn, _Units1Fn, mlp_stack_supported
+from .dense import Drop, dense_act, _RELUS, _MlpHeadFn, _Units1Fn, mlp_stack_supported
 from . import autograd as ag
 from . import ops
-from .deepfm import _BatchNormInfer, _dropout_train, _glorot_uniform_
+from .deepfm import _BatchNormInfer, _DropoutRng, _drop_rate, _dropout_train, _glorot_uniform_, dropout_rng_of
 from .input_layer import InputLayer
 from ._input import checked_forward as _checked_forward
 from ._input import raise_pending
@@ -29,7 +29,7 @@ def _glorot_normal_(w):  # glorot_normal_initializer, DeepCrossNetwork.py:397 ([
     return nn.init.trunc_normal_(w, std=std, a=-2 * std, b=2 * std)
 
 
-class DeepCrossNetwork(nn.Module):
+class DeepCrossNetwork(_DropoutRng, nn.Module):
     def __init__(self, model_dir=None, columns=None, cross_layer_num=2, dnn_hidden_units=None, dnn_dropout=None,
                  config=None, dnn_activation_fn=torch.relu, weight_column=None, optimizer=None, optimizer_spec=None,
                  batch_norm=True, l2_reg=None, learning_rate_spec=None):
@@ -71,16 +71,26 @@ class DeepCrossNetwork(nn.Module):
             return ag.cross_network(x0, self.cross_w, self.cross_b)
         return ops.cross_network(x0, self.cross_w.data, self.cross_b.data)       # :350-367
 
+    def _drop_site(self, net):
+        """(rate, generator state) of this training forward's dropout sites (site i = hidden layer i; :405-408, TRAIN only), the state advanced
+        by one draw -- or (None, None): no dropout in this forward, or not on the HIP path (CPU tensors)."""
+        rate = _drop_rate(self, self.hparams.get("dnn_dropout"), net)
+        return (rate, dropout_rng_of(self, net.device).advance()) if rate is not None else (None, None)
+
     def deep_architecture(self, net):
         n = len(self.hidden)
         bi = 0
+        rate, rng = self._drop_site(net)
         for i, lin in enumerate(self.hidden):                                    # :392-403
             bn = None
             if self.batch_norm and i < n - 1:
                 bn = self.bns[bi]
                 bi += 1
+            if rate is not None:                                                 # :405-408 (TRAIN only), after the BN: inside the layer's node
+                net = dense_act(lin, net, self.activation, bn=bn, drop=Drop(rate, rng, i, "after"))
+                continue
             net = dense_act(lin, net, self.activation, bn=bn)                    # dir_dense_f32 when covered; inference BN in its epilogue
-            net = _dropout_train(self, net, self.hparams.get("dnn_dropout"))    # :405-408 (TRAIN only), after the BN
+            net = _dropout_train(self, net, self.hparams.get("dnn_dropout"), i)  # (CPU tensors: the library's dropout)
         return net
 
     def _deep_logit(self, net, wd):
@@ -109,32 +119,40 @@ class DeepCrossNetwork(nn.Module):
         weights and the layer's ReLU in one pass over the activation, dir_units1_relu_backward_f32), the cross share with the
         elementwise backward (dense._Units1Fn).  As library ops the concat, the [B, d + h] x [d + h, 1] product and its backward were
         0.9 ms of the 8.8 ms step at 65 536 x (429 + 1024).  -> [B, 1]; where the last layer is not covered (a batch under dense.MIN_ROWS) the plain concat + dense(1) on the layers already run; None
-        before anything has run when the model has no such form (no hidden layer, no cross layer, dropout, eval())."""
+        before anything has run when the model has no such form (no hidden layer, no cross layer, dropout on CPU tensors, eval()).
+        With dnn_dropout every hidden layer's dropout (:405-408, after the batch norm) runs inside that layer's node, the last one's between
+        the layer and the head share inside _MlpHeadFn."""
         n = len(self.hidden)
-        if (not n or self.cross_layer_num <= 0 or self.hparams.get("dnn_dropout") or not self.training
+        if (not n or self.cross_layer_num <= 0 or not self.training
+                or (self.hparams.get("dnn_dropout") and _drop_rate(self, self.hparams.get("dnn_dropout"), x0) is None)
                 or self.logits_layer.bias is None or self.hidden[-1].out_features > 4096):
             return None
         d = self.column_num
         net, bi = x0, 0
+        rate, rng = self._drop_site(x0)
         for i, lin in enumerate(self.hidden[:-1]):                               # :392-403, as deep_architecture
             bn = None
             if self.batch_norm:
                 bn = self.bns[bi]
                 bi += 1
-            net = dense_act(lin, net, self.activation, bn=bn)
+            net = dense_act(lin, net, self.activation, bn=bn, drop=Drop(rate, rng, i, "after") if rate is not None else None)
         last = self.hidden[-1]
         if not mlp_stack_supported([last], net, self.activation):
             # the plain form from here: the layers below have run, and their batch norms have advanced the moving statistics -- once per step
             # (returning None sent forward() through deep_architecture, which ran them a second time at every batch under dense.MIN_ROWS)
-            deep = dense_act(last, net, self.activation)
+            deep = dense_act(last, net, self.activation, drop=Drop(rate, rng, n - 1, "after") if rate is not None else None)
             return self.logits_layer(torch.cat([cross, deep], dim=-1))           # :136-137
         wl = self.logits_layer.weight                                            # [1, d + h]
         from . import dense as _dense
-        _dense._FWD_BOUNDED[0] = bool(self.batch_norm) and n >= 2              # the last layer reads a batch-normalised activation: fp16 x 2 kernels
+        # the last layer reads a batch-normalised activation: fp16 x 2 kernels.  Behind a dropout that bound grows by 1 / keep_prob -- no promise
+        # is made then, the layer takes the row-scaled kernel with its own max pass
+        _dense._FWD_BOUNDED[0] = bool(self.batch_norm) and n >= 2 and rate is None
+        _dense._FWD_DROPOUT[0] = Drop(rate, rng, [n - 1]) if rate is not None else None
         try:
             deep_logit = _MlpHeadFn.apply(net, wl[:, d:], self.logits_layer.bias, last.weight, last.bias)
         finally:
             _dense._FWD_BOUNDED[0] = False
+            _dense._FWD_DROPOUT[0] = None
         return deep_logit + _Units1Fn.apply(cross, wl[:, :d], None)
 
     def _padded_cross_params(self):

@@ -16,7 +16,7 @@ import math
 import torch
 from torch import nn
 
-from .dense import dense_act, mlp_head, mlp_head_supported, mlp_stack, mlp_stack_supported, tower_infer, units1
+from .dense import Drop, dense_act, mlp_head, mlp_head_supported, mlp_stack, mlp_stack_supported, tower_infer, units1
 from . import autograd as ag
 from . import ops
 from ._input import checked_forward as _checked_forward
@@ -66,14 +66,55 @@ class _BatchNormInfer(nn.Module):
         return x * inv + (self.beta - mean * inv)
 
 
-def _dropout_train(module, net, rate):
-    """core_layers.dropout(net, rate, training=True) in TRAIN mode only (deepFM.py:301-302, DeepCrossNetwork.py:405-408)."""
+def dropout_rng_of(module, device=None):
+    """The module's dropout generator state (ops.DropoutState), created on first use on `device` (default: the current CUDA device) with
+    torch.initial_seed() as its seed -- a torch.manual_seed(...) before the first training forward decides the masks.  Asked for another
+    CUDA device later (the model moved), the state moves there with its seed and draw.  It is not a parameter or a buffer: state_dict()
+    does not hold it -- a checkpoint that is to resume the mask sequence stores model.dropout_rng.get_state() beside it."""
+    device = torch.device(device) if device is not None else None
+    if device is not None and device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    rng = module.__dict__.get("_dropout_rng")
+    if rng is None:
+        rng = ops.DropoutState(device=device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+        module.__dict__["_dropout_rng"] = rng
+    elif device is not None and rng.device != device:
+        rng.to(device)
+    return rng
+
+
+class _DropoutRng:
+    """model.dropout_rng: the ops.DropoutState behind the model's dropout sites (manual_seed / get_state / set_state).  The masks are this
+    library's Philox4x32-10 stream, not TensorFlow's; the state advances once per training forward and every site has its own stream_id."""
+
+    @property
+    def dropout_rng(self):
+        p = next(self.parameters(), None)
+        if p is not None and not p.is_cuda:
+            raise RuntimeError("model.dropout_rng lives on the GPU beside the model: move the model first (model.cuda()), then seed it "
+                               "(on CPU tensors dnn_dropout runs the library's dropout under torch's own generator)")
+        return dropout_rng_of(self, p.device if p is not None else None)
+
+
+def _drop_rate(module, rate, net):
+    """The rate when `net` goes through the HIP dropout in this forward: TRAIN mode, a CUDA float32 tensor, a rate set; else None."""
+    if rate and _train_mode(module) and net.is_cuda and net.dtype == torch.float32:
+        return float(rate)
+    return None
+
+
+def _dropout_train(module, net, rate, stream_id=0, rng=None):
+    """core_layers.dropout(net, rate, training=True) in TRAIN mode only (deepFM.py:301-302, DeepCrossNetwork.py:405-408): on the GPU the HIP
+    kernel with the masks of the module's generator state (rng, default dropout_rng_of(module)) at site stream_id -- the caller advances the
+    state once per forward; on CPU tensors the library's."""
     if rate and _train_mode(module):
+        if _drop_rate(module, rate, net) is not None:
+            return ag.dropout(net, float(rate), rng if rng is not None else dropout_rng_of(module, net.device), stream_id)
         return torch.nn.functional.dropout(net, p=float(rate), training=True)
     return net
 
 
-class DeepFM(nn.Module):
+class DeepFM(_DropoutRng, nn.Module):
     def __init__(self, model_dir=None, linear_feature_columns=None, linear_optimizer="Ftrl",
                  linear_sparse_combiner="sum", dnn_feature_columns=None, dnn_optimizer="Adagrad",
                  dnn_hidden_units=None, dnn_activation_fn=torch.relu, dnn_dropout=None, fm_embedding_size=None,
@@ -187,19 +228,25 @@ class DeepFM(nn.Module):
         return out
 
     def _dnn_logit_layers(self, net):
-        if not len(self.bns) and not self.hparams.get("dnn_dropout") and mlp_stack_supported(self.hidden, net, self.activation):
+        # dropout (deepFM.py:301-302, TRAIN only): site i = hidden layer i, one draw per training forward; the fused nodes take it along
+        rate = _drop_rate(self, self.hparams.get("dnn_dropout"), net)
+        rng = dropout_rng_of(self, net.device).advance() if rate is not None else None
+        if (not len(self.bns) and (rate is not None or not self.hparams.get("dnn_dropout"))
+                and mlp_stack_supported(self.hidden, net, self.activation)):
+            drop = Drop(rate, rng, list(range(len(self.hidden)))) if rate is not None else None
             if self.units == 1 and mlp_head_supported(self.hidden, self.logits_layer, net, self.activation):
-                return mlp_head(self.hidden, self.logits_layer, net, embedding_input=True)      # training: tower + logit layer as one autograd node
-            return self._logits_of(mlp_stack(self.hidden, net, embedding_input=True))           # training: the whole tower as one autograd node
+                return mlp_head(self.hidden, self.logits_layer, net, embedding_input=True, drop=drop)      # training: tower + logit layer as one autograd node
+            return self._logits_of(mlp_stack(self.hidden, net, embedding_input=True, drop=drop))           # training: the whole tower as one autograd node
         for i, lin in enumerate(self.hidden):                                   # deepFM.py:292-308
             if len(self.bns) and not _train_mode(self):                        # inference: no dropout, BN folded into the layer's epilogue
                 net = dense_act(lin, net, self.activation, bn=self.bns[i])
                 continue
-            if len(self.bns) and not self.hparams.get("dnn_dropout"):          # training without dropout: layer + batch norm as one autograd node
-                net = dense_act(lin, net, self.activation, bn=self.bns[i])
+            if len(self.bns) and (rate is not None or not self.hparams.get("dnn_dropout")):
+                # training: layer (+ dropout, :301-302, before the BN) + batch norm as one autograd node
+                net = dense_act(lin, net, self.activation, bn=self.bns[i], drop=Drop(rate, rng, i, "before") if rate is not None else None)
                 continue
             net = dense_act(lin, net, self.activation)                          # dir_dense_f32 when covered
-            net = _dropout_train(self, net, self.hparams.get("dnn_dropout"))    # :301-302 (TRAIN only), before the BN
+            net = _dropout_train(self, net, self.hparams.get("dnn_dropout"), i, rng)    # :301-302 (TRAIN only), before the BN
             if len(self.bns):
                 net = self.bns[i](net)
         return self._logits_of(net)                                              # :311-317

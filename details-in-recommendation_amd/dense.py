@@ -10,10 +10,22 @@ matrix-vector products: library forward, elementwise backward).
 Weight rows are handed to the kernel with a stride that is a multiple of 64 floats: a 416-float stride (1 664 bytes, the first
 DeepFM / DCN layer) costs the kernel -- and rocBLAS -- 20 % (tools/dense_sweep.py); the padded copy is 640 KB per layer.
 """
+import typing
+
 import torch
 import torch.nn.functional as F
 
 from . import ops
+
+
+class Drop(typing.NamedTuple):
+    """The dropout a training node takes along (TRAIN mode, CUDA tensors: the models decide).  sites: the stream id of the one site behind a
+    dense_act layer, or one id per hidden layer of an mlp_head / mlp_stack node.  order: where the site stands relative to the layer's batch
+    norm -- "before" (deepFM.py:301-308: dense, dropout, BN) or "after" (DeepCrossNetwork.py:400-408: dense, BN, dropout)."""
+    rate: float
+    state: "ops.DropoutState"
+    sites: typing.Union[int, typing.Sequence[int]]
+    order: str = "before"
 
 _RELUS = (torch.relu, F.relu, torch.nn.functional.relu)
 # Below this many rows a layer stays on the library: a 128-row tile per workgroup leaves most CUs idle on small batches, where
@@ -159,23 +171,38 @@ class _DenseBnFn(torch.autograd.Function):
     passes, a compare and a mask multiply), then the layer's weight / bias / data gradients as in _DenseFn."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, bn, relu, bounded=False):
+    def forward(ctx, x, weight, bias, gamma, beta, bn, relu, bounded=False, drop=None):
         xb = []
         y = ops.dense(x, _kernel_weight(x, weight), bias, relu=relu, xbits_out=xb)
+        # drop (a Drop with one site): dropout between the layer and the statistics ("before", deepFM.py:301-308) -- y is
+        # dropped in place, the statistics and the backward see the dropped activation -- or behind the affine (DeepCrossNetwork.py:400-408)
+        used = None
+        if drop is not None and drop.order == "before":
+            y, used = ops.dropout(y, drop.rate, drop.state, drop.sites, out=y, want_used=True)
         mean, inv, scale, shift = ops.bn_train_stats(y, gamma, beta, bn.moving_mean, bn.moving_variance, bn.eps, bn.momentum)
         ctx.relu = relu
         ctx.xbits = xb[0] if xb else None
         ctx.has_bias = bias is not None
-        ctx.save_for_backward(x, weight, y, mean, inv, gamma)
-        return torch.addcmul(shift, y, scale)
+        ctx.drop = drop
+        if drop is not None and drop.order == "after":
+            out, used = ops.bn_affine_dropout(y, scale, shift, drop.rate, drop.state, drop.sites, want_used=True)
+        else:
+            out = torch.addcmul(shift, y, scale)
+        ctx.save_for_backward(x, weight, y, mean, inv, gamma, used)
+        return out
 
     @staticmethod
     @torch.no_grad()
     def backward(ctx, g):
-        x, weight, y, mean, inv, gamma = ctx.saved_tensors
+        x, weight, y, mean, inv, gamma, used = ctx.saved_tensors
         if g.stride(1) != 1 or g.stride(0) % 4 or g.data_ptr() % 16:
             g = g.contiguous()
+        drop = ctx.drop
+        if drop is not None and drop.order == "after":               # through the dropout behind the affine: the forward's mask, regenerated
+            g = ops.dropout(g.contiguous(), drop.rate, drop.state, drop.sites, used=used)
         gpre, gbeta, ggamma = ops.bn_train_backward(g, y, mean, inv, gamma, relu_gate=ctx.relu)
+        if drop is not None and drop.order == "before":              # gpre is dL/d(dropped activation) (gated by it): back through the dropout
+            gpre = ops.dropout(gpre, drop.rate, drop.state, drop.sites, out=gpre, used=used)
         gx = None
         rb, ab = _gbits(gpre, ctx.xbits is not None, x.shape[1], ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         if ctx.needs_input_grad[0]:
@@ -183,32 +210,55 @@ class _DenseBnFn(torch.autograd.Function):
             gx = ops.dense(gpre, wt, None, relu=False, row_bits=rb) if ops.dense_supported(gpre, wt) else gpre @ weight
         gw, gb = _wb_grads(gpre, x, ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2], g_bits=ab, x_bits=ctx.xbits if ab is not None else None)
         return (gx, gw, gb, ggamma if gamma is not None and ctx.needs_input_grad[3] else None, gbeta if ctx.needs_input_grad[4] else None,
-                None, None, None)
+                None, None, None, None)
 
 
-def _dense_bn_train(bn, x, weight, bias, relu, bounded=False):
+def _dense_bn_train(bn, x, weight, bias, relu, bounded=False, drop=None):
     """The training forms of a covered hidden layer: with a batch norm in TRAIN mode the fused node, otherwise _DenseFn + the module.
-    bounded: the caller vouches that x is bounded by construction (the weight gradient may then take the fp16 x 2 kernel)."""
+    bounded: the caller vouches that x is bounded by construction (the weight gradient may then take the fp16 x 2 kernel).
+    drop: a Drop with one site, TRAIN mode only."""
     if (bn is not None and BN_TRAIN_FUSED and bn.training and torch.is_grad_enabled() and weight.shape[0] % 4 == 0 and weight.shape[0] <= 4096
             and x.shape[0] > 0):
-        return _DenseBnFn.apply(x, weight, bias, bn.gamma, bn.beta, bn, relu, bounded)
-    return _apply_bn(bn, _DenseFn.apply(x, weight, bias, relu, bounded))
+        return _DenseBnFn.apply(x, weight, bias, bn.gamma, bn.beta, bn, relu, bounded, drop)
+    return _bn_and_dropout(bn, _DenseFn.apply(x, weight, bias, relu, bounded), drop)
 
 
-def _forward_layers(ys, h, params, L, bounded, last_bits):
+def _bn_and_dropout(bn, y, drop):
+    """What follows a layer's activation when no fused node takes it: the batch norm module (or none) and the dropout node, in drop.order."""
+    if drop is None:
+        return _apply_bn(bn, y)
+    from . import autograd as ag
+    if drop.order == "before":
+        return _apply_bn(bn, ag.dropout(y, drop.rate, drop.state, drop.sites))
+    return ag.dropout(_apply_bn(bn, y), drop.rate, drop.state, drop.sites)
+
+
+def _forward_layers(ys, h, params, L, bounded, last_bits, drop=None):
     """The forward of a dense + ReLU stack on the row-scaled fp16 x 2 kernel where it is covered: layer 0 runs one max pass over its input,
     every layer's epilogue leaves the row / tensor maxima of its OUTPUT -- the next layer's row scales and, for the backward, the bound its
-    weight gradient scales that input by.  Appends the activations to ys; -> [max |input of layer l| as a [1] int32 device tensor or None]."""
+    weight gradient scales that input by.  Appends the activations to ys; -> [max |input of layer l| as a [1] int32 device tensor or None].
+    drop (a Drop with one site per layer): every layer's output is dropped in place (the appended activations are the
+    dropped ones).  The maxima the epilogue left describe the tensor BEFORE the dropout (too small by 1 / keep_prob: an fp16 overflow in the
+    next layer), so none is asked for or carried: the next layer runs its own max pass over what it really reads."""
     xbits, rb, carried_all = [], None, None
     for l in range(L):
-        left = [] if (l + 1 < L or last_bits) else None
+        left = [] if (l + 1 < L or last_bits) and drop is None else None
         xb = []
         h = ops.dense(h, _kernel_weight(h, params[2 * l]), params[2 * l + 1], relu=True, arith="auto_bounded" if bounded else None,
                       row_bits=rb, bits_out=left, xbits_out=xb)
         xbits.append(xb[0] if xb else carried_all)
         rb, carried_all = left[0] if left else (None, None)
+        if drop is not None:
+            ops.dropout(h, drop.rate, drop.state, drop.sites[l], out=h)        # (drops the `_dir_bits` hint of h as well)
         ys.append(h)
     return xbits
+
+
+def _inv_keep(drop):
+    """1 / keep_prob of a node's dropout, 1.0 without one: the factor its ReLU gates leave to be applied.  The saved activations are the dropped
+    ones d = (y / keep_prob) * m, and d > 0 already is m AND y > 0 (keep_prob > 0), so dL/dpre = dL/dd * (d > 0) / keep_prob: the scalar rides on
+    the small operand of the pass that is there anyway (the head weights of units1_relu_backward, the [N, K] weight of dense_gated)."""
+    return 1.0 if drop is None else 1.0 / (1.0 - float(drop.rate))
 
 
 class _MlpStackFn(torch.autograd.Function):
@@ -220,11 +270,13 @@ class _MlpStackFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, *params):
         bounded = bool(_FWD_BOUNDED[0])         # (set by mlp_stack around the apply: a flag, not a tensor argument)
+        drop = _FWD_DROPOUT[0]
         L = len(params) // 2
         ys, h = [], x
-        ctx.xbits = _forward_layers(ys, h, params, L, bounded, last_bits=False)
+        ctx.xbits = _forward_layers(ys, h, params, L, bounded, last_bits=False, drop=drop)
         h = ys[-1]
         ctx.L = L
+        ctx.inv_keep = _inv_keep(drop)
         ctx.save_for_backward(x, *params[0::2], *ys)
         return h
 
@@ -234,7 +286,11 @@ class _MlpStackFn(torch.autograd.Function):
         L = ctx.L
         saved = ctx.saved_tensors
         x, ws, ys = saved[0], saved[1:1 + L], saved[1 + L:]
-        g = (g * (ys[-1] > 0)).contiguous()
+        inv_keep = ctx.inv_keep
+        if inv_keep == 1.0:
+            g = (g * (ys[-1] > 0)).contiguous()
+        else:       # the gate as ONE pass (where(d > 0, g, 0)) and the factor 1 / keep_prob as the second: two passes over [B, H], as without dropout
+            g = torch.ops.aten.threshold_backward(g.contiguous(), ys[-1], 0.0).mul_(inv_keep)
         grads = [None] * (2 * L)
         gx = None
         carried = None
@@ -244,7 +300,7 @@ class _MlpStackFn(torch.autograd.Function):
             rb, ab = _gbits(g, xb is not None, xin.shape[1], l > 0 or ctx.needs_input_grad[0], ctx.needs_input_grad[1 + 2 * l], carried)
             grads[2 * l], grads[2 * l + 1] = _wb_grads(g, xin, ctx.needs_input_grad[1 + 2 * l], ctx.needs_input_grad[2 + 2 * l], g_bits=ab,
                                                        x_bits=xb if ab is not None else None)
-            wt = _kernel_weight(g, ws[l].t())
+            wt = _kernel_weight(g, ws[l].t() * inv_keep if (l > 0 and inv_keep != 1.0) else ws[l].t())
             if l > 0:
                 left = []                           # the row-scaled kernel leaves its output's row / tensor maxima: the next layer's scales
                 g = ops.dense_gated(g, wt, xin, row_bits=rb, bits_out=left)
@@ -264,11 +320,13 @@ class _MlpHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, head_w, head_b, *params):
         bounded = bool(_FWD_BOUNDED[0])
+        drop = _FWD_DROPOUT[0]
         L = len(params) // 2
         ys, h = [], x
-        ctx.xbits = _forward_layers(ys, h, params, L, bounded, last_bits=False)
+        ctx.xbits = _forward_layers(ys, h, params, L, bounded, last_bits=False, drop=drop)
         h = ys[-1]
         ctx.L = L
+        ctx.inv_keep = _inv_keep(drop)
         ctx.save_for_backward(x, head_w, *params[0::2], *ys)
         return ops.units1(h, head_w, head_b)        # (dir_units1_f32; the library ran it as a one-column GEMM: 26 us at 65 536 x 400, its GEMV 62)
 
@@ -279,7 +337,9 @@ class _MlpHeadFn(torch.autograd.Function):
         saved = ctx.saved_tensors
         x, head_w, ws, ys = saved[0], saved[1], saved[2:2 + L], saved[2 + L:]
         g_head_b = g.reshape(-1).sum(dim=0, keepdim=True) if ctx.needs_input_grad[2] else None
-        g, gw_head, gb_top, carried = ops.units1_relu_backward(g, head_w, ys[-1], want_bits=True)
+        inv_keep = ctx.inv_keep
+        # (with dropout: dpre_top = g * w / keep_prob where the dropped activation is positive; dw_head = sum g * d does not read the weights)
+        g, gw_head, gb_top, carried = ops.units1_relu_backward(g, head_w * inv_keep if inv_keep != 1.0 else head_w, ys[-1], want_bits=True)
         grads = [None] * (2 * L)
         gx = None
         for l in range(L - 1, -1, -1):
@@ -292,7 +352,7 @@ class _MlpHeadFn(torch.autograd.Function):
                 grads[2 * l + 1] = gb_top if ctx.needs_input_grad[4 + 2 * l] else None
             else:
                 grads[2 * l], grads[2 * l + 1] = _wb_grads(g, xin, ctx.needs_input_grad[3 + 2 * l], ctx.needs_input_grad[4 + 2 * l], g_bits=ab, x_bits=xb)
-            wt = _kernel_weight(g, ws[l].t())
+            wt = _kernel_weight(g, ws[l].t() * inv_keep if (l > 0 and inv_keep != 1.0) else ws[l].t())
             if l > 0:
                 left = []
                 g = ops.dense_gated(g, wt, xin, row_bits=rb, bits_out=left)
@@ -309,21 +369,25 @@ def mlp_head_supported(lins, head, x, activation):
 
 
 _FWD_BOUNDED = [False]      # the forward of the node being applied may take the fp16 x 2 layers (its input is an embedding concatenation)
+_FWD_DROPOUT = [None]       # the Drop (one site per layer) of the node being applied: every hidden layer's output is dropped
 
 
-def mlp_head(lins, head, x, embedding_input=False):
+def mlp_head(lins, head, x, embedding_input=False, drop=None):
     """head(relu(lin_L(... relu(lin_1(x))))) -> [B, 1] through _MlpHeadFn (check mlp_head_supported first).  embedding_input: the caller
     vouches that x is a concatenation of embedding rows (DeepFM's dnn input, ESMM's input layer over embedding columns): the forward layers
     and the weight gradients (g scaled by one power of two, x as it is) may then run the fp16 x 2 kernels; without it the first layer runs
-    the row-scaled general-input kernel and its weight gradient bf16 x 3."""
+    the row-scaled general-input kernel and its weight gradient bf16 x 3.
+    drop: a Drop with one site per layer -- dropout behind every hidden layer (deepFM.py:301-302, ESMM.py:143-144), TRAIN mode."""
     params = []
     for lin in lins:
         params += [lin.weight, lin.bias]
     _FWD_BOUNDED[0] = bool(embedding_input)
+    _FWD_DROPOUT[0] = drop
     try:
         return _MlpHeadFn.apply(x, head.weight, head.bias, *params)
     finally:
         _FWD_BOUNDED[0] = False
+        _FWD_DROPOUT[0] = None
 
 
 def mlp_stack_supported(lins, x, activation):
@@ -341,16 +405,18 @@ def mlp_stack_supported(lins, x, activation):
     return True
 
 
-def mlp_stack(lins, x, embedding_input=False):
-    """relu(lin_L(... relu(lin_1(x)))) through _MlpStackFn (check mlp_stack_supported first); embedding_input as in mlp_head."""
+def mlp_stack(lins, x, embedding_input=False, drop=None):
+    """relu(lin_L(... relu(lin_1(x)))) through _MlpStackFn (check mlp_stack_supported first); embedding_input, drop as in mlp_head."""
     params = []
     for lin in lins:
         params += [lin.weight, lin.bias]
     _FWD_BOUNDED[0] = bool(embedding_input)
+    _FWD_DROPOUT[0] = drop
     try:
         return _MlpStackFn.apply(x, *params)
     finally:
         _FWD_BOUNDED[0] = False
+        _FWD_DROPOUT[0] = None
 
 
 class _Units1Fn(torch.autograd.Function):
@@ -405,14 +471,16 @@ def _bn_affine(bn):
     return _BN_CACHE.get(id(bn), watched, build, bn.beta.data_ptr())
 
 
-def dense_act(lin, x, activation=None, bn=None, bounded_input=False):
+def dense_act(lin, x, activation=None, bn=None, bounded_input=False, drop=None):
     """activation(lin(x)) for an nn.Linear `lin`, on dir_dense_f32 when the layer is covered.  x may arrive row-padded with zero
     columns up to the next multiple of 4 (InputLayer(pad_to=4), inference): then only the weight gets its zero columns.
     bn: the batch-norm module that follows the activation (deepFM.py:303-308, DeepCrossNetwork.py:400-403) -- in inference it is
     folded into the kernel's epilogue (one pass over the layer's output instead of three); otherwise it is applied here.
     bounded_input: the caller vouches that x is bounded by construction (a batch-normalised activation, an embedding concatenation): in
-    training the layer's weight gradient may then run the fp16 x 2 kernel."""
-    y = _dense_act(lin, x, activation, bn, bounded_input)
+    training the layer's weight gradient may then run the fp16 x 2 kernel.
+    drop: a Drop with one site -- the dropout that follows the activation in TRAIN mode, before the batch norm or after it; the caller
+    passes it for CUDA tensors in TRAIN mode only."""
+    y = _dense_act(lin, x, activation, bn, bounded_input, drop)
     return y
 
 
@@ -420,14 +488,14 @@ def _apply_bn(bn, y):
     return bn(y) if bn is not None else y
 
 
-def _dense_act(lin, x, activation, bn, bounded=False):
+def _dense_act(lin, x, activation, bn, bounded=False, drop=None):
     relu = activation in _RELUS
     prepadded = x.dim() == 2 and x.shape[1] != lin.in_features and x.shape[1] == lin.in_features + (-lin.in_features) % 4
     if (activation is None or relu) and x.is_cuda and x.dim() == 2 and lin.out_features >= 16 and (
             x.shape[0] >= MIN_ROWS or ops.dense_small_covers(x.shape[0], lin.in_features + (-lin.in_features) % 4, lin.out_features)
             or ops.dense_mid_covers(x.shape[0], lin.in_features + (-lin.in_features) % 4, lin.out_features)):
         _route("hip", lin)
-        train = torch.is_grad_enabled() and (x.requires_grad or lin.weight.requires_grad)
+        train = torch.is_grad_enabled() and (x.requires_grad or lin.weight.requires_grad or drop is not None)
         fold = bn is not None and not (bn.training and torch.is_grad_enabled())
         ps, psh = _bn_affine(bn) if fold else (None, None)
         if prepadded and not train and x.dtype == torch.float32:
@@ -442,19 +510,19 @@ def _dense_act(lin, x, activation, bn, bounded=False):
             # to the next multiple of 4 -- one [B, in] copy (45 us at 65 536 x 429) against 200 us saved on the GEMM
             xp = F.pad(x, (0, pad))
             if train:
-                return _dense_bn_train(bn, xp, F.pad(lin.weight, (0, pad)), lin.bias, relu, bounded)     # pad's backward slices the gradients back
+                return _dense_bn_train(bn, xp, F.pad(lin.weight, (0, pad)), lin.bias, relu, bounded, drop)     # pad's backward slices the gradients back
             y = ops.dense(xp, _packed_cached(lin.weight, pad), lin.bias, relu=relu, post_scale=ps, post_shift=psh)
             return y if fold else _apply_bn(bn, y)
         if ops.dense_supported(x, lin.weight):
             if train:
-                return _dense_bn_train(bn, x, lin.weight, lin.bias, relu, bounded)
+                return _dense_bn_train(bn, x, lin.weight, lin.bias, relu, bounded, drop)
             y = ops.dense(x, _packed_cached(lin.weight), lin.bias, relu=relu, post_scale=ps, post_shift=psh)
             return y if fold else _apply_bn(bn, y)
     if prepadded:
         x = x[:, :lin.in_features]
     _route("library", lin)
     y = lin(x)
-    return _apply_bn(bn, activation(y) if activation is not None else y)
+    return _bn_and_dropout(bn, activation(y) if activation is not None else y, drop)
 
 
 def tower_infer(lins, x, activation, bns=None, head=None, adds=(), gather=None, embedding_input=False):

@@ -15,9 +15,9 @@ ESMM_W_D mirrors models/ESMM/ESMM_wide_deep.py (the wide & deep variant): every 
 import torch
 from torch import nn
 
-from .dense import dense_act, mlp_head, mlp_head_supported, mlp_stack, mlp_stack_supported, tower_infer, units1
+from .dense import Drop, dense_act, mlp_head, mlp_head_supported, mlp_stack, mlp_stack_supported, tower_infer, units1
 from .dcn import _glorot_normal_
-from .deepfm import _dropout_train, _glorot_uniform_
+from .deepfm import _DropoutRng, _drop_rate, _dropout_train, _glorot_uniform_, dropout_rng_of
 from .input_layer import InputLayer
 from ._input import checked_forward as _checked_forward
 from . import ops
@@ -29,6 +29,10 @@ class _BaseModel(nn.Module):
     def __init__(self, columns, hidden_units, activation, dropout=None):
         super().__init__()
         self.dropout = dropout
+        # the dropout sites of this tower are stream ids drop_stream_base + layer; a model of several towers (ESMM) hands every tower its base
+        # and, per training forward, the shared generator state in _drop_rng (None: the tower's own state, advanced here)
+        self.drop_stream_base = 0
+        self._drop_rng = None
         self.input_layer = InputLayer(columns)                                   # ESMM.py:135
         self.activation = activation
         self.hidden = nn.ModuleList()
@@ -62,13 +66,19 @@ class _BaseModel(nn.Module):
         fused = tower_infer(self.hidden, net, self.activation, head=self.logits, embedding_input=emb_in)      # inference: tower + logit layer in one launch
         if fused is not None:
             return fused
-        if not self.dropout and mlp_stack_supported(self.hidden, net, self.activation):
+        rate = _drop_rate(self, self.dropout, net)                               # ESMM.py:143-144 (TRAIN only): site = drop_stream_base + layer
+        rng = None
+        if rate is not None:
+            rng = self._drop_rng if self._drop_rng is not None else dropout_rng_of(self, net.device).advance()
+        sites = [self.drop_stream_base + i for i in range(len(self.hidden))]
+        if (rate is not None or not self.dropout) and mlp_stack_supported(self.hidden, net, self.activation):
+            drop = Drop(rate, rng, sites) if rate is not None else None
             if mlp_head_supported(self.hidden, self.logits, net, self.activation):
-                return mlp_head(self.hidden, self.logits, net, embedding_input=emb_in)   # training: tower + logit layer as one autograd node
-            return units1(self.logits, mlp_stack(self.hidden, net, embedding_input=emb_in))      # training: the whole tower as one autograd node
-        for lin in self.hidden:
+                return mlp_head(self.hidden, self.logits, net, embedding_input=emb_in, drop=drop)   # training: tower + logit layer as one autograd node
+            return units1(self.logits, mlp_stack(self.hidden, net, embedding_input=emb_in, drop=drop))      # training: the whole tower as one autograd node
+        for i, lin in enumerate(self.hidden):
             net = dense_act(lin, net, self.activation)                           # dir_dense_f32 when covered
-            net = _dropout_train(self, net, self.dropout)                        # ESMM.py:143-144 (TRAIN only)
+            net = _dropout_train(self, net, self.dropout, sites[i], rng)         # ESMM.py:143-144 (TRAIN only)
         return units1(self.logits, net)
 
 
@@ -148,7 +158,7 @@ def ctcvr_logits_of(ctr_logits, cvr_logits):
     return torch.log(p / (1 - p))
 
 
-class ESMM(nn.Module):
+class ESMM(_DropoutRng, nn.Module):
     def __init__(self, model_dir=None, columns=None, ctr_weight_column=None, ctcvr_weight_column=None,
                  dnn_hidden_units=None, dnn_dropout=None, config=None, dnn_activation_fn=torch.relu, optimizer=None):
         super().__init__()
@@ -158,13 +168,30 @@ class ESMM(nn.Module):
         hidden = list(dnn_hidden_units or [])
         self.ctr_model = _BaseModel(columns, hidden, dnn_activation_fn, dnn_dropout)          # ESMM.py:63-64
         self.cvr_model = _BaseModel(columns, hidden, dnn_activation_fn, dnn_dropout)          # ESMM.py:65-66
+        self.cvr_model.drop_stream_base = len(hidden)                                         # (the towers' dropout sites: distinct stream ids)
+
+    def _towers(self):
+        return [m for m in (getattr(self.ctr_model, "dnn", self.ctr_model), getattr(self.cvr_model, "dnn", self.cvr_model)) if m is not None]
+
+    def _run_towers(self, features, memo):
+        """Both sub-models on one draw of the model's dropout state (advanced once per training forward on the GPU)."""
+        towers = self._towers()
+        p = next(self.parameters(), None)
+        if self.hparams.get("dnn_dropout") and self.training and torch.is_grad_enabled() and p is not None and p.is_cuda:
+            rng = dropout_rng_of(self, p.device).advance()
+            for t in towers:
+                t._drop_rng = rng
+        try:
+            return self.ctr_model(features, memo), self.cvr_model(features, memo)
+        finally:
+            for t in towers:
+                t._drop_rng = None
 
     @_checked_forward
     def forward(self, features):
         """-> {'ctr_logits', 'ctcvr_logits'} (the `logits` dict of ESMM.py:77)."""
         memo = {}                                                                # both towers read the same columns: one id matrix
-        ctr_logits = self.ctr_model(features, memo)
-        cvr_logits = self.cvr_model(features, memo)
+        ctr_logits, cvr_logits = self._run_towers(features, memo)
         ctcvr_logits = ctcvr_logits_of(ctr_logits, cvr_logits)
         out = {"ctr_logits": ctr_logits, "ctcvr_logits": ctcvr_logits, "cvr_logits": cvr_logits}
         from ._input import raise_pending
@@ -219,6 +246,8 @@ class ESMM_W_D(ESMM):
         self.n_linear_columns = len(lin)
         self.ctr_model = _BaseModelWD(lin, dnn, hidden, dnn_activation_fn, dnn_dropout)           # ESMM_wide_deep.py:103-114
         self.cvr_model = _BaseModelWD(lin, dnn, hidden, dnn_activation_fn, dnn_dropout)           # :115-126
+        if self.cvr_model.dnn is not None:
+            self.cvr_model.dnn.drop_stream_base = len(hidden)
 
     def learning_rates(self):
         """(linear, dnn) learning rates of the reference's default optimisers (ESMM_wide_deep.py:30,33,72-73)."""

@@ -1692,6 +1692,111 @@ def bn_train_backward(g, y, mean, inv, gamma=None, relu_gate=False):
     return gy, vec[0], vec[1]
 
 
+class DropoutState:
+    """The generator state of the dropout kernels (include/dir_hip.h: dir_dropout_f32): two device words, (seed, draw).  The kernels make
+    their masks from it with Philox4x32-10 -- this library's stream, not TensorFlow's -- and never store one.  On the training path the
+    host never reads the words: advance() is a one-thread kernel, so a captured step replays with a fresh draw every time.
+    seed None: torch.initial_seed() (what torch.manual_seed(...) set).  get_state() / set_state() synchronise: checkpoints and tests."""
+
+    def __init__(self, seed=None, device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DropoutState lives on a CUDA (ROCm) device: the HIP path has no CPU fallback")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.words = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self.manual_seed(torch.initial_seed() if seed is None else seed)
+
+    def to(self, device):
+        """Move the words to another CUDA device, seed and draw kept (synchronises)."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("DropoutState lives on a CUDA (ROCm) device: the HIP path has no CPU fallback")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device != self.device:
+            self.words, self.device = self.words.to(device), device
+        return self
+
+    @staticmethod
+    def _signed(v):
+        v = int(v) & 0xFFFFFFFFFFFFFFFF
+        return v - (1 << 64) if v >= (1 << 63) else v
+
+    def manual_seed(self, seed):
+        """(seed, draw) = (seed, 0)."""
+        return self.set_state((seed, 0))
+
+    def set_state(self, state):
+        seed, draw = state
+        self.words.copy_(torch.tensor([self._signed(seed), int(draw) & 0xFFFFFFFF], dtype=torch.int64))
+        return self
+
+    def get_state(self):
+        seed, draw = self.words.tolist()
+        return (seed & 0xFFFFFFFFFFFFFFFF, draw)
+
+    def advance(self):
+        """draw += 1 on the device (dir_dropout_advance): the next forward's masks."""
+        _lib.check(_lib.load().dir_dropout_advance(_ptr(self.words), _stream()))
+        return self
+
+
+def _dropout_rate(rate):
+    rate = float(rate)
+    if not (0.0 <= rate < 1.0):
+        raise ValueError("dropout: rate must lie in [0, 1), got %r" % rate)
+    return rate
+
+
+def dropout(x, rate, state, stream_id=0, out=None, used=None, want_used=False, first=0):
+    """(x / (1 - rate)) * mask (include/dir_hip.h: dir_dropout_f32; deepFM.py:301-302): x a dense (contiguous) float32 CUDA tensor, state a
+    DropoutState, stream_id the dropout site.  out: None (a new tensor), x itself (in place) or a tensor of x's shape.  used (a [2] int64
+    device tensor a forward call left: its seed and draw): what to take instead of the state's words -- the backward's call, which then does not
+    read the state at all.  want_used: -> (out, used)."""
+    _dev(x, torch.float32, "x")
+    rate = _dropout_rate(rate)
+    if not x.is_contiguous():
+        raise ValueError("dropout: x must be contiguous (the element index is the flat index)")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("dropout: out must be a contiguous float32 CUDA tensor of x's shape")
+    left = torch.empty(2, dtype=torch.int64, device=x.device) if want_used else None
+    _lib.check(_lib.load().dir_dropout_f32(_ptr(x), _ptr(out), x.numel(), int(first), rate, _ptr(state.words), int(stream_id), _ptr(used), _ptr(left),
+                                           _stream()))
+    if hasattr(out, "_dir_bits"):
+        del out._dir_bits                       # maxima a dense kernel left on this tensor describe the values before the dropout
+    return (out, left) if want_used else out
+
+
+def dropout_mask(n, rate, state, stream_id=0, used=None, first=0):
+    """The mask dropout() applies to a tensor of n elements (uint8 [n]: 1 kept) for the state's current (seed, draw), or the pair in `used`
+    (include/dir_hip.h: dir_dropout_mask_u8).  Tests and diagnostics."""
+    rate = _dropout_rate(rate)
+    out = torch.empty(int(n), dtype=torch.uint8, device=state.device)
+    _lib.check(_lib.load().dir_dropout_mask_u8(int(n), int(first), rate, _ptr(state.words), int(stream_id), _ptr(used), _ptr(out), _stream()))
+    return out
+
+
+def bn_affine_dropout(y, scale, shift, rate, state, stream_id=0, used=None, want_used=False):
+    """dropout(y * scale + shift) in one pass (include/dir_hip.h: dir_bn_affine_dropout_f32; DeepCrossNetwork.py:400-408): y [B, N] as
+    bn_train_stats takes it, scale / shift [N] -> a new contiguous [B, N] tensor (and the draw it used)."""
+    _dev(y, torch.float32, "y")
+    rate = _dropout_rate(rate)
+    if not bn_train_supported(y):
+        raise ValueError("bn_affine_dropout: y must be float32 [B > 0, N] with N and its row stride multiples of 4, 16-byte aligned")
+    B, N = y.shape
+    scale, shift = scale.contiguous(), shift.contiguous()
+    if scale.data_ptr() % 16 or shift.data_ptr() % 16:
+        scale, shift = scale.clone(), shift.clone()
+    out = torch.empty((B, N), dtype=torch.float32, device=y.device)
+    left = torch.empty(2, dtype=torch.int64, device=y.device) if want_used else None
+    _lib.check(_lib.load().dir_bn_affine_dropout_f32(_ptr(y), y.stride(0), _ptr(scale), _ptr(shift), B, N, _ptr(out), out.stride(0), rate,
+                                                     _ptr(state.words), int(stream_id), _ptr(used), _ptr(left), _stream()))
+    return (out, left) if want_used else out
+
+
 def din_backward_supported(K, T, H1, H2):
     """Shapes the fused DIN backward covers (include/dir_hip.h: dir_din_attention_pool_backward_f32)."""
     return K == 64 and T <= 64 and H1 <= 80 and H2 <= 48 and H1 % 4 == 0 and H2 % 4 == 0

@@ -1465,6 +1465,35 @@ int dir_din_pool_rows_f32(const float* scores, const float* Hc, int K, const int
 int dir_din_pool_rows_backward_f32(const float* g, const float* Hc, int K, const float* w, const int64_t* row_off, int64_t B, int64_t N, int normalize,
                                    float* ds, float* dH, dir_stream_t stream);
 
+/* ---- dropout of the DNN towers in TRAIN mode (csrc/dropout.hip) -----------------------------------------------------------------------------
+ * Reference: core_layers.dropout(net, rate, training=True) (models/DeepFM/deepFM.py:301-302, models/DeepCrossNetwork/DeepCrossNetwork.py:405-408,
+ * models/ESMM/ESMM.py:143-144): out = (x / keep_prob) * m, m in {0, 1}, keep_prob = 1 - rate in fp32, the division correctly rounded (a dropped
+ * NaN / inf stays NaN).  The masks come from a counter-based generator and are never stored: Philox4x32-10 as published (multipliers
+ * 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, 10 rounds), one 128-bit block per four consecutive elements.  Element
+ * e = first + (flat index into the contiguous tensor): q = e >> 2, lane = e & 3, counter = (q & 0xffffffff, q >> 32, stream_id, draw),
+ * key = (seed & 0xffffffff, seed >> 32), u = float(r[lane] >> 8) * 2^-24, the element is kept iff u >= rate (fp32).  This is the library's own
+ * stream, not TensorFlow's.  stream_id tells the dropout sites of one forward apart, draw counts steps.
+ * state: device int64[2] = (seed, draw); the host never reads it on the training path.  rate in [0, 1) (else DIR_E_BADARG); rate == 0 copies.
+ *
+ * dir_philox4x32_10: HOST function, one block: counter4, key2 -> out4 (the known-answer test).
+ * dir_dropout_f32: out[i] = dropout(x[i]), i < n (any n; a tail of 1..3 elements and unaligned pointers take a scalar path); out may alias x.
+ *   used_in == NULL (forward): (seed, draw) are read from state, and one thread stores both to used_out (device int64[2], may be NULL).
+ *   used_in != NULL (backward): (seed, draw) are read from there and state is not looked at -- the gradient gets the forward's mask whatever
+ *   has happened to state since (dir_dropout_advance, a new seed).
+ *   The 16-byte path needs x and out 16-byte aligned and first % 4 == 0; anything else takes one element per thread (the same values).
+ * dir_dropout_mask_u8: the mask bytes (1 kept, 0 dropped) of the same elements; used (device int64[2] or NULL) as used_in.  Tests and diagnostics.
+ * dir_dropout_advance: one thread adds 1 to draw (mod 2^32).
+ * dir_bn_affine_dropout_f32: out[r, c] = dropout(y[r, c] * scale[c] + shift[c]) in one pass (the batch norm before the dropout:
+ *   DeepCrossNetwork.py:400-408); e = r N + c.  N and the row strides multiples of 4, 16-byte aligned pointers. */
+void dir_philox4x32_10(const uint32_t* counter4, const uint32_t* key2, uint32_t* out4);
+int dir_dropout_f32(const float* x, float* out, int64_t n, int64_t first, float rate, const int64_t* state, uint32_t stream_id,
+                    const int64_t* used_in, int64_t* used_out, dir_stream_t stream);
+int dir_dropout_mask_u8(int64_t n, int64_t first, float rate, const int64_t* state, uint32_t stream_id, const int64_t* used, uint8_t* out,
+                        dir_stream_t stream);
+int dir_dropout_advance(int64_t* state, dir_stream_t stream);
+int dir_bn_affine_dropout_f32(const float* y, int64_t y_ld, const float* scale, const float* shift, int64_t B, int N, float* out, int64_t out_ld,
+                              float rate, const int64_t* state, uint32_t stream_id, const int64_t* used_in, int64_t* used_out, dir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
