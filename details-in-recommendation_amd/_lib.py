@@ -113,6 +113,10 @@ SIGNATURES = {
     "dir_sparse_adam_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i64]),
     "dir_sparse_adam_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp]),
+    # ... over tables shared between slots: + slot_table (device int32 [F]), n_tables after the stream
+    "dir_sparse_adam_shared_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_float, ctypes.c_float,
+                                           ctypes.c_float, ctypes.c_float, ctypes.c_float, c_i64, c_vp, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp,
+                                           c_i32]),
     "dir_sparse_adam_payload_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i64]),
     "dir_sparse_adam_payload_norm_f32": (c_i32, [c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),   # norm2: ADAM_NORM_WORDS u64
     "dir_sparse_adam_payload_apply_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,

@@ -571,6 +571,8 @@ struct AdamUpd {
     int64_t ld;
     const double* norm2_sum = nullptr;         // [F] ||gradient of table f||^2 over ALL owners of a row-sharded table (the payload form: the
                                                // ranks' norm words added up exactly by the caller and rounded once)
+    const int* slot_table = nullptr;           // tables shared between slots (dir_sparse_adam_shared_f32): slot -> table among n_tab; the norm
+    int n_tab = 0;                             // words, row_base and the marks run over the TABLES, tables / ms / vs stay per slot
     __device__ __forceinline__ void one(float g, float den, float& m, float& v, float& w) const {
         if (clip > 0.f) g = (g * clip) / den;                     // tf.clip_by_norm: t * clip_norm / max(l2norm, clip_norm)
         m = m * b1 + g * (1.f - b1);
@@ -581,8 +583,9 @@ struct AdamUpd {
     __device__ __forceinline__ void apply(int f, int64_t id, int col, typename BV<VEC>::T g) const {
         using V = BV<VEC>;
         float den = clip;
-        if (clip > 0.f && norm2_sum) den = fmaxf(sqrtf((float)norm2_sum[f]), clip);
-        else if (clip > 0.f && norm2) den = fmaxf(sqrtf((float)adam_norm_value(norm2, f)), clip);
+        const int t = table_of(slot_table, f, n_tab);             // (f without sharing)
+        if (clip > 0.f && norm2_sum) den = fmaxf(sqrtf((float)norm2_sum[t]), clip);
+        else if (clip > 0.f && norm2) den = fmaxf(sqrtf((float)adam_norm_value(norm2, t)), clip);
         const int64_t off = id * ld + col;
         float* mp = ms[f] + off;
         float* vp = vs[f] + off;
@@ -596,7 +599,7 @@ struct AdamUpd {
         V::st(mp, m);
         V::st(vp, v);
         V::st(wp, w);
-        if (col == 0) mark[row_base[f] + id] = 1;
+        if (col == 0) mark[row_base[t] + id] = 1;
     }
 };
 
@@ -753,13 +756,21 @@ __device__ __forceinline__ void bag_apply(const AdamUpdW& upd, const BagSrc& bag
 template <int LPS>
 __global__ __launch_bounds__(256) void adam_decay_k(float* const* __restrict__ tables, float* const* __restrict__ ms, float* const* __restrict__ vs,
                                                     const int64_t* __restrict__ row_base, int64_t total_rows, int F,
-                                                    unsigned char* __restrict__ mark, float lr_t, float b1, float b2, float eps) {
+                                                    unsigned char* __restrict__ mark, float lr_t, float b1, float b2, float eps,
+                                                    const int* __restrict__ slot_table = nullptr, int n_slots = 0) {
+    // blockIdx.y = the table (F of them, row_base [F]).  Over tables shared between slots the pointer arrays are per SLOT: a table is
+    // swept ONCE, through the pointers of its first slot (a uniform scan of at most 64 map entries); one that no slot reads is left alone
     const int f = blockIdx.y;
+    int s = f;
+    if (slot_table) {
+        for (s = 0; s < n_slots && slot_table[s] != f; ++s) {}
+        if (s == n_slots) return;
+    }
     const int64_t r0 = row_base[f];
     const int64_t V = (f + 1 < F ? row_base[f + 1] : total_rows) - r0;
-    float* __restrict__ w = tables[f];
-    float* __restrict__ m = ms[f];
-    float* __restrict__ v = vs[f];
+    float* __restrict__ w = tables[s];
+    float* __restrict__ m = ms[s];
+    float* __restrict__ v = vs[s];
     const int c = threadIdx.x & (LPS - 1);
     // A workgroup walks ONE contiguous chunk of the table's rows, non-temporal loads and stores: six streams over 1.66 GB each.  (The
     // grid-stride form of round 3 -- consecutive accesses of a lane 2048 workgroups apart -- ran at 4.3-5.0 TB/s; the same change took the
@@ -964,8 +975,9 @@ __global__ __launch_bounds__(256) void adagrad_tile_k(U upd, int F, int K,
             } else if constexpr (IsNorm<U>::value) {
                 unsigned long long hi, lo;
                 adam_norm_split(V::dot(sum, sum, 0.f), hi, lo);
-                if (lo) atomicAdd(&nsq[f & 63], lo);
-                if (hi) atomicAdd(&nsq[64 + (f & 63)], hi);
+                const int w = table_of(slot_table, f, n_tab) & 63;      // the norm words go by TABLE: the run holds all of its slots' entries
+                if (lo) atomicAdd(&nsq[w], lo);
+                if (hi) atomicAdd(&nsq[64 + w], hi);
             } else {
                 upd.template apply<VEC>(f, id, c * VEC, sum);
             }
@@ -1034,8 +1046,9 @@ __global__ __launch_bounds__(256) void adagrad_fix_k(U upd, int F, int K,
     } else if constexpr (IsNorm<U>::value) {
         unsigned long long hi, lo;
         adam_norm_split(V::dot(sum, sum, 0.f), hi, lo);
-        if (lo) atomicAdd(upd.norm2 + (f & 63), lo);
-        if (hi) atomicAdd(upd.norm2 + 64 + (f & 63), hi);
+        const int w = table_of(slot_table, f, n_tab) & 63;
+        if (lo) atomicAdd(upd.norm2 + w, lo);
+        if (hi) atomicAdd(upd.norm2 + 64 + w, hi);
     } else {
         upd.template apply<VEC>(f, id, c * VEC, sum);
     }
@@ -1595,11 +1608,13 @@ extern "C" int dir_sparse_ftrl_rows_units_sorted_payload_f32(float* const* rows,
 
 // ---- tf.train.AdamOptimizer on the embedding tables ------------------------------------------------------------------------------
 // the streaming pass over every row of every table: unmarked rows decay and step, marked ones (stepped by AdamUpd) are unmarked
+// (F: the tables, grid y.  slot_table != nullptr: the pointer arrays are per slot, n_slots of them, and F counts the distinct tables)
 static int adam_decay_all(const char* name, float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* row_base,
-                          int64_t total_rows, unsigned char* mark, float lr_t, float beta1, float beta2, float eps, hipStream_t st) {
+                          int64_t total_rows, unsigned char* mark, float lr_t, float beta1, float beta2, float eps, hipStream_t st,
+                          const int* slot_table = nullptr, int n_slots = 0) {
     dim3 grid((unsigned)(kCUs * 8), (unsigned)F);
     switch (K / 4) {
-#define DIR_DECAY(L) case L: hipLaunchKernelGGL((adam_decay_k<L>), grid, dim3(256), 0, st, tables, ms, vs, row_base, total_rows, F, mark, lr_t, beta1, beta2, eps); break
+#define DIR_DECAY(L) case L: hipLaunchKernelGGL((adam_decay_k<L>), grid, dim3(256), 0, st, tables, ms, vs, row_base, total_rows, F, mark, lr_t, beta1, beta2, eps, slot_table, n_slots); break
         DIR_DECAY(1); DIR_DECAY(2); DIR_DECAY(4); DIR_DECAY(8); DIR_DECAY(16); DIR_DECAY(32); DIR_DECAY(64);
 #undef DIR_DECAY
         default: return fail(DIR_E_UNSUPPORTED, "%s: K=%d", name, K);
@@ -1616,11 +1631,12 @@ extern "C" int64_t dir_sparse_adam_workspace_bytes(int64_t B, int F, int K, int6
     return sorted + (int64_t)ADAM_NORM_BYTES + ((total_rows + 255) & ~(int64_t)255);      // + the norm words + the row marks (one byte per row)
 }
 
-extern "C" int dir_sparse_adam_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* ids,
-                                   int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, float lr_t, float beta1,
-                                   float beta2, float eps, float clip_norm, int64_t B, const int64_t* row_base, int64_t total_rows,
-                                   void* workspace, int64_t workspace_bytes, int first_call, dir_stream_t stream) {
-    const char* name = "dir_sparse_adam_f32";
+// dir_sparse_adam_f32 and dir_sparse_adam_shared_f32.  slot_table != nullptr: tables / ms / vs are per slot, row_base [n_tables] and
+// total_rows (and with them the keys, the norm words, the marks and the decay sweep) run over the distinct tables; nullptr: n_tables == F.
+static int sparse_adam_onehot(const char* name, float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* ids,
+                              int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, float lr_t, float beta1, float beta2,
+                              float eps, float clip_norm, int64_t B, const int64_t* row_base, int64_t total_rows, void* workspace,
+                              int64_t workspace_bytes, int first_call, dir_stream_t stream, const int32_t* slot_table, int n_tables) {
     DIR_CHECK_ARG(tables && ms && vs && row_base && workspace && F > 0 && K > 0 && B >= 0, "%s: bad argument", name);
     if (F > 64 || (K & 3) || 64 % (K / 4) || K / 4 > 64) return fail(DIR_E_UNSUPPORTED, "%s: F <= 64, K a multiple of 4 with K / 4 dividing 64 (F=%d K=%d)", name, F, K);
     DIR_CHECK_ARG(B == 0 || (ids && grad && grad_ld >= (int64_t)F * K), "%s: ids / grad", name);
@@ -1641,16 +1657,41 @@ extern "C" int dir_sparse_adam_f32(float* const* tables, float* const* ms, float
         const bool clip = clip_norm > 0.f;
         if (clip) {
             if (zero_async(norm2, ADAM_NORM_BYTES, st) != hipSuccess) return fail(DIR_E_HIP, "%s: memset failed", name);
-            const int rc = sparse_sorted_update(name, AdamNormUpd{norm2}, F, K, SortedSrc::of_ids(ids, stride_b, stride_f), grad, grad_ld,
-                                                (int64_t)K, B, row_base, total_rows, sorted_ws, sorted_bytes, stream);
+            const int rc = sparse_sorted_update(name, AdamNormUpd{norm2}, F, K, SortedSrc::of_ids(ids, stride_b, stride_f).shared(slot_table, n_tables),
+                                                grad, grad_ld, (int64_t)K, B, row_base, total_rows, sorted_ws, sorted_bytes, stream);
             if (rc != DIR_OK) return rc;
         }
-        const int rc = sparse_sorted_update(name, AdamUpd{tables, ms, vs, clip ? norm2 : nullptr, mark, row_base, lr_t, beta1, beta2, eps, clip_norm, (int64_t)K},
-                                            F, K, SortedSrc::of_ids(ids, stride_b, stride_f).reuse(clip ? sorted_ws : nullptr), grad, grad_ld,
-                                            (int64_t)K, B, row_base, total_rows, sorted_ws, sorted_bytes, stream);
+        const int rc = sparse_sorted_update(name, AdamUpd{tables, ms, vs, clip ? norm2 : nullptr, mark, row_base, lr_t, beta1, beta2, eps, clip_norm, (int64_t)K,
+                                                          nullptr, slot_table, n_tables},
+                                            F, K, SortedSrc::of_ids(ids, stride_b, stride_f).reuse(clip ? sorted_ws : nullptr).shared(slot_table, n_tables),
+                                            grad, grad_ld, (int64_t)K, B, row_base, total_rows, sorted_ws, sorted_bytes, stream);
         if (rc != DIR_OK) return rc;
     }
+    if (slot_table) return adam_decay_all(name, tables, ms, vs, n_tables, K, row_base, total_rows, mark, lr_t, beta1, beta2, eps, st, slot_table, F);
     return adam_decay_all(name, tables, ms, vs, F, K, row_base, total_rows, mark, lr_t, beta1, beta2, eps, st);
+}
+
+extern "C" int dir_sparse_adam_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* ids,
+                                   int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, float lr_t, float beta1,
+                                   float beta2, float eps, float clip_norm, int64_t B, const int64_t* row_base, int64_t total_rows,
+                                   void* workspace, int64_t workspace_bytes, int first_call, dir_stream_t stream) {
+    return sparse_adam_onehot("dir_sparse_adam_f32", tables, ms, vs, F, K, ids, stride_b, stride_f, grad, grad_ld, lr_t, beta1, beta2, eps,
+                              clip_norm, B, row_base, total_rows, workspace, workspace_bytes, first_call, stream, nullptr, F);
+}
+
+// ... over tables SHARED between slots (shared_embedding_columns), dir_sparse_adagrad_sorted_shared_f32's contract: a row's entries from all
+// of its slots are ONE run -- one ||S_r||^2 into its TABLE's norm words, one step of m / v / var, one mark -- and the sweep visits every
+// distinct table once.  The map is checked before anything else is: a NULL map with n_tables < F, or n_tables outside [1, F].
+extern "C" int dir_sparse_adam_shared_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* ids,
+                                          int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, float lr_t, float beta1,
+                                          float beta2, float eps, float clip_norm, int64_t B, const int64_t* row_base, int64_t total_rows,
+                                          void* workspace, int64_t workspace_bytes, int first_call, dir_stream_t stream,
+                                          const int32_t* slot_table, int n_tables) {
+    const char* name = "dir_sparse_adam_shared_f32";
+    DIR_CHECK_ARG(F > 0, "%s: bad argument", name);
+    if (int rc = shared_map_check(name, F, slot_table, n_tables)) return rc;
+    return sparse_adam_onehot(name, tables, ms, vs, F, K, ids, stride_b, stride_f, grad, grad_ld, lr_t, beta1, beta2, eps, clip_norm, B,
+                              row_base, total_rows, workspace, workspace_bytes, first_call, stream, slot_table, n_tables);
 }
 
 // ---- ... on row-sharded tables: the owner's step over the payload it received, in two halves --------------------------------------

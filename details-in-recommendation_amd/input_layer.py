@@ -107,21 +107,29 @@ class InputLayer(nn.Module):
         return [ops.SparseAdagrad(ts, lr, initial_accumulator_value=initial_accumulator_value).attach() for ts, idxs, _, _ in self._tablesets()
                 if self._owns_its_tables(idxs)]
 
-    def fused_sparse_adam(self, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0):
+    def fused_sparse_adam(self, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0, shared=False):
         """Attach the HIP tf.train.AdamOptimizer update (include/dir_hip.h: dir_sparse_adam_f32; the reference DCN's train_op on
         `embedding_weights`, DeepCrossNetwork.py:264-290) to every group of embedding columns it covers (no max_norm, K / 4 a power of
         two): backward() then steps ALL rows of those tables in place for one-hot inputs and they get no .grad.  -> (optimiser objects,
-        the parameters they own); set .lr_t on each before every backward (train_spec.TrainStep does)."""
+        the parameters they own); set .lr_t on each before every backward (train_spec.TrainStep does).  shared=True (what
+        TrainStep passes): a group that shares tables between its columns (shared_embedding_columns) is covered like any other
+        (dir_sparse_adam_shared_f32: a shared table is one variable); without it such a group is skipped, as before.  A group some
+        of whose tables are shared with a column OUTSIDE it gets none and keeps its sparse .grad, as under fused_sparse_adagrad.  Each optimiser lists its parameters ONCE per table: .owned[i] is the parameter of the table whose first
+        slot in that optimiser's TableSet is .owned_slots[i] (what step_table_grad takes)."""
         opts, owned = [], []
         for ts, idxs, _, mn in self._tablesets():
             if mn or not ts.device.type == "cuda" or not ops.SparseAdam.covers(ts):
                 continue
-            if ts.shared or not self._owns_its_tables(idxs):      # (the HIP Adam's norm words and decay sweep are per slot: shared tables keep .grad)
+            if ts.shared and not shared:
+                continue
+            if not self._owns_its_tables(idxs):                   # a table with a slot elsewhere: one step per group, with partial gradients
                 continue
             cw = self._col_weights()
-            opts.append(ops.SparseAdam(ts, beta1, beta2, eps, clip_norm).attach())
-            owned += [cw[i] for i in idxs]
-            opts[-1].owned = [cw[i] for i in idxs]          # parameter of table f of that optimiser's TableSet
+            opts.append(ops.SparseAdam(ts, beta1, beta2, eps, clip_norm, shared=shared).attach())
+            first = [ts.slots_of(t)[0] for t in range(ts.T)]      # (without sharing: every slot)
+            opts[-1].owned_slots = first
+            opts[-1].owned = [cw[idxs[f]] for f in first]
+            owned += opts[-1].owned
         return opts, owned
 
     def _indicator(self, c, features, device, B):

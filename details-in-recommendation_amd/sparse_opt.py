@@ -77,7 +77,8 @@ class _SortedOpt:
         self._share = None
 
     def _refuse_shared(self, entry):
-        """Only SparseAdagrad's one-hot steps know the slot -> table map: everything else refuses a set that shares tables."""
+        """Only the one-hot steps of SparseAdagrad and SparseAdam know the slot -> table map: everything else refuses a set that shares
+        tables."""
         if self.ts.shared:
             raise ValueError("%s does not cover tables shared between slots (slots %s read one table)"
                              % (entry, self.ts.slots_of(next(t for t in range(self.ts.T) if len(self.ts.slots_of(t)) > 1))))
@@ -312,19 +313,27 @@ class SparseAdam(_SortedOpt):
     On the shards of row-sharded tables the same step runs in two halves, norm_payload / step_payload, around the ranks' sum of the norm
     shares (shard.ShardedTables.enable_training_adam); norm_bags / step_bags are the same halves over the bag records of a multi-hot
     lookup (lookup_bags_train), on the same marks, norm words and sort area: one-hot and bag steps may alternate.  sort_reuses counts
-    the apply halves that ran on their norm half's sort; forget_sort() makes the next one sort for itself."""
+    the apply halves that ran on their norm half's sort; forget_sort() makes the next one sort for itself.
+    Over a set that shares tables between slots (shared_embedding_columns) step() and step_table_grad() treat a shared table as the ONE
+    variable it is (dir_sparse_adam_shared_f32): one m / v per table (.ms / .vs stay indexed by slot: the slots of a table hold the same
+    tensor), one clip norm over the sum of all its slots' gradients, one step per row, one sweep per table.  Such a set is taken with
+    shared=True only -- a TableSet shares by storage, whoever built it, and the step of a shared variable is not the per-slot step: the
+    caller says that it means one --; without it the constructor refuses the set, as before.  The owner-side halves always refuse it."""
 
-    def __init__(self, tables, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0):
+    def __init__(self, tables, beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0, shared=False):
         super().__init__(tables)
         ts = self.ts
-        self._refuse_shared("SparseAdam")       # (its norm words and decay sweep are per slot)
+        if not shared:
+            self._refuse_shared("SparseAdam without shared=True")
         if ts.ld != ts.K:
             raise ValueError("SparseAdam: plain [vocab, K] tables")
         self.beta1, self.beta2, self.eps, self.clip_norm = float(beta1), float(beta2), float(eps), float(clip_norm)
         self.lr_t = 0.0
-        self.ms = [torch.zeros_like(t) for t in ts.tables]
-        self.vs = [torch.zeros_like(t) for t in ts.tables]
-        self._slots = self.ms + self.vs
+        # one m / v per TABLE; .ms / .vs stay indexed by slot (the slots of a shared table hold the same tensor)
+        per_m, per_v = [torch.zeros_like(t) for t in ts.distinct], [torch.zeros_like(t) for t in ts.distinct]
+        self.ms = [per_m[t] for t in ts.slot_table]
+        self.vs = [per_v[t] for t in ts.slot_table]
+        self._slots = per_m + per_v
         self.m_ptrs, self.v_ptrs = self._ptr_array(self.ms), self._ptr_array(self.vs)
         self._ws_B = -1                         # step()'s buffer (_ws) holds its marks: reallocated only when B grows
         self._pws, self._norm2, self._marks, self._sorted = None, None, None, None      # the halves' sort area, norm words, row marks and sort token
@@ -357,9 +366,12 @@ class SparseAdam(_SortedOpt):
             self._ws_B = B
             first = 1
         ws, behind = _aligned(self._ws)
-        _lib.check(lib.dir_sparse_adam_f32(_ptr(ts.ptrs), _ptr(self.m_ptrs), _ptr(self.v_ptrs), ts.F, ts.K, _ptr(ids), sb, sf, _ptr(grad),
-                                           grad.stride(0), self.lr_t, self.beta1, self.beta2, self.eps, self.clip_norm, B, _ptr(self.row_base),
-                                           self.total_rows, ws, behind, first, _stream()))
+        args = (_ptr(ts.ptrs), _ptr(self.m_ptrs), _ptr(self.v_ptrs), ts.F, ts.K, _ptr(ids), sb, sf, _ptr(grad), grad.stride(0), self.lr_t,
+                self.beta1, self.beta2, self.eps, self.clip_norm, B, _ptr(self.row_base), self.total_rows, ws, behind, first, _stream())
+        if ts.shared:                           # keys, norm words, marks and the sweep over the distinct tables
+            _lib.check(lib.dir_sparse_adam_shared_f32(*args, _ptr(ts.slot_table_dev), ts.T))
+        else:
+            _lib.check(lib.dir_sparse_adam_f32(*args))
         self._written()
         self.steps += 1
 
@@ -424,6 +436,7 @@ class SparseAdam(_SortedOpt):
         < 2^32), row 1 the high word (the integer part): share = high + low * 2^-32, exact for ||g|| < 2^31.  The payload stays sorted in
         the workspace for step_payload."""
         ts = self.ts
+        self._refuse_shared("SparseAdam.norm_payload")
         lib, n, ws, behind = self._payload_area("SparseAdam.norm_payload", payload, grad)
         return self._norm(payload, None, lambda norm2, stream: lib.dir_sparse_adam_payload_norm_f32(
             ts.F, ts.K, _ptr(payload), n, _ptr(grad), _ptr(self.row_base), self.total_rows, norm2, ws, behind, stream))
@@ -434,6 +447,7 @@ class SparseAdam(_SortedOpt):
         high + low / 2^32; None exactly when clip_norm == 0), the others by the decay pass; n == 0 runs that pass alone.  The sort of a
         norm_payload call on the same payload just before is reused."""
         ts = self.ts
+        self._refuse_shared("SparseAdam.step_payload")
         lib, n, ws, behind = self._payload_area("SparseAdam.step_payload", payload, grad)
         self._apply("step_payload", payload, None, n > 0, norm2_global, lambda marks, sorted_, first, stream: lib.dir_sparse_adam_payload_apply_f32(
             _ptr(ts.ptrs), _ptr(self.m_ptrs), _ptr(self.v_ptrs), ts.F, ts.K, _ptr(payload), n, _ptr(grad), self.lr_t, self.beta1, self.beta2,
@@ -446,6 +460,7 @@ class SparseAdam(_SortedOpt):
         through the slot's max_norm clip derivative at the row's current value.  -> norm2 [2, F] device int64, as norm_payload.  The
         records stay sorted in the workspace for step_bags."""
         ts = self.ts
+        self._refuse_shared("SparseAdam.norm_bags")
         lib, ws, behind = self._bags_area("norm_bags", recv, P, cap_e, cap_b, grad_rows, slot_mn)
         return self._norm(recv, (P, cap_e, cap_b), lambda norm2, stream: lib.dir_sparse_adam_bags_norm_f32(
             _ptr(ts.ptrs), ts.F, ts.K, _ptr(recv), P, cap_e, cap_b, _ptr(grad_rows), _ptr(slot_mn), float(mn), _ptr(self.row_base),
@@ -457,6 +472,7 @@ class SparseAdam(_SortedOpt):
         float64 (None exactly when clip_norm == 0), the others by the decay pass; slabs without a live record run that pass alone.  The
         sort of a norm_bags call on the same slabs just before is reused."""
         ts = self.ts
+        self._refuse_shared("SparseAdam.step_bags")
         lib, ws, behind = self._bags_area("step_bags", recv, P, cap_e, cap_b, grad_rows, slot_mn)
         self._apply("step_bags", recv, (P, cap_e, cap_b), True, norm2_global, lambda marks, sorted_, first, stream: lib.dir_sparse_adam_bags_apply_f32(
             _ptr(ts.ptrs), _ptr(self.m_ptrs), _ptr(self.v_ptrs), ts.F, ts.K, _ptr(recv), P, cap_e, cap_b, _ptr(grad_rows), _ptr(slot_mn),
@@ -466,7 +482,9 @@ class SparseAdam(_SortedOpt):
     def step_table_grad(self, f, grad):
         """Table f's step from a gradient that arrived as its .grad instead of through the sink -- multi-hot / weighted columns, whose
         backward (autograd.EmbeddingBag) returns sparse row gradients: the same tf.train.AdamOptimizer step of ALL rows (clip_by_norm on
-        the table's gradient first) on this optimiser's m / v, with torch ops (not a hot path: the one-hot lookups take the HIP update)."""
+        the table's gradient first) on this optimiser's m / v, with torch ops (not a hot path: the one-hot lookups take the HIP update).
+        f is a SLOT.  A table shared between slots is one variable: autograd has summed every sharing column's contribution into the one
+        parameter's .grad, and the table takes ONE step -- call this once per table (any one of its slots), not once per slot."""
         t, m, v = self.ts.tables[f], self.ms[f], self.vs[f]
         g = (grad.coalesce().to_dense() if grad.is_sparse else grad).to(torch.float32)
         if self.clip_norm > 0:
@@ -474,7 +492,26 @@ class SparseAdam(_SortedOpt):
         m.mul_(self.beta1).add_(g, alpha=1.0 - self.beta1)
         v.mul_(self.beta2).addcmul_(g, g, value=1.0 - self.beta2)
         t.addcdiv_(m, v.sqrt().add_(self.eps), value=-self.lr_t)
-        mark_written(*self.ts.owners[f:f + 1])
+        owners = self.ts.owners                 # per slot, or each table's parameter once (InputLayer over shared columns)
+        i = f if len(owners) == self.ts.F else self.ts.slot_table[f]
+        mark_written(*owners[i:i + 1])
+
+    def state_dict(self):
+        """m and v of every DISTINCT table (a shared table's state once), in TableSet.distinct order, and the step count."""
+        first = [self.ts.slots_of(t)[0] for t in range(self.ts.T)]
+        return {"m": [self.ms[f].clone() for f in first], "v": [self.vs[f].clone() for f in first], "steps": self.steps}
+
+    def load_state_dict(self, state):
+        """Restore what state_dict() gave, in place (the kernels' pointer arrays stay valid)."""
+        first = [self.ts.slots_of(t)[0] for t in range(self.ts.T)]
+        if len(state["m"]) != len(first) or len(state["v"]) != len(first):
+            raise ValueError("SparseAdam.load_state_dict: %d tables, state of %d" % (len(first), len(state["m"])))
+        with torch.no_grad():
+            for f, m, v in zip(first, state["m"], state["v"]):
+                self.ms[f].copy_(m)
+                self.vs[f].copy_(v)
+        self.steps = int(state["steps"])
+        mark_written(*self._slots)
 
 
 class SparseFtrl(_SortedOpt):

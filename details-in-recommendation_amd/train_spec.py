@@ -212,7 +212,7 @@ class TrainStep:
         il = getattr(model, "input_layer", None)
         if params is None and cls is torch.optim.Adam and il is not None and hasattr(il, "fused_sparse_adam") and os.environ.get("DIR_TRAIN_HIP_ADAM", "1") == "1" \
                 and not kw.get("amsgrad") and not kw.get("weight_decay"):
-            self.sparse_adam, owned = il.fused_sparse_adam(betas[0], betas[1], self._tf_adam_eps, CLIP_NORM)
+            self.sparse_adam, owned = il.fused_sparse_adam(betas[0], betas[1], self._tf_adam_eps, CLIP_NORM, shared=True)
             owned = {id(p) for p in owned}
             self.params = [p for p in self.params if id(p) not in owned]
         self._beta1 = float(betas[0])
@@ -269,8 +269,10 @@ class TrainStep:
             self.after_backward()
         # Tables owned by the HIP Adam whose gradient did NOT go through the sink this step (multi-hot / weighted columns: their backward
         # returns sparse .grad): the same step on the same m / v, by torch ops -- never left without an optimiser, never accumulating.
+        # (.owned lists a table shared between columns once, with the slot to step it through: one variable, one step)
         for opt in self.sparse_adam:
-            for f, p in enumerate(getattr(opt, "owned", ())):
+            owned = getattr(opt, "owned", ())
+            for f, p in zip(getattr(opt, "owned_slots", range(len(owned))), owned):
                 if p.grad is not None:
                     opt.step_table_grad(f, p.grad)
                     p.grad = None

@@ -1264,6 +1264,26 @@ int dir_sparse_adam_f32(float* const* tables, float* const* ms, float* const* vs
                         float clip_norm, int64_t B, const int64_t* row_base, int64_t total_rows, void* workspace, int64_t workspace_bytes,
                         int first_call, dir_stream_t stream);
 
+/* dir_sparse_adam_shared_f32: dir_sparse_adam_f32 over tables SHARED between slots (shared_embedding_columns): the same call with
+ * two trailing arguments, under dir_sparse_adagrad_sorted_shared_f32's contract.  tables / ms / vs stay device arrays [F] of per-SLOT
+ * pointers (the slots of one table hold the same pointer, in all three); slot_table: DEVICE int32 [F], slot f's table among the
+ * n_tables distinct ones; row_base: DEVICE int64 [n_tables] and total_rows run over the DISTINCT tables.  The key of entry (b, f) is
+ * row_base[slot_table[f]] + id, pruned against that table's rows (and where the map value is outside [0, n_tables)); the pairs take the
+ * global sort, so a row's entries from ALL of its slots form one run in entry order e = b*F + f.  A shared variable has ONE gradient:
+ *   - the norm words go by table (word t low, 64 + t high): a run adds ||S_r||^2 of its sum over all slots -- ||S_a + S_b||^2, the cross
+ *     term included, as tf.clip_by_norm sees the variable's gradient --, and a row is clipped with its table's norm;
+ *   - a touched row takes ONE step of m / v / var with the summed gradient and sets one mark, at row_base[table] + id;
+ *   - the streaming pass visits every distinct table once (through the pointers of its first slot), not once per slot.
+ * workspace: dir_sparse_adam_workspace_bytes(B, F, K, total_rows) with total_rows over the distinct tables; the marks cover those rows.
+ * slot_table == NULL (n_tables == F) is the unshared call: the same tables, m and v as dir_sparse_adam_f32 bit for bit.  An identity map
+ * gives the same keys through the global sort: bit for bit too, except for B >= 4096 with pruned ids (the sort-plan caveat of
+ * dir_sparse_adagrad_sorted_shared_f32: about an ulp per run sum).  Limits as dir_sparse_adam_f32; 1 <= n_tables <= F.  Every argument
+ * is checked before the first HIP call. */
+int dir_sparse_adam_shared_f32(float* const* tables, float* const* ms, float* const* vs, int F, int K, const int64_t* ids,
+                               int64_t stride_b, int64_t stride_f, const float* grad, int64_t grad_ld, float lr_t, float beta1, float beta2,
+                               float eps, float clip_norm, int64_t B, const int64_t* row_base, int64_t total_rows, void* workspace,
+                               int64_t workspace_bytes, int first_call, dir_stream_t stream, const int32_t* slot_table, int n_tables);
+
 /* Owner side of a SHARDED backward: the n entries are the payload of dir_shard_bucket / dir_gather_packed_f32
  * (p = local_row * F + slot, p < 0 pruned) as received from all ranks, grad is [n, K] in the same order, tables / accums /
  * row_base / total_rows describe this rank's shards.  Workspace: dir_sparse_adagrad_sorted_workspace_bytes(n, 1, K, total_rows). */
