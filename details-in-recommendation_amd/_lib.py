@@ -276,6 +276,9 @@ SIGNATURES = {
     "dir_dropout_mask_u8": (c_i32, [c_i64, c_i64, ctypes.c_float, c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp]),
     "dir_dropout_advance": (c_i32, [c_vp, c_vp]),
     "dir_bn_affine_dropout_f32": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, ctypes.c_float, c_vp, ctypes.c_uint32, c_vp, c_vp, c_vp]),
+    # grouped ranking metrics (csrc/rank_metrics.hip): scores, labels, weights or NULL, offsets, G, the seven per-group outputs, stream
+    "dir_group_rank_limits": (c_i32, [ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
+    "dir_group_rank_stats_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 DIR_OK, DIR_E_BADARG, DIR_E_RANGE, DIR_E_HIP, DIR_E_UNSUPPORTED = 0, -1, -2, -3, -4

@@ -14,6 +14,7 @@ Reference closures (relative to /root/reference):
   cross_op / cross_network   _cross_op/_cross_architecture models/DeepCrossNetwork/DeepCrossNetwork.py:336-367
   din_attention_pool         (no reference code; README.md:27)
   cin_layer                  (no reference code; README.md:28)
+  group_rank_stats           _hit/_ndcg/_mrr, weighted_loss metrics/NCF_evaluation/ndcg_hr_mrr.py:14-84, metrics/weighted_loss/weighted_loss.py:27-50
 """
 import ctypes
 import os
@@ -1795,6 +1796,42 @@ def bn_affine_dropout(y, scale, shift, rate, state, stream_id=0, used=None, want
     _lib.check(_lib.load().dir_bn_affine_dropout_f32(_ptr(y), y.stride(0), _ptr(scale), _ptr(shift), B, N, _ptr(out), out.stride(0), rate,
                                                      _ptr(state.words), int(stream_id), _ptr(used), _ptr(left), _stream()))
     return (out, left) if want_used else out
+
+
+RANK_STATS = ("n_pos", "n_neg", "gt", "eq", "mis_w", "tot_w", "rank")
+
+
+def group_rank_limits():
+    """(wave_max, tile) of dir_group_rank_stats_f32: the largest group one wave takes, and the LDS tile of the workgroup route."""
+    w, t = ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.load().dir_group_rank_limits(ctypes.byref(w), ctypes.byref(t)))
+    return w.value, t.value
+
+
+def group_rank_stats(scores, labels, weights, offsets):
+    """Per-group pair statistics of the grouped ranking metrics (include/dir_hip.h: dir_group_rank_stats_f32; metrics/NCF_evaluation/
+    ndcg_hr_mrr.py:58-84, metrics/weighted_loss/weighted_loss.py:27-50).  scores, labels, weights (or None: ones): float32 [n] contiguous CUDA
+    tensors; offsets: int64 [G + 1], non-decreasing, offsets[G] <= n (not read on the host) -> {"n_pos", "n_neg", "gt", "eq", "rank": int64 [G],
+    "mis_w", "tot_w": float64 [G]}.  One launch, no host read."""
+    _dev(scores, torch.float32, "scores")
+    _dev(labels, torch.float32, "labels")
+    _dev(offsets, torch.int64, "offsets")
+    if weights is not None:
+        _dev(weights, torch.float32, "weights")
+    flat = [("scores", scores), ("labels", labels)] + ([("weights", weights)] if weights is not None else [])
+    for name, t in flat:
+        if t.dim() != 1 or t.shape != scores.shape or not t.is_contiguous() or t.device != scores.device:
+            raise ValueError("group_rank_stats: %s must be a contiguous 1-d tensor of scores' length on scores' device" % name)
+    if offsets.dim() != 1 or offsets.numel() < 1 or not offsets.is_contiguous() or offsets.device != scores.device:
+        raise ValueError("group_rank_stats: offsets must be a contiguous int64 [G + 1] tensor on scores' device")
+    G = offsets.numel() - 1
+    out = {k: torch.empty(G, dtype=torch.float64 if k in ("mis_w", "tot_w") else torch.int64, device=scores.device) for k in RANK_STATS}
+    if scores.numel() == 0:                        # only empty groups: an empty tensor has no address to hand over
+        scores = labels = torch.zeros(1, dtype=torch.float32, device=offsets.device)
+        weights = None
+    _lib.check(_lib.load().dir_group_rank_stats_f32(_ptr(scores), _ptr(labels), _ptr(weights), _ptr(offsets), G,
+                                                    *[_ptr(out[k]) for k in RANK_STATS], _stream()))
+    return out
 
 
 def din_backward_supported(K, T, H1, H2):

@@ -1514,6 +1514,27 @@ int dir_dropout_advance(int64_t* state, dir_stream_t stream);
 int dir_bn_affine_dropout_f32(const float* y, int64_t y_ld, const float* scale, const float* shift, int64_t B, int N, float* out, int64_t out_ld,
                               float rate, const int64_t* state, uint32_t stream_id, const int64_t* used_in, int64_t* used_out, dir_stream_t stream);
 
+/* ---- grouped ranking metrics: per-group pair statistics (csrc/rank_metrics.hip) -------------------------------------------------------------
+ * Reference: metrics/NCF_evaluation/ndcg_hr_mrr.py:14-44,58-84 (HR / NDCG / MRR@10 of one positive among 99 negatives) and
+ * metrics/weighted_loss/weighted_loss.py:27-50,80-81 (the per-user weighted mis-ordering loss); GAUC is arXiv:1706.06978's user-weighted AUC.
+ * Group g is the entries offsets[g] .. offsets[g + 1] - 1 of scores / labels / weights (fp32; weights NULL: all 1), in their given order;
+ * offsets: device int64 [G + 1], non-decreasing, offsets[G] <= the arrays' length (a group with offsets[g + 1] <= offsets[g] is empty).
+ * P = {e : labels[e] > 0.5}, N the rest; for i in P: a_i = |{j in N : s_j > s_i}|, e_i = |{j in N : s_j == s_i}| (fp32 compares).  Per group:
+ *   n_pos, n_neg (int64)   |P|, |N|
+ *   gt, eq (int64)         sum_i (n_neg - a_i - e_i), sum_i e_i
+ *   mis_w, tot_w (float64) sum_i w_i (a_i + e_i), sum_i w_i n_neg: the weights widened exactly, each term one product, summed in a fixed order
+ *   rank (int64)           n_pos == 1, the positive at i: 1 + |{j != i : s_j > s_i}| + |{j < i : s_j == s_i}| (its place in a stable descending
+ *                          sort, from 1); otherwise 0
+ * Empty groups give zeros; a group of one class gives zero pair counts.  Scores are expected to be finite: a NaN score is neither above,
+ * below nor equal to anything.  Integer outputs are exact and two runs give the same float64 bits (no floating-point atomics).
+ * The route of a group is taken on the device from its offsets: up to wave_max entries one wave per group (four groups per workgroup), above
+ * that one workgroup per group with the negatives staged through LDS in tiles of `tile` scores -- O(n^2 / 256) compares per thread, any n; a
+ * group is never split over workgroups.  Stream-ordered, no host read; G == 0 is a no-op.
+ * dir_group_rank_limits: HOST function, the two route limits (what the tests take their edge sizes from). */
+int dir_group_rank_limits(int* wave_max, int* tile);
+int dir_group_rank_stats_f32(const float* scores, const float* labels, const float* weights, const int64_t* offsets, int64_t G, int64_t* n_pos,
+                             int64_t* n_neg, int64_t* gt, int64_t* eq, double* mis_w, double* tot_w, int64_t* rank, dir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
