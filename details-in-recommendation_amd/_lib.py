@@ -279,6 +279,11 @@ SIGNATURES = {
     # grouped ranking metrics (csrc/rank_metrics.hip): scores, labels, weights or NULL, offsets, G, the seven per-group outputs, stream
     "dir_group_rank_limits": (c_i32, [ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
     "dir_group_rank_stats_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    # matrix factorisation (csrc/mf.hip): P, Q, bu, bi, [b0,] ids, stride_b, stride_f, ... ; the sampler: users, B, offsets, items, num_items, n_neg,
+    # state, stream_id, first, out, status, stream
+    "dir_mf_score_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "dir_mf_score_backward_f32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, ctypes.c_float, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "dir_neg_sample_i64": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i32, c_vp, ctypes.c_uint32, c_i64, c_vp, c_vp, c_vp]),
 }
 
 DIR_OK, DIR_E_BADARG, DIR_E_RANGE, DIR_E_HIP, DIR_E_UNSUPPORTED = 0, -1, -2, -3, -4

@@ -494,6 +494,59 @@ class DinPoolRows(torch.autograd.Function):
         return ds, dH, None, None, None
 
 
+class MfScore(torch.autograd.Function):
+    """logits [B, C] = mf_score(P, Q, ids, bu, bi, b0) (ops.mf_score: models/LFM/Mixture_1/MF_model.py:164-194), backward in HIP
+    (ops.mf_score_backward: the rows are read again, nothing of size [B, C, K] is saved).  l2: the backward ADDS l2 * (looked-up row / bias)
+    per occurrence -- the gradient of l2 * tf.nn.l2_loss(looked-up rows) (MF_model.py:200-206), whose VALUE the caller adds to its loss
+    without a graph (mf.BiasedMF.create_loss does); it is not scaled by the incoming gradient.
+    row_sink / bias_sink: callables (ids, grad [B, (1 + C) K]) / (ids, gbias [B, 1 + C]) of fused sparse optimisers over
+    TableSet([P] + [Q] * C) / TableSet([bu] + [bi] * C): with a sink the variables get no .grad.  Without one they get coalesced sparse
+    .grads (Q's and bi's C slots concatenated).  b0's gradient is dlogits.sum()."""
+
+    @staticmethod
+    def forward(ctx, ids, l2, row_sink, bias_sink, P, Q, bu, bi, b0):
+        det = lambda t: t.detach() if t is not None else None      # noqa: E731
+        out = ops.mf_score(det(P), det(Q), ids, det(bu), det(bi), det(b0))
+        ctx.l2, ctx.row_sink, ctx.bias_sink = float(l2), row_sink, bias_sink
+        ctx.has = (bu is not None, b0 is not None)
+        ctx.save_for_backward(ids, P, Q, *([bu, bi] if bu is not None else []), *([b0] if b0 is not None else []))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ids, P, Q, *rest = ctx.saved_tensors
+        has_bias, has_b0 = ctx.has
+        bu, bi = (rest[0], rest[1]) if has_bias else (None, None)
+        b0 = rest[-1] if has_b0 else None
+        det = lambda t: t.detach() if t is not None else None      # noqa: E731
+        g = g.contiguous()
+        grad, gbias = ops.mf_score_backward(det(P), det(Q), ids, g, det(bu), det(bi), l2=ctx.l2)
+        B, C, K = ids.shape[0], ids.shape[1] - 1, P.shape[1]
+        gP = gQ = gbu = gbi = gb0 = None
+        if ctx.row_sink is not None:
+            ctx.row_sink(ids, grad)
+        else:
+            users, items = ids[:, 0].contiguous(), ids[:, 1:].reshape(-1)
+            gP = _sparse_rows(_in_range(users, P.shape[0]), grad[:, :K], P.shape[0]).coalesce()
+            gQ = _sparse_rows(_in_range(items, Q.shape[0]), grad[:, K:].reshape(B * C, K), Q.shape[0]).coalesce()
+        if has_bias:
+            if ctx.bias_sink is not None:
+                ctx.bias_sink(ids, gbias)
+            else:
+                users, items = ids[:, 0].contiguous(), ids[:, 1:].reshape(-1)
+                two_d = bu.dim() == 2
+                gu, gi = gbias[:, 0], gbias[:, 1:].reshape(-1)
+                gbu = _sparse_rows(_in_range(users, bu.shape[0]), gu.unsqueeze(1) if two_d else gu, bu.shape[0]).coalesce()
+                gbi = _sparse_rows(_in_range(items, bi.shape[0]), gi.unsqueeze(1) if two_d else gi, bi.shape[0]).coalesce()
+        if has_b0:
+            gb0 = g.sum().reshape(b0.shape)
+        return None, None, None, None, gP, gQ, gbu, gbi, gb0
+
+
+def mf_score(P, Q, ids, bu=None, bi=None, b0=None, l2=0.0, row_sink=None, bias_sink=None):
+    return MfScore.apply(ids, l2, row_sink, bias_sink, P, Q, bu, bi, b0)
+
+
 def gather_fm(ts, ids, tables):
     return GatherFm.apply(ts, ids, *tables)
 

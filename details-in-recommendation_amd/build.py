@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(CSRC, "_build")
 LIB = os.path.join(HERE, "libdir_hip.so")
-SOURCES = ["capi.cpp", "embedding_bag.hip", "linear_cross.hip", "ids.hip", "cross.hip", "shard_bags.hip", "shard_linear.hip", "din.hip", "din_wave.hip", "din_pack.hip", "din_bwd_rows.hip", "din_rows_train.hip", "cin.hip", "cin_bf3.hip", "cin_dw_bf3.hip", "cin_dw_sym_bf3.hip", "cin_pool.hip", "cin_pooled.hip", "cin_bwd.hip", "backward.hip", "rows_scatter.hip", "radix_sort.hip", "dense.hip", "dense_bf3.hip", "tower_bf3.hip", "tower_cs.hip", "dense_dw_bf3.hip", "head_bwd.hip", "bn_train.hip", "dropout.hip", "rank_metrics.hip", "diag.hip"]
+SOURCES = ["capi.cpp", "embedding_bag.hip", "linear_cross.hip", "ids.hip", "cross.hip", "shard_bags.hip", "shard_linear.hip", "din.hip", "din_wave.hip", "din_pack.hip", "din_bwd_rows.hip", "din_rows_train.hip", "cin.hip", "cin_bf3.hip", "cin_dw_bf3.hip", "cin_dw_sym_bf3.hip", "cin_pool.hip", "cin_pooled.hip", "cin_bwd.hip", "backward.hip", "rows_scatter.hip", "radix_sort.hip", "dense.hip", "dense_bf3.hip", "tower_bf3.hip", "tower_cs.hip", "dense_dw_bf3.hip", "head_bwd.hip", "bn_train.hip", "dropout.hip", "rank_metrics.hip", "mf.hip", "diag.hip"]
 # per-file flags: cin_bwd's epilogues read the MFMA results on the VALU, so keep them in VGPRs (no v_accvgpr_read)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"cin_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
@@ -45,6 +45,7 @@ EXTRA_FLAGS = {"cin_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "tower_cs.hip": NO_PACKED_FP32,
                "dropout.hip": NO_PACKED_FP32,             # (elementwise, on the training stream beside the other streams' bf16-MFMA kernels)
                "rank_metrics.hip": NO_PACKED_FP32,        # (evaluation beside a training or serving stream's bf16-MFMA kernels)
+               "mf.hip": NO_PACKED_FP32,                  # (score / sampler streams beside another stream's bf16-MFMA kernels)
                "din_bwd_rows.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"] + NO_PACKED_FP32}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",

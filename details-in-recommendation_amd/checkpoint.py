@@ -77,6 +77,9 @@ def tf_variable_map(model):
             for i, lin in enumerate(tower.hidden):
                 _lin("%s/hiddenlayer_%d" % (scope, i), lin, m)                                  # ESMM.py:137-142
             _lin("%s/dense" % scope, tower.logits, m)                                           # ESMM.py:146
+    elif hasattr(model, "tf_names") and hasattr(model, "user_emb"):                             # mf.BiasedMF / Svd / BPR: MF_model.py:166-175
+        for attr, name in model.tf_names().items():
+            m[name] = (getattr(model, attr), None)
     else:
         raise TypeError("no TensorFlow name mapping for %s" % type(model).__name__)
     return m

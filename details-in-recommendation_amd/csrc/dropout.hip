@@ -18,27 +18,9 @@
 // step is in profiles/NOTES.md R9.1 (the kernels alone have not been timed against the copy ceiling).  Compiled without packed fp32 VALU
 // instructions (build.py: NO_PACKED_FP32): the kernels may share a SIMD with another stream's bf16-MFMA kernel.
 #include "common.hpp"
+#include "philox.hpp"      // Philox4, philox4x32_10 (shared with csrc/mf.hip's negative sampler)
 
 namespace dir {
-
-struct Philox4 { uint32_t v[4]; };
-
-__host__ __device__ inline uint32_t philox_mulhi(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32); }
-
-__host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = philox_mulhi(M0, c0), lo0 = M0 * c0;
-        const uint32_t hi1 = philox_mulhi(M1, c2), lo1 = M1 * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += W0; k1 += W1;
-    }
-    Philox4 o;
-    o.v[0] = c0; o.v[1] = c1; o.v[2] = c2; o.v[3] = c3;
-    return o;
-}
 
 // What every kernel of this file needs to make the mask of element e
 struct DropCtx {

@@ -15,6 +15,8 @@ Reference closures (relative to /root/reference):
   din_attention_pool         (no reference code; README.md:27)
   cin_layer                  (no reference code; README.md:28)
   group_rank_stats           _hit/_ndcg/_mrr, weighted_loss metrics/NCF_evaluation/ndcg_hr_mrr.py:14-84, metrics/weighted_loss/weighted_loss.py:27-50
+  mf_score / _backward       BaseMFModel._logit_fn         models/LFM/Mixture_1/MF_model.py:164-206
+  neg_sample                 (the rejection loop)          models/BPR/bpr_sampler.py:102-111
 """
 import ctypes
 import os
@@ -1832,6 +1834,124 @@ def group_rank_stats(scores, labels, weights, offsets):
     _lib.check(_lib.load().dir_group_rank_stats_f32(_ptr(scores), _ptr(labels), _ptr(weights), _ptr(offsets), G,
                                                     *[_ptr(out[k]) for k in RANK_STATS], _stream()))
     return out
+
+
+def _mf_args(name, P, Q, ids, bu, bi):
+    """The shared checks of mf_score / mf_score_backward -> (B, C, K, stride_b, stride_f)."""
+    _dev(P, torch.float32, "P")
+    _dev(Q, torch.float32, "Q")
+    _dev(ids, torch.int64, "ids")
+    if P.dim() != 2 or Q.dim() != 2 or P.shape[1] != Q.shape[1] or not P.is_contiguous() or not Q.is_contiguous():
+        raise ValueError("%s: P [U, K] and Q [I, K] must be contiguous tables of one K" % name)
+    K = int(P.shape[1])
+    if K % 4 or not 4 <= K <= 256:
+        raise ValueError("%s: K=%d is not covered (a multiple of 4 in [4, 256])" % (name, K))
+    if ids.dim() != 2 or ids.shape[1] < 2:
+        raise ValueError("%s: ids must be [B, 1 + C] with C >= 1 (column 0 the user, the rest items), got %s" % (name, tuple(ids.shape)))
+    if (bu is None) != (bi is None):
+        raise ValueError("%s: bu and bi go together" % name)
+    for nm, b, t in (("bu", bu, P), ("bi", bi, Q)):
+        if b is not None:
+            _dev(b, torch.float32, nm)
+            if b.numel() != t.shape[0] or not b.is_contiguous():
+                raise ValueError("%s: %s must be a contiguous [%d] / [%d, 1] tensor" % (name, nm, t.shape[0], t.shape[0]))
+    return ids.shape[0], ids.shape[1] - 1, K, ids.stride(0), ids.stride(1)
+
+
+def mf_score(P, Q, ids, bu=None, bi=None, b0=None, out=None):
+    """logits [B, C] = sum_k P[u, k] Q[i_c, k] + ((bu[u] + bi[i_c]) + b0) in one launch (include/dir_hip.h: dir_mf_score_f32;
+    models/LFM/Mixture_1/MF_model.py:164-194).  ids: int64 [B, 1 + C], any strides -- column 0 rows of P [U, K], columns 1 .. C rows of
+    Q [I, K]; bu [U] / bi [I] together or not at all, b0 a one-element device tensor or None.  Bitwise reproducible."""
+    B, C, K, sb, sf = _mf_args("mf_score", P, Q, ids, bu, bi)
+    if b0 is not None:
+        _dev(b0, torch.float32, "b0")
+        if b0.numel() != 1:
+            raise ValueError("mf_score: b0 must hold one element")
+    if out is None:
+        out = torch.empty((B, C), dtype=torch.float32, device=P.device)
+    elif out.shape != (B, C) or out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("mf_score: out must be a contiguous float32 CUDA tensor [B, C]")
+    _lib.check(_lib.load().dir_mf_score_f32(_ptr(P), _ptr(Q), _ptr(bu), _ptr(bi), _ptr(b0), _ptr(ids), sb, sf, B, C, K, _ptr(out), _stream()))
+    return out
+
+
+def mf_score_backward(P, Q, ids, dlogits, bu=None, bi=None, l2=0.0):
+    """The backward of mf_score (include/dir_hip.h: dir_mf_score_backward_f32) -> (grad [B, (1 + C) K], gbias [B, 1 + C]): the row and bias
+    gradients per (sample, slot) -- what ops.SparseAdagrad / SparseAdam .step(ids, grad) take over TableSet([P] + [Q] * C) and
+    TableSet([bu] + [bi] * C).  l2: the coefficient of tf.nn.l2_loss on the looked-up rows and biases, per occurrence (MF_model.py:200-206).
+    Without bu / bi, gbias holds the plain sums of dlogits."""
+    B, C, K, sb, sf = _mf_args("mf_score_backward", P, Q, ids, bu, bi)
+    _dev(dlogits, torch.float32, "dlogits")
+    if dlogits.shape != (B, C):
+        raise ValueError("mf_score_backward: dlogits must be [B, C] = %s, got %s" % ((B, C), tuple(dlogits.shape)))
+    dlogits = dlogits.contiguous()
+    grad = torch.empty((B, (1 + C) * K), dtype=torch.float32, device=P.device)
+    gbias = torch.empty((B, 1 + C), dtype=torch.float32, device=P.device)
+    _lib.check(_lib.load().dir_mf_score_backward_f32(_ptr(P), _ptr(Q), _ptr(bu), _ptr(bi), _ptr(ids), sb, sf, _ptr(dlogits), float(l2), B, C, K,
+                                                     _ptr(grad), _ptr(gbias), _stream()))
+    return grad, gbias
+
+
+class UserItems:
+    """Every user's interacted items as a CSR on the device: offsets int64 [U + 1], items int64 [nnz] ascending and distinct inside a user
+    (what neg_sample bisects).  The constructor refuses a user who has interacted with every item -- nothing could be drawn for them --: one
+    synchronising check, at construction only."""
+
+    def __init__(self, offsets, items, num_items, _check=True):
+        for name, t in (("offsets", offsets), ("items", items)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 1:
+                raise TypeError("UserItems: %s must be a 1-d int64 tensor" % name)
+        if offsets.numel() < 1 or offsets.device != items.device:
+            raise ValueError("UserItems: offsets [U + 1] and items live on one device")
+        self.offsets, self.items = offsets.contiguous(), items.contiguous()
+        self.num_users, self.num_items = offsets.numel() - 1, int(num_items)
+        if self.num_items < 1:
+            raise ValueError("UserItems: num_items must be at least 1, got %r" % num_items)
+        self.device = offsets.device
+        if _check and self.num_users:
+            worst = int((self.offsets[1:] - self.offsets[:-1]).max())
+            if worst >= self.num_items:
+                raise ValueError("UserItems: a user has interacted with %d of %d items: no negative is left to draw" % (worst, self.num_items))
+
+    @classmethod
+    def from_pairs(cls, users, items, num_users, num_items):
+        """From (user, item) interaction pairs in any order, duplicates allowed: sorted and de-duplicated on the pairs' device."""
+        users, items = users.reshape(-1).to(torch.int64), items.reshape(-1).to(torch.int64)
+        if users.numel() != items.numel():
+            raise ValueError("UserItems.from_pairs: users and items must pair up")
+        num_users, num_items = int(num_users), int(num_items)
+        key = torch.unique(users * num_items + items)                # sorted: by user, then by item
+        u, it = torch.div(key, num_items, rounding_mode="floor"), key % num_items
+        offsets = torch.zeros(num_users + 1, dtype=torch.int64, device=users.device)
+        if key.numel():
+            torch.cumsum(torch.bincount(u, minlength=num_users)[:num_users], 0, out=offsets[1:])
+        return cls(offsets, it, num_items)
+
+
+def neg_sample(users, user_items, n_neg, state, stream_id=0, first=0, out=None, return_status=False):
+    """neg [B, n_neg] int64: for every user of users [B], n_neg items drawn uniformly from those the user has not interacted with
+    (include/dir_hip.h: dir_neg_sample_i64; the distribution of models/BPR/bpr_sampler.py:102-111's rejection loop, without the loop).
+    user_items: a UserItems; state: a DropoutState (its (seed, draw) key the draws: advance() it between steps); stream_id / first tell
+    samplers and batches of one draw apart.  return_status=True adds the device int32 status word (non-zero: some user had no negative
+    left and got -1); nothing synchronises."""
+    _dev(users, torch.int64, "users")
+    if users.dim() != 1:
+        raise ValueError("neg_sample: users must be a vector")
+    users = users.contiguous()
+    B, n_neg = users.numel(), int(n_neg)
+    if n_neg < 1:
+        raise ValueError("neg_sample: n_neg must be at least 1")
+    if user_items.device != users.device:
+        raise ValueError("neg_sample: user_items lives on %s, users on %s" % (user_items.device, users.device))
+    if out is None:
+        out = torch.empty((B, n_neg), dtype=torch.int64, device=users.device)
+    elif out.shape != (B, n_neg) or out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("neg_sample: out must be a contiguous int64 CUDA tensor [B, n_neg]")
+    status = torch.zeros(1, dtype=torch.int32, device=users.device)
+    items = user_items.items if user_items.items.numel() else user_items.offsets       # (no interactions at all: any valid address, never read)
+    _lib.check(_lib.load().dir_neg_sample_i64(_ptr(users), B, _ptr(user_items.offsets), _ptr(items), user_items.num_items, n_neg,
+                                              _ptr(state.words), int(stream_id), int(first), _ptr(out), _ptr(status), _stream()))
+    return (out, status) if return_status else out
 
 
 def din_backward_supported(K, T, H1, H2):

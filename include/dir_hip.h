@@ -1535,6 +1535,35 @@ int dir_group_rank_limits(int* wave_max, int* tile);
 int dir_group_rank_stats_f32(const float* scores, const float* labels, const float* weights, const int64_t* offsets, int64_t G, int64_t* n_pos,
                              int64_t* n_neg, int64_t* gt, int64_t* eq, double* mis_w, double* tot_w, int64_t* rank, dir_stream_t stream);
 
+/* ---- matrix factorisation: fused gather-and-score, its backward, the negative sampler (csrc/mf.hip) ------------------------------------------
+ * Reference: models/LFM/Mixture_1/MF_model.py:164-206 (BaseMFModel._logit_fn / _get_loss), models/LFM/Mixture_2/model.py:74-90 (Svd: no
+ * biases), models/BPR/bpr_sampler.py:102-111 (the rejection loop whose distribution the sampler reproduces without looping).
+ * ids: device int64 [B, 1 + C] with strides stride_b / stride_f (in elements): column 0 the row of P [U, K], columns 1 .. C rows of Q [I, K];
+ * 0 <= id < vocab is the caller's precondition (dir_check_ids).  P, Q: contiguous fp32 rows, 16-byte aligned.  K % 4 == 0, 4 <= K <= 256,
+ * C >= 1 (else DIR_E_BADARG).  bu [U] / bi [I]: NULL together (no intercepts); b0: a device scalar or NULL.  B == 0 is a no-op.
+ * dir_mf_score_f32: logits [B, C] (contiguous) = sum_k P[u, k] Q[i_c, k] + ((bu[u] + bi[i_c]) + b0); the dot in a fixed order (k order inside a
+ *   lane's four floats, then a fixed tree over the lanes of the sample): two calls give the same bits.
+ * dir_mf_score_backward_f32: dlogits [B, C] contiguous ->
+ *   grad  [B, (1 + C) K] (contiguous, 16-byte aligned): slot 0 = sum_c dl[b, c] Q[i_c] + l2 P[u] (c order), slot 1 + c = dl[b, c] P[u] + l2 Q[i_c]
+ *   gbias [B, 1 + C] or NULL:                           sum_c dl[b, c] + l2 bu[u]           and           dl[b, c] + l2 bi[i_c]
+ *   -- the gradient slabs of the sorted sparse optimisers for the same ids matrix over the tables [P, Q x C] / [bu, bi x C].  The l2 terms are
+ *   the gradient of l2 * tf.nn.l2_loss(looked-up rows), per occurrence (MF_model.py:200-206); l2 == 0 skips them (bu / bi may be NULL then
+ *   with gbias given).  d b0 = the sum of dlogits, left to the caller.  The rows are read again; nothing of size [B, C, K] is kept.
+ * dir_neg_sample_i64: out [B, n_neg] = for every (b, c) an item drawn uniformly from the items user users[b] has not interacted with.
+ *   offsets [U + 1] / items: the CSR of every user's items, ascending and distinct per user.  With n_u the user's count:
+ *   k = mulhi64(w, num_items - n_u), p = the smallest position with items[p] - p > k (n_u if none; <= 64 bisection steps), out = k + p.
+ *   w = r[0] | r[1] << 32 of ONE Philox4x32-10 block per draw: counter = (e & 0xffffffff, e >> 32, stream_id, draw), e = first + b n_neg + c,
+ *   key = (seed & 0xffffffff, seed >> 32), (seed, draw) = state (device int64[2], as dir_dropout_f32's).  An item's probability differs from
+ *   uniform by at most (num_items - n_u) / 2^64 relatively.  n_u >= num_items: out = -1 and status[0] (device int32, zeroed by the caller) = 1.
+ * All three: kernel launches only -- no host read, no atomics, bounded loops -- so a training step that uses them can be captured. */
+int dir_mf_score_f32(const float* P, const float* Q, const float* bu, const float* bi, const float* b0, const int64_t* ids, int64_t stride_b,
+                     int64_t stride_f, int64_t B, int C, int K, float* logits, dir_stream_t stream);
+int dir_mf_score_backward_f32(const float* P, const float* Q, const float* bu, const float* bi, const int64_t* ids, int64_t stride_b,
+                              int64_t stride_f, const float* dlogits, float l2, int64_t B, int C, int K, float* grad, float* gbias,
+                              dir_stream_t stream);
+int dir_neg_sample_i64(const int64_t* users, int64_t B, const int64_t* offsets, const int64_t* items, int64_t num_items, int n_neg,
+                       const int64_t* state, uint32_t stream_id, int64_t first, int64_t* out, int32_t* status, dir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
